@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frame-pairs matched+RANSAC'd per second (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (Hamming match -> select -> RANSAC, the whole
 Node::matchNodePair pair op) over one batch of candidate pairs of the synthetic
@@ -12,8 +12,15 @@ torch.distributed.run) every rank holds all nodes, the global pair list (N x 400
 is sharded pair k -> rank k mod N, and each step ends with the RCCL all-gather of the
 MatchingResult PODs: weak scaling.
 
-Rank 0 prints ONE JSON line.  The timed region (K steps between barrier + synchronize) is run REPEATS = 7 times in
-the invocation: `value` / `ms_per_step` are the median repetition, `repeats` lists all of them.  The head of the line is
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up (at least W steps and at least WARMUP_MIN_S), times ONE
+region of exactly K steps (between barrier + synchronize), writes the last step's results if --dump-outputs is given, and prints the head of the line: `metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config` (and, with N > 1, `gather`).  --dump-outputs DIR
+writes what the last timed step computed -- the result records the caller of the pair path receives (rank 0: the
+gathered records at N > 1) -- as DIR/<field>.npy in float32 / float64, list entries past a record's length zeroed, at
+most 64 MB (a seeded sample of records above that); the inputs are seeded, so two builds compare output for output.
+
+Everything below is --full only.  The timed region is run REPEATS = 7 times in the invocation: `value` / `ms_per_step`
+are the median repetition, `repeats` lists all of them.  The head of the line is
 self-sufficient: `roofline` carries, as flat numbers, the fraction and the average launch time of every
 kernel family the line reports (`match_*`, `sift_*`, `detect_*`, `sift_extract_*`, `heavy_*`) and the headline measured a
 second time with the library's DEFAULT launch path (`default_path_*`: plain launches, no hipGraph); every `*_avg_launch_ms`
@@ -42,7 +49,8 @@ N_FRAMES = 200
 PAIRS_PER_FRAME = 20
 MAX_MATCHES = 300
 SEED = 20260923
-REPEATS = 7                                # repetitions of the timed region (median reported)
+REPEATS = 7                                # repetitions of the timed region (median reported; --full)
+WARMUP_MIN_S = 0.2                         # a plain run's warm-up: at least --warmup steps and at least this long
 PMC_SUMMARY = "profiles/r06_pmc_summary.json"   # static counter figures (tools/profile_round.sh + tools/make_pmc_summary.py)
 PMC_FALLBACK = "profiles/r05_pmc_summary.json"
 # Aggregates of every workload this file prints a number for, as the ORACLE computes them (tools/make_bench_expected.py:
@@ -85,6 +93,56 @@ def pair_aggregates(res):
     """Sums over result records (RESULT_DTYPE or COMPACT_DTYPE): what the oracle constants of the pair workloads are."""
     return {"edges": int((res["id1"] >= 0).sum()), "real_iterations": int(res["real_iterations"].astype(np.int64).sum()),
             "inliers": int(res["n_inl"].astype(np.int64).sum())}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20261016
+
+
+def dump_outputs(dirpath, records, inlier_lists=None):
+    """--dump-outputs: the last timed step's result records -> DIR/<field>.npy.  `records`: RESULT_DTYPE (N = 1), or what the
+    all-gather left on rank 0 (RESULT_DTYPE, COMPACT_DTYPE, or INLIER_HEADER_DTYPE headers with `inlier_lists`, every rank's
+    (headers, list) of its inlier stream).  Integer fields become float64 (exact), float fields keep their width; the
+    per-match arrays become float32 [n, RGBDFE_MAX_MATCHES] with the entries past the record's length zeroed (the device
+    leaves them unspecified); the inlier mask becomes 0 / 1 per match position.  Above DUMP_LIMIT_BYTES a seeded sample of
+    records -- the same rows in every file, listed in sample_rows.npy -- is written."""
+    from rgbdslam_v2_amd._lib import RGBDFE_MAX_MATCHES
+    n = len(records)
+    names = records.dtype.names
+    pos = np.arange(RGBDFE_MAX_MATCHES)
+    out = {}
+    for f in names:
+        if f not in ("pad0", "first_inlier", "all_q", "all_t", "all_hd", "inlier_mask"):
+            a = records[f]
+            out[f] = a.astype(a.dtype if a.dtype.kind == "f" else np.float64)
+    valid = pos[None, :] < records["n_all"].astype(np.int64)[:, None]
+    for f in ("all_q", "all_t", "all_hd"):
+        if f in names:
+            out[f] = np.where(valid, records[f][:, :RGBDFE_MAX_MATCHES], 0).astype(np.float32)
+    if "inlier_mask" in names:
+        bits = np.unpackbits(np.ascontiguousarray(records["inlier_mask"]).view(np.uint8).reshape(n, -1), axis=1,
+                             bitorder="little")[:, :RGBDFE_MAX_MATCHES]
+        out["inlier_mask"] = np.where(valid, bits, 0).astype(np.float32)
+    if inlier_lists is not None:   # (query row, train row) of every inlier match, per record
+        qs, ts = [], []
+        for hdr, lst in inlier_lists:
+            lst = np.append(np.asarray(lst, np.uint32), np.uint32(0))
+            ok = pos[None, :] < hdr["n_inl"].astype(np.int64)[:, None]
+            e = lst[np.minimum(hdr["first_inlier"].astype(np.int64)[:, None] + pos[None, :], len(lst) - 1)]
+            qs.append(np.where(ok, e & 0xFFFF, 0).astype(np.float32))
+            ts.append(np.where(ok, e >> 16, 0).astype(np.float32))
+        out["inlier_q_row"] = np.concatenate(qs) if qs else np.zeros((0, RGBDFE_MAX_MATCHES), np.float32)
+        out["inlier_t_row"] = np.concatenate(ts) if ts else np.zeros((0, RGBDFE_MAX_MATCHES), np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        k = int(n * DUMP_LIMIT_BYTES * 0.98 / total)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+        out = {f: a[rows] for f, a in out.items()}
+        out["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(dirpath, exist_ok=True)
+    for f, a in out.items():
+        np.save(os.path.join(dirpath, f + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
 
 
 def features_checksum(frames):
@@ -229,6 +287,11 @@ def main():
                          "header + inlier mask, the lists stay behind) or the whole 1744-byte record")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result records as DIR/<field>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed regions, the default-launch-path leg, serial stage "
+                         "times and rooflines, the oracle parity check, the sub-records and the CPU baselines")
     args = ap.parse_args()
     # The launch chain of an ORB pair batch as a cached hipGraph (rgbdfe_set_graph_capture): off by default in the library --
     # an open capture makes device-wide synchronisations on OTHER threads of the process fail -- on here, where every HIP
@@ -466,18 +529,33 @@ def main():
             state["gathers"] += 1
 
     fe.set_profiling(True)          # before the warm-up: its steps then take the very path the timed steps take
-    for _ in range(args.warmup):
-        step()
-    if inliers:
-        flush()
-    fe.synchronize()
-    torch.cuda.synchronize()
+    t_warm = time.perf_counter()
+    n_warm = args.warmup
+    while True:
+        for _ in range(n_warm):
+            step()
+        if inliers:
+            flush()
+        fe.synchronize()
+        torch.cuda.synchronize()
+        # A plain run times ONE region: its warm-up lasts at least WARMUP_MIN_S (the first ~20 ms after an idle period run
+        # 6 - 7 % slow; --full's median of REPEATS regions does not need it).  Every rank runs the same number of steps.
+        if args.full:
+            break
+        more = torch.tensor([0 if time.perf_counter() - t_warm >= WARMUP_MIN_S else 1], dtype=torch.int32,
+                            device=cdev if gather_on else "cpu")
+        if gather_on:
+            dist.all_reduce(more, op=dist.ReduceOp.MAX)
+        if not int(more.item()):
+            break
+        n_warm = 10
     state["bytes"] = state["gathers"] = 0
     fe.reset_kernel_time()
     # The timed region -- exactly K steps between barrier + synchronize on both sides, max over ranks -- REPEATS times;
     # the median repetition is the reported one (one region lasts a few tens of ms: single runs spread by several %).
+    # (a plain run: one region of exactly K steps)
     rep_elapsed = []
-    for _rep in range(REPEATS):
+    for _rep in range(REPEATS if args.full else 1):
         if world > 1:
             dist.barrier()
         fe.synchronize()
@@ -509,7 +587,7 @@ def main():
     # The same timed region once more on the library's DEFAULT launch path (graph capture off: plain launches -- what a
     # multi-threaded integration runs): reported beside the headline, never instead of it.
     plain_elapsed = None
-    if not sift and os.environ.get("RGBDFE_GRAPHS") != "0":
+    if args.full and not sift and os.environ.get("RGBDFE_GRAPHS") != "0":
         fe.set_graph_capture(False)
         for _ in range(max(args.warmup, 4)):
             step()
@@ -548,25 +626,26 @@ def main():
     # In the timed region two batches share the chip, so a stage's HIP-event span there is inflated by its neighbour
     # and can exceed ms_per_step; the serial steps give stage times that add up to a step time measured the same way.
     iso = {}
-    fe.reset_kernel_time()
-    fe.set_profiling(True)
-    n_serial = 5
-    torch.cuda.synchronize()
-    ts0 = time.perf_counter()
-    for _ in range(n_serial):
-        if sift:
-            tk = fe.submit_sift_pair_list(pq, pt, d_local[0].data_ptr())
-        else:
-            tk = fe.submit_pair_list(pq, pt, d_local[0].data_ptr())
-        fe.wait_ticket(tk, None)
-    fe.synchronize()
-    serial_ms = (time.perf_counter() - ts0) / n_serial * 1e3
-    fe.set_profiling(False)
-    for nme, kk in (("match", k_match), ("ransac", KERNEL_RANSAC), ("sift_finish", KERNEL_SIFT_FINISH)):
-        ms, nl, _ = fe.kernel_time(kk)
-        if nl:
-            iso["serial_%s_ms" % nme] = round(ms / nl, 4)
-    iso["serial_ms_per_step"] = round(serial_ms, 4)
+    if args.full:
+        fe.reset_kernel_time()
+        fe.set_profiling(True)
+        n_serial = 5
+        torch.cuda.synchronize()
+        ts0 = time.perf_counter()
+        for _ in range(n_serial):
+            if sift:
+                tk = fe.submit_sift_pair_list(pq, pt, d_local[0].data_ptr())
+            else:
+                tk = fe.submit_pair_list(pq, pt, d_local[0].data_ptr())
+            fe.wait_ticket(tk, None)
+        fe.synchronize()
+        serial_ms = (time.perf_counter() - ts0) / n_serial * 1e3
+        fe.set_profiling(False)
+        for nme, kk in (("match", k_match), ("ransac", KERNEL_RANSAC), ("sift_finish", KERNEL_SIFT_FINISH)):
+            ms, nl, _ = fe.kernel_time(kk)
+            if nl:
+                iso["serial_%s_ms" % nme] = round(ms / nl, 4)
+        iso["serial_ms_per_step"] = round(serial_ms, 4)
 
     total_pairs = sum(counts) * args.steps
     value = total_pairs / elapsed
@@ -580,6 +659,7 @@ def main():
     # N = 1: this rank's records; N > 1: what the all-gather of the last step left on rank 0 -- every rank's records, as the
     # consumer of the gather sees them -- against the oracle's sums over the world x 4000 pairs of the global list
     list_entries = None
+    inlier_lists = None
     if gather_on:
         torch.cuda.synchronize()
         if inliers:
@@ -589,6 +669,7 @@ def main():
             parsed = [parse_inlier_stream(g[r], n_pad, totals[r]) for r in range(world)]
             res_all = np.concatenate([parsed[r][0][:counts[r]] for r in range(world)])
             list_entries = int(sum(totals))
+            inlier_lists = [(parsed[r][0][:counts[r]], parsed[r][1]) for r in range(world)]
             # every header's list lies inside its rank's list block, lists follow each other without gaps
             for r in range(world):
                 h = parsed[r][0][:counts[r]]
@@ -599,7 +680,9 @@ def main():
             res_all = np.concatenate([g[r, :counts[r]] for r in range(world)])
     else:
         res_all = res
-    parity = parity_check(("orb", args.depth_noise, world) if default_workload else None, res_all) if len(res_all) else None
+    parity = None
+    if args.full and len(res_all):
+        parity = parity_check(("orb", args.depth_noise, world) if default_workload else None, res_all)
     if parity is not None and gather_on:
         parity["records"] = "gathered on rank 0: %d records of %d ranks" % (len(res_all), world)
         if list_entries is not None:
@@ -629,11 +712,9 @@ def main():
                                          "select_ransac": round(rsc_ovl, 4)},
             "note": "value / ms_per_step: pipelined timed region; serial_*: 5 extra steps with one batch in flight (roofline uses these)",
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res_all, inlier_lists)
         if sift:
-            # configs[3]: the dense contraction.  FLOP per pair = 2 * Nq * Nt * 128 on the bf16 MFMA
-            # (dense peak 2.5 PFLOP/s, MI355X_MICROARCH.md); reported for the MFMA kernel itself.
-            flop = 2.0 * N * N * 128 * n_local
-            tf = flop / (ham_ser * 1e-3) / 1e12 if ham_ser else 0.0
             out = {
                 "metric": "frame-pairs matched+RANSAC/sec, 640x480 SIFT-1000 (128-d float, bf16 MFMA)",
                 "value": round(value, 2), "unit": "frame-pairs/s", "n_gpus": world,
@@ -645,46 +726,24 @@ def main():
                                        "pairs/frame, %d frames" % (N, args.pairs_per_frame, F),
                            "pairs_per_gpu_per_step": n_local, "edge_fraction": round(edge_frac, 4),
                            "mean_ransac_iterations": round(mean_iters, 2)},
-                "roofline": {"bound": "mfma", "kernel": "sift_dot_top2", "achieved": round(tf, 3),
-                             "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 5),
-                             "traffic": None, "flop_per_pair": 2.0 * N * N * 128,
-                             "pairs_per_launch": n_local, "avg_launch_ms": ham_ser, "time_basis": "serial"},
-                "repeats": repeats, "timing": timing,
             }
+            if args.full:
+                # configs[3]: the dense contraction.  FLOP per pair = 2 * Nq * Nt * 128 on the bf16 MFMA
+                # (dense peak 2.5 PFLOP/s, MI355X_MICROARCH.md); reported for the MFMA kernel itself.
+                flop = 2.0 * N * N * 128 * n_local
+                tf = flop / (ham_ser * 1e-3) / 1e12 if ham_ser else 0.0
+                out.update({
+                    "roofline": {"bound": "mfma", "kernel": "sift_dot_top2", "achieved": round(tf, 3),
+                                 "peak": 2500.0, "unit": "TFLOP/s", "frac": round(tf / 2500.0, 5),
+                                 "traffic": None, "flop_per_pair": 2.0 * N * N * 128,
+                                 "pairs_per_launch": n_local, "avg_launch_ms": ham_ser, "time_basis": "serial"},
+                    "repeats": repeats, "timing": timing,
+                })
             print(json.dumps(out), flush=True)
             fe.close()
             if gather_on:
                 dist.destroy_process_group()
             return
-        dominant = "hamming_nn" if ham_ser >= rsc_ser else "select_ransac"
-        dom_ms, dom_bytes = (ham_ser, b_ham) if dominant == "hamming_nn" else (rsc_ser, b_rsc)
-        achieved = (dom_bytes * n_local) / (dom_ms * 1e-3) / 1e9 if dom_ms else 0.0
-        achieved_pipe = (dom_bytes * n_local) / (ms_per_step * 1e-3) / 1e9
-        pmc, pmc_src = load_pmc()
-        mrf = match_roofline(N, n_local, ham_ser, fe.hamming_mode)
-        roofline = {
-            # the contract's block: ALGORITHMIC bytes of the dominant kernel / its launch time / HBM peak
-            "bound": "hbm", "limiter": "valu_issue", "kernel": dominant, "achieved": round(achieved, 3),
-            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-            "frac_pipelined": round(achieved_pipe / HBM_PEAK_GBS, 6),    # / ms_per_step of the timed region (batches overlap)
-            "traffic": static_traffic(pmc, "orb" if args.depth_noise >= 0.005 else "ransac_heavy", dominant, n_local),
-            "traffic_source": pmc_src,
-            "algorithmic_bytes_per_pair": dom_bytes, "pairs_per_launch": n_local,
-            "avg_launch_ms": round(dom_ms, 4), "time_basis": "serial, HIP events, this run",
-            "step_ms_serial": iso.get("serial_ms_per_step"), "step_ms_pipelined": round(ms_per_step, 4),
-            "pair_path_GBs": round(value / world * b_pair / 1e9, 3),
-            # ---- every kernel family of the line, flat (filled in below as the sub-records run): fraction of ITS roofline and
-            #      the serial launch time the fraction was formed with
-            "match_frac": mrf["frac"] if mrf else None, "match_avg_launch_ms": mrf["avg_launch_ms"] if mrf else None,
-            "match_peak_tflops": mrf["peak"] if mrf and mrf.get("bound") == "mfma" else None,
-        }
-        if plain_elapsed is not None:   # the headline on the library's default launch path (no hipGraph)
-            roofline["default_path_value"] = round(total_pairs / plain_elapsed, 2)
-            roofline["default_path_ms_per_step"] = round(plain_elapsed / args.steps * 1e3, 4)
-        iss = issue_roofline(pmc, pmc_src, "orb" if args.depth_noise >= 0.005 else "ransac_heavy", N, n_local,
-                             ham_ser, rsc_ser, fe.hamming_mode)
-        if (iss.get("stages") or {}).get("select_ransac"):
-            roofline["issue_frac"] = iss["stages"]["select_ransac"]["frac"]
         out = {
             "metric": "frame-pairs matched+RANSAC/sec, 640x480 ORB-1000",
             "value": round(value, 2), "unit": "frame-pairs/s", "n_gpus": world,
@@ -700,15 +759,47 @@ def main():
                        "graph_capture": os.environ.get("RGBDFE_GRAPHS") != "0",
                        "depth_noise_sigma_over_z2": args.depth_noise,
                        "edge_fraction": round(edge_frac, 4), "mean_ransac_iterations": round(mean_iters, 2)},
-            "roofline": roofline,
-            "cpu_baseline": None,
-            "match_roofline": mrf,
-            "issue_roofline": iss,
-            "repeats": repeats, "parity_check": parity,
-            "timing": timing,
         }
-        if world != 1 or args.no_cpu_baseline:
-            del out["cpu_baseline"]
+        if args.full:
+            dominant = "hamming_nn" if ham_ser >= rsc_ser else "select_ransac"
+            dom_ms, dom_bytes = (ham_ser, b_ham) if dominant == "hamming_nn" else (rsc_ser, b_rsc)
+            achieved = (dom_bytes * n_local) / (dom_ms * 1e-3) / 1e9 if dom_ms else 0.0
+            achieved_pipe = (dom_bytes * n_local) / (ms_per_step * 1e-3) / 1e9
+            pmc, pmc_src = load_pmc()
+            mrf = match_roofline(N, n_local, ham_ser, fe.hamming_mode)
+            roofline = {
+                # the contract's block: ALGORITHMIC bytes of the dominant kernel / its launch time / HBM peak
+                "bound": "hbm", "limiter": "valu_issue", "kernel": dominant, "achieved": round(achieved, 3),
+                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                "frac_pipelined": round(achieved_pipe / HBM_PEAK_GBS, 6),    # / ms_per_step of the timed region (batches overlap)
+                "traffic": static_traffic(pmc, "orb" if args.depth_noise >= 0.005 else "ransac_heavy", dominant, n_local),
+                "traffic_source": pmc_src,
+                "algorithmic_bytes_per_pair": dom_bytes, "pairs_per_launch": n_local,
+                "avg_launch_ms": round(dom_ms, 4), "time_basis": "serial, HIP events, this run",
+                "step_ms_serial": iso.get("serial_ms_per_step"), "step_ms_pipelined": round(ms_per_step, 4),
+                "pair_path_GBs": round(value / world * b_pair / 1e9, 3),
+                # ---- every kernel family of the line, flat (filled in below as the sub-records run): fraction of ITS roofline and
+                #      the serial launch time the fraction was formed with
+                "match_frac": mrf["frac"] if mrf else None, "match_avg_launch_ms": mrf["avg_launch_ms"] if mrf else None,
+                "match_peak_tflops": mrf["peak"] if mrf and mrf.get("bound") == "mfma" else None,
+            }
+            if plain_elapsed is not None:   # the headline on the library's default launch path (no hipGraph)
+                roofline["default_path_value"] = round(total_pairs / plain_elapsed, 2)
+                roofline["default_path_ms_per_step"] = round(plain_elapsed / args.steps * 1e3, 4)
+            iss = issue_roofline(pmc, pmc_src, "orb" if args.depth_noise >= 0.005 else "ransac_heavy", N, n_local,
+                                 ham_ser, rsc_ser, fe.hamming_mode)
+            if (iss.get("stages") or {}).get("select_ransac"):
+                roofline["issue_frac"] = iss["stages"]["select_ransac"]["frac"]
+            out.update({
+                "roofline": roofline,
+                "cpu_baseline": None,
+                "match_roofline": mrf,
+                "issue_roofline": iss,
+                "repeats": repeats, "parity_check": parity,
+                "timing": timing,
+            })
+            if world != 1 or args.no_cpu_baseline:
+                del out["cpu_baseline"]
         if gather_on:
             per_step = gather_bytes_timed / max(gathers_timed, 1)
             out["gather"] = {"payload_option": args.gather,
@@ -729,7 +820,7 @@ def main():
                              "distinct_devices": len({d.split(" ", 2)[2] for d in rank_devices}) if rank_devices else None,
                              "transport": "RCCL ncclAllGather via torch.distributed (nccl backend)" if backend == "nccl"
                                           else "host tensors (%s; test mode)" % backend}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             fe.close()
             fe = None
             try:
@@ -787,7 +878,7 @@ def main():
         head("heavy", out.get("ransac_heavy"), (("ms_per_step", ("ms_per_step",)), ("serial_stage_ms", ("serial_stage_ms", "select_ransac")),
                                                 ("issue_frac", ("issue_roofline", "stages", "select_ransac", "frac")),
                                                 ("traffic", ("roofline", "traffic"))))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(seq, pq, pt, SEED, 1e-4, args.cpu_seconds)
             ref = cpu_reference_code(seq, pq, pt, SEED, 1e-4, 5.0)
             if ref is not None:

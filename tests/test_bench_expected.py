@@ -57,6 +57,57 @@ def test_aggregates_read_full_and_compact_records_alike():
     assert bench.pair_aggregates(c) == want
 
 
+def _random_records(n, seed):
+    """RESULT_DTYPE records with random bytes everywhere -- also past n_all, where the device leaves the lists unspecified."""
+    rng = np.random.default_rng(seed)
+    r = np.zeros(n, RESULT_DTYPE)
+    r.view(np.uint8)[:] = rng.integers(0, 256, r.nbytes, dtype=np.uint8)
+    r["n_all"] = rng.integers(0, 321, n)
+    r["rmse"], r["info_scale"] = rng.random(n), rng.random(n)
+    r["trafo"] = rng.standard_normal((n, 16))
+    bits = rng.integers(0, 2, (n, 320)).astype(np.uint8)
+    r["inlier_mask"] = np.packbits(bits, axis=1, bitorder="little").view("<u8")
+    r["n_inl"] = (bits * (np.arange(320)[None, :] < r["n_all"][:, None])).sum(1)
+    return r
+
+
+def test_dump_outputs_writes_the_records_as_a_caller_reads_them(tmp_path):
+    """--dump-outputs: float32 / float64 files only; list entries past a record's length and the padding are not written, so
+    two builds compare equal exactly when the records a caller reads are equal; the inlier-stream form of the same records
+    (the N > 1 gather payload) dumps the same header fields and, per record, the inlier matches in mask order."""
+    from rgbdslam_v2_amd._lib import inlier_stream_of
+    r = _random_records(60, 1)
+    names = bench.dump_outputs(str(tmp_path / "full"), r)
+    d = {k: np.load(tmp_path / "full" / (k + ".npy")) for k in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and "pad0" not in d
+    assert np.array_equal(d["id1"], r["id1"]) and np.array_equal(d["trafo"], r["trafo"])
+    assert np.array_equal(d["info_scale"], r["info_scale"]) and d["all_q"].shape == (60, 320)
+    r2 = r.copy()
+    r2["all_q"][np.arange(320)[None, :] >= r2["n_all"][:, None]] ^= 0x5A5A     # what lies past n_all is not an output
+    r2["pad0"] ^= 1
+    names2 = bench.dump_outputs(str(tmp_path / "full2"), r2)
+    assert names2 == names and all(np.array_equal(d[k], np.load(tmp_path / "full2" / (k + ".npy"))) for k in names)
+    hdr, lst = inlier_stream_of(r, 60)
+    bench.dump_outputs(str(tmp_path / "stream"), hdr, [(hdr, lst)])
+    q = np.load(tmp_path / "stream" / "inlier_q_row.npy")
+    for i in range(60):
+        want = d["all_q"][i][d["inlier_mask"][i] > 0]
+        assert np.array_equal(q[i, :len(want)], want) and not q[i, len(want):].any()
+    for k in ("id1", "id2", "n_all", "n_inl", "rmse", "trafo", "info_scale", "real_iterations"):
+        assert np.array_equal(np.load(tmp_path / "stream" / (k + ".npy")), d[k]), k
+
+
+def test_dump_outputs_samples_records_above_64_mb(tmp_path):
+    r = np.tile(_random_records(50, 2), 300)            # 15000 records: ~77 MB as float arrays
+    names = bench.dump_outputs(str(tmp_path), r)
+    total = sum((tmp_path / (k + ".npy")).stat().st_size for k in names)
+    rows = np.load(tmp_path / "sample_rows.npy").astype(np.int64)
+    assert total <= 64 << 20 and 0 < len(rows) < len(r) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "id1.npy"), r["id1"][rows])
+    bench.dump_outputs(str(tmp_path / "again"), r)       # seeded: the same rows every time
+    assert np.array_equal(np.load(tmp_path / "again" / "sample_rows.npy"), rows)
+
+
 def test_a_sample_of_the_constants_is_rederived_by_the_oracle():
     """The first 300 pairs of the world-2 global pair list: the oracle's sums over them are reproducible here in a second
     (the whole file takes three minutes: tools/make_bench_expected.py), and the shard a rank owns is every world-th pair."""

@@ -9,7 +9,7 @@ i=0
 for setting in "$@"; do
   i=$((i+1)); [ "$setting" = "-" ] && setting=""
   for noise in $NOISES; do
-    env $setting timeout 300 python bench.py --steps 20 --warmup 25 --no-extras --no-cpu-baseline --depth-noise $noise > $O/s${i}_n${noise}_$rep.json 2> $O/s${i}_n${noise}_$rep.err
+    env $setting timeout 300 python bench.py --full --steps 20 --warmup 25 --no-extras --no-cpu-baseline --depth-noise $noise > $O/s${i}_n${noise}_$rep.json 2> $O/s${i}_n${noise}_$rep.err
     python - <<PY
 import json
 try:

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for tag in "$@"; do
   LIBF=$PWD/rgbdslam_v2_amd/librgbdfe_$tag.so; [ "$tag" = base ] && LIBF=$PWD/rgbdslam_v2_amd/librgbdfe.so
   for noise in $NOISES; do
-    RGBDFE_LIB=$LIBF timeout 300 python bench.py --steps 20 --warmup 25 --no-extras --no-cpu-baseline --depth-noise $noise > $O/${tag}_n${noise}_$rep.json 2> $O/${tag}_n${noise}_$rep.err
+    RGBDFE_LIB=$LIBF timeout 300 python bench.py --full --steps 20 --warmup 25 --no-extras --no-cpu-baseline --depth-noise $noise > $O/${tag}_n${noise}_$rep.json 2> $O/${tag}_n${noise}_$rep.err
     python - <<PY
 import json
 try:

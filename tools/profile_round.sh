@@ -19,7 +19,7 @@ WL=${*:-orb orb_serial heavy heavy_serial sift sift_serial detect_640x480_orb100
 REPO=$PWD
 ROOT=$REPO/gpurun_out/prof_$TAG
 export TMPDIR=/tmp
-B="python $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+B="python $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
 SQ2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
 MF="SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"
@@ -45,7 +45,7 @@ for W in $WL; do
       CONFIG=$([ $W = sift_serial ] && echo sift || echo orb) NOISE=$([ $W = heavy_serial ] && echo 0.002 || echo 0.01) GRAFT_REPO_ROOT=$REPO bash tools/trace_serial.sh > $ROOT/$W/last_batch.txt 2>&1
       rm -rf $ROOT/$W/trace; mkdir -p $ROOT/$W/trace; cp -r $REPO/gpurun_out/trace_serial/* $ROOT/$W/trace/ 2>/dev/null;;
     heavy) run_passes heavy "$B --depth-noise 0.002" fetch write sq sq2 mfma; python tools/summarize_prof.py $ROOT/heavy > $ROOT/heavy/summary.txt 2>&1;;
-    sift)  run_passes sift "python $REPO/bench.py --config sift --frames 100 --steps 5 --warmup 1" fetch write mfma; python tools/summarize_prof.py $ROOT/sift > $ROOT/sift/summary.txt 2>&1;;
+    sift)  run_passes sift "python $REPO/bench.py --full --config sift --frames 100 --steps 5 --warmup 1" fetch write mfma; python tools/summarize_prof.py $ROOT/sift > $ROOT/sift/summary.txt 2>&1;;
     detect_640x480_orb1000)  run_passes $W "python $REPO/tools/detect_workload.py orb 640 480 1000 112 2" fetch write;;
     detect_1280x960_orb4000) run_passes $W "python $REPO/tools/detect_workload.py orb 1280 960 4000 56 2" fetch write;;
     sift_extract_640x480)    run_passes $W "python $REPO/tools/detect_workload.py sift_batch 640 480 0 32 3" fetch write;;

@@ -1,6 +1,6 @@
 set -u
 REPO=$PWD; OUT=$REPO/gpurun_out/prof_sift2; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_LDS --output-format csv -d $OUT/pmc -o p -- python $REPO/bench.py --config sift --steps 3 --warmup 1 > $OUT/b.json 2> $OUT/err.txt
+rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_LDS --output-format csv -d $OUT/pmc -o p -- python $REPO/bench.py --full --config sift --steps 3 --warmup 1 > $OUT/b.json 2> $OUT/err.txt
 cd $REPO
 python - <<PY
 import csv, glob, collections

@@ -5,7 +5,7 @@ O=gpurun_out/${1:-r04_ab}; mkdir -p $O
 timeout 900 python -m pytest tests -q -m gpu -x > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 $O/pytest_gpu.log
 for noise in 0.01 0.002; do
 for split in 1 0; do
-  RGBDFE_RANSAC_SPLIT=$split timeout 300 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline --depth-noise $noise > $O/bench_n${noise}_s$split.json 2> $O/bench_n${noise}_s$split.err
+  RGBDFE_RANSAC_SPLIT=$split timeout 300 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline --depth-noise $noise > $O/bench_n${noise}_s$split.json 2> $O/bench_n${noise}_s$split.err
   echo "noise $noise split $split rc=$?"
   python - <<PY
 import json
