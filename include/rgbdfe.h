@@ -555,7 +555,8 @@ int rgbdfe_detect_describe_cloud(rgbdfe_ctx* ctx, const uint8_t* gray, const uin
                                  uint8_t* descriptors, float* xyz1, int32_t* n_out);
 /* pieces, for A/B against cv::ORB: detect() of one image with a fixed FAST threshold (no grid,
  * feature_adjuster.cpp:94) and compute() for given keypoints (may drop border keypoints and
- * regroups them by octave, like cv::ORB::compute). */
+ * regroups them by octave, like cv::ORB::compute).  rgbdfe_orb_detect returns RGBDFE_ERR_CAPACITY with *n_out = the number
+ * of keypoints (none written) when `capacity` rows are too few. */
 int rgbdfe_orb_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
                       int32_t fast_threshold, rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
 int rgbdfe_orb_compute(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int32_t cols,

@@ -57,9 +57,9 @@ int rgbdfe_orb_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
   std::vector<std::vector<KpOut>> out(1);
   if (rc == RGBDFE_OK) rc = ctx->orb.detect_pass({1}, {fast_threshold}, out, ctx->stream, err);
   if (rc != RGBDFE_OK) return fail(ctx, rc, err);
-  if ((int)out[0].size() > capacity) out[0].resize((size_t)capacity);
-  kp_to_abi(out[0], keypoints);
   *n_out = (int32_t)out[0].size();
+  if ((int)out[0].size() > capacity) return fail(ctx, RGBDFE_ERR_CAPACITY, "more ORB keypoints than the output array holds");
+  kp_to_abi(out[0], keypoints);
   return RGBDFE_OK;
 }
 

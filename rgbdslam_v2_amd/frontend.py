@@ -436,7 +436,8 @@ class FrontEnd:
             return [(kp[f, : cnt[f]].copy(), desc[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy()) for f in range(n)]
 
     def orb_detect(self, gray, mask, fast_threshold, capacity=60000):
-        """cv::ORB::create(10000,1.2,8,15,0,2,HARRIS,31,thr)->detect(gray, kps, mask) (feature_adjuster.cpp:94)."""
+        """cv::ORB::create(10000,1.2,8,15,0,2,HARRIS,31,thr)->detect(gray, kps, mask) (feature_adjuster.cpp:94).
+        Raises RgbdfeError (RGBDFE_ERR_CAPACITY) when more than `capacity` keypoints are found."""
         gray = np.ascontiguousarray(gray, np.uint8)
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         kp = np.zeros(capacity, _lib.KEYPOINT_DTYPE)
