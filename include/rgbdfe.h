@@ -591,6 +591,29 @@ int rgbdfe_sift_describe(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int
 int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, int32_t rows, int32_t cols,
                              int32_t max_keypoints, int32_t out_stride, rgbdfe_keypoint* keypoints, float* desc128,
                              int32_t* n_out);
+/* Node::Node's SIFTGPU branch for a run of frames (node.cpp:147-176, 695-769, 1557-1571), straight into resident nodes: the
+ * SIFTGPU counterpart of rgbdfe_detect_describe_batch_nodes.  Frame f's node equals what rgbdfe_sift_detect (or the batch),
+ * then rgbdfe_sift_node_features(..., max_keypoints, use_root_sift) -- rgbdfe_sift_node_features_min_depth with kp_size =
+ * the keypoints' size under rgbdfe_set_feature_min_depth(ctx, 1) -- then rgbdfe_upload_float_node(node_ids[f],
+ * feature_descriptors, 128, xyz1, n) give: kind 2 (the FLANN branch, rgbdfe_match_flann_pair_list), same rows, same bits.
+ * The descriptors and points stay on the device from the extraction to the slabs; depth[f] is a rows x cols float image.
+ * max_keypoints serves both as SiftGPU's "-tc2" limit and as projectTo3DSiftGPU's cut (the first max_keypoints survivors in
+ * list order, :748), as in the reference; it must lie in [1, the context's max_keypoints] (RGBDFE_ERR_INVALID_ARG).
+ * node_ids is required: a negative id means no node for that frame, an id may appear once.  The node table follows
+ * rgbdfe_detect_describe_batch_nodes: free slots are checked for the whole batch before any work (each fresh id counts once),
+ * a frame without features that have depth becomes an empty node (n = 0), an existing id -- of any kind -- is rewritten in
+ * place after the pair lanes that may read it have finished.
+ * Host outputs, each optional (NULL: not written; all three NULL: no descriptor crosses to the host): keypoints = the kept
+ * keypoints (feature_locations_2d_ after the erase and the cut, fields as rgbdfe_sift_detect reports them), xyz1 = 4 floats
+ * per point, feature_descriptors = 128 floats per row; frame f's rows start at row f * out_stride.  n_out[f] is always
+ * written; RGBDFE_ERR_CAPACITY when a frame keeps more than out_stride rows and a host output was asked for (n_out is
+ * complete, the nodes and the other frames' rows are valid). */
+int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray,
+                                   const float* const* depth, int32_t rows, int32_t cols,
+                                   double fx, double fy, double cx, double cy, double depth_scaling,
+                                   int32_t max_keypoints, int32_t use_root_sift, const int32_t* node_ids,
+                                   int32_t out_stride, rgbdfe_keypoint* keypoints, float* xyz1,
+                                   float* feature_descriptors, int32_t* n_out);
 /* stage access for parity tests: the pyramid geometry of the latest frame, one Gaussian plane (octave index from 0, level
  * 0 .. levels-1; padded width x height floats), the keypoint candidates of one (octave, DoG level) as rows of
  * (x, y, extremum sign, dx, dy, ds) in list order, before the feature-count limit */

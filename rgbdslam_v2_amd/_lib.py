@@ -329,6 +329,9 @@ def load():
     L.rgbdfe_sift_describe.argtypes = [ctx, vp, i32, i32, vp, i32, vp]
     L.rgbdfe_sift_detect_batch.restype = C.c_int
     L.rgbdfe_sift_detect_batch.argtypes = [ctx, i32, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.rgbdfe_sift_detect_batch_nodes.restype = C.c_int
+    L.rgbdfe_sift_detect_batch_nodes.argtypes = [ctx, i32, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                 C.c_double, i32, i32, vp, i32, vp, vp, vp, vp]
     L.rgbdfe_sift_geometry.restype = C.c_int
     L.rgbdfe_sift_geometry.argtypes = [ctx] + [C.POINTER(i32)] * 4
     L.rgbdfe_sift_debug_plane.restype = C.c_int
@@ -384,4 +387,5 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_match_flann_pair_list", "rgbdfe_upload_node_keypoints",
     "rgbdfe_match_pair_list_allgather_compact", "rgbdfe_pack_compact", "rgbdfe_sizeof_compact_result",
     "rgbdfe_group_submit_us", "rgbdfe_sift_detect", "rgbdfe_sift_detect_batch", "rgbdfe_sift_describe", "rgbdfe_sift_geometry", "rgbdfe_sift_debug_plane", "rgbdfe_sift_debug_candidates",
+    "rgbdfe_sift_detect_batch_nodes",
 ]

@@ -85,8 +85,10 @@ void rgbdfe_destroy(rgbdfe_ctx* ctx) {
   // every stream this context has work on -- not the device: another context's thread may be capturing a hipGraph
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& ln : ctx->lanes) if (ln.stream) (void)hipStreamSynchronize(ln.stream);
-  for (hipStream_t st : {ctx->orb_upload_stream, ctx->orb_compute_stream, ctx->sift_stream1, ctx->sift_stream2, ctx->sift_stream3})
+  for (hipStream_t st : {ctx->orb_upload_stream, ctx->orb_compute_stream, ctx->sift_stream1, ctx->sift_stream2, ctx->sift_stream3,
+                        ctx->sn.depth_stream})
     if (st) (void)hipStreamSynchronize(st);
+  sift_nodes_release(ctx);
   drain_pending(ctx);
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   for (auto& ge : ctx->graphs) { (void)hipGraphExecDestroy(ge.exec); (void)hipGraphDestroy(ge.graph); }

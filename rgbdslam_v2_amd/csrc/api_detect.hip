@@ -1,6 +1,8 @@
 // api_detect.hip -- the feature path: ORB detect / describe (single calls, super-frames), SIFT extraction
 // (one of the host-side translation units of librgbdfe.so; shared declarations: rgbdfe_host.h)
 #include <chrono>
+#include <future>
+#include <unordered_set>
 
 #include "rgbdfe_host.h"
 
@@ -242,6 +244,256 @@ int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* c
             (int)n_frames, now() - t_call, t_step[0], t_step[1], t_step[2], t_step[3], t_step[4],
             ctx->sift.stage_us + ctx->sift2.stage_us + ctx->sift3.stage_us - stage0);
   if (overflow) return fail(ctx, RGBDFE_ERR_CAPACITY, "more SIFT features in a frame than out_stride rows");
+  return RGBDFE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SIFTGPU front end for a recorded run: detect -> projectTo3DSiftGPU -> RootSIFT -> resident node
+// ---------------------------------------------------------------------------------------------
+void sift_nodes_release(rgbdfe_ctx* ctx) {
+  rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
+  for (void* p : {(void*)sn.d_depth, (void*)sn.d_n, (void*)sn.d_xyz_out, (void*)sn.d_feat_out, (void*)sn.d_kept_out})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)sn.h_depth, (void*)sn.h_n, (void*)sn.h_xyz_out, (void*)sn.h_feat_out, (void*)sn.h_kept_out})
+    if (p) (void)hipHostFree(p);
+  for (hipEvent_t e : sn.depth_done) if (e) (void)hipEventDestroy(e);
+  if (sn.depth_stream) (void)hipStreamDestroy(sn.depth_stream);
+  sn = rgbdfe_ctx::SiftNodeBufs{};
+}
+
+// the buffers of rgbdfe_sift_detect_batch_nodes for frames of `plane` pixels (reallocated when the size changes); the host-output
+// rows are allocated with the first call that asks for them
+static int sift_nodes_prepare(rgbdfe_ctx* ctx, size_t plane, bool host_out) {
+  rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
+  constexpr size_t S = 3 * (size_t)kSiftNodeFramesMax;
+  const size_t rows = S * (size_t)ctx->cfg.max_keypoints;
+  if (sn.plane != plane) {
+    if (sn.depth_stream) HIP_TRY(ctx, hipStreamSynchronize(sn.depth_stream));
+    if (sn.d_depth) (void)hipFree(sn.d_depth);
+    if (sn.h_depth) (void)hipHostFree(sn.h_depth);
+    sn.d_depth = nullptr; sn.h_depth = nullptr; sn.plane = 0;
+    if (hipMalloc((void**)&sn.d_depth, S * plane * 4) != hipSuccess ||
+        hipHostMalloc((void**)&sn.h_depth, S * plane * 4, hipHostMallocDefault) != hipSuccess)
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "SIFT node depth staging");
+    sn.plane = plane;
+  }
+  if (!sn.d_n) {
+    if (hipMalloc((void**)&sn.d_n, S * 4) != hipSuccess || hipHostMalloc((void**)&sn.h_n, S * 4, hipHostMallocDefault) != hipSuccess)
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "SIFT node counts");
+    HIP_TRY(ctx, create_side_stream(&sn.depth_stream, -1));   // uploads: behind everything else
+    for (hipEvent_t& e : sn.depth_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (host_out && !sn.d_xyz_out) {
+    if (hipMalloc((void**)&sn.d_xyz_out, rows * 16) != hipSuccess || hipMalloc((void**)&sn.d_feat_out, rows * 512) != hipSuccess ||
+        hipMalloc((void**)&sn.d_kept_out, rows * 4) != hipSuccess ||
+        hipHostMalloc((void**)&sn.h_xyz_out, rows * 16, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&sn.h_feat_out, rows * 512, hipHostMallocDefault) != hipSuccess ||
+        hipHostMalloc((void**)&sn.h_kept_out, rows * 4, hipHostMallocDefault) != hipSuccess)
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "SIFT node output rows");
+  }
+  return RGBDFE_OK;
+}
+
+// Node::Node's SIFTGPU branch (node.cpp:147-176, 695-769, 1557-1571) for a run of frames, node by node into the slabs: the
+// chunk pipeline of rgbdfe_sift_detect_batch, with the descriptor launch writing device memory only and one sift_nodes launch
+// per chunk behind it (sift_nodes.hip).  The depth images of a chunk are staged by a helper thread and copied on a stream of
+// their own while the chunk is extracted; the node launch waits for them by an event.  The host reads the chunk's node counts
+// (and the host outputs, when asked for) once, after the wait it does for the chunk's keypoints anyway.
+int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const float* const* depth,
+                                   int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling,
+                                   int32_t max_keypoints, int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride,
+                                   rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out) {
+  if (!ctx || n_frames < 0 || rows < 1 || cols < 1 || out_stride < 0 ||
+      (n_frames > 0 && (!gray || !depth || !node_ids || !n_out)))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  if (max_keypoints < 1 || max_keypoints > ctx->cfg.max_keypoints)
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "max_keypoints must lie in [1, the context's max_keypoints (node rows)]");
+  for (int32_t f = 0; f < n_frames; ++f)
+    if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
+  {
+    std::unordered_set<int32_t> seen;
+    for (int32_t f = 0; f < n_frames; ++f)
+      if (node_ids[f] >= 0 && !seen.insert(node_ids[f]).second) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
+  if (n_frames == 0) return RGBDFE_OK;
+  const bool host_out = keypoints || xyz1 || feature_descriptors;
+  int rc = ensure_sift(ctx);
+  if (rc == RGBDFE_OK) rc = sift_nodes_prepare(ctx, (size_t)rows * (size_t)cols, host_out);
+  if (rc != RGBDFE_OK) return rc;
+  // the node table, all-or-nothing on capacity as rgbdfe_detect_describe_batch_nodes: every fresh id takes a slot (a frame
+  // without features becomes an empty node), checked before any work; existing nodes are rewritten in place once the pair
+  // lanes that may read them have finished
+  std::vector<int64_t> slot_of((size_t)n_frames, -1);
+  {
+    bool overwrite = false;
+    size_t fresh = 0;
+    for (int32_t f = 0; f < n_frames; ++f) {
+      if (node_ids[f] < 0) continue;
+      if (ctx->nodes.count(node_ids[f]) != 0) overwrite = true;
+      else ++fresh;
+    }
+    if (fresh > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
+    if (overwrite)
+      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+    for (int32_t f = 0; f < n_frames; ++f) {
+      if (node_ids[f] < 0) continue;
+      auto it = ctx->nodes.find(node_ids[f]);
+      if (it != ctx->nodes.end()) { slot_of[(size_t)f] = it->second.slot; continue; }
+      const uint32_t slot = ctx->free_slots.back();
+      ctx->free_slots.pop_back();
+      ctx->nodes[node_ids[f]] = NodeEntry{slot, 0u, 2u, 0u};   // registered before anything can fail: no slot goes missing
+      slot_of[(size_t)f] = slot;
+    }
+  }
+  rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
+  constexpr int B = SiftExtractor::kMaxBatch, D = 3;
+  static_assert(B == kSiftNodeFramesMax, "a chunk is one node launch");
+  const int32_t n_chunks = (n_frames + B - 1) / B;
+  const size_t plane = sn.plane, mk = (size_t)ctx->cfg.max_keypoints;
+  SiftExtractor* ex[D] = {&ctx->sift, &ctx->sift2, &ctx->sift3};
+  if (n_chunks > 1 && !ctx->sift_stream3) {
+    if (!ctx->sift_stream1) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream1, +1));
+    if (!ctx->sift_stream2) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream2, +1));
+    HIP_TRY(ctx, create_side_stream(&ctx->sift_stream3, +1));
+  }
+  hipStream_t st[D] = {ctx->sift_stream1 ? ctx->sift_stream1 : ctx->stream, ctx->sift_stream2 ? ctx->sift_stream2 : ctx->stream,
+                       ctx->sift_stream3 ? ctx->sift_stream3 : ctx->stream};
+  struct DeviceDescriptors {   // the extractors hand their descriptors to the node launch for the length of this call
+    SiftExtractor** ex;
+    DeviceDescriptors(SiftExtractor** e) : ex(e) { for (int i = 0; i < D; ++i) ex[i]->desc_device = true; }
+    ~DeviceDescriptors() { for (int i = 0; i < D; ++i) ex[i]->desc_device = false; }
+  } device_descriptors(ex);
+  std::vector<SiftKey> keys[D][B];
+  const float* desc[D][B];
+  bool overflow = false;
+  std::string err;
+  auto count_of = [&](int32_t c) { return std::min<int32_t>(B, n_frames - c * B); };
+  const int dev = ctx->cfg.device_id;
+  // helper thread per chunk: the caller's depth images -> pinned set c % D -> device set c % D (depth stream), then the set's
+  // event.  The set's previous user, chunk c - D, has been waited for (finish_outputs) before chunk c is begun.
+  std::future<hipError_t> staged[D];
+  auto stage_depth = [&](int32_t c) {
+    const int set = c % D, nf = count_of(c);
+    const float* const* src = depth + (size_t)c * B;
+    float* h = sn.h_depth + (size_t)set * B * plane;
+    float* d = sn.d_depth + (size_t)set * B * plane;
+    hipStream_t ds = sn.depth_stream;
+    hipEvent_t ev = sn.depth_done[set];
+    staged[set] = std::async(std::launch::async, [=]() -> hipError_t {
+      hipError_t e = hipSetDevice(dev);
+      for (int k = 0; k < nf; ++k) memcpy(h + (size_t)k * plane, src[k], plane * 4);
+      if (e == hipSuccess) e = hipMemcpyAsync(d, h, (size_t)nf * plane * 4, hipMemcpyHostToDevice, ds);
+      if (e == hipSuccess) e = hipEventRecord(ev, ds);
+      return e;
+    });
+  };
+  auto begin = [&](int32_t c) -> int {
+    stage_depth(c);
+    return ex[c % D]->begin_batch(gray + (size_t)c * B, count_of(c), rows, cols, st[c % D], err);
+  };
+  // behind chunk c's descriptor launch: its node launch, then the counts (and host outputs) on their way back
+  auto launch_nodes = [&](int32_t c) -> int {
+    const int set = c % D, nf = count_of(c);
+    const hipError_t se = staged[set].get();
+    if (se != hipSuccess) { err = std::string("depth staging: ") + hipGetErrorString(se); return RGBDFE_ERR_HIP; }
+    hipStream_t s = st[set];
+    if (hipStreamWaitEvent(s, sn.depth_done[set], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
+    const SiftExtractor& X = *ex[set];
+    SiftNodeChunk ch{};
+    ch.n_frames = nf;
+    ch.n_out = sn.d_n + (size_t)set * B;
+    for (int k = 0; k < nf; ++k) {
+      const int32_t f = c * B + k;
+      const SiftExtractor::FrameState& F = X.fs[(size_t)k];
+      SiftNodeFrame& o = ch.frame[k];
+      o.n_keys = X.fin_grand2 > 0 ? F.total : 0;
+      if (o.n_keys > 0) {
+        o.keys = X.d_keys + F.base;
+        o.desc = reinterpret_cast<const float2*>(X.d_desc + (size_t)F.base * 128);
+      }
+      o.depth = sn.d_depth + ((size_t)set * B + k) * plane;
+      if (slot_of[(size_t)f] >= 0) {
+        const size_t row0 = (size_t)slot_of[(size_t)f] * mk;
+        o.xyz = ctx->d_xyz + row0;
+        o.feat = reinterpret_cast<float2*>(ctx->d_sift_f32 + row0 * 128);
+      }
+      const size_t r0 = ((size_t)set * B + k) * mk;
+      if (xyz1) o.xyz_out = sn.d_xyz_out + r0;
+      if (feature_descriptors) o.feat_out = reinterpret_cast<float2*>(sn.d_feat_out + r0 * 128);
+      if (keypoints) o.kept_out = sn.d_kept_out + r0;
+    }
+    launch_sift_nodes(ch, rows, cols, (float)(1. / fx), (float)(1. / fy), (float)cx, (float)cy, depth_scaling, max_keypoints,
+                      ctx->feature_min_depth, use_root_sift != 0, s);
+    hipError_t e = hipGetLastError();
+    const size_t r0 = (size_t)set * B * mk, nr = (size_t)nf * mk;
+    if (e == hipSuccess) e = hipMemcpyAsync(sn.h_n + (size_t)set * B, ch.n_out, (size_t)nf * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && xyz1) e = hipMemcpyAsync(sn.h_xyz_out + r0, sn.d_xyz_out + r0, nr * 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && feature_descriptors)
+      e = hipMemcpyAsync(sn.h_feat_out + r0 * 128, sn.d_feat_out + r0 * 128, nr * 512, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && keypoints) e = hipMemcpyAsync(sn.h_kept_out + r0, sn.d_kept_out + r0, nr * 4, hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) { err = std::string("SIFT node launch: ") + hipGetErrorString(e); return RGBDFE_ERR_HIP; }
+    return RGBDFE_OK;
+  };
+  // after chunk c's wait: the node table and the caller's arrays
+  auto finish_nodes = [&](int32_t c) -> int {
+    const int set = c % D, nf = count_of(c);
+    if (hipStreamSynchronize(st[set]) != hipSuccess) { err = "hipStreamSynchronize"; return RGBDFE_ERR_HIP; }
+    for (int k = 0; k < nf; ++k) {
+      const int32_t f = c * B + k;
+      const int32_t n = sn.h_n[(size_t)set * B + k];
+      n_out[f] = n;
+      if (node_ids[f] >= 0) ctx->nodes[node_ids[f]] = NodeEntry{(uint32_t)slot_of[(size_t)f], (uint32_t)n, 2u, 0u};
+      if (!host_out) continue;
+      if (n > out_stride) { overflow = true; continue; }
+      const size_t r0 = ((size_t)set * B + k) * mk;
+      if (keypoints) {
+        const std::vector<SiftKey>& K = keys[set][k];
+        const int32_t* kept = sn.h_kept_out + r0;
+        rgbdfe_keypoint* kp = keypoints + (size_t)f * out_stride;
+        for (int32_t i = 0; i < n; ++i) {
+          const SiftKey& q = K[(size_t)kept[i]];
+          kp[i].x = q.x;
+          kp[i].y = q.y;
+          kp[i].size = (float)(12.0 * q.s);
+          kp[i].angle = (float)(q.o * 180.0 / 3.1415927);
+          kp[i].response = 0.f;
+          kp[i].octave = 0;
+        }
+      }
+      if (xyz1 && n > 0) memcpy(xyz1 + (size_t)f * out_stride * 4, sn.h_xyz_out + r0, (size_t)n * 16);
+      if (feature_descriptors && n > 0)
+        memcpy(feature_descriptors + (size_t)f * out_stride * 128, sn.h_feat_out + r0 * 128, (size_t)n * 512);
+    }
+    return RGBDFE_OK;
+  };
+  auto drain = [&]() {
+    for (int i = 0; i < D; ++i) if (staged[i].valid()) (void)staged[i].get();
+    for (int i = 0; i < D; ++i) (void)hipStreamSynchronize(st[i]);
+    (void)hipStreamSynchronize(sn.depth_stream);
+  };
+#define SIFT_NODE_STEP(expr)                                       \
+  do {                                                             \
+    const int rc_ = (expr);                                        \
+    if (rc_ != RGBDFE_OK) { drain(); return fail(ctx, rc_, err); } \
+  } while (0)
+  // the order of rgbdfe_sift_detect_batch, with the node launch behind each descriptor launch and the node table / outputs of
+  // chunk c - 1 where that function copies its outputs out
+  for (int32_t c = 0; c < std::min<int32_t>(2, n_chunks); ++c) SIFT_NODE_STEP(begin(c));
+  SIFT_NODE_STEP(ex[0]->finish_orientations(max_keypoints, st[0], err));
+  for (int32_t c = 0; c < n_chunks; ++c) {
+    SIFT_NODE_STEP(ex[c % D]->finish_descriptors(st[c % D], err));
+    SIFT_NODE_STEP(launch_nodes(c));
+    if (c + 2 < n_chunks) SIFT_NODE_STEP(begin(c + 2));
+    if (c >= 1) SIFT_NODE_STEP(finish_nodes(c - 1));
+    if (c + 1 < n_chunks) SIFT_NODE_STEP(ex[(c + 1) % D]->finish_orientations(max_keypoints, st[(c + 1) % D], err));
+    SIFT_NODE_STEP(ex[c % D]->finish_outputs(keys[c % D], desc[c % D], st[c % D], err));
+  }
+  SIFT_NODE_STEP(finish_nodes(n_chunks - 1));
+#undef SIFT_NODE_STEP
+  if (overflow) return fail(ctx, RGBDFE_ERR_CAPACITY, "more kept SIFT features in a frame than out_stride rows");
   return RGBDFE_OK;
 }
 

@@ -249,7 +249,7 @@ int rgbdfe_synchronize(rgbdfe_ctx* ctx) {
 }
 
 
-static int ensure_sift(rgbdfe_ctx* ctx) {
+int ensure_sift(rgbdfe_ctx* ctx) {
   if (ctx->sift_ready) return RGBDFE_OK;
   const size_t rows = (size_t)ctx->cfg.max_nodes * (size_t)ctx->cfg.max_keypoints + 16;
   const size_t np = (size_t)ctx->cfg.max_pairs_per_batch, mk = (size_t)ctx->cfg.max_keypoints;

@@ -16,6 +16,7 @@
 // sift_pack_kernel re-packs the used descriptors densely (:752-766) and applies
 // squareroot_descriptor_space (src/node.cpp:1557-1571, RootSIFT) to the feature_descriptors_ copy.
 #include "rgbdfe_internal.h"
+#include "project3d_device.h"
 
 namespace rgbdfe {
 
@@ -40,13 +41,9 @@ __global__ __launch_bounds__(256) void project_to_3d_kernel(
       const bool bad = !TRUNC && (px >= (float)cols || px < 0.f || py >= (float)rows || py < 0.f ||
                                   __builtin_isnan(px) || __builtin_isnan(py));
       if (TRUNC) {
-        // v_cvt_i32_f32 truncates, saturates and maps NaN to 0
-        int r = (int)py, c = (int)px;
-        r = min(max(r, 0), rows - 1);
-        c = min(max(c, 0), cols - 1);
         // z_gathered: getMinDepthInNeighborhood's value under "use_feature_min_depth" (:731) instead of the pixel (:733)
-        const float zraw = z_gathered ? z_gathered[i] : depth[(size_t)r * (size_t)cols + (size_t)c];
-        Z = (float)((double)zraw * depth_scaling);
+        const float zraw = z_gathered ? z_gathered[i] : depth[sift_depth_index(px, py, rows, cols)];
+        Z = scaled_depth(zraw, depth_scaling);
         keep = !__builtin_isnan(Z);  // :736
       } else if (!bad) {
         // depth.at<float>(round(y), round(x)): std::round = half away from zero (node.cpp:942).
@@ -57,7 +54,7 @@ __global__ __launch_bounds__(256) void project_to_3d_kernel(
         c = c >= cols ? cols - 1 : c;
         // z_gathered: the caller has looked depth(round(y), round(x)) up already (the image stays on the host)
         const float zraw = z_gathered ? z_gathered[i] : depth[(size_t)r * (size_t)cols + (size_t)c];
-        Z = (float)((double)zraw * depth_scaling);
+        Z = scaled_depth(zraw, depth_scaling);
         keep = !__builtin_isnan(Z);  // node.cpp:947
       }
     }
@@ -71,13 +68,7 @@ __global__ __launch_bounds__(256) void project_to_3d_kernel(
     const uint32_t chunk_total = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
     const uint32_t pos = off + rank;
     if (keep && pos < (uint32_t)max_keypoints) {
-      // backProject (misc2.h:62-64): ((u - cx) * z) * fxinv in float
-      float4 o;
-      o.x = (px - cx) * Z * fxinv;
-      o.y = (py - cy) * Z * fyinv;
-      o.z = Z;
-      o.w = 1.0f;  // node.cpp:955
-      xyz1[pos] = o;
+      xyz1[pos] = back_project(px, py, Z, cx, cy, fxinv, fyinv);  // misc2.h:62-64, node.cpp:955
       kept_idx[pos] = i;
     }
     base += chunk_total;
@@ -134,10 +125,8 @@ __global__ __launch_bounds__(256) void project_cloud_kernel(const float2* __rest
 }
 
 // One wave per kept keypoint: row y of `raw` (siftgpu_descriptors) and of `feat`
-// (feature_descriptors_) <- descriptors_in[kept_idx[y]]; `feat` is RootSIFT-normalised when asked.
-// Lane l holds columns 2l, 2l+1.  The L1 norm follows cv::reduce's float accumulation order
-// (a0 over columns 0,2,..,124,126,127; a1 over 1,3,..,125; a0 + a1): a strictly sequential chain, fed
-// by v_readlane so that the whole wave computes it uniformly.
+// (feature_descriptors_) <- descriptors_in[kept_idx[y]]; `feat` is RootSIFT-normalised when asked
+// (root_sift_row, project3d_device.h: lane l holds columns 2l, 2l+1).
 __global__ __launch_bounds__(256) void sift_pack_kernel(const float2* __restrict__ in,
                                                        const int32_t* __restrict__ kept_idx,
                                                        const int32_t* __restrict__ n_ptr, int root_sift,
@@ -148,26 +137,7 @@ __global__ __launch_bounds__(256) void sift_pack_kernel(const float2* __restrict
   const float2 v = in[(size_t)kept_idx[y] * 64 + lane];
   raw[(size_t)y * 64 + lane] = v;
   if (!feat) return;
-  float2 o = v;
-  if (root_sift) {
-    o.x = fabsf(v.x);  // cv::abs (:1561)
-    o.y = fabsf(v.y);
-    auto lane_f = [](float f, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f), l)); };
-    float a0 = lane_f(o.x, 0), a1 = lane_f(o.y, 0);
-#pragma unroll
-    for (int l = 1; l < 63; ++l) {
-      a0 = a0 + lane_f(o.x, l);
-      a1 = a1 + lane_f(o.y, l);
-    }
-    a0 = a0 + lane_f(o.x, 63);
-    a0 = a0 + lane_f(o.y, 63);
-    const float sum = a0 + a1;
-    if (sum != 0.0f) {  // :1565
-      o.x = sqrtf(o.x / sum);  // :1569
-      o.y = sqrtf(o.y / sum);
-    }
-  }
-  feat[(size_t)y * 64 + lane] = o;
+  feat[(size_t)y * 64 + lane] = root_sift ? root_sift_row(v) : v;
 }
 
 void launch_project_to_3d(const float* kp_xy, int n_kp, const float* depth, int rows, int cols,
@@ -256,23 +226,8 @@ __global__ __launch_bounds__(64) void min_depth_kernel(const float* __restrict__
                                                        int rows, int cols, float* __restrict__ z_out) {
   const int i = blockIdx.x;
   if (i >= n_kp) return;
-  const float cx = kp[3 * i], cy = kp[3 * i + 1], diameter = kp[3 * i + 2];
-  const int radius = (int)((diameter - 1) / 2);
-  int top = (int)(cy - (float)radius); top = top < 0 ? 0 : top;
-  int left = (int)(cx - (float)radius); left = left < 0 ? 0 : left;
-  int bot = (int)(cy + (float)radius); bot = bot > rows ? rows : bot;
-  int right = (int)(cx + (float)radius); right = right > cols ? cols : right;
-  float mn = 3.402823466e+38f;
-  bool found = false;
-  for (int r = top; r < bot; ++r)
-    for (int c = left + (int)threadIdx.x; c < right; c += 64) {
-      const float v = depth[(size_t)r * (size_t)cols + (size_t)c];
-      if (v < mn) { mn = v; found = true; }  // NaN never compares less: skipped, as in cv::minMaxLoc
-    }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) mn = fminf(mn, __shfl_xor(mn, d));  // no NaN among the partial minima
-  found = __ballot(found) != 0ull;
-  if (threadIdx.x == 0) z_out[i] = (found && mn != 0.0f) ? mn : __builtin_nanf("");
+  const float z = min_depth_in_neighbourhood(kp[3 * i], kp[3 * i + 1], kp[3 * i + 2], depth, rows, cols, (int)threadIdx.x);
+  if (threadIdx.x == 0) z_out[i] = z;
 }
 
 // kp: n_kp x (x, y, size); z_out[i] = getMinDepthInNeighborhood(depth, (x, y), size)

@@ -284,6 +284,17 @@ struct rgbdfe_ctx {
   SiftExtractor sift2, sift3;   // rgbdfe_sift_detect_batch rotates over three extractors (three chunks in flight)
   hipStream_t sift_stream1 = nullptr, sift_stream2 = nullptr, sift_stream3 = nullptr;
   SiftExtractor sift;  // rgbdfe_sift_detect (sift_extract.hip)
+  // rgbdfe_sift_detect_batch_nodes: per chunk set (3 of them, 8 frames each) the pinned staging and the device copy of the
+  // depth images, the node counts and the host-output rows (8 x max_keypoints); the depth copies go on a stream of their own
+  struct SiftNodeBufs {
+    size_t plane = 0;                                   // floats per depth image
+    float* h_depth = nullptr; float* d_depth = nullptr;
+    int32_t* d_n = nullptr; int32_t* h_n = nullptr;
+    float4* d_xyz_out = nullptr; float* d_feat_out = nullptr; int32_t* d_kept_out = nullptr;
+    float4* h_xyz_out = nullptr; float* h_feat_out = nullptr; int32_t* h_kept_out = nullptr;
+    hipStream_t depth_stream = nullptr;
+    hipEvent_t depth_done[3] = {};
+  } sn;
   int orb_max_keypoints = 0;  // 0 = detector not configured yet
   std::unordered_map<int32_t, NodeEntry> nodes;
   std::unordered_map<int32_t, CloudEntry> clouds;
@@ -346,6 +357,8 @@ namespace impl {
 int upload_nodes_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const uint8_t* const* desc,
                         const float* const* xyz1, const int32_t* counts);
 void ensure_detector(rgbdfe_ctx* ctx);
+int ensure_sift(rgbdfe_ctx* ctx);                 // the float / bf16 node slabs (api_pairs.hip)
+void sift_nodes_release(rgbdfe_ctx* ctx);        // rgbdfe_ctx::sn (api_detect.hip)
 void kp_to_abi(const std::vector<KpOut>& v, rgbdfe_keypoint* out);
 void rgbdfe_default_config(rgbdfe_config* cfg);
 int rgbdfe_create(const rgbdfe_config* cfg, rgbdfe_ctx** out);
@@ -380,6 +393,7 @@ int rgbdfe_orb_compute(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int32
 int rgbdfe_sift_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* /*mask*/, int32_t rows, int32_t cols, int32_t max_keypoints, rgbdfe_keypoint* keypoints, float* desc128, int32_t capacity, int32_t* n_out);
 int rgbdfe_sift_describe(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int32_t cols, rgbdfe_keypoint* keypoints, int32_t n, float* desc128);
 int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, int32_t rows, int32_t cols, int32_t max_keypoints, int32_t out_stride, rgbdfe_keypoint* keypoints, float* desc128, int32_t* n_out);
+int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t max_keypoints, int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride, rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out);
 int rgbdfe_sift_debug_plane(rgbdfe_ctx* ctx, int32_t octave, int32_t level, float* out, int32_t capacity_floats, int32_t* w, int32_t* h);
 int rgbdfe_sift_debug_candidates(rgbdfe_ctx* ctx, int32_t octave, int32_t dog_level, float* out, int32_t capacity_rows, int32_t* n);
 int rgbdfe_sift_geometry(rgbdfe_ctx* ctx, int32_t* octave_min, int32_t* octave_num, int32_t* levels, int32_t* dog_levels);

@@ -255,4 +255,16 @@ void launch_emm(const EmmJob* jobs, int n_jobs, int ch, int cw, int skip_step, d
 void launch_sift_pack(const float* desc_in, const int32_t* kept_idx, const int32_t* n_ptr, int max_rows,
                       bool root_sift, float* raw, float* feat, hipStream_t stream);
 
+// rgbdfe_sift_detect_batch_nodes (sift_nodes.hip): frame f of a chunk -- its kept SIFT features (x, y, KeyPoint::size, -) and
+// unnormalised descriptors, its depth image -- becomes the rows [0, n_out[f]) of the destinations: the node's slab rows
+// (xyz / feat; NULL for a frame without a node) and the chunk's host-output rows (*_out; NULL when nothing goes back)
+constexpr int kSiftNodeFramesMax = 8;   // = SiftExtractor::kMaxBatch
+struct SiftNodeFrame {
+  const float4* keys; const float2* desc; const float* depth; int n_keys;
+  float4* xyz; float2* feat; float4* xyz_out; float2* feat_out; int32_t* kept_out;
+};
+struct SiftNodeChunk { int n_frames; int32_t* n_out; SiftNodeFrame frame[kSiftNodeFramesMax]; };
+void launch_sift_nodes(const SiftNodeChunk& ch, int rows, int cols, float fxinv, float fyinv, float cx, float cy,
+                       double depth_scaling, int max_keypoints, bool min_depth, bool root_sift, hipStream_t stream);
+
 }  // namespace rgbdfe

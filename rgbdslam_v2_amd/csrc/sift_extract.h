@@ -90,6 +90,10 @@ struct SiftExtractor {
   float4* d_feat = nullptr; size_t feat_cap = 0;       // feature list (x, y, scale, packed / final orientation)
   float* d_desc = nullptr; size_t desc_cap = 0;
   float* h_desc = nullptr; size_t h_desc_cap = 0;      // pinned: the descriptors of the latest call (128 floats per feature)
+  // desc_device (rgbdfe_sift_detect_batch_nodes): the descriptor launch writes d_desc and nothing goes to the host; the kept
+  // features (x, y, KeyPoint::size = 12 * scale, 0) are uploaded to d_keys, frame f's at row fs[f].base, beside them
+  bool desc_device = false;
+  float4* d_keys = nullptr; float4* h_keys = nullptr; size_t keys_cap = 0;
   int* h_counts = nullptr;                             // pinned: per-level totals, 64 per frame
   float* h_stage = nullptr; size_t stage_floats = 0;   // pinned staging for lists (all frames of a batch)
   // The three read-backs of a batch -- the levels' candidate counts, the oriented features, the descriptors -- are stored into

@@ -336,6 +336,9 @@ void SiftExtractor::release() {
   if (h_jobs) (void)hipHostFree(h_jobs);
   if (h_desc) (void)hipHostFree(h_desc);
   h_desc = nullptr; h_desc_cap = 0;
+  if (d_keys) (void)hipFree(d_keys);
+  if (h_keys) (void)hipHostFree(h_keys);
+  d_keys = nullptr; h_keys = nullptr; keys_cap = 0;
   d_gray = nullptr; d_input = d_up = d_planes = nullptr; d_flags = nullptr; d_rowcnt = d_rowoff = d_lvltot = nullptr;
   d_levels = nullptr; d_cand = nullptr; d_feat = nullptr; d_desc = nullptr; h_counts = nullptr; h_stage = nullptr;
   d_jobs = nullptr; h_jobs = nullptr;
@@ -668,10 +671,27 @@ int SiftExtractor::finish_descriptors(hipStream_t s, std::string& err) {
     SIFT_HIP(hipHostMalloc((void**)&h_desc, (size_t)grand2 * 128 * 4 * 2, hipHostMallocDefault));
     h_desc_cap = (size_t)grand2 * 128 * 2;
   }
+  if (desc_device) {   // the kept features' image coordinates and sizes, as rgbdfe_sift_detect reports them, for the node launch
+    if ((size_t)grand2 > keys_cap) {
+      if (d_keys) (void)hipFree(d_keys);
+      if (h_keys) (void)hipHostFree(h_keys);
+      d_keys = nullptr; h_keys = nullptr; keys_cap = 0;
+      SIFT_HIP(hipMalloc((void**)&d_keys, (size_t)grand2 * 2 * sizeof(float4)));
+      SIFT_HIP(hipHostMalloc((void**)&h_keys, (size_t)grand2 * 2 * sizeof(float4), hipHostMallocDefault));
+      keys_cap = (size_t)grand2 * 2;
+    }
+    for (int f = 0; f < nf; ++f) {
+      const FrameState& F = fs[(size_t)f];
+      const float* k = F.keybuf.data() + (size_t)F.erased * 4;
+      for (int i = 0; i < F.total; ++i, k += 4) h_keys[(size_t)F.base + i] = make_float4(k[0], k[1], (float)(12.0 * k[2]), 0.f);
+    }
+    SIFT_HIP(hipMemcpyAsync(d_keys, h_keys, (size_t)grand2 * sizeof(float4), hipMemcpyHostToDevice, s));
+  }
+  const bool to_host = host_write && !desc_device;
   hipLaunchKernelGGL(sift_descriptor_kernel, dim3(max_total2, NF), dim3(64), 0, s, static_cast<const LevelJobs*>(d_jobs), d_feat,
-                     (float2*)(host_write ? h_desc : d_desc), 3.0f);
+                     (float2*)(to_host ? h_desc : d_desc), 3.0f);
   SIFT_HIP(hipGetLastError());
-  if (!host_write) SIFT_HIP(hipMemcpyAsync(h_desc, d_desc, (size_t)grand2 * 128 * 4, hipMemcpyDeviceToHost, s));
+  if (!host_write && !desc_device) SIFT_HIP(hipMemcpyAsync(h_desc, d_desc, (size_t)grand2 * 128 * 4, hipMemcpyDeviceToHost, s));
   fin_grand2 = grand2;
   return RGBDFE_OK;
 }

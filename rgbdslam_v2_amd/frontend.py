@@ -523,6 +523,56 @@ class FrontEnd:
                 return [(kp[f, : cnt[f]], desc[f, : cnt[f]]) for f in range(n)]
             return [(kp[f, : cnt[f]].copy(), desc[f, : cnt[f]].copy()) for f in range(n)]
 
+    def sift_detect_batch_nodes(self, grays, depths, fx, fy, cx, cy, node_ids, depth_scaling=1.0, max_keypoints: int = 1000,
+                                use_root_sift=True, return_features=True, copy=True):
+        """rgbdfe_sift_detect_batch_nodes: Node::Node's SIFTGPU branch over a run of frames of one size -- SIFT extraction,
+        projectTo3DSiftGPU and RootSIFT -- with frame f's features becoming the resident float node node_ids[f] (a negative
+        id: no node) without passing through the host.  The nodes equal sift_detect_batch -> sift_node_features ->
+        upload_float_node.  Returns per frame (keypoints, xyz1, feature_descriptors), or only the counts (an int32 array)
+        when return_features is False (no host outputs: nothing but the counts comes back).  copy=False returns views of
+        output arrays this object keeps and reuses for the next call of the same shape."""
+        n = len(grays)
+        if n == 0:
+            return [] if return_features else np.zeros(0, np.int32)
+        g = [np.ascontiguousarray(x, np.uint8) for x in grays]
+        d = [np.ascontiguousarray(x, np.float32) for x in depths]
+        rows, cols = g[0].shape
+        if len(d) != n:
+            raise ValueError("one depth image per frame")
+        for a in g + d:
+            if a.shape != (rows, cols):
+                raise ValueError("all frames of a batch share one size")
+        ids = np.ascontiguousarray(node_ids, np.int32)
+        if ids.shape != (n,):
+            raise ValueError("node_ids must hold one id per frame")
+        max_keypoints = int(max_keypoints)
+        vp = C.c_void_p * n
+        pg = vp(*[x.ctypes.data for x in g])
+        pd = vp(*[x.ctypes.data for x in d])
+        cnt = np.zeros(n, np.int32)
+        if not return_features:
+            self._check(self._L.rgbdfe_sift_detect_batch_nodes(
+                self._ctx, n, C.cast(pg, C.c_void_p), C.cast(pd, C.c_void_p), rows, cols, fx, fy, cx, cy, depth_scaling,
+                max_keypoints, int(bool(use_root_sift)), ids.ctypes.data, 0, None, None, None, cnt.ctypes.data))
+            return cnt
+        stride = max(max_keypoints, 1)   # a frame keeps at most max_keypoints rows
+        cache = getattr(self, "_sift_nodes_out", None)
+        if copy or cache is None or cache[0] != (n, stride):
+            kp = np.zeros((n, stride), _lib.KEYPOINT_DTYPE)
+            xyz = np.zeros((n, stride, 4), np.float32)
+            feat = np.zeros((n, stride, 128), np.float32)
+            if not copy:
+                self._sift_nodes_out = ((n, stride), kp, xyz, feat)
+        else:
+            kp, xyz, feat = cache[1], cache[2], cache[3]
+        self._check(self._L.rgbdfe_sift_detect_batch_nodes(
+            self._ctx, n, C.cast(pg, C.c_void_p), C.cast(pd, C.c_void_p), rows, cols, fx, fy, cx, cy, depth_scaling,
+            max_keypoints, int(bool(use_root_sift)), ids.ctypes.data, stride, kp.ctypes.data, xyz.ctypes.data,
+            feat.ctypes.data, cnt.ctypes.data))
+        if not copy:
+            return [(kp[f, : cnt[f]], xyz[f, : cnt[f]], feat[f, : cnt[f]]) for f in range(n)]
+        return [(kp[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy(), feat[f, : cnt[f]].copy()) for f in range(n)]
+
     def sift_geometry(self):
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.rgbdfe_sift_geometry(self._ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
