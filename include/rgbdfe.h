@@ -491,16 +491,28 @@ int rgbdfe_place_recognition_batch(rgbdfe_ctx* ctx, const int32_t* query_ids, in
  * max_keypoints entries: keypoints, descriptors (32 bytes each), xyz1 (4 floats each). */
 typedef struct {
   float x, y;       /* cv::KeyPoint::pt (level-0 pixel coordinates) */
-  float size;       /* 31 * scale of the octave */
-  float angle;      /* degrees (cv::fastAtan2 of the intensity centroid) */
-  float response;   /* Harris response */
-  int32_t octave;   /* pyramid level */
+  float size;       /* 31 * scale of the octave; FAST: 7 */
+  float angle;      /* degrees (cv::fastAtan2 of the intensity centroid); FAST: -1 */
+  float response;   /* Harris response; FAST: the FAST score (cornerScore) */
+  int32_t octave;   /* pyramid level; FAST: 0 */
 } rgbdfe_keypoint;
 /* parameter_server.cpp:83,87,89; resets the per-cell thresholds */
 int rgbdfe_detector_configure(rgbdfe_ctx* ctx, int32_t max_keypoints, int32_t grid_resolution,
                               int32_t adjuster_max_iterations);
 /* the current per-cell FAST thresholds (grid_resolution^2 doubles) */
 int rgbdfe_detector_thresholds(rgbdfe_ctx* ctx, double* thresholds, int32_t* n_cells);
+/* Parameter "feature_detector_type" (parameter_server.cpp, createDetector in features.cpp:63-113) with the default ORB
+ * extractor.  RGBDFE_DETECTOR_ORB (the default): the grid of adaptive cv::ORB detectors.  RGBDFE_DETECTOR_FAST: the same grid
+ * and threshold adaptation around cv::FastFeatureDetector (DetectorAdjuster("FAST", 20), feature_adjuster.cpp:88-91):
+ * keypoints of size 7, angle -1, response = FAST score, octave 0, then Node::Node's ORB-extractor steps (removeDepthless,
+ * retainBest(max_keypoints), cv::ORB::compute, projectTo3D; node.cpp:183-210).  rgbdfe_detect_describe, _batch, _batch_nodes,
+ * _cloud and rgbdfe_detector_thresholds follow the type; the detector configuration (rgbdfe_detector_configure) is shared.
+ * Setting a type resets the per-cell thresholds to 20, as a fresh createDetector does; an unknown type is
+ * RGBDFE_ERR_INVALID_ARG.  Under FAST, rgbdfe_detect_describe_batch_nodes accepts NULL keypoints / descriptors / xyz1 (any
+ * of them): those host outputs are not written, the nodes are. */
+#define RGBDFE_DETECTOR_ORB 0
+#define RGBDFE_DETECTOR_FAST 1
+int rgbdfe_set_detector_type(rgbdfe_ctx* ctx, int32_t type);
 /* "use_feature_min_depth" (parameter_server.cpp:90, default off): a keypoint's depth is the nearest valid depth in its
  * neighbourhood (getMinDepthInNeighborhood, misc.cpp:774-793) instead of the pixel under it -- in removeDepthless
  * (node.cpp:82) and projectTo3D (:940).  rgbdfe_set_feature_min_depth switches rgbdfe_detect_describe(_batch) over;
@@ -561,6 +573,12 @@ int rgbdfe_orb_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
                       int32_t fast_threshold, rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
 int rgbdfe_orb_compute(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int32_t cols,
                        rgbdfe_keypoint* keypoints, int32_t n, uint8_t* descriptors, int32_t* n_out);
+/* A/B piece of the FAST detector: cv::FastFeatureDetector::create(threshold)->detect(gray, keypoints, mask) on one whole
+ * image (no grid): FAST-9/16 with non-maximum suppression, then KeyPointsFilter::runByPixelsMask; keypoints in raster order,
+ * size 7, angle -1, response = score, octave 0.  threshold is clamped to [0, 255] as cv::FAST does.  Returns
+ * RGBDFE_ERR_CAPACITY with *n_out = the number of keypoints (none written) when `capacity` rows are too few. */
+int rgbdfe_fast_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
+                       int32_t threshold, rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
 
 /* ---- SIFT extraction (feature_detector_type / feature_extractor_type == "SIFTGPU") ---------------------------------
  * rgbdfe_sift_detect replaces SiftGPUWrapper::detect (sift_gpu_wrapper.h:49, sift_gpu_wrapper.cpp:113-167; called from

@@ -98,6 +98,28 @@ class FrontEnd {
   }
   rgbdfe_ctx* get() const { return ctx_.get(); }
 
+  // Parameter "feature_detector_type" with the default ORB extractor (createDetector, features.cpp:63-113): "ORB" or "FAST";
+  // the per-cell thresholds restart at 20.  Throws on any other type.
+  void setDetectorType(const std::string& type) {
+    const int t = type == "FAST" ? RGBDFE_DETECTOR_FAST : type == "ORB" ? RGBDFE_DETECTOR_ORB : -1;
+    const int st = rgbdfe_set_detector_type(ctx_.get(), t);
+    if (st != RGBDFE_OK) throw std::runtime_error("feature_detector_type " + type + ": " + rgbdfe_status_string(st));
+  }
+  // cv::FastFeatureDetector::create(threshold)->detect(image, keypoints, mask) on the whole image (the A/B piece of the FAST
+  // detector); mask may be nullptr.  Throws on failure.
+  std::vector<rgbdfe_keypoint> fastDetect(const uint8_t* gray, const uint8_t* mask, int rows, int cols, int threshold) const {
+    std::vector<rgbdfe_keypoint> kp(4096);
+    int32_t n = 0;
+    int st = rgbdfe_fast_detect(ctx_.get(), gray, mask, rows, cols, threshold, kp.data(), (int32_t)kp.size(), &n);
+    if (st == RGBDFE_ERR_CAPACITY) {  // n = the number found: once more with room for all of them
+      kp.resize((size_t)n);
+      st = rgbdfe_fast_detect(ctx_.get(), gray, mask, rows, cols, threshold, kp.data(), (int32_t)kp.size(), &n);
+    }
+    if (st != RGBDFE_OK) throw std::runtime_error(std::string("rgbdfe_fast_detect: ") + rgbdfe_last_error(ctx_.get()));
+    kp.resize((size_t)n);
+    return kp;
+  }
+
  private:
   std::shared_ptr<rgbdfe_ctx> ctx_;
 };

@@ -217,6 +217,10 @@ def load():
                                          C.c_double, C.c_double, vp, vp, vp, C.POINTER(i32)]
     L.rgbdfe_orb_detect.restype = C.c_int
     L.rgbdfe_orb_detect.argtypes = [ctx, vp, vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
+    L.rgbdfe_set_detector_type.restype = C.c_int
+    L.rgbdfe_set_detector_type.argtypes = [ctx, i32]
+    L.rgbdfe_fast_detect.restype = C.c_int
+    L.rgbdfe_fast_detect.argtypes = [ctx, vp, vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
     L.rgbdfe_orb_compute.restype = C.c_int
     L.rgbdfe_orb_compute.argtypes = [ctx, vp, i32, i32, vp, i32, vp, C.POINTER(i32)]
     L.rgbdfe_synchronize.restype = C.c_int
@@ -387,5 +391,5 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_match_flann_pair_list", "rgbdfe_upload_node_keypoints",
     "rgbdfe_match_pair_list_allgather_compact", "rgbdfe_pack_compact", "rgbdfe_sizeof_compact_result",
     "rgbdfe_group_submit_us", "rgbdfe_sift_detect", "rgbdfe_sift_detect_batch", "rgbdfe_sift_describe", "rgbdfe_sift_geometry", "rgbdfe_sift_debug_plane", "rgbdfe_sift_debug_candidates",
-    "rgbdfe_sift_detect_batch_nodes",
+    "rgbdfe_sift_detect_batch_nodes", "rgbdfe_set_detector_type", "rgbdfe_fast_detect",
 ]

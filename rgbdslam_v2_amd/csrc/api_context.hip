@@ -86,7 +86,7 @@ void rgbdfe_destroy(rgbdfe_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& ln : ctx->lanes) if (ln.stream) (void)hipStreamSynchronize(ln.stream);
   for (hipStream_t st : {ctx->orb_upload_stream, ctx->orb_compute_stream, ctx->sift_stream1, ctx->sift_stream2, ctx->sift_stream3,
-                        ctx->sn.depth_stream})
+                        ctx->sn.depth_stream, ctx->fast.st, ctx->fast.up})
     if (st) (void)hipStreamSynchronize(st);
   sift_nodes_release(ctx);
   drain_pending(ctx);

@@ -758,6 +758,9 @@ int rgbdfe_detect_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* 
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   ensure_detector(ctx);
+  if (ctx->detector_type == RGBDFE_DETECTOR_FAST)  // feature_detector_type "FAST" (api_fast.hip)
+    return fast_detect_describe(ctx, 1, &gray, &mask, &depth, rows, cols, fx, fy, cx, cy, depth_scaling, ctx->orb_max_keypoints,
+                                keypoints, descriptors, xyz1, n_out, nullptr);
   DetectFrame fr;
   fr.ctx = ctx; fr.gray = gray; fr.mask = mask; fr.depth = depth; fr.rows = rows; fr.cols = cols;
   fr.fx = fx; fr.fy = fy; fr.cx = cx; fr.cy = cy; fr.depth_scaling = depth_scaling;
@@ -1177,14 +1180,17 @@ int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_
                                  const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx,
                                  double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints,
                                  uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids) {
-  if (!ctx || n_frames < 0 || (n_frames > 0 && (!gray || !depth || !keypoints || !descriptors || !xyz1 || !n_out)) ||
-      rows < 1 || cols < 1)
+  if (!ctx || n_frames < 0 || (n_frames > 0 && (!gray || !depth || !n_out)) || rows < 1 || cols < 1)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   if (node_ids)
     for (int32_t f = 0; f < n_frames; ++f)
       for (int32_t j = 0; j < f; ++j)
         if (node_ids[f] >= 0 && node_ids[j] == node_ids[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
   std::lock_guard<std::mutex> g(ctx->mu);
+  // (the host outputs may be NULL only where the nodes are the outputs: FAST with node_ids)
+  const bool fast = ctx->detector_type == RGBDFE_DETECTOR_FAST;
+  if (n_frames > 0 && !(fast && node_ids) && (!keypoints || !descriptors || !xyz1))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   ensure_detector(ctx);
   if (n_frames > 0 && out_stride < ctx->orb_max_keypoints)
@@ -1192,6 +1198,9 @@ int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_
   for (int32_t f = 0; f < n_frames; ++f)
     if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
   if (n_frames == 0) return RGBDFE_OK;
+  if (fast)  // feature_detector_type "FAST" (api_fast.hip): its own chunked pipeline, nodes written by its kernels
+    return fast_detect_describe(ctx, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling, out_stride, keypoints,
+                                descriptors, xyz1, n_out, node_ids);
   {  // several frames per launch chain (above) unless switched off or the detector is in a mode only the frame path has
     static const bool super_env = !(getenv("RGBDFE_DETECT_SUPER") && atoi(getenv("RGBDFE_DETECT_SUPER")) == 0);
     if (super_env && n_frames >= 2 && !ctx->feature_min_depth && ctx->orb.grid * ctx->orb.grid * 2 <= 64)

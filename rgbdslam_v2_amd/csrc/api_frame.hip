@@ -341,24 +341,33 @@ int rgbdfe_detect_describe_cloud(rgbdfe_ctx* ctx, const uint8_t* gray, const uin
   OrbWorkspace& orb = ctx->orb;
   const int max_kp = ctx->orb_max_keypoints;
   std::string err;
-  int rc = orb.prepare(cols, rows, true, err);
-  if (rc != RGBDFE_OK) return fail(ctx, rc, err);
-  orb.cell_mask_nonzero.assign((size_t)orb.n_cells, mask ? 0 : 1);
-  if (mask)
-    for (int c = 0; c < orb.n_cells; ++c) {
-      const OrbWorkspace::Cell& ce = orb.cells[c];
-      char nz = 0;
-      for (int y = 0; y < ce.h && !nz; ++y) {
-        const uint8_t* r = mask + (size_t)(ce.y0 + y) * cols + ce.x0;
-        for (int x = 0; x < ce.w; ++x)
-          if (r[x]) { nz = 1; break; }
-      }
-      orb.cell_mask_nonzero[c] = nz;
-    }
-  rc = orb.upload_and_build(gray, mask, ctx->stream, err);
   std::vector<KpOut> kps;
-  if (rc == RGBDFE_OK) rc = orb.grid_detect(kps, ctx->stream, err);
-  if (rc != RGBDFE_OK) return fail(ctx, rc, err);
+  int rc;
+  if (ctx->detector_type == RGBDFE_DETECTOR_FAST) {  // feature_detector_type "FAST": the grid's keypoints from api_fast.hip
+    rc = fast_grid_keypoints(ctx, gray, mask, rows, cols, kps);
+    if (rc != RGBDFE_OK) return rc;
+    rc = orb.prepare(cols, rows, false, err);       // cv::ORB::compute below: the frame image only (octave-0 keypoints)
+    if (rc == RGBDFE_OK) rc = orb.upload_and_build(gray, nullptr, ctx->stream, err);
+    if (rc != RGBDFE_OK) return fail(ctx, rc, err);
+  } else {
+    rc = orb.prepare(cols, rows, true, err);
+    if (rc != RGBDFE_OK) return fail(ctx, rc, err);
+    orb.cell_mask_nonzero.assign((size_t)orb.n_cells, mask ? 0 : 1);
+    if (mask)
+      for (int c = 0; c < orb.n_cells; ++c) {
+        const OrbWorkspace::Cell& ce = orb.cells[c];
+        char nz = 0;
+        for (int y = 0; y < ce.h && !nz; ++y) {
+          const uint8_t* r = mask + (size_t)(ce.y0 + y) * cols + ce.x0;
+          for (int x = 0; x < ce.w; ++x)
+            if (r[x]) { nz = 1; break; }
+        }
+        orb.cell_mask_nonzero[c] = nz;
+      }
+    rc = orb.upload_and_build(gray, mask, ctx->stream, err);
+    if (rc == RGBDFE_OK) rc = orb.grid_detect(kps, ctx->stream, err);
+    if (rc != RGBDFE_OK) return fail(ctx, rc, err);
+  }
   *n_out = 0;
   const int n_det = (int)kps.size();
   std::vector<float> xy((size_t)n_det * 2), pxyz((size_t)n_det * 4);

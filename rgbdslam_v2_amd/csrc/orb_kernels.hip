@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "orb_internal.h"
+#include "fast_device.h"
 
 namespace rgbdfe {
 
@@ -186,40 +187,9 @@ __global__ __launch_bounds__(kPyrThreads) void orb_pyramid_kernel(uint8_t* __res
 // -a0).  So with  P = max_arcs min_{k in arc} d[k]  and  N = max_arcs min_{k in arc} -d[k]  (d = centre - ring):
 //   corner  <=>  max(P, N) > t,      score = max(P, N) - 1.
 // An arc minimum is min3 over three min3's (9 = 3 x 3, v_min3_i32), the maximum over the 16 arcs eight max3's: ~100 integer
-// operations per pixel, no branches, the same integers as the reference's loops.
+// operations per pixel, no branches, the same integers as the reference's loops (fast_arc_score, fast_device.h: shared
+// with the FAST detector of fast_detect.hip).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int min3i(int a, int b, int c) { return min(min(a, b), c); }
-__device__ __forceinline__ int max3i(int a, int b, int c) { return max(max(a, b), c); }
-
-// ptr -> the centre pixel inside an LDS tile of row stride `stride`
-__device__ __forceinline__ int fast_arc_score(const uint8_t* __restrict__ ptr, int stride) {
-  const int v = ptr[0];
-  int d[16];
-  d[0] = v - ptr[3 * stride];       d[1] = v - ptr[1 + 3 * stride];   d[2] = v - ptr[2 + 2 * stride];
-  d[3] = v - ptr[3 + stride];       d[4] = v - ptr[3];                d[5] = v - ptr[3 - stride];
-  d[6] = v - ptr[2 - 2 * stride];   d[7] = v - ptr[1 - 3 * stride];   d[8] = v - ptr[-3 * stride];
-  d[9] = v - ptr[-1 - 3 * stride];  d[10] = v - ptr[-2 - 2 * stride]; d[11] = v - ptr[-3 - stride];
-  d[12] = v - ptr[-3];              d[13] = v - ptr[-3 + stride];     d[14] = v - ptr[-2 + 2 * stride];
-  d[15] = v - ptr[-1 + 3 * stride];
-  int lo3[16], hi3[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    lo3[k] = min3i(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
-    hi3[k] = max3i(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
-  }
-  int P = -256, N = 256;
-#pragma unroll
-  for (int k = 0; k < 16; k += 2) {
-    const int p0 = min3i(lo3[k], lo3[(k + 3) & 15], lo3[(k + 6) & 15]);
-    const int p1 = min3i(lo3[k + 1], lo3[(k + 4) & 15], lo3[(k + 7) & 15]);
-    P = max3i(P, p0, p1);
-    const int n0 = max3i(hi3[k], hi3[(k + 3) & 15], hi3[(k + 6) & 15]);
-    const int n1 = max3i(hi3[k + 1], hi3[(k + 4) & 15], hi3[(k + 7) & 15]);
-    N = min3i(N, n0, n1);
-  }
-  return max(P, -N);
-}
-
 // A workgroup owns 64 x 16 pixels of one (cell, level) image: the source tile with a halo of 4 goes through LDS (unaligned
 // dword loads), the scores of the 66 x 18 pixels around the tile are computed into LDS, and the 3x3 test + mask + border
 // filters run from there -- no score plane leaves the workgroup, only the survivors' scores (sparse byte stores into the plane

@@ -330,6 +330,17 @@ int rgbdfe_detector_configure(rgbdfe_ctx* ctx, int32_t max_keypoints, int32_t gr
   return RGBDFE_FIRST(ctx, impl::rgbdfe_detector_configure(c, max_keypoints, grid_resolution, adjuster_max_iterations));
 }
 
+int rgbdfe_set_detector_type(rgbdfe_ctx* ctx, int32_t type) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_set_detector_type(c, type));
+}
+
+int rgbdfe_fast_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols, int32_t threshold,
+                       rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_fast_detect(c, gray, mask, rows, cols, threshold, keypoints, capacity, n_out));
+}
+
 int rgbdfe_detector_thresholds(rgbdfe_ctx* ctx, double* thresholds, int32_t* n_cells) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;
   return RGBDFE_FIRST(ctx, impl::rgbdfe_detector_thresholds(c, thresholds, n_cells));
@@ -390,7 +401,17 @@ int rgbdfe_detect_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const 
                                                                 depth_scaling, out_stride, keypoints, descriptors, xyz1, n_out,
                                                                 node_ids));
   // several devices behind the handle: the frames are processed on the first one, the nodes go to all of them from the host
-  // outputs (every device holds every node)
+  // outputs (every device holds every node).  FAST takes NULL host outputs: the rows then pass through arrays of this call.
+  std::vector<rgbdfe_keypoint> kp_tmp;
+  std::vector<uint8_t> desc_tmp;
+  std::vector<float> xyz_tmp;
+  if (n_frames > 0 && out_stride > 0 && rgbdfe_device_context(ctx, 0)->detector_type == RGBDFE_DETECTOR_FAST &&
+      (!keypoints || !descriptors || !xyz1)) {
+    const size_t rows_all = (size_t)n_frames * (size_t)out_stride;
+    if (!keypoints) { kp_tmp.resize(rows_all); keypoints = kp_tmp.data(); }
+    if (!descriptors) { desc_tmp.resize(rows_all * 32); descriptors = desc_tmp.data(); }
+    if (!xyz1) { xyz_tmp.resize(rows_all * 4); xyz1 = xyz_tmp.data(); }
+  }
   int rc = RGBDFE_FIRST(ctx, impl::rgbdfe_detect_describe_batch(c, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy,
                                                                 depth_scaling, out_stride, keypoints, descriptors, xyz1, n_out));
   if (rc != RGBDFE_OK) return rc;

@@ -23,6 +23,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "fast_host.h"
 #include "orb_host.h"
 #include "sift_extract.h"
 #include "rgbdfe_internal.h"
@@ -296,6 +297,10 @@ struct rgbdfe_ctx {
     hipEvent_t depth_done[3] = {};
   } sn;
   int orb_max_keypoints = 0;  // 0 = detector not configured yet
+  // feature_detector_type (rgbdfe_set_detector_type): RGBDFE_DETECTOR_ORB or RGBDFE_DETECTOR_FAST.  Both use the detector
+  // configuration and the per-cell thresholds of `orb` (the reference's one detector_ object); FAST runs in `fast`.
+  int32_t detector_type = RGBDFE_DETECTOR_ORB;
+  FastWorkspace fast;
   std::unordered_map<int32_t, NodeEntry> nodes;
   std::unordered_map<int32_t, CloudEntry> clouds;
   double emm_q_lo = 0.0, emm_q_hi = 0.0;  // cdf boundaries 0.001 / 0.999 as arguments of erf
@@ -359,6 +364,14 @@ int upload_nodes_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
 void ensure_detector(rgbdfe_ctx* ctx);
 int ensure_sift(rgbdfe_ctx* ctx);                 // the float / bf16 node slabs (api_pairs.hip)
 void sift_nodes_release(rgbdfe_ctx* ctx);        // rgbdfe_ctx::sn (api_detect.hip)
+// feature_detector_type "FAST" (api_fast.hip): Node::Node's feature path for n_frames frames (the host outputs may be NULL
+// when node_ids is given), and the grid detector's keypoints of one frame alone (the point-cloud path)
+int fast_detect_describe(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
+                         const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy,
+                         double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors,
+                         float* xyz1, int32_t* n_out, const int32_t* node_ids);
+int fast_grid_keypoints(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
+                        std::vector<KpOut>& kps);
 void kp_to_abi(const std::vector<KpOut>& v, rgbdfe_keypoint* out);
 void rgbdfe_default_config(rgbdfe_config* cfg);
 int rgbdfe_create(const rgbdfe_config* cfg, rgbdfe_ctx** out);
@@ -387,6 +400,8 @@ int rgbdfe_match_sift_pair_list(rgbdfe_ctx* ctx, const int32_t* query_ids, const
 int rgbdfe_submit_sift_pair_list(rgbdfe_ctx* ctx, const int32_t* query_ids, const int32_t* train_ids, int32_t n_pairs, void* d_out, void* d_out_dist, int64_t* ticket);
 int rgbdfe_sift_match_nodes(rgbdfe_ctx* ctx, int32_t query_id, int32_t train_id, int32_t* match_q, int32_t* match_t, float* match_dist, int32_t* n_matches);
 int rgbdfe_detector_configure(rgbdfe_ctx* ctx, int32_t max_keypoints, int32_t grid_resolution, int32_t adjuster_max_iterations);
+int rgbdfe_set_detector_type(rgbdfe_ctx* ctx, int32_t type);
+int rgbdfe_fast_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols, int32_t threshold, rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
 int rgbdfe_detector_thresholds(rgbdfe_ctx* ctx, double* thresholds, int32_t* n_cells);
 int rgbdfe_orb_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols, int32_t fast_threshold, rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
 int rgbdfe_orb_compute(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int32_t cols, rgbdfe_keypoint* keypoints, int32_t n, uint8_t* descriptors, int32_t* n_out);

@@ -337,6 +337,28 @@ class FrontEnd:
         self._check(self._L.rgbdfe_detector_configure(self._ctx, max_keypoints, grid_resolution,
                                                       adjuster_max_iterations))
 
+    DETECTOR_TYPES = {"ORB": 0, "FAST": 1}
+
+    def set_detector_type(self, name: str):
+        """Parameter "feature_detector_type" with the default ORB extractor: "ORB" (the default) or "FAST"
+        (rgbdfe_set_detector_type).  detect_describe(_batch), detect_describe_cloud and detector_thresholds follow it;
+        the per-cell thresholds restart at 20, as a fresh createDetector does."""
+        if name not in self.DETECTOR_TYPES:
+            raise ValueError("feature_detector_type must be one of %s" % sorted(self.DETECTOR_TYPES))
+        self._check(self._L.rgbdfe_set_detector_type(self._ctx, self.DETECTOR_TYPES[name]))
+
+    def fast_detect(self, gray, mask, threshold, capacity=60000):
+        """cv::FastFeatureDetector::create(threshold)->detect(gray, kps, mask) on the whole image (no grid).
+        Raises RgbdfeError (RGBDFE_ERR_CAPACITY) when more than `capacity` keypoints are found."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        kp = np.zeros(max(capacity, 1), _lib.KEYPOINT_DTYPE)
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_fast_detect(self._ctx, gray.ctypes.data, None if m is None else m.ctypes.data,
+                                               gray.shape[0], gray.shape[1], threshold, kp.ctypes.data, capacity,
+                                               C.byref(n)))
+        return kp[: n.value].copy()
+
     def detector_thresholds(self):
         t = np.zeros(64, np.float64)
         n = C.c_int32(0)
@@ -386,13 +408,15 @@ class FrontEnd:
             fx, fy, cx, cy, depth_scaling, max_keypoints, kept.ctypes.data, xyz.ctypes.data, C.byref(k)))
         return kept[: k.value].copy(), xyz[: k.value].copy()
 
-    def detect_describe_batch(self, grays, masks, depths, fx, fy, cx, cy, depth_scaling=1.0, node_ids=None, copy=True):
+    def detect_describe_batch(self, grays, masks, depths, fx, fy, cx, cy, depth_scaling=1.0, node_ids=None, copy=True,
+                              host_outputs=True):
         """A run of frames through the same detector state, in order (rgbdfe_detect_describe_batch): the results of
         calling detect_describe frame by frame, with frame k+1's upload overlapped with frame k's detection.
         Returns a list of (keypoints, descriptors, xyz1) per frame.  node_ids: frame f's features also become the resident
         node node_ids[f] (rgbdfe_detect_describe_batch_nodes; a negative id: no node).  copy=False returns views of the
         output arrays this object keeps and reuses for its next call (what an integration with its own buffers does;
-        sift_detect_batch has the same switch): valid until then."""
+        sift_detect_batch has the same switch): valid until then.  host_outputs=False (with node_ids, under the FAST
+        detector): the features go to the nodes only and the per-frame counts are returned."""
         n = len(grays)
         if n == 0:
             return []
@@ -424,9 +448,12 @@ class FrontEnd:
                 ids = np.ascontiguousarray(node_ids, np.int32)
                 if ids.shape != (n,):
                     raise ValueError("node_ids must hold one id per frame")
+                outs = (kp.ctypes.data, desc.ctypes.data, xyz.ctypes.data) if host_outputs else (None, None, None)
                 self._check(self._L.rgbdfe_detect_describe_batch_nodes(
                     self._ctx, n, C.cast(pg, C.c_void_p), C.cast(pm, C.c_void_p), C.cast(pd, C.c_void_p), rows, cols, fx, fy, cx, cy,
-                    depth_scaling, cap, kp.ctypes.data, desc.ctypes.data, xyz.ctypes.data, cnt.ctypes.data, ids.ctypes.data))
+                    depth_scaling, cap, *outs, cnt.ctypes.data, ids.ctypes.data))
+                if not host_outputs:
+                    return cnt.copy()
             else:
                 self._check(self._L.rgbdfe_detect_describe_batch(
                     self._ctx, n, C.cast(pg, C.c_void_p), C.cast(pm, C.c_void_p), C.cast(pd, C.c_void_p), rows, cols, fx, fy, cx, cy,
