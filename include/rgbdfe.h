@@ -632,6 +632,42 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
                                    int32_t max_keypoints, int32_t use_root_sift, const int32_t* node_ids,
                                    int32_t out_stride, rgbdfe_keypoint* keypoints, float* xyz1,
                                    float* feature_descriptors, int32_t* n_out);
+
+/* ---- SIFTGPU descriptors behind the grid detector (feature_detector_type ORB / FAST, feature_extractor_type SIFTGPU) ----
+ * rgbdfe_detect is detector->detect alone (node.cpp:160) for the context's detector type and grid state: the grid-adapted
+ * detector's aggregate (feature_adjuster.cpp:185-317) in aggregate order -- no removeDepthless, no retainBest -- with the
+ * detector's own fields (ORB: size 31 * 1.2^octave, angle, Harris response, octave; FAST: size 7, angle -1, score, octave 0).
+ * The per-cell thresholds advance exactly as rgbdfe_detect_describe advances them on the same frame.  The aggregate never
+ * holds more than max_total = floor(1.5 * max_keypoints) keypoints (keepStrongest(max_total / cells) per cell): a smaller
+ * capacity is RGBDFE_ERR_INVALID_ARG, refused before any state changes. */
+int rgbdfe_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
+                  rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
+/* Node::Node's steps for that setting, one frame (node.cpp:160, 165-176): rgbdfe_detect -> projectTo3D (node.cpp:900-965:
+ * the first max_keypoints keypoints with depth, in aggregate order) -> SiftGPUWrapper::detect with that list
+ * (rgbdfe_sift_describe) -> projectTo3DSiftGPU + RootSIFT under use_root_sift (rgbdfe_sift_node_features).  The same bits as
+ * those calls composed; rgbdfe_set_feature_min_depth switches both depth lookups to the _min_depth forms.  When projectTo3D
+ * keeps no keypoint the wrapper gets an EMPTY list and SiftGPU detects on its own (sift_gpu_wrapper.cpp:133,
+ * SiftPyramid.cpp:154-156): the frame then gets rgbdfe_sift_detect(..., max_keypoints) -> rgbdfe_sift_node_features.
+ * max_keypoints is the detector's (rgbdfe_detector_configure); outputs hold that many rows: keypoints (as the wrapper rebuilds
+ * them: size 12 * scale, angle in degrees, response = octave = 0), xyz1 (4 floats), siftgpu_descriptors and
+ * feature_descriptors (128 floats; feature_descriptors may be NULL). */
+int rgbdfe_detect_sift_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, const float* depth, int32_t rows,
+                                int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling,
+                                int32_t use_root_sift, rgbdfe_keypoint* keypoints, float* xyz1, float* siftgpu_descriptors,
+                                float* feature_descriptors, int32_t* n_out);
+/* A run of frames through the same detector state: n_frames calls of rgbdfe_detect_sift_describe, each followed by
+ * rgbdfe_upload_float_node(node_ids[f], feature_descriptors, 128, xyz1, n) -- kind 2 nodes, what
+ * rgbdfe_match_flann_pair_list reads.  node_ids is required (negative: no node; an id may appear once); the node table follows
+ * rgbdfe_detect_describe_batch_nodes (free slots checked for the whole batch first, a frame without features becomes an empty
+ * node, an existing id is rewritten in place).  mask may be NULL or hold NULL entries; out_stride >= max_keypoints
+ * (RGBDFE_ERR_INVALID_ARG); each host output may be NULL; frame f's rows start at row f * out_stride, n_out[f] of them.
+ * Up to 8 frames share every launch after the detection; with all host outputs NULL no descriptor crosses
+ * PCIe.  Multi-device handles process the frames on the first device and hand the nodes to the others. */
+int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray,
+                                            const uint8_t* const* mask, const float* const* depth, int32_t rows, int32_t cols,
+                                            double fx, double fy, double cx, double cy, double depth_scaling,
+                                            int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride,
+                                            rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out);
 /* stage access for parity tests: the pyramid geometry of the latest frame, one Gaussian plane (octave index from 0, level
  * 0 .. levels-1; padded width x height floats), the keypoint candidates of one (octave, DoG level) as rows of
  * (x, y, extremum sign, dx, dy, ds) in list order, before the feature-count limit */

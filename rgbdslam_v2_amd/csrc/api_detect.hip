@@ -771,6 +771,40 @@ int rgbdfe_detect_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* 
   return rc;
 }
 
+int detect_aggregate(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
+                     std::vector<KpOut>& kps) {
+  if (ctx->detector_type == RGBDFE_DETECTOR_FAST)  // feature_detector_type "FAST" (api_fast.hip)
+    return fast_grid_keypoints(ctx, gray, mask, rows, cols, kps);
+  DetectFrame fr;
+  fr.ctx = ctx; fr.gray = gray; fr.mask = mask; fr.rows = rows; fr.cols = cols;
+  const int rc = fr.detect(false, nullptr);
+  if (rc != RGBDFE_OK) return rc;
+  kps = std::move(fr.kps);
+  return RGBDFE_OK;
+}
+
+// detector->detect alone (node.cpp:160): the grid detector's aggregate (feature_adjuster.cpp:185-317) in aggregate order, with
+// the per-cell thresholds advanced exactly as rgbdfe_detect_describe advances them -- its detection step, stopped before
+// removeDepthless.  keepStrongest(max_total / cells) per cell bounds the aggregate by max_total, so a smaller capacity is
+// refused before the detector's state changes.
+int rgbdfe_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
+                  rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out) {
+  if (!ctx || !gray || rows < 1 || cols < 1 || !keypoints || !n_out) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  ensure_detector(ctx);
+  if (capacity < ctx->orb.max_total)
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "capacity below the aggregate's bound floor(1.5 * max_keypoints)");
+  *n_out = 0;
+  std::vector<KpOut> kps;
+  const int rc = detect_aggregate(ctx, gray, mask, rows, cols, kps);
+  if (rc != RGBDFE_OK) return rc;
+  if ((int64_t)kps.size() > (int64_t)capacity) return fail(ctx, RGBDFE_ERR_INTERNAL, "aggregate larger than max_total");
+  kp_to_abi(kps, keypoints);
+  *n_out = (int32_t)kps.size();
+  return RGBDFE_OK;
+}
+
 // ---- rgbdfe_detect_describe_batch, super-frame form -----------------------------------------------------------------
 constexpr int kSuperFrames = 7;   // frames per super-frame at least (large frames)
 // B = 64 / grid^2 (7 for the 3 x 3 grid) frames share every launch: one upload, one pyramid chain (7 launches), one blur,

@@ -497,6 +497,72 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
   return RGBDFE_OK;
 }
 
+int rgbdfe_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
+                  rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_detect(c, gray, mask, rows, cols, keypoints, capacity, n_out));
+}
+
+int rgbdfe_detect_sift_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, const float* depth, int32_t rows,
+                                int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling,
+                                int32_t use_root_sift, rgbdfe_keypoint* keypoints, float* xyz1, float* siftgpu_descriptors,
+                                float* feature_descriptors, int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_detect_sift_describe(c, gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling,
+                                                             use_root_sift, keypoints, xyz1, siftgpu_descriptors,
+                                                             feature_descriptors, n_out));
+}
+
+int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray,
+                                            const uint8_t* const* mask, const float* const* depth, int32_t rows, int32_t cols,
+                                            double fx, double fy, double cx, double cy, double depth_scaling,
+                                            int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride,
+                                            rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  if (!RGBDFE_IS_GROUP(ctx))
+    return RGBDFE_FIRST(ctx, impl::rgbdfe_detect_sift_describe_batch_nodes(c, n_frames, gray, mask, depth, rows, cols, fx, fy, cx,
+                                                                           cy, depth_scaling, use_root_sift, node_ids, out_stride,
+                                                                           keypoints, xyz1, feature_descriptors, n_out));
+  // several devices behind the handle: the frames are processed on the first one, into its nodes and into host rows of the
+  // detector's max_keypoints per frame (a frame keeps no more); the other devices get the nodes from those rows (every device
+  // holds every node), the caller's arrays get them at out_stride
+  if (n_frames < 0 || (n_frames > 0 && (!node_ids || !n_out)))
+    return guarded(ctx, [&]() -> int { return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments"); });
+  int R = 0;
+  int rc = guarded(ctx, [&]() -> int { R = impl::detector_max_keypoints(ctx->group->children[0]); return RGBDFE_OK; });
+  if (rc != RGBDFE_OK) return rc;
+  if (n_frames > 0 && out_stride < R)
+    return guarded(ctx, [&]() -> int { return fail(ctx, RGBDFE_ERR_INVALID_ARG, "out_stride below the detector's max_keypoints"); });
+  const size_t mk = (size_t)R, nf = (size_t)n_frames;
+  std::vector<rgbdfe_keypoint> kp(keypoints ? nf * mk : 0);
+  std::vector<float> xyz(nf * mk * 4), feat(nf * mk * 128);
+  rc = RGBDFE_FIRST(ctx, impl::rgbdfe_detect_sift_describe_batch_nodes(c, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy,
+                                                                      depth_scaling, use_root_sift, node_ids, R,
+                                                                      keypoints ? kp.data() : nullptr, xyz.data(), feat.data(),
+                                                                      n_out));
+  if (rc != RGBDFE_OK) return rc;
+  rc = guarded(ctx, [&]() -> int {
+    return group_run(ctx, [&](int i) -> int {
+      if (i == 0) return RGBDFE_OK;
+      rgbdfe_ctx* c = ctx->group->children[(size_t)i];
+      for (size_t f = 0; f < nf; ++f) {
+        if (node_ids[f] < 0) continue;
+        const int r = impl::rgbdfe_upload_float_node(c, node_ids[f], feat.data() + f * mk * 128, 128, xyz.data() + f * mk * 4, n_out[f]);
+        if (r != RGBDFE_OK) return r;
+      }
+      return RGBDFE_OK;
+    });
+  });
+  if (rc != RGBDFE_OK) return rc;
+  for (size_t f = 0; f < nf; ++f) {
+    const size_t n = (size_t)n_out[f], o = f * (size_t)out_stride;
+    if (keypoints && n) memcpy(keypoints + o, kp.data() + f * mk, n * sizeof(rgbdfe_keypoint));
+    if (xyz1 && n) memcpy(xyz1 + o * 4, xyz.data() + f * mk * 4, n * 16);
+    if (feature_descriptors && n) memcpy(feature_descriptors + o * 128, feat.data() + f * mk * 128, n * 512);
+  }
+  return RGBDFE_OK;
+}
+
 int rgbdfe_sift_debug_plane(rgbdfe_ctx* ctx, int32_t octave, int32_t level, float* out, int32_t capacity_floats, int32_t* w,
                             int32_t* h) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

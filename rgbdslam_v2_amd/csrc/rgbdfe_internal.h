@@ -264,6 +264,21 @@ struct SiftNodeFrame {
   float4* xyz; float2* feat; float4* xyz_out; float2* feat_out; int32_t* kept_out;
 };
 struct SiftNodeChunk { int n_frames; int32_t* n_out; SiftNodeFrame frame[kSiftNodeFramesMax]; };
+// rgbdfe_detect_sift_describe(_batch_nodes) (sift_keys.hip): frame f's aggregate (rgbdfe_keypoint rows) -> projectTo3D's kept
+// keypoints in aggregate order, cut at max_keypoints, as SiftGPU keys (x, y, size / 12, angle in radians: the wrapper's double
+// arithmetic stored as float), as the keypoints the wrapper rebuilds (rgbdfe_keypoint rows) and as the node launch's
+// (x, y, size, 0) rows; n_out[f] = the count (0: the wrapper's empty-list path)
+struct SiftKeysFrame {
+  const rgbdfe_keypoint* agg; const float* depth; int n_agg;
+  float4* keys; rgbdfe_keypoint* rebuilt; float4* node_keys;
+};
+struct SiftKeysChunk { int n_frames; int32_t* n_out; SiftKeysFrame frame[kSiftNodeFramesMax]; };
+void launch_sift_keys_from_detector(const SiftKeysChunk& ch, int rows, int cols, double depth_scaling, int max_keypoints,
+                                    bool min_depth, hipStream_t stream);
+// descriptor rows into the callers' order: out row (f, r) = src row map[f * stride + r] (a zero row for -1), r < n[f]
+struct SiftGather { int n_frames; int n[kSiftNodeFramesMax]; };
+void launch_sift_rows_gather(const float* src, const int32_t* map, const SiftGather& g, size_t stride, float* out,
+                             hipStream_t stream);
 void launch_sift_nodes(const SiftNodeChunk& ch, int rows, int cols, float fxinv, float fyinv, float cx, float cy,
                        double depth_scaling, int max_keypoints, bool min_depth, bool root_sift, hipStream_t stream);
 

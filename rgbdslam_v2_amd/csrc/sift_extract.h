@@ -52,6 +52,12 @@ struct SiftExtractor {
   // descriptors for the caller's keypoints (x, y, scale, orientation): SiftGPUWrapper::detect's second mode
   int describe(const uint8_t* gray, int rows, int cols, const SiftKey* keys_in, int n, const float** desc, hipStream_t s,
                std::string& err);
+  // the same for nf <= kMaxBatch frames in one pyramid chain and ONE descriptor launch: keys[f] (n[f] of them, host) are
+  // assigned to their levels as describe() does; frame f's descriptors land in the callers' order at device rows
+  // out + f * out_stride * 128 (zero rows for a keypoint in no band).  map: device / pinned int scratch of nf * out_stride.
+  // Everything is enqueued on s; nothing comes back.
+  int describe_frames(const uint8_t* const* gray, int nf, int rows, int cols, const SiftKey* const* keys, const int* n,
+                      float* out, size_t out_stride, int32_t* d_map, int32_t* h_map, hipStream_t s, std::string& err);
   int enqueue_pyramid(const uint8_t* const* gray, int nf, hipStream_t s, std::string& err);
   // stage access for the parity tests: a Gaussian plane of the latest call's FIRST frame / the keypoint candidates of one
   // (octave, dog level) of that frame as (x, y, sign, dx, dy, ds) in list order, before the feature-count limits

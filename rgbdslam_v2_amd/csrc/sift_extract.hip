@@ -797,6 +797,83 @@ int SiftExtractor::describe(const uint8_t* gray, int rows, int cols, const SiftK
   return RGBDFE_OK;
 }
 
+int SiftExtractor::describe_frames(const uint8_t* const* gray, int nf, int rows, int cols, const SiftKey* const* keys, const int* n,
+                                   float* out, size_t out_stride, int32_t* d_map, int32_t* h_map, hipStream_t s, std::string& err) {
+  if (nf < 1 || nf > kMaxBatch) { err = "SIFT batch size out of range"; return RGBDFE_ERR_INVALID_ARG; }
+  int rc = prepare(rows, cols, nf, s, err);
+  if (rc != RGBDFE_OK) return rc;
+  rc = enqueue_pyramid(gray, nf, s, err);
+  if (rc != RGBDFE_OK) return rc;
+  const double full_turn = 2.0 * 3.14159265358979323846;
+  const float sigma_half_step = powf(2.0f, 0.5f / kDogLevels);
+  const float offset = 0.5f;   // GlobalUtil::_LoweOrigin = 0
+  LevelJobs* hj = static_cast<LevelJobs*>(h_jobs);
+  int grand = 0, max_total = 0;
+  for (int f = 0; f < nf; ++f) {   // describe()'s level assignment, frame by frame, into one batch-wide list
+    LevelJobs& dj = hj[f];
+    memset(&dj, 0, sizeof(LevelJobs));
+    int32_t* map = h_map + (size_t)f * out_stride;
+    for (int k = 0; k < n[f]; ++k) map[k] = -1;
+    int total = 0;
+    float octave_sigma = octave_min >= 0 ? float(1 << octave_min) : 1.0f / (1 << (-octave_min));
+    for (int i = 0; i < octave_num; ++i, octave_sigma *= 2.0f)
+      for (int j = 0; j < kDogLevels; ++j) {
+        const float level_sg = level_sigma(j) * octave_sigma;
+        const float sigma_min = level_sg / sigma_half_step, sigma_max = level_sg * sigma_half_step;
+        int kept = 0;
+        for (int k = 0; k < n[f]; ++k) {
+          const SiftKey& q = keys[f][k];
+          const float sigmak = q.s;
+          if ((sigmak >= sigma_min && sigmak < sigma_max) || (sigmak < sigma_min && i == 0 && j == 0) ||
+              (sigmak > sigma_max && i == octave_num - 1 && j == kDogLevels - 1)) {
+            if ((size_t)(grand + total + kept + 1) * 4 > stage_floats || (size_t)(grand + total + kept + 1) > feat_cap * (size_t)frames_cap) {
+              err = "more SIFT keypoints than the feature buffer holds";
+              return RGBDFE_ERR_CAPACITY;
+            }
+            float* e = h_stage + (size_t)(grand + total + kept) * 4;
+            e[0] = (q.x - offset) / octave_sigma + 0.5f;
+            e[1] = (q.y - offset) / octave_sigma + 0.5f;
+            e[2] = q.s / octave_sigma;
+            e[3] = (float)fmod(full_turn - q.o, full_turn);
+            map[k] = grand + total + kept;   // the last band that takes a keypoint wins, as in describe()
+            ++kept;
+          }
+        }
+        if (kept == 0) continue;
+        const int m = dj.n++;
+        dj.begin[m] = total;
+        dj.g[m] = oct[i].g[j + 1] + (size_t)f * planes_floats;
+        dj.w[m] = oct[i].w; dj.h[m] = oct[i].h;
+        total += kept;
+      }
+    dj.begin[dj.n] = total;
+    dj.base = grand;
+    grand += total;
+    max_total = std::max(max_total, total);
+  }
+  if ((size_t)grand * 128 > desc_cap) {
+    if (d_desc) (void)hipFree(d_desc);
+    d_desc = nullptr; desc_cap = 0;
+    SIFT_HIP(hipMalloc((void**)&d_desc, (size_t)grand * 128 * 4 * 2));
+    desc_cap = (size_t)grand * 128 * 2;
+  }
+  if (grand > 0) {
+    SIFT_HIP(hipMemcpyAsync(d_feat, h_stage, (size_t)grand * 16, hipMemcpyHostToDevice, s));
+    SIFT_HIP(hipMemcpyAsync(d_jobs, h_jobs, sizeof(LevelJobs) * (size_t)nf, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(sift_descriptor_kernel, dim3(max_total, nf), dim3(64), 0, s, static_cast<const LevelJobs*>(d_jobs), d_feat,
+                       (float2*)d_desc, 3.0f);
+    SIFT_HIP(hipGetLastError());
+  }
+  SIFT_HIP(hipMemcpyAsync(d_map, h_map, (size_t)nf * out_stride * 4, hipMemcpyHostToDevice, s));
+  SiftGather g{};
+  g.n_frames = nf;
+  for (int f = 0; f < nf; ++f) g.n[f] = n[f];
+  launch_sift_rows_gather(d_desc, d_map, g, out_stride, out, s);
+  SIFT_HIP(hipGetLastError());
+  // h_stage / h_jobs / h_map are read by the copies above: the caller synchronises s before this object is used again
+  return RGBDFE_OK;
+}
+
 int SiftExtractor::debug_plane(int octave, int level, std::vector<float>& out, int* w, int* h, hipStream_t s) {
   if (octave < 0 || octave >= octave_num || level < 0 || level >= kLevels || !d_planes) return RGBDFE_ERR_INVALID_ARG;
   out.resize(oct[octave].plane);

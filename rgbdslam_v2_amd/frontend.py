@@ -600,6 +600,82 @@ class FrontEnd:
             return [(kp[f, : cnt[f]], xyz[f, : cnt[f]], feat[f, : cnt[f]]) for f in range(n)]
         return [(kp[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy(), feat[f, : cnt[f]].copy()) for f in range(n)]
 
+    def _detector_max_total(self):
+        return int(1.5 * getattr(self, "_max_keypoints", 600))
+
+    def detect(self, gray, mask=None, capacity=None):
+        """rgbdfe_detect: detector->detect alone (node.cpp:160) -- the grid detector's aggregate, in aggregate order, before
+        removeDepthless; the per-cell thresholds advance as in detect_describe.  capacity defaults to max_total =
+        floor(1.5 * max_keypoints), the aggregate's bound; less is refused (RGBDFE_ERR_INVALID_ARG)."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        cap = self._detector_max_total() if capacity is None else int(capacity)
+        kp = np.zeros(max(cap, 1), _lib.KEYPOINT_DTYPE)
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_detect(self._ctx, gray.ctypes.data, None if m is None else m.ctypes.data, gray.shape[0],
+                                          gray.shape[1], kp.ctypes.data, cap, C.byref(n)))
+        return kp[: n.value].copy()
+
+    def detect_sift_describe(self, gray, mask, depth, fx, fy, cx, cy, depth_scaling=1.0, use_root_sift=True):
+        """rgbdfe_detect_sift_describe: Node::Node with feature_detector_type ORB / FAST (the context's detector type) and
+        feature_extractor_type SIFTGPU for one frame -- detect -> projectTo3D -> SiftGPU descriptors at the kept keypoints ->
+        projectTo3DSiftGPU (+ RootSIFT).  A frame whose keypoints all lack depth gets SiftGPU's own detection (the wrapper's
+        empty-list behaviour).  Returns (keypoints, xyz1 [n,4], siftgpu_descriptors [n,128], feature_descriptors [n,128])."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        depth = np.ascontiguousarray(depth, np.float32)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        cap = max(getattr(self, "_max_keypoints", 600), 1)
+        kp = np.zeros(cap, _lib.KEYPOINT_DTYPE)
+        xyz = np.zeros((cap, 4), np.float32)
+        raw = np.zeros((cap, 128), np.float32)
+        feat = np.zeros((cap, 128), np.float32)
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_detect_sift_describe(
+            self._ctx, gray.ctypes.data, None if m is None else m.ctypes.data, depth.ctypes.data, gray.shape[0], gray.shape[1],
+            fx, fy, cx, cy, depth_scaling, int(bool(use_root_sift)), kp.ctypes.data, xyz.ctypes.data, raw.ctypes.data,
+            feat.ctypes.data, C.byref(n)))
+        k = n.value
+        return kp[:k].copy(), xyz[:k].copy(), raw[:k].copy(), feat[:k].copy()
+
+    def detect_sift_describe_batch_nodes(self, grays, masks, depths, fx, fy, cx, cy, node_ids, depth_scaling=1.0,
+                                         use_root_sift=True, return_features=True):
+        """rgbdfe_detect_sift_describe_batch_nodes: detect_sift_describe over a run of frames of one size (the thresholds
+        carry over), frame f's features becoming the float node node_ids[f] (a negative id: no node).  masks may be None or
+        hold None entries.  Returns per frame (keypoints, xyz1, feature_descriptors), or only the counts (an int32 array)
+        when return_features is False (no host outputs)."""
+        n = len(grays)
+        if n == 0:
+            return [] if return_features else np.zeros(0, np.int32)
+        g = [np.ascontiguousarray(x, np.uint8) for x in grays]
+        d = [np.ascontiguousarray(x, np.float32) for x in depths]
+        rows, cols = g[0].shape
+        if len(d) != n or (masks is not None and len(masks) != n):
+            raise ValueError("one depth image (and mask, when given) per frame")
+        ms = [None] * n if masks is None else [None if x is None else np.ascontiguousarray(x, np.uint8) for x in masks]
+        for a in g + d + [x for x in ms if x is not None]:
+            if a.shape != (rows, cols):
+                raise ValueError("all frames of a batch share one size")
+        ids = np.ascontiguousarray(node_ids, np.int32)
+        if ids.shape != (n,):
+            raise ValueError("node_ids must hold one id per frame")
+        vp = C.c_void_p * n
+        pg = vp(*[x.ctypes.data for x in g])
+        pd = vp(*[x.ctypes.data for x in d])
+        pm = vp(*[None if x is None else x.ctypes.data for x in ms])
+        stride = max(getattr(self, "_max_keypoints", 600), 1)
+        cnt = np.zeros(n, np.int32)
+        args = (self._ctx, n, C.cast(pg, C.c_void_p), C.cast(pm, C.c_void_p), C.cast(pd, C.c_void_p), rows, cols, fx, fy, cx,
+                cy, depth_scaling, int(bool(use_root_sift)), ids.ctypes.data, stride)
+        if not return_features:
+            self._check(self._L.rgbdfe_detect_sift_describe_batch_nodes(*args, None, None, None, cnt.ctypes.data))
+            return cnt
+        kp = np.zeros((n, stride), _lib.KEYPOINT_DTYPE)
+        xyz = np.zeros((n, stride, 4), np.float32)
+        feat = np.zeros((n, stride, 128), np.float32)
+        self._check(self._L.rgbdfe_detect_sift_describe_batch_nodes(*args, kp.ctypes.data, xyz.ctypes.data, feat.ctypes.data,
+                                                                    cnt.ctypes.data))
+        return [(kp[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy(), feat[f, : cnt[f]].copy()) for f in range(n)]
+
     def sift_geometry(self):
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.rgbdfe_sift_geometry(self._ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
