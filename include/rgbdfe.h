@@ -668,6 +668,35 @@ int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, c
                                             double fx, double fy, double cx, double cy, double depth_scaling,
                                             int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride,
                                             rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out);
+
+/* ---- ORB descriptors behind SiftGPU's detection (feature_detector_type SIFTGPU, feature_extractor_type ORB) --------------
+ * Node::Node's steps for that setting, one frame (node.cpp:149-152, 183-210): SiftGPUWrapper::detect's own detection with
+ * "-tc2 max_keypoints" (its descriptors are never computed), the keypoints as the wrapper rebuilds them (size 12 * scale, angle
+ * in degrees, response = octave = 0), removeDepthless, retainBest(max_keypoints) + resize (every response is 0: the first
+ * max_keypoints survivors in SiftGPU's list order), cv::ORB::compute (the 31-pixel border filter, rBRIEF at each keypoint's own
+ * angle on level 0), projectTo3D.  The cut comes before the border filter, so a frame can keep fewer than max_keypoints rows
+ * although SiftGPU found more.  The same bits as rgbdfe_sift_detect(..., max_keypoints) -> removeDepthless and the cut ->
+ * rgbdfe_orb_compute -> rgbdfe_project_to_3d; rgbdfe_set_feature_min_depth switches both depth lookups to the neighbourhood
+ * of size 12 * scale (rgbdfe_project_to_3d_min_depth).  max_keypoints must lie in [1, the context's max_keypoints]
+ * (RGBDFE_ERR_INVALID_ARG).  Outputs hold max_keypoints rows: keypoints, descriptors (32 bytes), xyz1 (4 floats); the node is
+ * matched by the ORB branch (rgbdfe_upload_node, rgbdfe_match_pair_list). */
+int rgbdfe_sift_detect_orb_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const float* depth, int32_t rows, int32_t cols,
+                                    double fx, double fy, double cx, double cy, double depth_scaling, int32_t max_keypoints,
+                                    rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out);
+/* A run of frames of one size: n_frames calls of rgbdfe_sift_detect_orb_describe, each followed by rgbdfe_upload_node(node_ids[f],
+ * descriptors, xyz1, n) -- kind 0 (ORB) nodes, what rgbdfe_match_pair_list reads; the keypoints never cross PCIe between the
+ * SIFT detection and the nodes.  node_ids is required (negative: no node; an id may appear once); the node table follows
+ * rgbdfe_detect_describe_batch_nodes (free slots checked for the whole batch first, a frame without features becomes an empty
+ * node, an existing id of any kind is rewritten in place after the pair lanes that may read it have finished).  Each host
+ * output may be NULL (all NULL: nothing but n_out comes back); frame f's rows start at row f * out_stride, n_out[f] of them;
+ * out_stride < max_keypoints while an output is asked for is RGBDFE_ERR_CAPACITY, refused before any work.  Up to 8 frames
+ * share every launch.  Multi-device handles process the frames on the first device and hand the nodes to
+ * the others. */
+int rgbdfe_sift_detect_orb_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray,
+                                                const float* const* depth, int32_t rows, int32_t cols, double fx, double fy,
+                                                double cx, double cy, double depth_scaling, int32_t max_keypoints,
+                                                const int32_t* node_ids, int32_t out_stride, rgbdfe_keypoint* keypoints,
+                                                uint8_t* descriptors, float* xyz1, int32_t* n_out);
 /* stage access for parity tests: the pyramid geometry of the latest frame, one Gaussian plane (octave index from 0, level
  * 0 .. levels-1; padded width x height floats), the keypoint candidates of one (octave, DoG level) as rows of
  * (x, y, extremum sign, dx, dy, ds) in list order, before the feature-count limit */

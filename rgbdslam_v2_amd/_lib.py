@@ -344,6 +344,12 @@ def load():
     L.rgbdfe_detect_sift_describe_batch_nodes.restype = C.c_int
     L.rgbdfe_detect_sift_describe_batch_nodes.argtypes = [ctx, i32, vp, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double,
                                                           C.c_double, C.c_double, i32, vp, i32, vp, vp, vp, vp]
+    L.rgbdfe_sift_detect_orb_describe.restype = C.c_int
+    L.rgbdfe_sift_detect_orb_describe.argtypes = [ctx, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                  C.c_double, i32, vp, vp, vp, C.POINTER(i32)]
+    L.rgbdfe_sift_detect_orb_describe_batch_nodes.restype = C.c_int
+    L.rgbdfe_sift_detect_orb_describe_batch_nodes.argtypes = [ctx, i32, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double,
+                                                              C.c_double, C.c_double, i32, vp, i32, vp, vp, vp, vp]
     L.rgbdfe_sift_geometry.restype = C.c_int
     L.rgbdfe_sift_geometry.argtypes = [ctx] + [C.POINTER(i32)] * 4
     L.rgbdfe_sift_debug_plane.restype = C.c_int
@@ -401,4 +407,5 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_group_submit_us", "rgbdfe_sift_detect", "rgbdfe_sift_detect_batch", "rgbdfe_sift_describe", "rgbdfe_sift_geometry", "rgbdfe_sift_debug_plane", "rgbdfe_sift_debug_candidates",
     "rgbdfe_sift_detect_batch_nodes", "rgbdfe_set_detector_type", "rgbdfe_fast_detect",
     "rgbdfe_detect", "rgbdfe_detect_sift_describe", "rgbdfe_detect_sift_describe_batch_nodes",
+    "rgbdfe_sift_detect_orb_describe", "rgbdfe_sift_detect_orb_describe_batch_nodes",
 ]

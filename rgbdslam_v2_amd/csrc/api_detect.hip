@@ -263,7 +263,7 @@ void sift_nodes_release(rgbdfe_ctx* ctx) {
 
 // the buffers of rgbdfe_sift_detect_batch_nodes for frames of `plane` pixels (reallocated when the size changes); the host-output
 // rows are allocated with the first call that asks for them
-static int sift_nodes_prepare(rgbdfe_ctx* ctx, size_t plane, bool host_out) {
+int sift_nodes_prepare(rgbdfe_ctx* ctx, size_t plane, bool host_out) {
   rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
   constexpr size_t S = 3 * (size_t)kSiftNodeFramesMax;
   const size_t rows = S * (size_t)ctx->cfg.max_keypoints;

@@ -406,14 +406,8 @@ __global__ __launch_bounds__(256) void fast_select_kernel(const FastGeom g, cons
 
 // ------------------------------------------------------------------------------------------------
 // rBRIEF (computeOrbDescriptors, WTA_K = 2) of level-0 keypoints at angle -1 degree: orb_brief_kernel's sampling for a
-// frame-indexed list; a wave per keypoint, the 32 bytes leave as eight dwords
+// frame-indexed list (brief_level0_dword, fast_device.h); a wave per keypoint, the 32 bytes leave as eight dwords
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect101_f(int p, int len) {
-  if (len == 1) return 0;
-  while (p < 0 || p >= len) p = p < 0 ? -p : 2 * len - 2 - p;
-  return p;
-}
-
 __global__ __launch_bounds__(256) void fast_brief_kernel(const uint8_t* __restrict__ gray, const uint8_t* __restrict__ blur,
                                                          uint32_t plane, int rows, int cols, const FastKp* __restrict__ list,
                                                          int list_cap, const int32_t* __restrict__ n_out,
@@ -424,31 +418,9 @@ __global__ __launch_bounds__(256) void fast_brief_kernel(const uint8_t* __restri
   if (k >= n_out[f]) return;
   const int lane = threadIdx.x & 63;
   const FastKp kp = list[(size_t)f * list_cap + k];
-  const uint8_t* __restrict__ raw = gray + (size_t)f * plane;
-  const uint8_t* __restrict__ bl = blur + (size_t)f * plane;
-  const int byte = lane >> 1, half = lane & 1;
-  int bits = 0;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int test = byte * 8 + half * 4 + t;
-    int v[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const float px = (float)pattern[(test * 2 + e) * 2], py = (float)pattern[(test * 2 + e) * 2 + 1];
-      const float x = px * a - py * b;
-      const float y = px * b + py * a;
-      const int ix = (int)kp.x + __float2int_rn(x), iy = (int)kp.y + __float2int_rn(y);
-      if (ix >= 0 && ix < cols && iy >= 0 && iy < rows)
-        v[e] = bl[(size_t)iy * cols + ix];
-      else  // the unblurred reflect-101 border copyMakeBorder wrote before the in-place blur
-        v[e] = raw[(size_t)reflect101_f(iy, rows) * cols + reflect101_f(ix, cols)];
-    }
-    bits |= (v[0] < v[1]) << (half * 4 + t);
-  }
-  bits |= __shfl_xor(bits, 1);   // lane 2j: byte j
-  const int d = lane & 7;        // lanes 0..7: dword d = bytes 4d .. 4d + 3
-  const uint32_t word = (uint32_t)(__shfl(bits, 8 * d) & 255) | ((uint32_t)(__shfl(bits, 8 * d + 2) & 255) << 8) |
-                        ((uint32_t)(__shfl(bits, 8 * d + 4) & 255) << 16) | ((uint32_t)(__shfl(bits, 8 * d + 6) & 255) << 24);
+  const uint32_t word = brief_level0_dword(gray + (size_t)f * plane, blur + (size_t)f * plane, rows, cols, (int)kp.x, (int)kp.y,
+                                           a, b, pattern, lane);
+  const int d = lane & 7;
   if (lane < 8) {
     const FastFrameOut o = outs[f];
     if (o.node_desc) o.node_desc[(size_t)k * 8 + d] = word;

@@ -563,6 +563,67 @@ int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, c
   return RGBDFE_OK;
 }
 
+int rgbdfe_sift_detect_orb_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const float* depth, int32_t rows, int32_t cols, double fx,
+                                    double fy, double cx, double cy, double depth_scaling, int32_t max_keypoints,
+                                    rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_sift_detect_orb_describe(c, gray, depth, rows, cols, fx, fy, cx, cy, depth_scaling,
+                                                                 max_keypoints, keypoints, descriptors, xyz1, n_out));
+}
+
+int rgbdfe_sift_detect_orb_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray,
+                                                const float* const* depth, int32_t rows, int32_t cols, double fx, double fy,
+                                                double cx, double cy, double depth_scaling, int32_t max_keypoints,
+                                                const int32_t* node_ids, int32_t out_stride, rgbdfe_keypoint* keypoints,
+                                                uint8_t* descriptors, float* xyz1, int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  if (!RGBDFE_IS_GROUP(ctx))
+    return RGBDFE_FIRST(ctx, impl::rgbdfe_sift_detect_orb_describe_batch_nodes(c, n_frames, gray, depth, rows, cols, fx, fy, cx, cy,
+                                                                               depth_scaling, max_keypoints, node_ids, out_stride,
+                                                                               keypoints, descriptors, xyz1, n_out));
+  // several devices behind the handle: the frames are processed on the first one, into its nodes and into host rows of
+  // max_keypoints per frame (a frame keeps no more); the other devices get the nodes from those rows (every device holds
+  // every node), the caller's arrays get them at out_stride
+  if (n_frames < 0 || out_stride < 0 || max_keypoints < 1 || (n_frames > 0 && (!node_ids || !n_out)))
+    return guarded(ctx, [&]() -> int { return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments"); });
+  if (n_frames > 0 && (keypoints || descriptors || xyz1) && out_stride < max_keypoints)
+    return guarded(ctx, [&]() -> int {
+      return fail(ctx, RGBDFE_ERR_CAPACITY, "out_stride below max_keypoints while a host output is asked for");
+    });
+  const size_t mk = (size_t)max_keypoints, nf = (size_t)n_frames;
+  std::vector<rgbdfe_keypoint> kp(keypoints ? nf * mk : 0);
+  std::vector<uint8_t> desc(nf * mk * 32);
+  std::vector<float> xyz(nf * mk * 4);
+  int rc = RGBDFE_FIRST(ctx, impl::rgbdfe_sift_detect_orb_describe_batch_nodes(c, n_frames, gray, depth, rows, cols, fx, fy, cx, cy,
+                                                                               depth_scaling, max_keypoints, node_ids, max_keypoints,
+                                                                               keypoints ? kp.data() : nullptr, desc.data(),
+                                                                               xyz.data(), n_out));
+  if (rc != RGBDFE_OK) return rc;
+  std::vector<int32_t> ids, cnt;
+  std::vector<const uint8_t*> dp;
+  std::vector<const float*> xp;
+  for (size_t f = 0; f < nf; ++f)
+    if (node_ids[f] >= 0) {
+      ids.push_back(node_ids[f]); cnt.push_back(n_out[f]);
+      dp.push_back(desc.data() + f * mk * 32); xp.push_back(xyz.data() + f * mk * 4);
+    }
+  rc = guarded(ctx, [&]() -> int {
+    return group_run(ctx, [&](int i) -> int {
+      if (i == 0) return RGBDFE_OK;
+      return impl::rgbdfe_upload_nodes(ctx->group->children[(size_t)i], (int32_t)ids.size(), ids.data(), dp.data(), xp.data(),
+                                       cnt.data());
+    });
+  });
+  if (rc != RGBDFE_OK) return rc;
+  for (size_t f = 0; f < nf; ++f) {
+    const size_t n = (size_t)n_out[f], o = f * (size_t)out_stride;
+    if (keypoints && n) memcpy(keypoints + o, kp.data() + f * mk, n * sizeof(rgbdfe_keypoint));
+    if (descriptors && n) memcpy(descriptors + o * 32, desc.data() + f * mk * 32, n * 32);
+    if (xyz1 && n) memcpy(xyz1 + o * 4, xyz.data() + f * mk * 4, n * 16);
+  }
+  return RGBDFE_OK;
+}
+
 int rgbdfe_sift_debug_plane(rgbdfe_ctx* ctx, int32_t octave, int32_t level, float* out, int32_t capacity_floats, int32_t* w,
                             int32_t* h) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

@@ -304,6 +304,14 @@ struct rgbdfe_ctx {
     void* dev = nullptr; void* pin = nullptr;
     float* d_qdesc = nullptr; float4* d_qkeys = nullptr; size_t q_cap = 0;   // SiftGPU's own features of empty-list frames
   } sb;
+  // rgbdfe_sift_detect_orb_describe(_batch_nodes) (api_sift_orb.hip): per chunk set (3 of them, 8 frames each) the blurred
+  // frames, the described keypoints, the output rows (max_keypoints per frame) and the counts on the device and their
+  // page-locked copies, laid out by api_sift_orb; the depth images travel through `sn`'s staging
+  struct SiftOrbBufs {
+    int rows = 0, cols = 0;
+    void* dev = nullptr; void* pin = nullptr;
+    int8_t* d_pattern = nullptr;   // rBRIEF's bit pattern
+  } so;
   int orb_max_keypoints = 0;  // 0 = detector not configured yet
   // feature_detector_type (rgbdfe_set_detector_type): RGBDFE_DETECTOR_ORB or RGBDFE_DETECTOR_FAST.  Both use the detector
   // configuration and the per-cell thresholds of `orb` (the reference's one detector_ object); FAST runs in `fast`.
@@ -373,6 +381,9 @@ void ensure_detector(rgbdfe_ctx* ctx);
 int ensure_sift(rgbdfe_ctx* ctx);                 // the float / bf16 node slabs (api_pairs.hip)
 void sift_nodes_release(rgbdfe_ctx* ctx);        // rgbdfe_ctx::sn (api_detect.hip)
 void sift_behind_release(rgbdfe_ctx* ctx);       // rgbdfe_ctx::sb (api_sift_behind.hip)
+void sift_orb_release(rgbdfe_ctx* ctx);          // rgbdfe_ctx::so (api_sift_orb.hip)
+// rgbdfe_ctx::sn for frames of `plane` pixels: the depth staging and the counts, the host-output rows when host_out (api_detect.hip)
+int sift_nodes_prepare(rgbdfe_ctx* ctx, size_t plane, bool host_out);
 int detector_max_keypoints(rgbdfe_ctx* ctx);     // the detector's max_keypoints (rgbdfe_detector_configure; 600 by default)
 // the grid detector's aggregate of one frame (detector->detect, node.cpp:160) for the context's type; ctx->mu held
 int detect_aggregate(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
@@ -439,6 +450,8 @@ int rgbdfe_detect_describe_cloud(rgbdfe_ctx* ctx, const uint8_t* gray, const uin
 int rgbdfe_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols, rgbdfe_keypoint* keypoints, int32_t capacity, int32_t* n_out);
 int rgbdfe_detect_sift_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, const float* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t use_root_sift, rgbdfe_keypoint* keypoints, float* xyz1, float* siftgpu_descriptors, float* feature_descriptors, int32_t* n_out);
 int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask, const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride, rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out);
+int rgbdfe_sift_detect_orb_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const float* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t max_keypoints, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out);
+int rgbdfe_sift_detect_orb_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t max_keypoints, const int32_t* node_ids, int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out);
 int rgbdfe_sift_node_features(rgbdfe_ctx* ctx, const float* kp_xy, const float* kp_size, int32_t n_kp, const float* desc_in, const float* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t max_keypoints, int32_t use_root_sift, int32_t* kept_idx, float* xyz1, float* siftgpu_descriptors, float* feature_descriptors, int32_t* n_out);
 int rgbdfe_depth_to_mono8(rgbdfe_ctx* ctx, const void* depth, int32_t depth_is_u16, int32_t rows, int32_t cols, uint8_t* mono8, float* depth_m);
 int rgbdfe_upload_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* depth, int32_t rows, int32_t cols, const uint8_t* rgb, int32_t rgb_channels, int32_t encoding_bgr, double fx, double fy, double cx, double cy, double depth_scaling, double min_depth, int32_t cloud_skip, float* cloud_out);

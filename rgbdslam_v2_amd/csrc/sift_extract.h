@@ -99,7 +99,10 @@ struct SiftExtractor {
   // desc_device (rgbdfe_sift_detect_batch_nodes): the descriptor launch writes d_desc and nothing goes to the host; the kept
   // features (x, y, KeyPoint::size = 12 * scale, 0) are uploaded to d_keys, frame f's at row fs[f].base, beside them
   bool desc_device = false;
-  float4* d_keys = nullptr; float4* h_keys = nullptr; size_t keys_cap = 0;
+  // keys_only (rgbdfe_sift_detect_orb_describe*): the pipeline stops after the orientations -- no descriptor launch, no
+  // descriptor read-back; d_keys holds the kept features as SiftOrbKey rows (two float4 each, rgbdfe_internal.h)
+  bool keys_only = false;
+  float4* d_keys = nullptr; float4* h_keys = nullptr; size_t keys_cap = 0;   // (capacity in float4 rows)
   int* h_counts = nullptr;                             // pinned: per-level totals, 64 per frame
   float* h_stage = nullptr; size_t stage_floats = 0;   // pinned staging for lists (all frames of a batch)
   // The three read-backs of a batch -- the levels' candidate counts, the oriented features, the descriptors -- are stored into

@@ -28,6 +28,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 
 #include "rgbdfe_internal.h"
 #include "sift_pyramid_kernels.h"
@@ -653,6 +654,32 @@ int SiftExtractor::finish_descriptors(hipStream_t s, std::string& err) {
   if (grand2 == 0) return RGBDFE_OK;
   if ((size_t)grand2 > feat_cap * (size_t)frames_cap) { err = "more SIFT features than the feature buffer holds"; return RGBDFE_ERR_CAPACITY; }
   if ((size_t)grand2 * 4 > stage_floats) { err = "SIFT staging buffer too small"; return RGBDFE_ERR_CAPACITY; }
+  if (keys_only) {   // the kept features for the ORB describer (sift_orb.hip) and no descriptor launch
+    if ((size_t)grand2 * 2 > keys_cap) {
+      if (d_keys) (void)hipFree(d_keys);
+      if (h_keys) (void)hipHostFree(h_keys);
+      d_keys = nullptr; h_keys = nullptr; keys_cap = 0;
+      SIFT_HIP(hipMalloc((void**)&d_keys, (size_t)grand2 * 4 * sizeof(float4)));
+      SIFT_HIP(hipHostMalloc((void**)&h_keys, (size_t)grand2 * 4 * sizeof(float4), hipHostMallocDefault));
+      keys_cap = (size_t)grand2 * 4;
+    }
+    for (int f = 0; f < nf; ++f) {
+      const FrameState& F = fs[(size_t)f];
+      const float* k = F.keybuf.data() + (size_t)F.erased * 4;
+      for (int i = 0; i < F.total; ++i, k += 4) {
+        // cv::ORB::compute's rotation of the keypoint the wrapper rebuilds (angle = o * 180 / 3.1415927 in double, stored as
+        // float): the double functions of the host's libm rounded to float, as rgbdfe_orb_compute and the oracle form it
+        float angle = (float)((double)k[3] * 180.0 / 3.1415927);
+        angle *= (float)(M_PI / 180.f);
+        float4* row = h_keys + ((size_t)F.base + i) * 2;
+        row[0] = make_float4(k[0], k[1], k[2], k[3]);
+        row[1] = make_float4((float)std::cos((double)angle), (float)std::sin((double)angle), 0.f, 0.f);
+      }
+    }
+    SIFT_HIP(hipMemcpyAsync(d_keys, h_keys, (size_t)grand2 * 2 * sizeof(float4), hipMemcpyHostToDevice, s));
+    fin_grand2 = grand2;
+    return RGBDFE_OK;
+  }
   if ((size_t)grand2 * 128 > desc_cap) {
     if (d_desc) (void)hipFree(d_desc);
     d_desc = nullptr; desc_cap = 0;
@@ -705,7 +732,7 @@ int SiftExtractor::finish_outputs(std::vector<SiftKey>* keys, const float** desc
   SIFT_HIP(hipStreamSynchronize(s));
   for (int f = 0; f < nf; ++f) {
     const FrameState& F = fs[(size_t)f];
-    desc[f] = h_desc + (size_t)F.base * 128;
+    desc[f] = keys_only ? nullptr : h_desc + (size_t)F.base * 128;
     keys[f].resize((size_t)F.total);
     if (F.total > 0) memcpy(keys[f].data(), F.keybuf.data() + (size_t)F.erased * 4, (size_t)F.total * 16);
   }

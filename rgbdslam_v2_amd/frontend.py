@@ -676,6 +676,59 @@ class FrontEnd:
                                                                     cnt.ctypes.data))
         return [(kp[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy(), feat[f, : cnt[f]].copy()) for f in range(n)]
 
+    def sift_detect_orb_describe(self, gray, depth, fx, fy, cx, cy, depth_scaling=1.0, max_keypoints: int = 1000):
+        """rgbdfe_sift_detect_orb_describe: Node::Node with feature_detector_type SIFTGPU and feature_extractor_type ORB for one
+        frame -- SiftGPU's own detection, removeDepthless, the max_keypoints cut, cv::ORB::compute, projectTo3D.  Returns
+        (keypoints, descriptors [n, 32] uint8, xyz1 [n, 4])."""
+        gray = np.ascontiguousarray(gray, np.uint8)
+        depth = np.ascontiguousarray(depth, np.float32)
+        cap = max(int(max_keypoints), 1)
+        kp = np.zeros(cap, _lib.KEYPOINT_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        xyz = np.zeros((cap, 4), np.float32)
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_sift_detect_orb_describe(
+            self._ctx, gray.ctypes.data, depth.ctypes.data, gray.shape[0], gray.shape[1], fx, fy, cx, cy, depth_scaling,
+            int(max_keypoints), kp.ctypes.data, desc.ctypes.data, xyz.ctypes.data, C.byref(n)))
+        k = n.value
+        return kp[:k].copy(), desc[:k].copy(), xyz[:k].copy()
+
+    def sift_detect_orb_describe_batch_nodes(self, grays, depths, fx, fy, cx, cy, node_ids, depth_scaling=1.0,
+                                             max_keypoints: int = 1000, return_features=True):
+        """rgbdfe_sift_detect_orb_describe_batch_nodes: sift_detect_orb_describe over a run of frames of one size, frame f's
+        features becoming the ORB node node_ids[f] (a negative id: no node).  Returns per frame (keypoints, descriptors,
+        xyz1), or only the counts (an int32 array) when return_features is False (no host outputs)."""
+        n = len(grays)
+        if n == 0:
+            return [] if return_features else np.zeros(0, np.int32)
+        g = [np.ascontiguousarray(x, np.uint8) for x in grays]
+        d = [np.ascontiguousarray(x, np.float32) for x in depths]
+        rows, cols = g[0].shape
+        if len(d) != n:
+            raise ValueError("one depth image per frame")
+        for a in g + d:
+            if a.shape != (rows, cols):
+                raise ValueError("all frames of a batch share one size")
+        ids = np.ascontiguousarray(node_ids, np.int32)
+        if ids.shape != (n,):
+            raise ValueError("node_ids must hold one id per frame")
+        vp = C.c_void_p * n
+        pg = vp(*[x.ctypes.data for x in g])
+        pd = vp(*[x.ctypes.data for x in d])
+        cnt = np.zeros(n, np.int32)
+        args = (self._ctx, n, C.cast(pg, C.c_void_p), C.cast(pd, C.c_void_p), rows, cols, fx, fy, cx, cy, depth_scaling,
+                int(max_keypoints), ids.ctypes.data)
+        if not return_features:
+            self._check(self._L.rgbdfe_sift_detect_orb_describe_batch_nodes(*args, 0, None, None, None, cnt.ctypes.data))
+            return cnt
+        stride = max(int(max_keypoints), 1)
+        kp = np.zeros((n, stride), _lib.KEYPOINT_DTYPE)
+        desc = np.zeros((n, stride, 32), np.uint8)
+        xyz = np.zeros((n, stride, 4), np.float32)
+        self._check(self._L.rgbdfe_sift_detect_orb_describe_batch_nodes(*args, stride, kp.ctypes.data, desc.ctypes.data,
+                                                                        xyz.ctypes.data, cnt.ctypes.data))
+        return [(kp[f, : cnt[f]].copy(), desc[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy()) for f in range(n)]
+
     def sift_geometry(self):
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.rgbdfe_sift_geometry(self._ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
