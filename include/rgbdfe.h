@@ -706,6 +706,59 @@ int rgbdfe_sift_debug_plane(rgbdfe_ctx* ctx, int32_t octave, int32_t level, floa
 int rgbdfe_sift_debug_candidates(rgbdfe_ctx* ctx, int32_t octave, int32_t dog_level, float* out, int32_t capacity_rows,
                                  int32_t* n);
 
+/* ---- sensor frames -------------------------------------------------------- */
+/* The frames as the sensor messages carry them: a colour (or mono) image and a raw depth image, possibly of another size.
+ * The library does the listener's and Node::Node's image preparation on the device (csrc/ingest.hip), in front of the
+ * detect / describe / project chain of the entry points above.  In the reference's order:
+ *  1. Depth size.  If the depth image's size differs from the visual image's, every later step sees the depth image
+ *     resampled to the visual size by nearest neighbour on the raw samples (openni_listener.cpp:651-655): source column
+ *     min(floor(x * (1.0 / ((double)dst_cols / src_cols))), src_cols - 1), rows alike, in double (OpenCV 3.3 resizeNN).
+ *  2. depthToCV8UC1 (misc.cpp:414-430).  32FC1: mono8 = convertTo(CV_8UC1, 100).  16UC1: mono8 = convertTo(CV_8UC1, 0.05,
+ *     -25) and depth_m = convertTo(CV_32FC1, 0.001): the bytes and bits of rgbdfe_depth_to_mono8.  A 16UC1 hole therefore
+ *     is 0.0f, not NaN: removeDepthless keeps keypoints on it, and the mask is zero below about 0.5 m.
+ *  3. Gray (node.cpp:139-144).  MONO8: the bytes themselves.  RGB8 and BGR8 are both CV_8UC3, and the reference applies
+ *     CV_RGB2GRAY to the channels AS STORED whatever the encoding: gray = (c0*4899 + c1*9617 + c2*1868 + 8192) >> 14
+ *     (OpenCV 3.3 RGB2Gray<uchar>).  A bgr8 frame gets the red weight on its blue channel; that is reproduced, not mended.
+ *  4. Node::Node's steps as the existing entry points perform them, with the context's detector type
+ *     (RGBDFE_DETECTOR_ORB / _FAST), grid state, thresholds and rgbdfe_set_feature_min_depth mode.
+ *  5. Cloud (node.cpp:126-132): createXYZRGBPointCloud on the float depth of step 2 and the visual image as stored, with
+ *     the caller's encoding_bgr (a parameter in the reference, not derived from the message).
+ * Contract: a sensor call gives, bit for bit, what the corresponding existing call gives when it is fed the three planes of
+ * rgbdfe_ingest_frame for the same frame.  The SIFTGPU detector / extractor combinations are served by
+ * rgbdfe_ingest_frame followed by the existing calls.  Not covered: Bayer and 4-channel images. */
+#define RGBDFE_VISUAL_MONO8 0   /* CV_8UC1: used as it is (node.cpp:142-143) */
+#define RGBDFE_VISUAL_RGB8  1   /* CV_8UC3 */
+#define RGBDFE_VISUAL_BGR8  2   /* CV_8UC3; differs from RGB8 only for the cloud's colour */
+#define RGBDFE_DEPTH_32FC1  0   /* metres, NaN = no measurement */
+#define RGBDFE_DEPTH_16UC1  1   /* millimetres, 0 = no measurement */
+typedef struct rgbdfe_sensor_frame {
+  const uint8_t* visual; int32_t visual_rows, visual_cols, visual_step /* bytes per row */, visual_encoding;
+  const void*    depth;  int32_t depth_rows,  depth_cols,  depth_step  /* bytes per row */, depth_encoding;
+} rgbdfe_sensor_frame;
+int rgbdfe_sizeof_sensor_frame(void);
+/* Steps 1-3: what the listener and Node::Node hand to detector->detect / removeDepthless / projectTo3D.  Outputs are
+ * visual_rows x visual_cols, each may be NULL. */
+int rgbdfe_ingest_frame(rgbdfe_ctx* ctx, const rgbdfe_sensor_frame* frame, uint8_t* gray, uint8_t* mono8, float* depth_m);
+/* rgbdfe_detect_describe on a sensor frame (the context's detector type, ORB extractor). */
+int rgbdfe_sensor_detect_describe(rgbdfe_ctx* ctx, const rgbdfe_sensor_frame* frame, double fx, double fy, double cx, double cy,
+                                  double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1,
+                                  int32_t* n_out);
+typedef struct rgbdfe_sensor_cloud {   /* NULL pointer = no clouds */
+  int32_t cloud_skip; int32_t encoding_bgr; double min_depth;
+} rgbdfe_sensor_cloud;
+/* rgbdfe_detect_describe_batch_nodes on a run of sensor frames of one geometry (visual size, depth size, both encodings);
+ * node_ids may be NULL (= rgbdfe_detect_describe_batch).  With `cloud` (which needs node_ids), frame f's structured cloud
+ * is also kept under node_ids[f] as rgbdfe_upload_node_cloud would keep it.  Everything that can be refused
+ * (RGBDFE_ERR_INVALID_ARG: NULL frame / image pointers, unknown encodings, a step smaller than a row, non-positive sizes,
+ * frames that differ in geometry, a cloud_skip that does not divide the visual size, cloud without node_ids) is refused
+ * before any detector state changes.  Node-table rules and the multi-device behaviour are those of
+ * rgbdfe_detect_describe_batch_nodes. */
+int rgbdfe_sensor_detect_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_frame* frames,
+                                              double fx, double fy, double cx, double cy, double depth_scaling,
+                                              int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors,
+                                              float* xyz1, int32_t* n_out, const int32_t* node_ids,
+                                              const rgbdfe_sensor_cloud* cloud);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, every launch of the dominant kernels is bracketed by HIP events on the
  * stream it runs on; totals are read back with rgbdfe_get_kernel_time. */

@@ -159,6 +159,19 @@ class SiftGPUWrapper {
   int max_keypoints_;
 };
 
+// A colour (or mono) image and a raw depth image as the sensor messages carry them (rgbdfe_sensor_frame): what
+// OpenNIListener::noCloudCallback receives.  visual_encoding: RGBDFE_VISUAL_MONO8 / _RGB8 / _BGR8 (sensor_msgs "mono8" / "rgb8" /
+// "bgr8"); depth_encoding: RGBDFE_DEPTH_32FC1 (metres) / _16UC1 (millimetres).  Steps are bytes per row (cv::Mat::step).
+struct SensorFrame : rgbdfe_sensor_frame {
+  SensorFrame(const uint8_t* visual_data, int visual_rows_, int visual_cols_, size_t visual_step_, int visual_encoding_,
+              const void* depth_data, int depth_rows_, int depth_cols_, size_t depth_step_, int depth_encoding_) {
+    visual = visual_data; visual_rows = visual_rows_; visual_cols = visual_cols_; visual_step = (int32_t)visual_step_;
+    visual_encoding = visual_encoding_;
+    depth = depth_data; depth_rows = depth_rows_; depth_cols = depth_cols_; depth_step = (int32_t)depth_step_;
+    depth_encoding = depth_encoding_;
+  }
+};
+
 class Node {  // the slice of src/node.h the pair path touches
  public:
   // feature_descriptors: n x 32 bytes (cv::Mat CV_8U, continuous); feature_locations_3d: n x (x,y,z,1)
@@ -180,6 +193,26 @@ class Node {  // the slice of src/node.h the pair path touches
     int32_t n = 0;
     if (rgbdfe_detect_describe(fe_.get(), gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling, kp.data(),
                                feature_descriptors_.data(), feature_locations_3d_.data(), &n) != RGBDFE_OK)
+      n = 0;
+    n_ = n;
+    feature_descriptors_.resize((size_t)n * 32);
+    feature_locations_3d_.resize((size_t)n * 4);
+    feature_locations_2d_.assign(kp.begin(), kp.begin() + n);
+    matchable_ = n > 0 && rgbdfe_upload_node(fe_.get(), id_, feature_descriptors_.data(), feature_locations_3d_.data(), n) == RGBDFE_OK;
+  }
+  // The same constructor on the images as the listener receives them (openni_listener.cpp:651-659 + node.cpp:139-210): the
+  // depth image is resampled to the visual size where it differs, depthToCV8UC1 makes the detection mask (and metres of a
+  // 16UC1 image), a CV_8UC3 image goes through CV_RGB2GRAY -- all on the device, in front of the steps above
+  // (rgbdfe_sensor_detect_describe).
+  Node(const FrontEnd& fe, int id, const SensorFrame& frame, double fx, double fy, double cx, double cy, double depth_scaling,
+       int max_keypoints)
+      : id_(id), fe_(fe), n_(0) {
+    std::vector<rgbdfe_keypoint> kp((size_t)max_keypoints);
+    feature_descriptors_.resize((size_t)max_keypoints * 32);
+    feature_locations_3d_.resize((size_t)max_keypoints * 4);
+    int32_t n = 0;
+    if (rgbdfe_sensor_detect_describe(fe_.get(), &frame, fx, fy, cx, cy, depth_scaling, kp.data(), feature_descriptors_.data(),
+                                      feature_locations_3d_.data(), &n) != RGBDFE_OK)
       n = 0;
     n_ = n;
     feature_descriptors_.resize((size_t)n * 32);

@@ -64,6 +64,23 @@ class RgbdfeMatchResult(C.Structure):
     ]
 
 
+VISUAL_MONO8, VISUAL_RGB8, VISUAL_BGR8 = 0, 1, 2   # RGBDFE_VISUAL_*
+DEPTH_32FC1, DEPTH_16UC1 = 0, 1                     # RGBDFE_DEPTH_*
+
+
+class RgbdfeSensorFrame(C.Structure):   # rgbdfe_sensor_frame
+    _fields_ = [
+        ("visual", C.c_void_p), ("visual_rows", C.c_int32), ("visual_cols", C.c_int32), ("visual_step", C.c_int32),
+        ("visual_encoding", C.c_int32),
+        ("depth", C.c_void_p), ("depth_rows", C.c_int32), ("depth_cols", C.c_int32), ("depth_step", C.c_int32),
+        ("depth_encoding", C.c_int32),
+    ]
+
+
+class RgbdfeSensorCloud(C.Structure):   # rgbdfe_sensor_cloud
+    _fields_ = [("cloud_skip", C.c_int32), ("encoding_bgr", C.c_int32), ("min_depth", C.c_double)]
+
+
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4")])
 
@@ -350,6 +367,18 @@ def load():
     L.rgbdfe_sift_detect_orb_describe_batch_nodes.restype = C.c_int
     L.rgbdfe_sift_detect_orb_describe_batch_nodes.argtypes = [ctx, i32, vp, vp, i32, i32, C.c_double, C.c_double, C.c_double,
                                                               C.c_double, C.c_double, i32, vp, i32, vp, vp, vp, vp]
+    L.rgbdfe_sizeof_sensor_frame.restype = C.c_int
+    if L.rgbdfe_sizeof_sensor_frame() != C.sizeof(RgbdfeSensorFrame):
+        raise RgbdfeError("rgbdfe_sensor_frame layout mismatch between librgbdfe.so and the binding")
+    L.rgbdfe_ingest_frame.restype = C.c_int
+    L.rgbdfe_ingest_frame.argtypes = [ctx, C.POINTER(RgbdfeSensorFrame), vp, vp, vp]
+    L.rgbdfe_sensor_detect_describe.restype = C.c_int
+    L.rgbdfe_sensor_detect_describe.argtypes = [ctx, C.POINTER(RgbdfeSensorFrame), C.c_double, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, vp, vp, vp, C.POINTER(i32)]
+    L.rgbdfe_sensor_detect_describe_batch_nodes.restype = C.c_int
+    L.rgbdfe_sensor_detect_describe_batch_nodes.argtypes = [ctx, i32, C.POINTER(RgbdfeSensorFrame), C.c_double, C.c_double,
+                                                            C.c_double, C.c_double, C.c_double, i32, vp, vp, vp, vp, vp,
+                                                            C.POINTER(RgbdfeSensorCloud)]
     L.rgbdfe_sift_geometry.restype = C.c_int
     L.rgbdfe_sift_geometry.argtypes = [ctx] + [C.POINTER(i32)] * 4
     L.rgbdfe_sift_debug_plane.restype = C.c_int
@@ -408,4 +437,6 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_sift_detect_batch_nodes", "rgbdfe_set_detector_type", "rgbdfe_fast_detect",
     "rgbdfe_detect", "rgbdfe_detect_sift_describe", "rgbdfe_detect_sift_describe_batch_nodes",
     "rgbdfe_sift_detect_orb_describe", "rgbdfe_sift_detect_orb_describe_batch_nodes",
+    "rgbdfe_sizeof_sensor_frame", "rgbdfe_ingest_frame", "rgbdfe_sensor_detect_describe",
+    "rgbdfe_sensor_detect_describe_batch_nodes",
 ]

@@ -91,6 +91,7 @@ void rgbdfe_destroy(rgbdfe_ctx* ctx) {
   sift_nodes_release(ctx);
   sift_behind_release(ctx);
   sift_orb_release(ctx);
+  sensor_release(ctx);
   drain_pending(ctx);
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   for (auto& ge : ctx->graphs) { (void)hipGraphExecDestroy(ge.exec); (void)hipGraphDestroy(ge.graph); }

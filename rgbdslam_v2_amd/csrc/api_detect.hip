@@ -545,11 +545,16 @@ int rgbdfe_sift_geometry(rgbdfe_ctx* ctx, int32_t* octave_min, int32_t* octave_n
 struct DetectFrame {
   rgbdfe_ctx* ctx = nullptr;
   const uint8_t* gray = nullptr; const uint8_t* mask = nullptr; const float* depth = nullptr;
+  // a sensor frame in place of the three planes (rgbdfe_sensor_detect_describe*): frame `sframe` of the run; its float depth
+  // plane (min-depth mode only) is ctx->sensor.d_depth[depth_set], written by the ingest launch behind the frame's upload
+  const SensorRun* sensor = nullptr;
+  int sframe = 0, depth_set = 0;
   int32_t rows = 0, cols = 0;
   double fx = 0, fy = 0, cx = 0, cy = 0, depth_scaling = 1;
   rgbdfe_keypoint* keypoints = nullptr; uint8_t* descriptors = nullptr; float* xyz1 = nullptr; int32_t* n_out = nullptr;
   std::vector<KpOut> kps;
   std::vector<float> zmin;
+  float depth_px(int r, int c) const { return sensor ? sensor->depth_at(sframe, r, c) : depth[(size_t)r * cols + c]; }
   std::vector<uint8_t> desc;
   std::vector<int> order;  // compute(): positions, in the list handed to it, of the keypoints it keeps, in output order
   std::vector<float> xyz_in_big, xyz_out_big;
@@ -573,8 +578,13 @@ struct DetectFrame {
     int rc = orb.prepare(cols, rows, true, err);
     if (rc != RGBDFE_OK) return fail(ctx, rc, err);
     // hasNonZero(sub_mask) per cell (feature_adjuster.cpp:175-183)
-    orb.cell_mask_nonzero.assign((size_t)orb.n_cells, mask ? 0 : 1);
-    if (mask)
+    orb.cell_mask_nonzero.assign((size_t)orb.n_cells, (mask || sensor) ? 0 : 1);
+    if (sensor)
+      for (int c = 0; c < orb.n_cells; ++c) {
+        const OrbWorkspace::Cell& ce = orb.cells[c];
+        orb.cell_mask_nonzero[c] = sensor->mask_nonzero(sframe, ce.x0, ce.y0, ce.w, ce.h) ? 1 : 0;
+      }
+    else if (mask)
       for (int c = 0; c < orb.n_cells; ++c) {
         const OrbWorkspace::Cell& ce = orb.cells[c];
         char nz = 0;
@@ -587,7 +597,15 @@ struct DetectFrame {
       }
     // the depth image stays on the host: removeDepthless and projectTo3D look at one pixel per keypoint
     lap(0);
-    if (!uploaded) rc = orb.upload_and_build(gray, mask, ctx->stream, err, -1, /*defer_blur=*/true);
+    if (!uploaded && sensor) {  // raw bytes up, the ingest kernel writes [gray | mask] into the pool (and the depth plane)
+      sensor->stage(sframe, ctx->sensor.h_raw[0]);
+      IngestParams o{};
+      o.gray = orb.d_pool; o.mask = orb.d_pool + (size_t)rows * cols;
+      o.depth_m = ctx->feature_min_depth ? ctx->sensor.d_depth[depth_set] : nullptr;
+      rc = sensor_upload_ingest(ctx, *sensor, 0, 0, 1, o, ctx->stream);
+      if (rc != RGBDFE_OK) return rc;
+      rc = orb.build_uploaded(ctx->stream, err, -1, /*defer_blur=*/true);
+    } else if (!uploaded) rc = orb.upload_and_build(gray, mask, ctx->stream, err, -1, /*defer_blur=*/true);
     lap(1);
     orb.before_wait = prefetch;
     const double pass_before = tm ? orb.timing.us[2] + orb.timing.us[3] + orb.timing.us[4] : 0;
@@ -623,13 +641,13 @@ struct DetectFrame {
       const size_t b_kp = ((size_t)n0 * 12 + 255) & ~(size_t)255;
       rc = ensure_scratch(ctx, b_depth + b_kp + (size_t)n0 * 4 + 256);
       if (rc != RGBDFE_OK) return rc;
-      float* d_depth = (float*)ctx->d_scratch;
+      float* d_depth = sensor ? ctx->sensor.d_depth[depth_set] : (float*)ctx->d_scratch;
       float* d_kps3 = (float*)((char*)ctx->d_scratch + b_depth);
       float* d_z = (float*)((char*)ctx->d_scratch + b_depth + b_kp);
       std::vector<float> h3((size_t)n0 * 3);
       for (int i = 0; i < n0; ++i) { h3[3 * i] = kps[i].x; h3[3 * i + 1] = kps[i].y; h3[3 * i + 2] = kps[i].size; }
       zmin.resize((size_t)n0);
-      HIP_TRY(ctx, hipMemcpyAsync(d_depth, depth, (size_t)rows * cols * 4, hipMemcpyHostToDevice, st));
+      if (!sensor) HIP_TRY(ctx, hipMemcpyAsync(d_depth, depth, (size_t)rows * cols * 4, hipMemcpyHostToDevice, st));
       HIP_TRY(ctx, hipMemcpyAsync(d_kps3, h3.data(), h3.size() * 4, hipMemcpyHostToDevice, st));
       launch_min_depth(d_kps3, n0, d_depth, rows, cols, d_z, st);
       HIP_TRY(ctx, hipGetLastError());
@@ -651,6 +669,7 @@ struct DetectFrame {
       // one scattered read of the 1.2 MB depth image per keypoint: issue them all before the first is needed (the loop
       // below otherwise pays a cache miss per keypoint, ~100 us per frame)
       for (const KpOut& k : kps) {
+        if (sensor) break;
         if (!(k.x >= 0 && k.x < (float)cols && k.y >= 0 && k.y < (float)rows)) continue;
         int r = (int)roundf(k.y), c = (int)roundf(k.x);
         r = r >= rows ? rows - 1 : r;
@@ -663,7 +682,7 @@ struct DetectFrame {
         int r = (int)roundf(k.y), c = (int)roundf(k.x);
         r = r >= rows ? rows - 1 : r;
         c = c >= cols ? cols - 1 : c;
-        if (std::isnan(depth[(size_t)r * cols + c])) continue;
+        if (std::isnan(depth_px(r, c))) continue;
         kps[m++] = k;
       }
       kps.resize(m);
@@ -709,7 +728,7 @@ struct DetectFrame {
         int r = (int)roundf(kps[i].y), c = (int)roundf(kps[i].x);
         r = r >= rows ? rows - 1 : r;
         c = c >= cols ? cols - 1 : c;
-        xyz_in[(size_t)2 * n + i] = depth[(size_t)r * cols + c];
+        xyz_in[(size_t)2 * n + i] = depth_px(r, c);
       }
       if (hipMemcpyAsync(orb.d_kpxy, xyz_in, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)
         return RGBDFE_ERR_HIP;
@@ -763,6 +782,21 @@ int rgbdfe_detect_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* 
                                 keypoints, descriptors, xyz1, n_out, nullptr);
   DetectFrame fr;
   fr.ctx = ctx; fr.gray = gray; fr.mask = mask; fr.depth = depth; fr.rows = rows; fr.cols = cols;
+  fr.fx = fx; fr.fy = fy; fr.cx = cx; fr.cy = cy; fr.depth_scaling = depth_scaling;
+  fr.keypoints = keypoints; fr.descriptors = descriptors; fr.xyz1 = xyz1; fr.n_out = n_out;
+  int rc = fr.detect(false, nullptr);
+  if (rc == RGBDFE_OK) rc = fr.describe_enqueue(ctx->stream);
+  if (rc == RGBDFE_OK) rc = fr.finish(ctx->stream);
+  return rc;
+}
+
+// rgbdfe_detect_describe on frame 0 of a sensor run (the ORB type; the caller holds the lock, has set the device, ensured
+// the detector and ctx->sensor's buffers for one frame)
+int detect_describe_sensor_frame(rgbdfe_ctx* ctx, const SensorRun& run, double fx, double fy, double cx, double cy,
+                                 double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1,
+                                 int32_t* n_out) {
+  DetectFrame fr;
+  fr.ctx = ctx; fr.sensor = &run; fr.sframe = 0; fr.depth_set = 0; fr.rows = run.H; fr.cols = run.W;
   fr.fx = fx; fr.fy = fy; fr.cx = cx; fr.cy = cy; fr.depth_scaling = depth_scaling;
   fr.keypoints = keypoints; fr.descriptors = descriptors; fr.xyz1 = xyz1; fr.n_out = n_out;
   int rc = fr.detect(false, nullptr);
@@ -831,8 +865,9 @@ struct SuperFrameJob {  // one frame of a super-frame, between detection and cop
 // removeDepthless (node.cpp:67-97, :186) + retainBest(max_keypoints) (:188-191) + the CPU half of cv::ORB::compute +
 // projectTo3D's depth look-ups (node.cpp:942) for one frame: DetectFrame::describe_enqueue's host work, no HIP calls
 void super_describe_prepare(const OrbWorkspace& orb, SuperFrameJob& j, int frame_in_super, const float* depth, int rows,
-                            int cols, int max_kp) {
+                            int cols, int max_kp, const SensorRun* sensor = nullptr, int sframe = 0) {
   std::vector<KpOut>& kps = j.kps;
+  auto depth_px = [&](int r, int c) { return sensor ? sensor->depth_at(sframe, r, c) : depth[(size_t)r * cols + c]; };
   if (j.deferred) orb.select_frame(j.pv, frame_in_super, j.thr.data(), kps);
   size_t m = 0;
   for (const KpOut& k : kps) {
@@ -840,7 +875,7 @@ void super_describe_prepare(const OrbWorkspace& orb, SuperFrameJob& j, int frame
     int r = (int)roundf(k.y), c = (int)roundf(k.x);
     r = r >= rows ? rows - 1 : r;
     c = c >= cols ? cols - 1 : c;
-    if (std::isnan(depth[(size_t)r * cols + c])) continue;
+    if (std::isnan(depth_px(r, c))) continue;
     kps[m++] = k;
   }
   kps.resize(m);
@@ -866,14 +901,15 @@ void super_describe_prepare(const OrbWorkspace& orb, SuperFrameJob& j, int frame
     int r = (int)roundf(kps[i].y), c = (int)roundf(kps[i].x);
     r = r >= rows ? rows - 1 : r;
     c = c >= cols ? cols - 1 : c;
-    j.xyz_in[(size_t)2 * n + i] = depth[(size_t)r * cols + c];
+    j.xyz_in[(size_t)2 * n + i] = depth_px(r, c);
   }
 }
 
 int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
                                 const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx,
                                 double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints,
-                                uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids) {
+                                uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids,
+                                const SensorRun* sensor) {
   OrbWorkspace& orb = ctx->orb_super;
   const OrbWorkspace& one = ctx->orb;
   const int pc = one.grid * one.grid;
@@ -892,6 +928,11 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
   int rc = orb.prepare(cols, rows, true, err, B);
   if (rc == RGBDFE_OK) rc = orb.ensure_alt(err);
   if (rc != RGBDFE_OK) return fail(ctx, rc, err);
+  // sensor frames: a raw staging buffer per image staging buffer, a raw device buffer per image set
+  if (sensor) {
+    rc = sensor_ensure(ctx, OrbWorkspace::kStages, OrbWorkspace::kSets, sensor->frame_bytes * (size_t)B, 0, 0);
+    if (rc != RGBDFE_OK) return rc;
+  }
   if (!ctx->orb_upload_stream) {
     HIP_TRY(ctx, create_side_stream(&ctx->orb_upload_stream, -1));   // uploads + pyramids: behind everything else
     HIP_TRY(ctx, create_side_stream(&ctx->orb_compute_stream, +1));  // descriptions: short, the host waits for them
@@ -953,6 +994,11 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
       // (2 W H bytes per frame through one core's memcpy would bound the whole pipeline: 75 us per 640 x 480 frame)
       for (int k = 0; k < count_of(s); ++k) {
         const int f = first_of(s) + k;
+        if (sensor) {  // the raw bytes, nothing else: the ingest kernel behind the upload makes the planes
+          uint8_t* dst = ctx->sensor.h_raw[s % NS] + (size_t)k * sensor->frame_bytes;
+          stage_pool.submit([sensor, f, dst] { sensor->stage(f, dst); });
+          continue;
+        }
         stage_pool.submit([&orb, &gray, &mask, f, s, k, NS] { orb.stage_image_at(gray[f], mask ? mask[f] : nullptr, s % NS, k); });
       }
       stage_pool.wait_all();
@@ -989,7 +1035,15 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
       cv.wait(l, [&] { return staged > s; });
     }
     if (s >= D && hipStreamWaitEvent(up, ctx->orb_describe_done[s % D], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
-    const int r = orb.enqueue_staged_super(count_of(s), up, err, s % D, s % NS);
+    int r;
+    if (sensor) {  // frame k's [gray | mask] pair at k * 2WH of the set's pool (orb_host.hip enqueue_staged_super)
+      IngestParams o{};
+      o.gray = orb.pool_set[s % D]; o.mask = o.gray + (size_t)rows * cols;
+      o.gray_stride = o.mask_stride = (size_t)2 * rows * cols;
+      r = sensor_upload_ingest(ctx, *sensor, s % NS, s % D, count_of(s), o, up);
+      if (r != RGBDFE_OK) { err.clear(); return r; }
+      r = orb.build_uploaded(up, err, s % D, false);
+    } else r = orb.enqueue_staged_super(count_of(s), up, err, s % D, s % NS);
     if (r != RGBDFE_OK) return r;
     if (hipEventRecord(ctx->orb_upload_done[s % D], up) != hipSuccess) { err = "hipEventRecord"; return RGBDFE_ERR_HIP; }
     return RGBDFE_OK;
@@ -998,9 +1052,10 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
   auto start_prepare = [&](int s) {
     std::vector<SuperFrameJob>& J = jobs[s & 1];
     for (int k = 0; k < count_of(s); ++k) {
-      const float* dp = depth[first_of(s) + k];
+      const int sf = first_of(s) + k;
+      const float* dp = sensor ? nullptr : depth[sf];
       SuperFrameJob* j = &J[(size_t)k];
-      pool.submit([&orb, j, k, dp, rows, cols, max_kp] { super_describe_prepare(orb, *j, k, dp, rows, cols, max_kp); });
+      pool.submit([&orb, j, k, dp, rows, cols, max_kp, sensor, sf] { super_describe_prepare(orb, *j, k, dp, rows, cols, max_kp, sensor, sf); });
     }
   };
   // device half: one descriptor-record upload, one rBRIEF launch, one projectTo3D launch per frame, three read-backs
@@ -1117,6 +1172,13 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
     // hasNonZero(sub_mask) per (frame, cell) (feature_adjuster.cpp:175-183)
     orb.cell_mask_nonzero.assign((size_t)orb.n_cells, 1);
     for (int k = 0; k < nf; ++k) {
+      if (sensor) {
+        for (int c9 = 0; c9 < pc; ++c9) {
+          const OrbWorkspace::Cell& ce = orb.cells[(size_t)k * pc + c9];
+          orb.cell_mask_nonzero[(size_t)k * pc + c9] = sensor->mask_nonzero(first_of(s) + k, ce.x0, ce.y0, ce.w, ce.h) ? 1 : 0;
+        }
+        continue;
+      }
       const uint8_t* mk = mask ? mask[first_of(s) + k] : nullptr;
       if (!mk) continue;
       for (int c9 = 0; c9 < pc; ++c9) {
@@ -1207,14 +1269,16 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
 static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
                                         const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx,
                                         double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints,
-                                        uint8_t* descriptors, float* xyz1, int32_t* n_out);
+                                        uint8_t* descriptors, float* xyz1, int32_t* n_out, const SensorRun* sensor);
 // node_ids (may be NULL): frame f's features also become the resident node node_ids[f] (>= 0), see
 // rgbdfe_detect_describe_batch_nodes
 int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
                                  const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx,
                                  double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints,
-                                 uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids) {
-  if (!ctx || n_frames < 0 || (n_frames > 0 && (!gray || !depth || !n_out)) || rows < 1 || cols < 1)
+                                 uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids,
+                                 const SensorRun* sensor) {
+  // (sensor: a validated run of sensor frames in place of the three plane arrays, which are NULL then; api_sensor.hip)
+  if (!ctx || n_frames < 0 || (n_frames > 0 && ((!sensor && (!gray || !depth)) || !n_out)) || rows < 1 || cols < 1)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   if (node_ids)
     for (int32_t f = 0; f < n_frames; ++f)
@@ -1229,20 +1293,24 @@ int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_
   ensure_detector(ctx);
   if (n_frames > 0 && out_stride < ctx->orb_max_keypoints)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "out_stride must be at least the configured max_keypoints");
-  for (int32_t f = 0; f < n_frames; ++f)
+  for (int32_t f = 0; f < n_frames && !sensor; ++f)
     if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
   if (n_frames == 0) return RGBDFE_OK;
+  if (sensor) {
+    const int rc_dev = sensor_run_device(ctx, const_cast<SensorRun&>(*sensor));   // the resampling tables
+    if (rc_dev != RGBDFE_OK) return rc_dev;
+  }
   if (fast)  // feature_detector_type "FAST" (api_fast.hip): its own chunked pipeline, nodes written by its kernels
     return fast_detect_describe(ctx, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling, out_stride, keypoints,
-                                descriptors, xyz1, n_out, node_ids);
+                                descriptors, xyz1, n_out, node_ids, sensor);
   {  // several frames per launch chain (above) unless switched off or the detector is in a mode only the frame path has
     static const bool super_env = !(getenv("RGBDFE_DETECT_SUPER") && atoi(getenv("RGBDFE_DETECT_SUPER")) == 0);
     if (super_env && n_frames >= 2 && !ctx->feature_min_depth && ctx->orb.grid * ctx->orb.grid * 2 <= 64)
       return detect_describe_batch_super(ctx, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling, out_stride,
-                                         keypoints, descriptors, xyz1, n_out, node_ids);
+                                         keypoints, descriptors, xyz1, n_out, node_ids, sensor);
   }
   const int rc_frames = detect_describe_batch_frames(ctx, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling,
-                                                    out_stride, keypoints, descriptors, xyz1, n_out);
+                                                    out_stride, keypoints, descriptors, xyz1, n_out, sensor);
   if (rc_frames != RGBDFE_OK || !node_ids) return rc_frames;
   // the frame-by-frame pipeline hands its nodes over from the host outputs
   std::vector<int32_t> ids, cnt;
@@ -1259,7 +1327,7 @@ int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_
 static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
                                         const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx,
                                         double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints,
-                                        uint8_t* descriptors, float* xyz1, int32_t* n_out) {
+                                        uint8_t* descriptors, float* xyz1, int32_t* n_out, const SensorRun* sensor) {
   OrbWorkspace& orb = ctx->orb;
   std::string err;
   int rc = orb.prepare(cols, rows, true, err);
@@ -1272,6 +1340,10 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
     for (hipEvent_t& e : ctx->orb_describe_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   hipStream_t up = ctx->orb_upload_stream;
+  if (sensor) {  // frame f's raw bytes and float depth plane live in set f & 1 too
+    rc = sensor_ensure(ctx, 2, 2, sensor->frame_bytes, ctx->feature_min_depth ? 2 : 0, (size_t)rows * cols);
+    if (rc != RGBDFE_OK) return rc;
+  }
   // Frame f lives in image set f & 1 (device pyramid + pinned staging buffer).  A helper thread copies the caller's
   // pageable images of frame f into the set's staging buffer as soon as frame f - 2 has been detected (its upload from that
   // buffer is complete then) -- CPU work only: two host threads inside the HIP runtime at once serialise on its locks, and
@@ -1289,7 +1361,8 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
         cv.wait(l, [&] { return stop || detected >= f - 1; });
         if (stop) return;
       }
-      orb.stage_images(gray[f], mask ? mask[f] : nullptr, f & 1);
+      if (sensor) sensor->stage(f, ctx->sensor.h_raw[f & 1]);
+      else orb.stage_images(gray[f], mask ? mask[f] : nullptr, f & 1);
       std::lock_guard<std::mutex> l(m);
       staged = f + 1;
       cv.notify_all();
@@ -1311,7 +1384,9 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
   std::vector<DetectFrame> fr((size_t)2);
   auto init = [&](DetectFrame& d, int32_t f) {
     d = DetectFrame();
-    d.ctx = ctx; d.gray = gray[f]; d.mask = mask ? mask[f] : nullptr; d.depth = depth[f]; d.rows = rows; d.cols = cols;
+    d.ctx = ctx; d.rows = rows; d.cols = cols;
+    if (sensor) { d.sensor = sensor; d.sframe = f; d.depth_set = f & 1; }
+    else { d.gray = gray[f]; d.mask = mask ? mask[f] : nullptr; d.depth = depth[f]; }
     d.fx = fx; d.fy = fy; d.cx = cx; d.cy = cy; d.depth_scaling = depth_scaling;
     d.keypoints = keypoints + (size_t)f * out_stride; d.descriptors = descriptors + (size_t)f * out_stride * 32;
     d.xyz1 = xyz1 + (size_t)f * out_stride * 4; d.n_out = n_out + f;
@@ -1323,7 +1398,15 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
     }
     // the set was frame f - 2's: its description (second stream) reads the pyramid this upload overwrites
     if (f >= 2 && hipStreamWaitEvent(up, ctx->orb_describe_done[f & 1], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
-    const int r = orb.enqueue_staged(mask != nullptr && mask[f] != nullptr, up, err, f & 1);
+    int r;
+    if (sensor) {
+      IngestParams o{};
+      o.gray = orb.pool_set[f & 1]; o.mask = o.gray + (size_t)rows * cols;
+      o.depth_m = ctx->feature_min_depth ? ctx->sensor.d_depth[f & 1] : nullptr;
+      r = sensor_upload_ingest(ctx, *sensor, f & 1, f & 1, 1, o, up);
+      if (r != RGBDFE_OK) { err.clear(); return r; }
+      r = orb.build_uploaded(up, err, f & 1, false);
+    } else r = orb.enqueue_staged(mask != nullptr && mask[f] != nullptr, up, err, f & 1);
     if (r != RGBDFE_OK) return r;
     if (hipEventRecord(ctx->orb_upload_done[f & 1], up) != hipSuccess) { err = "hipEventRecord"; return RGBDFE_ERR_HIP; }
     return RGBDFE_OK;

@@ -187,6 +187,7 @@ struct FastCall {
   rgbdfe_ctx* ctx = nullptr;
   int32_t n_frames = 0;
   const uint8_t* const* gray = nullptr; const uint8_t* const* mask = nullptr; const float* const* depth = nullptr;
+  const SensorRun* sensor = nullptr;   // sensor frames in place of the three plane arrays: ingest.hip's kernel fills the chunk's planes
   int32_t rows = 0, cols = 0;
   bool grid = true, describe = true;
   int fixed_thr = -1;
@@ -211,6 +212,7 @@ int FastCall::run(std::string& err) {
   const int K = FastWorkspace::kSlots;
   for (int i = 0; i < std::min(K, n_chunks); ++i)
     if ((rc = fw.ensure_slot(i, B, err)) != RGBDFE_OK) return rc;
+  if (sensor && (rc = sensor_ensure(ctx, K, K, sensor->frame_bytes * (size_t)B, 0, 0)) != RGBDFE_OK) { err.clear(); return rc; }
   hipStream_t st = fw.st, up = fw.up;
   const size_t plane = fw.plane;
   const int cells = fw.geom.n_cells;
@@ -239,8 +241,10 @@ int FastCall::run(std::string& err) {
     for (int k = 0; k < nf; ++k) {
       const int f = first_of(c) + k;
       const uint8_t* mk = mask ? mask[f] : nullptr;
-      s.h_has_mask[k] = mk ? 1 : 0;
-      auto job = [&s, &plane, this, f, k, mk, B]() {
+      s.h_has_mask[k] = (mk || sensor) ? 1 : 0;
+      uint8_t* const raw = sensor ? ctx->sensor.h_raw[c % K] + (size_t)k * sensor->frame_bytes : nullptr;
+      auto job = [&s, &plane, this, f, k, mk, B, raw]() {
+        if (sensor) { sensor->stage(f, raw); return; }   // the raw bytes, nothing else
         memcpy(s.h_img + (size_t)k * plane, gray[f], plane);
         if (mk) memcpy(s.h_img + ((size_t)B + k) * plane, mk, plane);
         if (describe) memcpy(s.h_depth + (size_t)k * plane, depth[f], plane * 4);
@@ -319,11 +323,19 @@ int FastCall::run(std::string& err) {
       s.h_outs[k] = o;
     }
     // uploads + the blur (it needs nothing but the gray images) on their own stream
-    if (hipMemcpyAsync(s.d_img, s.h_img, (size_t)nf * plane, hipMemcpyHostToDevice, up) != hipSuccess ||
-        (any_mask && hipMemcpyAsync(s.d_img + (size_t)B * plane, s.h_img + (size_t)B * plane, (size_t)nf * plane,
+    if (sensor) {  // frame k: gray at k x plane, mask at (B + k) x plane of d_img, depth at k x plane of d_depth
+      IngestParams o{};
+      o.gray = s.d_img; o.gray_stride = plane;
+      o.mask = s.d_img + (size_t)B * plane; o.mask_stride = plane;
+      if (describe) { o.depth_m = s.d_depth; o.depth_stride = plane; }
+      const int r = sensor_upload_ingest(ctx, *sensor, c % K, c % K, nf, o, up);
+      if (r != RGBDFE_OK) { err.clear(); return r; }
+    }
+    if ((!sensor && hipMemcpyAsync(s.d_img, s.h_img, (size_t)nf * plane, hipMemcpyHostToDevice, up) != hipSuccess) ||
+        (!sensor && any_mask && hipMemcpyAsync(s.d_img + (size_t)B * plane, s.h_img + (size_t)B * plane, (size_t)nf * plane,
                                     hipMemcpyHostToDevice, up) != hipSuccess) ||
         hipMemcpyAsync(s.d_has_mask, s.h_has_mask, (size_t)nf * 4, hipMemcpyHostToDevice, up) != hipSuccess ||
-        (describe && hipMemcpyAsync(s.d_depth, s.h_depth, (size_t)nf * plane * 4, hipMemcpyHostToDevice, up) != hipSuccess) ||
+        (!sensor && describe && hipMemcpyAsync(s.d_depth, s.h_depth, (size_t)nf * plane * 4, hipMemcpyHostToDevice, up) != hipSuccess) ||
         hipMemcpyAsync(s.d_outs, s.h_outs, (size_t)nf * sizeof(FastFrameOut), hipMemcpyHostToDevice, up) != hipSuccess) {
       err = "FAST chunk upload";
       return RGBDFE_ERR_HIP;
@@ -419,7 +431,7 @@ int FastCall::run(std::string& err) {
 int fast_detect_describe(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
                          const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy,
                          double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors,
-                         float* xyz1, int32_t* n_out, const int32_t* node_ids) {
+                         float* xyz1, int32_t* n_out, const int32_t* node_ids, const SensorRun* sensor) {
   if (n_frames == 0) return RGBDFE_OK;
   const int max_kp = ctx->orb_max_keypoints;
   if (node_ids) {  // all-or-nothing on capacity, as the ORB batch (every fresh id counted: empty frames become empty nodes)
@@ -441,7 +453,7 @@ int fast_detect_describe(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const
   call.ctx = ctx; call.n_frames = n_frames; call.gray = gray; call.mask = mask; call.depth = depth; call.rows = rows; call.cols = cols;
   call.fx = fx; call.fy = fy; call.cx = cx; call.cy = cy; call.depth_scaling = depth_scaling;
   call.out_stride = out_stride; call.keypoints = keypoints; call.descriptors = descriptors; call.xyz1 = xyz1; call.n_out = n_out;
-  call.node_ids = node_ids;
+  call.node_ids = node_ids; call.sensor = sensor;
   std::string err;
   const int rc = call.run(err);
   if (rc != RGBDFE_OK) return fail(ctx, rc, err.empty() ? "FAST detection failed" : err);

@@ -12,15 +12,11 @@
 // on the host (bisection with the host's libm erf, then the exact pre-image under the IEEE division by
 // sigma * SQRT_2; api_frame.hip), so neither a device erf nor a division enters the decision.
 #include "rgbdfe_internal.h"
+#include "depth_convert.h"
 
 namespace rgbdfe {
 
-// saturate_cast<uchar>(cvRound(t)): round half to even; NaN / out-of-int-range -> 0 (cvtss2si indefinite)
-__device__ __forceinline__ uint8_t sat_u8_rne(float t) {
-  if (!(t > -2147483648.0f && t < 2147483648.0f)) return 0;
-  const int r = (int)rintf(t);
-  return (uint8_t)min(max(r, 0), 255);
-}
+// (saturate_cast<uchar>(cvRound(.)) and the two convertTo expressions: depth_convert.h, shared with ingest.hip)
 
 __global__ __launch_bounds__(256) void depth_to_mono8_f32_kernel(const float* __restrict__ depth, size_t n,
                                                                 uint8_t* __restrict__ mono8) {
@@ -28,11 +24,11 @@ __global__ __launch_bounds__(256) void depth_to_mono8_f32_kernel(const float* __
   const size_t i4 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     const float4 d = *reinterpret_cast<const float4*>(depth + i4);
-    const uint32_t o = (uint32_t)sat_u8_rne(d.x * 100.0f + 0.0f) | ((uint32_t)sat_u8_rne(d.y * 100.0f + 0.0f) << 8) |
-                       ((uint32_t)sat_u8_rne(d.z * 100.0f + 0.0f) << 16) | ((uint32_t)sat_u8_rne(d.w * 100.0f + 0.0f) << 24);
+    const uint32_t o = (uint32_t)depth_f32_to_mono8(d.x) | ((uint32_t)depth_f32_to_mono8(d.y) << 8) |
+                       ((uint32_t)depth_f32_to_mono8(d.z) << 16) | ((uint32_t)depth_f32_to_mono8(d.w) << 24);
     *reinterpret_cast<uint32_t*>(mono8 + i4) = o;
   } else {
-    for (size_t i = i4; i < n; ++i) mono8[i] = sat_u8_rne(depth[i] * 100.0f + 0.0f);
+    for (size_t i = i4; i < n; ++i) mono8[i] = depth_f32_to_mono8(depth[i]);
   }
 }
 
@@ -41,8 +37,8 @@ __global__ __launch_bounds__(256) void depth_u16_kernel(const uint16_t* __restri
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float v = (float)depth_mm[i];
-  mono8[i] = sat_u8_rne(v * 0.05f + -25.0f);  // misc.cpp:423
-  depth_m[i] = v * 0.001f + 0.0f;             // misc.cpp:424
+  mono8[i] = depth_mm_to_mono8(v);    // misc.cpp:423
+  depth_m[i] = depth_mm_to_metres(v);  // misc.cpp:424
 }
 
 // One lane per cloud point (vi, ui) <- depth pixel (vi*s, ui*s); the reference's running color_idx /

@@ -32,6 +32,7 @@ struct OrbWorkspace {
   // that is constant between two prepare() calls: safe beside a detection running on the current set.
   int upload_and_build(const uint8_t* gray, const uint8_t* mask, hipStream_t s, std::string& err, int set = -1,
                        bool defer_blur = false);
+  int build_uploaded(hipStream_t s, std::string& err, int set = -1, bool defer_blur = false);  // pyramids + blur of a pool already filled
   void build_pyramids(uint8_t* pool, hipStream_t s);
   void stage_images(const uint8_t* gray, const uint8_t* mask, int set);          // CPU half (any thread)
   void stage_image_at(const uint8_t* gray, const uint8_t* mask, int stage, int k);  // super-frame: frame k of staging buffer `stage`

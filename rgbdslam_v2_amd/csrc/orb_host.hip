@@ -466,7 +466,6 @@ void OrbWorkspace::build_pyramids(uint8_t* pool, hipStream_t s) {
 int OrbWorkspace::upload_and_build(const uint8_t* gray, const uint8_t* mask, hipStream_t s, std::string& err, int set,
                                    bool defer_blur) {
   uint8_t* const d_pool = set < 0 ? this->d_pool : pool_set[set];  // shadow the members: the code below is set-agnostic
-  uint8_t* const d_blur = set < 0 ? this->d_blur : blur_set[set];
   uint8_t* const h_img = set < 0 ? this->h_img : himg_set[set];
   // Page-locked caller images (hipHostMalloc / hipHostRegister, e.g. through rgbdfe_host_register) go to the device
   // directly; the frame's results are waited for before the call returns, so the buffers are the caller's again then.
@@ -501,6 +500,14 @@ int OrbWorkspace::upload_and_build(const uint8_t* gray, const uint8_t* mask, hip
     }
     if (!mask) ORB_HIP(hipMemsetAsync(d_pool + img, 255, img, s));
   }
+  return build_uploaded(s, err, set, defer_blur);
+}
+
+// the device half behind an upload: the pyramids and the blur of the [gray | mask] pairs that are in the set's pool already
+// (upload_and_build above; the sensor entry points, whose ingest kernel writes them there)
+int OrbWorkspace::build_uploaded(hipStream_t s, std::string& err, int set, bool defer_blur) {
+  uint8_t* const d_pool = set < 0 ? this->d_pool : pool_set[set];
+  uint8_t* const d_blur = set < 0 ? this->d_blur : blur_set[set];
   build_pyramids(d_pool, s);
   // The blurred levels are the descriptor kernel's input, not the detector's: on the single-call path (one stream) the blur
   // is enqueued by the first detection pass BEHIND its read-back, so that the pass does not queue up behind it.

@@ -426,6 +426,67 @@ int rgbdfe_detect_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const 
   return RGBDFE_ALL(ctx, impl::rgbdfe_upload_nodes(c, (int32_t)ids.size(), ids.data(), dp.data(), xp.data(), cnt.data()));
 }
 
+// ---- sensor frames (api_sensor.hip)
+int rgbdfe_sizeof_sensor_frame(void) { return (int)sizeof(rgbdfe_sensor_frame); }
+
+int rgbdfe_ingest_frame(rgbdfe_ctx* ctx, const rgbdfe_sensor_frame* frame, uint8_t* gray, uint8_t* mono8, float* depth_m) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_ingest_frame(c, frame, gray, mono8, depth_m));
+}
+
+int rgbdfe_sensor_detect_describe(rgbdfe_ctx* ctx, const rgbdfe_sensor_frame* frame, double fx, double fy, double cx, double cy,
+                                  double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1,
+                                  int32_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_sensor_detect_describe(c, frame, fx, fy, cx, cy, depth_scaling, keypoints, descriptors,
+                                                               xyz1, n_out));
+}
+
+int rgbdfe_sensor_detect_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_frame* frames, double fx,
+                                              double fy, double cx, double cy, double depth_scaling, int32_t out_stride,
+                                              rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out,
+                                              const int32_t* node_ids, const rgbdfe_sensor_cloud* cloud) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  // everything about the frames and the cloud request that can be refused, before any detector state changes
+  int rc = guarded(ctx, [&]() -> int {
+    SensorRun run;
+    return impl::sensor_batch_validate(ctx, n_frames, frames, node_ids, cloud, run);
+  });
+  if (rc != RGBDFE_OK) return rc;
+  if (!RGBDFE_IS_GROUP(ctx)) {
+    rc = RGBDFE_FIRST(ctx, impl::rgbdfe_sensor_detect_describe_batch(c, n_frames, frames, fx, fy, cx, cy, depth_scaling, out_stride,
+                                                                     keypoints, descriptors, xyz1, n_out, node_ids));
+  } else {
+    // several devices behind the handle, as rgbdfe_detect_describe_batch_nodes: the frames are processed on the first one,
+    // the nodes go to all of them from the host outputs
+    std::vector<rgbdfe_keypoint> kp_tmp;
+    std::vector<uint8_t> desc_tmp;
+    std::vector<float> xyz_tmp;
+    if (node_ids && n_frames > 0 && out_stride > 0 && rgbdfe_device_context(ctx, 0)->detector_type == RGBDFE_DETECTOR_FAST &&
+        (!keypoints || !descriptors || !xyz1)) {
+      const size_t rows_all = (size_t)n_frames * (size_t)out_stride;
+      if (!keypoints) { kp_tmp.resize(rows_all); keypoints = kp_tmp.data(); }
+      if (!descriptors) { desc_tmp.resize(rows_all * 32); descriptors = desc_tmp.data(); }
+      if (!xyz1) { xyz_tmp.resize(rows_all * 4); xyz1 = xyz_tmp.data(); }
+    }
+    rc = RGBDFE_FIRST(ctx, impl::rgbdfe_sensor_detect_describe_batch(c, n_frames, frames, fx, fy, cx, cy, depth_scaling, out_stride,
+                                                                     keypoints, descriptors, xyz1, n_out, nullptr));
+    if (rc == RGBDFE_OK && node_ids) {
+      std::vector<int32_t> ids, cnt;
+      std::vector<const uint8_t*> dp;
+      std::vector<const float*> xp;
+      for (int32_t f = 0; f < n_frames; ++f)
+        if (node_ids[f] >= 0) {
+          ids.push_back(node_ids[f]); cnt.push_back(n_out[f]);
+          dp.push_back(descriptors + (size_t)f * out_stride * 32); xp.push_back(xyz1 + (size_t)f * out_stride * 4);
+        }
+      rc = RGBDFE_ALL(ctx, impl::rgbdfe_upload_nodes(c, (int32_t)ids.size(), ids.data(), dp.data(), xp.data(), cnt.data()));
+    }
+  }
+  if (rc != RGBDFE_OK || !cloud) return rc;
+  return RGBDFE_ALL(ctx, impl::rgbdfe_sensor_clouds(c, n_frames, frames, fx, fy, cx, cy, depth_scaling, node_ids, cloud));
+}
+
 int rgbdfe_sift_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
                        int32_t max_keypoints, rgbdfe_keypoint* keypoints, float* desc128, int32_t capacity, int32_t* n_out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

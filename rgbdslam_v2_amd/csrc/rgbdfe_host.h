@@ -27,6 +27,7 @@
 #include "orb_host.h"
 #include "sift_extract.h"
 #include "rgbdfe_internal.h"
+#include "sensor_host.h"
 
 using namespace rgbdfe;
 
@@ -312,6 +313,18 @@ struct rgbdfe_ctx {
     void* dev = nullptr; void* pin = nullptr;
     int8_t* d_pattern = nullptr;   // rBRIEF's bit pattern
   } so;
+  // the sensor entry points (api_sensor.hip): page-locked and device buffers for the frames' raw bytes (one per staging
+  // buffer / image set / chunk slot of the pipeline that uses them), the float depth planes of the single-frame paths and
+  // the resampling tables of the latest geometry
+  struct SensorBufs {
+    static constexpr int kPinned = 6, kDevice = 3;
+    uint8_t* h_raw[kPinned] = {}; size_t h_cap[kPinned] = {};
+    uint8_t* d_raw[kDevice] = {}; size_t d_cap[kDevice] = {};
+    float* d_depth[2] = {}; size_t depth_cap[2] = {};
+    uint8_t* d_planes = nullptr; size_t planes_cap = 0;   // rgbdfe_ingest_frame: gray | mono8
+    int32_t* d_maps = nullptr; size_t maps_cap = 0;
+    int maps_key[4] = {0, 0, 0, 0};                       // W, H, dW, dH of the tables in d_maps
+  } sensor;
   int orb_max_keypoints = 0;  // 0 = detector not configured yet
   // feature_detector_type (rgbdfe_set_detector_type): RGBDFE_DETECTOR_ORB or RGBDFE_DETECTOR_FAST.  Both use the detector
   // configuration and the per-cell thresholds of `orb` (the reference's one detector_ object); FAST runs in `fast`.
@@ -382,6 +395,10 @@ int ensure_sift(rgbdfe_ctx* ctx);                 // the float / bf16 node slabs
 void sift_nodes_release(rgbdfe_ctx* ctx);        // rgbdfe_ctx::sn (api_detect.hip)
 void sift_behind_release(rgbdfe_ctx* ctx);       // rgbdfe_ctx::sb (api_sift_behind.hip)
 void sift_orb_release(rgbdfe_ctx* ctx);          // rgbdfe_ctx::so (api_sift_orb.hip)
+void sensor_release(rgbdfe_ctx* ctx);            // rgbdfe_ctx::sensor (api_sensor.hip)
+// rgbdfe_ctx::sensor: n_pinned page-locked and n_device device buffers of `bytes` each for raw frames, and (depth_planes of
+// them, at most 2) float planes of `plane` pixels
+int sensor_ensure(rgbdfe_ctx* ctx, int n_pinned, int n_device, size_t bytes, int depth_planes, size_t plane);
 // rgbdfe_ctx::sn for frames of `plane` pixels: the depth staging and the counts, the host-output rows when host_out (api_detect.hip)
 int sift_nodes_prepare(rgbdfe_ctx* ctx, size_t plane, bool host_out);
 int detector_max_keypoints(rgbdfe_ctx* ctx);     // the detector's max_keypoints (rgbdfe_detector_configure; 600 by default)
@@ -393,10 +410,30 @@ int detect_aggregate(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, 
 int fast_detect_describe(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
                          const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy,
                          double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors,
-                         float* xyz1, int32_t* n_out, const int32_t* node_ids);
+                         float* xyz1, int32_t* n_out, const int32_t* node_ids, const SensorRun* sensor = nullptr);
 int fast_grid_keypoints(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
                         std::vector<KpOut>& kps);
 void kp_to_abi(const std::vector<KpOut>& v, rgbdfe_keypoint* out);
+// ---- sensor frames (api_sensor.hip; the ORB single-frame form in api_detect.hip)
+int sensor_run_build(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_frame* frames, SensorRun& run);   // validation + index tables
+int sensor_run_device(rgbdfe_ctx* ctx, SensorRun& run);                                                     // the tables on the device
+int sensor_batch_validate(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_frame* frames, const int32_t* node_ids,
+                          const rgbdfe_sensor_cloud* cloud, SensorRun& run);
+// nf raw frames staged in ctx->sensor.h_raw[hbuf] -> d_raw[dbuf] on `s`, then the ingest launch into the outputs named in `outs`
+int sensor_upload_ingest(rgbdfe_ctx* ctx, const SensorRun& run, int hbuf, int dbuf, int nf, IngestParams outs, hipStream_t s);
+int detect_describe_sensor_frame(rgbdfe_ctx* ctx, const SensorRun& run, double fx, double fy, double cx, double cy,
+                                 double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1,
+                                 int32_t* n_out);
+int rgbdfe_ingest_frame(rgbdfe_ctx* ctx, const rgbdfe_sensor_frame* frame, uint8_t* gray, uint8_t* mono8, float* depth_m);
+int rgbdfe_sensor_detect_describe(rgbdfe_ctx* ctx, const rgbdfe_sensor_frame* frame, double fx, double fy, double cx, double cy,
+                                  double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1,
+                                  int32_t* n_out);
+int rgbdfe_sensor_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_frame* frames, double fx, double fy,
+                                        double cx, double cy, double depth_scaling, int32_t out_stride,
+                                        rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out,
+                                        const int32_t* node_ids);
+int rgbdfe_sensor_clouds(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_frame* frames, double fx, double fy, double cx,
+                         double cy, double depth_scaling, const int32_t* node_ids, const rgbdfe_sensor_cloud* cloud);
 void rgbdfe_default_config(rgbdfe_config* cfg);
 int rgbdfe_create(const rgbdfe_config* cfg, rgbdfe_ctx** out);
 void rgbdfe_destroy(rgbdfe_ctx* ctx);
@@ -437,7 +474,7 @@ int rgbdfe_sift_debug_plane(rgbdfe_ctx* ctx, int32_t octave, int32_t level, floa
 int rgbdfe_sift_debug_candidates(rgbdfe_ctx* ctx, int32_t octave, int32_t dog_level, float* out, int32_t capacity_rows, int32_t* n);
 int rgbdfe_sift_geometry(rgbdfe_ctx* ctx, int32_t* octave_min, int32_t* octave_num, int32_t* levels, int32_t* dog_levels);
 int rgbdfe_detect_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, const float* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out);
-int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask, const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids = nullptr);
+int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask, const float* const* depth, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling, int32_t out_stride, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1, int32_t* n_out, const int32_t* node_ids = nullptr, const SensorRun* sensor = nullptr);
 int rgbdfe_hamming_nn_nodes(rgbdfe_ctx* ctx, int32_t query_id, int32_t train_id, int32_t* out_hd, int32_t* out_idx);
 int rgbdfe_place_recognition_batch(rgbdfe_ctx* ctx, const int32_t* query_ids, int32_t n_queries, const int32_t* candidate_offsets, const int32_t* candidate_ids, int32_t k_neighbours, int32_t max_hd, int32_t max_out, int32_t* out_ids, float* out_scores, int32_t* out_counts);
 int rgbdfe_place_recognition(rgbdfe_ctx* ctx, int32_t query_id, const int32_t* candidate_ids, int32_t n_candidates, int32_t k_neighbours, int32_t max_hd, int32_t max_out, int32_t* out_ids, float* out_scores, int32_t* n_out);

@@ -462,6 +462,92 @@ class FrontEnd:
                 return [(kp[f, : cnt[f]], desc[f, : cnt[f]], xyz[f, : cnt[f]]) for f in range(n)]
             return [(kp[f, : cnt[f]].copy(), desc[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy()) for f in range(n)]
 
+    # ---- sensor frames: the images as the sensor messages carry them (include/rgbdfe.h, "sensor frames")
+    @staticmethod
+    def _sensor_frame(visual, depth, visual_encoding=None):
+        """(rgbdfe_sensor_frame, the arrays it points into) of a visual image ([H, W] uint8 = mono8, [H, W, 3] uint8 = "rgb8" or
+        "bgr8") and a depth image (float32 = 32FC1 metres, uint16 = 16UC1 millimetres).  Row strides are taken from the arrays;
+        the pixels of a row must be contiguous."""
+        v = np.asarray(visual)
+        d = np.asarray(depth)
+        if v.dtype != np.uint8 or v.ndim not in (2, 3) or (v.ndim == 3 and v.shape[2] != 3):
+            raise ValueError("visual image: [H, W] or [H, W, 3] uint8")
+        if d.ndim != 2 or d.dtype not in (np.dtype(np.float32), np.dtype(np.uint16)):
+            raise ValueError("depth image: [H, W] float32 (metres) or uint16 (millimetres)")
+        ch = 1 if v.ndim == 2 else 3
+        if (v.ndim == 3 and v.strides[2] != 1) or v.strides[1] != ch or v.strides[0] < v.shape[1] * ch:
+            v = np.ascontiguousarray(v)
+        if d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize:
+            d = np.ascontiguousarray(d)
+        if ch == 1:
+            enc = _lib.VISUAL_MONO8
+        else:
+            enc = {None: _lib.VISUAL_RGB8, "rgb8": _lib.VISUAL_RGB8, "bgr8": _lib.VISUAL_BGR8}[visual_encoding]
+        fr = _lib.RgbdfeSensorFrame(
+            v.ctypes.data, v.shape[0], v.shape[1], v.strides[0], enc,
+            d.ctypes.data, d.shape[0], d.shape[1], d.strides[0], _lib.DEPTH_16UC1 if d.dtype == np.uint16 else _lib.DEPTH_32FC1)
+        return fr, (v, d)
+
+    def ingest_frame(self, visual, depth, visual_encoding=None, gray=True, mono8=True, depth_m=True):
+        """The listener's and Node::Node's image preparation of one sensor frame on the device (rgbdfe_ingest_frame): returns
+        (gray, mono8 mask, depth in metres) at the visual image's size; an output that is switched off is None."""
+        fr, keep = self._sensor_frame(visual, depth, visual_encoding)
+        shape = (fr.visual_rows, fr.visual_cols)
+        g = np.zeros(shape, np.uint8) if gray else None
+        m = np.zeros(shape, np.uint8) if mono8 else None
+        dm = np.zeros(shape, np.float32) if depth_m else None
+        self._check(self._L.rgbdfe_ingest_frame(self._ctx, C.byref(fr), None if g is None else g.ctypes.data,
+                                                None if m is None else m.ctypes.data, None if dm is None else dm.ctypes.data))
+        del keep
+        return g, m, dm
+
+    def sensor_detect_describe(self, visual, depth, fx, fy, cx, cy, depth_scaling=1.0, visual_encoding=None):
+        """detect_describe on a sensor frame (rgbdfe_sensor_detect_describe): the results of detect_describe on the planes of
+        ingest_frame.  Returns (keypoints KEYPOINT_DTYPE, descriptors [n,32] uint8, xyz1 [n,4] float32)."""
+        fr, keep = self._sensor_frame(visual, depth, visual_encoding)
+        cap = getattr(self, "_max_keypoints", 600)
+        kp = np.zeros(cap, _lib.KEYPOINT_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        xyz = np.zeros((cap, 4), np.float32)
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_sensor_detect_describe(self._ctx, C.byref(fr), fx, fy, cx, cy, depth_scaling, kp.ctypes.data,
+                                                          desc.ctypes.data, xyz.ctypes.data, C.byref(n)))
+        del keep
+        return kp[: n.value].copy(), desc[: n.value].copy(), xyz[: n.value].copy()
+
+    def sensor_detect_describe_batch_nodes(self, visuals, depths, fx, fy, cx, cy, depth_scaling=1.0, node_ids=None,
+                                           visual_encoding=None, host_outputs=True, cloud_skip=None, cloud_encoding_bgr=False,
+                                           cloud_min_depth=0.0):
+        """detect_describe_batch on a run of sensor frames of one geometry (rgbdfe_sensor_detect_describe_batch_nodes).  Returns
+        a list of (keypoints, descriptors, xyz1) per frame, or the per-frame counts with host_outputs=False (node_ids, FAST
+        detector).  cloud_skip: frame f's structured cloud is also kept under node_ids[f] (upload_node_cloud's)."""
+        n = len(visuals)
+        if n == 0:
+            return []
+        built = [self._sensor_frame(visuals[i], depths[i], visual_encoding) for i in range(n)]
+        frames = (_lib.RgbdfeSensorFrame * n)(*[b[0] for b in built])
+        cap = getattr(self, "_max_keypoints", 600)
+        kp = np.zeros((n, cap), _lib.KEYPOINT_DTYPE)
+        desc = np.zeros((n, cap, 32), np.uint8)
+        xyz = np.zeros((n, cap, 4), np.float32)
+        cnt = np.zeros(n, np.int32)
+        ids = None
+        if node_ids is not None:
+            ids = np.ascontiguousarray(node_ids, np.int32)
+            if ids.shape != (n,):
+                raise ValueError("node_ids must hold one id per frame")
+        cloud = None
+        if cloud_skip is not None:
+            cloud = C.pointer(_lib.RgbdfeSensorCloud(int(cloud_skip), 1 if cloud_encoding_bgr else 0, float(cloud_min_depth)))
+        outs = (kp.ctypes.data, desc.ctypes.data, xyz.ctypes.data) if host_outputs else (None, None, None)
+        self._check(self._L.rgbdfe_sensor_detect_describe_batch_nodes(
+            self._ctx, n, frames, fx, fy, cx, cy, depth_scaling, cap, *outs, cnt.ctypes.data,
+            None if ids is None else ids.ctypes.data, cloud))
+        del built
+        if not host_outputs:
+            return cnt.copy()
+        return [(kp[f, : cnt[f]].copy(), desc[f, : cnt[f]].copy(), xyz[f, : cnt[f]].copy()) for f in range(n)]
+
     def orb_detect(self, gray, mask, fast_threshold, capacity=60000):
         """cv::ORB::create(10000,1.2,8,15,0,2,HARRIS,31,thr)->detect(gray, kps, mask) (feature_adjuster.cpp:94).
         Raises RgbdfeError (RGBDFE_ERR_CAPACITY) when more than `capacity` keypoints are found."""
