@@ -428,6 +428,39 @@ int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all,
                                      double observability_threshold, double* quality);
 
+/* ---- map assembly: the resident node clouds as one world-frame cloud --------------------------------------
+ * rgbdfe_assemble_map is transformAndAppendPointCloud (misc.cpp:183-238, the non-HEMACLOUDS form) over a list of
+ *   resident node clouds: the loop of GraphManager::saveAllCloudsToFile (graph_mgr_io.cpp:529-552), on the device.
+ *   node_ids are processed in the order given (pass graph_ order, without the nodes that have no valid estimate); an
+ *   id may appear more than once; clouds of different sizes may be mixed.  transforms: n_nodes x 16 floats, each a
+ *   column-major Matrix4f = pcl_ros::transformAsMatrix(world2cam); the composition world2cam = cam2rgb *
+ *   eigenTransf2TF(v->estimate()) stays with the caller.  maximum_depth is the parameter of that name, taken as
+ *   float: negative or NaN disables the range clip, +inf (the reference default) never clips.
+ *   preserve_raster == 0 ("preserve_raster_on_save" off): points beyond the range (squared distance in float >
+ *   maximum_depth squared) and points with a NaN coordinate are dropped, the others are transformed; the output is
+ *   the kept points in (node, point) order.  preserve_raster != 0: every point keeps its row; a point beyond the
+ *   range gets quiet-NaN coordinates (0x7fc00000) and keeps its rgb word, a point with a NaN coordinate is copied
+ *   untransformed (the finite x, y "at 1 m" beside a NaN z of createXYZRGBPointCloud included).
+ *   out: capacity rows of 4 floats (x, y, z, rgb bits).  *n_out = rows of the assembled cloud; node_offsets (may be
+ *   NULL; n_nodes + 1 entries) = the first output row of every node, node_offsets[n_nodes] = *n_out, in both modes.
+ *   capacity < *n_out: RGBDFE_ERR_CAPACITY with *n_out = the needed size (out's contents are then unspecified); the
+ *   sum of the listed clouds' sizes always suffices.  An id without a cloud: RGBDFE_ERR_UNKNOWN_NODE, before any
+ *   device work.  n_nodes == 0: RGBDFE_OK, *n_out = 0.
+ * rgbdfe_assemble_map_device: the same with `d_out` a device pointer of the context's device (the first device of a
+ *   multi-device handle); no point crosses to the host.  The kernels run on `stream` (NULL: the context's own); the
+ *   call returns when they have finished.  n_out and node_offsets are host pointers.
+ * rgbdfe_download_node_cloud: the resident cloud of a node -- rows x cols x 4 floats exactly as cloud_out of
+ *   rgbdfe_upload_node_cloud would have received them, also for the clouds the sensor batch path keeps.  rows / cols
+ *   (may be NULL) are set whenever the node has a cloud; capacity_points < rows x cols: RGBDFE_ERR_CAPACITY. */
+int rgbdfe_assemble_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                        double maximum_depth, int32_t preserve_raster, float* out, int64_t capacity, int64_t* n_out,
+                        int64_t* node_offsets);
+int rgbdfe_assemble_map_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                               double maximum_depth, int32_t preserve_raster, void* d_out, int64_t capacity,
+                               int64_t* n_out, int64_t* node_offsets, void* stream);
+int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_out, int64_t capacity_points,
+                               int32_t* rows, int32_t* cols);
+
 /* ---- candidate selection for loop closure ----------------------------------
  * rgbdfe_potential_edge_targets is GraphManager::getPotentialEdgeTargetsWithDijkstra (graph_manager.cpp:204-324): the
  * ids of the earlier nodes a new node is to be compared with -- `sequential_targets` direct predecessors, then

@@ -303,6 +303,15 @@ class Node {  // the slice of src/node.h the pair path touches
     return rgbdfe_upload_node_cloud(fe_.get(), id_, depth, rows, cols, rgb, rgb_channels, encoding_bgr ? 1 : 0, fx, fy,
                                     cx, cy, depth_scaling, minimum_depth, cloud_creation_skip_step, nullptr) == RGBDFE_OK;
   }
+  // ... and a copy of it for the host: rows x cols x (x, y, z, rgb bits), also for a cloud the sensor batch path has kept
+  bool pointCloud(std::vector<float>* cloud, int* rows = nullptr, int* cols = nullptr) const {
+    int32_t r = 0, c = 0;
+    if (rgbdfe_download_node_cloud(fe_.get(), id_, nullptr, 0, &r, &c) != RGBDFE_ERR_CAPACITY) return false;
+    cloud->resize((size_t)r * (size_t)c * 4);
+    if (rows) *rows = r;
+    if (cols) *cols = c;
+    return rgbdfe_download_node_cloud(fe_.get(), id_, cloud->data(), (int64_t)r * c, &r, &c) == RGBDFE_OK;
+  }
   // feature_locations_2d_ (node.h:160): only the g2o pair refinement reads them (params.g2o_iterations > 0,
   // node.cpp:1222-1268); kp_xy = n x (u, v)
   bool setKeypoints(const float* kp_xy) { return rgbdfe_upload_node_keypoints(fe_.get(), id_, kp_xy, n_) == RGBDFE_OK; }
@@ -393,6 +402,31 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
   const FrontEnd& fe_;
   std::unique_ptr<rgbdfe_pose_graph, void (*)(rgbdfe_pose_graph*)> topology_;
 };
+
+// The loop of GraphManager::saveAllCloudsToFile (src/graph_mgr_io.cpp:529-552): transformAndAppendPointCloud
+// (src/misc.cpp:183-238) for the pc_col of every listed node, on the device.  node_ids in graph_ order without the nodes
+// that have no valid estimate; world2cam = n x 16 floats, the column-major Matrix4f of pcl_ros::transformAsMatrix(cam2rgb *
+// eigenTransf2TF(v->estimate())) per node; maximum_depth and preserve_raster_on_save are the parameters of those names.
+// aggregate_cloud = rows of (x, y, z, rgb bits); node_offsets (optional) = the first row of every node, then the row count.
+inline bool assembleAllClouds(const FrontEnd& fe, const std::vector<int32_t>& node_ids, const std::vector<float>& world2cam,
+                              double maximum_depth, bool preserve_raster_on_save, std::vector<float>* aggregate_cloud,
+                              std::vector<int64_t>* node_offsets = nullptr) {
+  if (world2cam.size() != node_ids.size() * 16) return false;
+  std::vector<int64_t> off(node_ids.size() + 1, 0);
+  int64_t n = 0;
+  const int32_t raster = preserve_raster_on_save ? 1 : 0;
+  // the size first (RGBDFE_ERR_CAPACITY reports it; an empty result is RGBDFE_OK), then the points
+  int rc = rgbdfe_assemble_map(fe.get(), (int32_t)node_ids.size(), node_ids.data(), world2cam.data(), maximum_depth, raster,
+                               nullptr, 0, &n, off.data());
+  if (rc != RGBDFE_OK && rc != RGBDFE_ERR_CAPACITY) return false;
+  aggregate_cloud->resize((size_t)n * 4);
+  if (rc == RGBDFE_ERR_CAPACITY &&
+      rgbdfe_assemble_map(fe.get(), (int32_t)node_ids.size(), node_ids.data(), world2cam.data(), maximum_depth, raster,
+                          aggregate_cloud->data(), n, &n, off.data()) != RGBDFE_OK)
+    return false;
+  if (node_offsets) *node_offsets = off;
+  return true;
+}
 
 // 4x4 inverse of a column-major float matrix (the reference calls Eigen's Matrix4f::inverse(), node.cpp:1536):
 // Gauss-Jordan with partial pivoting in double, rounded to float

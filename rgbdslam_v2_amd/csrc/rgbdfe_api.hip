@@ -824,6 +824,28 @@ int rgbdfe_release_node_cloud(rgbdfe_ctx* ctx, int32_t node_id) {
   return RGBDFE_ALL(ctx, impl::rgbdfe_release_node_cloud(c, node_id));
 }
 
+// the clouds are replicated on every device of a group: served from the first one, like the other read-only frame-level calls
+int rgbdfe_assemble_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth,
+                        int32_t preserve_raster, float* out, int64_t capacity, int64_t* n_out, int64_t* node_offsets) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_assemble_map(c, n_nodes, node_ids, transforms, maximum_depth, preserve_raster, out, capacity,
+                                                     n_out, node_offsets));
+}
+
+int rgbdfe_assemble_map_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                               double maximum_depth, int32_t preserve_raster, void* d_out, int64_t capacity, int64_t* n_out,
+                               int64_t* node_offsets, void* stream) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_assemble_map_device(c, n_nodes, node_ids, transforms, maximum_depth, preserve_raster, d_out,
+                                                            capacity, n_out, node_offsets, stream));
+}
+
+int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_out, int64_t capacity_points, int32_t* rows,
+                               int32_t* cols) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_download_node_cloud(c, node_id, cloud_out, capacity_points, rows, cols));
+}
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

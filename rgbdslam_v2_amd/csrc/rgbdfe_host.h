@@ -1,6 +1,6 @@
 // rgbdfe_host.h -- what the host-side translation units of librgbdfe.so share: the context (node store, lanes, graph cache,
 // staging), the batch machinery's entry points (api_batches.hip), the single-device implementation of every entry point
-// (namespace impl: api_context / api_pairs / api_detect / api_frame.hip) and the multi-device group (api_group.hip).
+// (namespace impl: api_context / api_pairs / api_detect / api_frame / api_map.hip) and the multi-device group (api_group.hip).
 // rgbdfe_api.hip holds the extern "C" layer only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -385,7 +385,7 @@ int wait_ticket(rgbdfe_ctx* ctx, int64_t ticket, hipStream_t stream);
       return fail(ctx, RGBDFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
-// ---- the single-device implementation of the entry points (api_context / api_pairs / api_detect / api_frame.hip)
+// ---- the single-device implementation of the entry points (api_context / api_pairs / api_detect / api_frame / api_map.hip)
 namespace impl {
 // helpers shared between the implementation files
 int upload_nodes_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const uint8_t* const* desc,
@@ -493,6 +493,9 @@ int rgbdfe_sift_node_features(rgbdfe_ctx* ctx, const float* kp_xy, const float* 
 int rgbdfe_depth_to_mono8(rgbdfe_ctx* ctx, const void* depth, int32_t depth_is_u16, int32_t rows, int32_t cols, uint8_t* mono8, float* depth_m);
 int rgbdfe_upload_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* depth, int32_t rows, int32_t cols, const uint8_t* rgb, int32_t rgb_channels, int32_t encoding_bgr, double fx, double fy, double cx, double cy, double depth_scaling, double min_depth, int32_t cloud_skip, float* cloud_out);
 int rgbdfe_release_node_cloud(rgbdfe_ctx* ctx, int32_t node_id);
+int rgbdfe_assemble_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth, int32_t preserve_raster, float* out, int64_t capacity, int64_t* n_out, int64_t* node_offsets);
+int rgbdfe_assemble_map_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth, int32_t preserve_raster, void* d_out, int64_t capacity, int64_t* n_out, int64_t* node_offsets, void* stream);
+int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_out, int64_t capacity_points, int32_t* rows, int32_t* cols);
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids, const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out);
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all, double observability_threshold, double* quality);
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);

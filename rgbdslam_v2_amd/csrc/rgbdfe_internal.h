@@ -252,6 +252,26 @@ void launch_create_cloud(const float* depth, int rows, int cols, const uint8_t* 
 void launch_decimate_cloud(const float4* cloud, int ch, int cw, int skip_step, float4* out, hipStream_t stream);
 void launch_emm(const EmmJob* jobs, int n_jobs, int ch, int cw, int skip_step, double d_lo, double d_hi,
                 uint32_t* counts, hipStream_t stream);
+// map_assembly.hip: transformAndAppendPointCloud (misc.cpp:183-238) over a list of resident clouds.  The (node, point)
+// sequence is cut into tiles of kMapTile points that never cross a node; the table has n_nodes + 1 rows (the last one a
+// sentinel: first_point = all points, first_tile = all tiles), tile_node[t] = the node of tile t.
+constexpr uint32_t kMapTile = 1024;
+struct MapNode {
+  const float4* cloud;
+  int64_t first_point;   // points of the nodes listed before this one (its first row in raster mode)
+  uint32_t n_points;
+  uint32_t first_tile;
+  float R[9], t[3];      // rot (row-major) and trans of the Matrix4f
+};
+static_assert(sizeof(MapNode) == 72, "MapNode layout");
+void launch_map_raster(const MapNode* nodes, const uint32_t* tile_node, uint32_t n_tiles, bool clip, float md2, float4* out,
+                       hipStream_t stream);
+// compact mode, first half: tile_count[t] = kept points of tile t; tile_first[t] = those in front of tile t
+// (tile_first[n_tiles] = the total); node_first[k] = first output row of node k (node_first[n_nodes] = the total)
+void launch_map_count_scan(const MapNode* nodes, const uint32_t* tile_node, uint32_t n_nodes, uint32_t n_tiles, bool clip,
+                           float md2, uint32_t* tile_count, int64_t* tile_first, int64_t* node_first, hipStream_t stream);
+void launch_map_write(const MapNode* nodes, const uint32_t* tile_node, uint32_t n_tiles, const int64_t* tile_first, bool clip,
+                      float md2, float4* out, hipStream_t stream);
 void launch_sift_pack(const float* desc_in, const int32_t* kept_idx, const int32_t* n_ptr, int max_rows,
                       bool root_sift, float* raw, float* feat, hipStream_t stream);
 

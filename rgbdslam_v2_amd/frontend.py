@@ -1075,6 +1075,73 @@ class FrontEnd:
     def release_node_cloud(self, node_id):
         self._check(self._L.rgbdfe_release_node_cloud(self._ctx, int(node_id)))
 
+    def node_cloud(self, node_id):
+        """The node's resident structured cloud, rows x cols x 4 float32 (x, y, z, rgb bits): what upload_node_cloud's
+        return_cloud=True returned; also for the clouds sensor_detect_describe_batch_nodes keeps."""
+        rows, cols = C.c_int32(0), C.c_int32(0)
+        st = self._L.rgbdfe_download_node_cloud(self._ctx, int(node_id), None, 0, C.byref(rows), C.byref(cols))
+        if st != -5:  # RGBDFE_ERR_CAPACITY: rows, cols are set (anything else: an unknown node)
+            self._check(st)
+        out = np.empty((rows.value, cols.value, 4), np.float32)
+        self._check(self._L.rgbdfe_download_node_cloud(self._ctx, int(node_id), out.ctypes.data, rows.value * cols.value,
+                                                       C.byref(rows), C.byref(cols)))
+        return out
+
+    def _map_args(self, node_ids, transforms):
+        node_ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        T = np.ascontiguousarray(np.asarray(transforms, np.float32).reshape(-1, 4, 4).transpose(0, 2, 1))  # column-major
+        if len(T) != len(node_ids):
+            raise ValueError("one 4 x 4 transform per listed node")
+        return node_ids, T
+
+    def assemble_map(self, node_ids, transforms, maximum_depth=float("inf"), preserve_raster=False, return_offsets=False,
+                     capacity=None, out=None):
+        """transformAndAppendPointCloud (misc.cpp:183-238) over the resident clouds of node_ids, in that order:
+        GraphManager::saveAllCloudsToFile's aggregate cloud.  transforms: n x 4 x 4 (row-major numpy matrices, the
+        Matrix4f of world2cam per node).  Returns the [n, 4] float32 points (x, y, z, rgb bits), with return_offsets also
+        the int64 first row of every node (n_nodes + 1 entries).  capacity: rows of the output buffer; by default the
+        kept points are counted first (compact mode) and the buffer is sized to them.  out: a contiguous [capacity, 4]
+        float32 array to assemble into (the result is a view of its first rows)."""
+        node_ids, T = self._map_args(node_ids, transforms)
+        n = len(node_ids)
+        n_out = C.c_int64(0)
+        offsets = np.zeros(n + 1, np.int64)
+
+        def call(out, cap):
+            return self._L.rgbdfe_assemble_map(self._ctx, n, node_ids.ctypes.data, T.ctypes.data, float(maximum_depth),
+                                               int(bool(preserve_raster)), out.ctypes.data if out is not None else None,
+                                               cap, C.byref(n_out), offsets.ctypes.data)
+        if out is not None:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.ndim == 2 and out.shape[1] == 4 and
+                    out.flags.c_contiguous):
+                raise ValueError("out must be a contiguous [capacity, 4] float32 array")
+            capacity = len(out)
+        elif capacity is None:
+            st = call(None, 0)  # the size: RGBDFE_ERR_CAPACITY with n_out set, or OK for an empty cloud
+            if st != -5:
+                self._check(st)
+            capacity = n_out.value
+        if out is None:
+            out = np.empty((int(capacity), 4), np.float32)
+        self._check(call(out, int(capacity)))
+        out = out[:n_out.value]
+        return (out, offsets) if return_offsets else out
+
+    def assemble_map_device(self, node_ids, transforms, out, maximum_depth=float("inf"), preserve_raster=False,
+                            return_offsets=False, stream=None):
+        """assemble_map into `out`, a contiguous float32 torch tensor [capacity, 4] on this context's device; no point
+        crosses to the host.  Returns the number of rows written (and the offsets)."""
+        node_ids, T = self._map_args(node_ids, transforms)
+        if not (out.is_cuda and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 4 and out.element_size() == 4):
+            raise ValueError("out must be a contiguous [capacity, 4] float32 tensor on the device")
+        n = len(node_ids)
+        n_out = C.c_int64(0)
+        offsets = np.zeros(n + 1, np.int64)
+        self._check(self._L.rgbdfe_assemble_map_device(
+            self._ctx, n, node_ids.ctypes.data, T.ctypes.data, float(maximum_depth), int(bool(preserve_raster)),
+            out.data_ptr() if out.shape[0] else None, int(out.shape[0]), C.byref(n_out), offsets.ctypes.data, stream))
+        return (n_out.value, offsets) if return_offsets else n_out.value
+
     def observation_likelihood(self, new_ids, old_ids, transforms, emm_skip_step=8):
         """observationLikelihood (misc.cpp:814-969) for a batch of directed edges; transforms: n x 4 x 4
         (row-major numpy matrices, new -> old).  Returns an n x 4 uint32 array (inliers, outliers, occluded, all)."""
