@@ -178,6 +178,71 @@ const char* rgbdfe_status_string(int status) {
 
 const char* rgbdfe_last_error(rgbdfe_ctx* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
+}  // namespace impl
+
+// ---- the node table (rgbdfe_host.h); ctx->mu is held
+namespace rgbdfe_host {
+
+int wait_for_pair_lanes(rgbdfe_ctx* ctx) {
+  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  return RGBDFE_OK;
+}
+
+static int no_free_slot(rgbdfe_ctx* ctx) { return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)"); }
+
+// a free slot becomes the empty node `node_id` of `kind`: the slot and the entry that names it change hands together
+static uint32_t register_fresh_node(rgbdfe_ctx* ctx, int32_t node_id, uint32_t kind) {
+  const uint32_t slot = ctx->free_slots.back();
+  ctx->free_slots.pop_back();
+  ctx->nodes[node_id] = NodeEntry{slot, 0u, kind, 0u};
+  return slot;
+}
+
+int acquire_node_slot(rgbdfe_ctx* ctx, int32_t node_id, uint32_t kind, uint32_t* slot, bool lanes_idle) {
+  auto it = ctx->nodes.find(node_id);
+  if (it != ctx->nodes.end()) {  // overwrite in place: wait for batches that may still read it
+    *slot = it->second.slot;
+    return lanes_idle ? RGBDFE_OK : wait_for_pair_lanes(ctx);
+  }
+  if (ctx->free_slots.empty()) return no_free_slot(ctx);
+  *slot = register_fresh_node(ctx, node_id, kind);
+  return RGBDFE_OK;
+}
+
+bool node_id_twice(int32_t n, const int32_t* node_ids, bool negative_is_none) {
+  std::unordered_set<int32_t> seen;
+  seen.reserve((size_t)n * 2);
+  for (int32_t i = 0; i < n; ++i)
+    if (!(negative_is_none && node_ids[i] < 0) && !seen.insert(node_ids[i]).second) return true;
+  return false;
+}
+
+int reserve_node_slots(rgbdfe_ctx* ctx, int32_t n, const int32_t* node_ids, uint32_t kind, std::vector<int64_t>* slot_of,
+                       const char* twice, bool negative_is_none) {
+  if (node_id_twice(n, node_ids, negative_is_none)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, twice);
+  auto none = [&](int32_t i) { return negative_is_none && node_ids[i] < 0; };
+  size_t fresh = 0, resident = 0;
+  for (int32_t i = 0; i < n; ++i)
+    if (!none(i)) ++(ctx->nodes.count(node_ids[i]) ? resident : fresh);
+  if (fresh > ctx->free_slots.size()) return no_free_slot(ctx);
+  if (resident > 0) {  // nodes rewritten in place: wait for batches that may still read them
+    const int rc = wait_for_pair_lanes(ctx);
+    if (rc != RGBDFE_OK) return rc;
+  }
+  if (!slot_of) return RGBDFE_OK;
+  slot_of->assign((size_t)n, -1);
+  for (int32_t i = 0; i < n; ++i) {
+    if (none(i)) continue;
+    auto it = ctx->nodes.find(node_ids[i]);
+    (*slot_of)[(size_t)i] = it != ctx->nodes.end() ? it->second.slot : register_fresh_node(ctx, node_ids[i], kind);
+  }
+  return RGBDFE_OK;
+}
+
+}  // namespace rgbdfe_host
+
+namespace impl {
+
 static int upload_common(rgbdfe_ctx* ctx, int32_t node_id, const void* desc, const void* xyz1,
                          int32_t n, hipMemcpyKind kind, hipStream_t stream, bool sync) {
   if (!ctx || n < 0 || (n > 0 && (!desc || !xyz1))) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad upload arguments");
@@ -185,15 +250,8 @@ static int upload_common(rgbdfe_ctx* ctx, int32_t node_id, const void* desc, con
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   uint32_t slot;
-  auto it = ctx->nodes.find(node_id);
-  if (it != ctx->nodes.end()) {
-    slot = it->second.slot;  // overwrite in place: wait for batches that may still read it
-    for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
-  } else {
-    if (ctx->free_slots.empty()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    slot = ctx->free_slots.back();
-    ctx->free_slots.pop_back();
-  }
+  const int rc = acquire_node_slot(ctx, node_id, 0u, &slot);
+  if (rc != RGBDFE_OK) return rc;
   const size_t row0 = (size_t)slot * (size_t)ctx->cfg.max_keypoints;
   if (n > 0) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_desc + row0 * 8, desc, (size_t)n * 32, kind, stream));
@@ -237,20 +295,16 @@ int rgbdfe_upload_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
 
 int upload_nodes_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const uint8_t* const* desc,
                                const float* const* xyz1, const int32_t* counts) {
-  size_t rows = 0, fresh = 0;
-  bool overwrite = false;
-  std::unordered_set<int32_t> seen;
-  seen.reserve((size_t)n_nodes * 2);
+  size_t rows = 0;
   for (int32_t i = 0; i < n_nodes; ++i) {
     if (counts[i] < 0 || (counts[i] > 0 && (!desc[i] || !xyz1[i]))) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad upload arguments");
     if (counts[i] > ctx->cfg.max_keypoints) return fail(ctx, RGBDFE_ERR_CAPACITY, "node has more rows than max_keypoints");
-    if (!seen.insert(node_ids[i]).second) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice in one upload");
-    if (ctx->nodes.count(node_ids[i])) overwrite = true; else ++fresh;
     rows += (size_t)counts[i];
   }
-  if (fresh > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-  if (overwrite)  // nodes rewritten in place: wait for batches that may still read them
-    for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  std::vector<int64_t> slot_of;
+  const int rc = reserve_node_slots(ctx, n_nodes, node_ids, 0u, &slot_of, "a node id appears twice in one upload",
+                                    false);   // (any int32 is an id here, as for rgbdfe_upload_node)
+  if (rc != RGBDFE_OK) return rc;
   if (rows * 48 > ctx->upload_stage_bytes) {
     if (ctx->upload_stage) (void)hipHostFree(ctx->upload_stage);
     ctx->upload_stage = nullptr; ctx->upload_stage_bytes = 0;
@@ -258,16 +312,13 @@ int upload_nodes_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
     ctx->upload_stage_bytes = rows * 48 * 2;
   }
   uint8_t* stage = ctx->upload_stage;
-  // A node is registered BEFORE its copies are enqueued, so a failing enqueue leaves no slot unaccounted for: the node is
+  // Every node is registered by now (reserve_node_slots), so a failing enqueue leaves no slot unaccounted for: the node is
   // resident with whatever reached it (the caller gets the error and uploads it again or releases it).  Whatever the
   // outcome, the copies out of the pinned stage have ended when this returns -- the next call overwrites the stage.
   hipError_t err = hipSuccess;
   for (int32_t i = 0; i < n_nodes && err == hipSuccess; ++i) {
     const int32_t n = counts[i];
-    uint32_t slot;
-    auto it = ctx->nodes.find(node_ids[i]);
-    if (it != ctx->nodes.end()) slot = it->second.slot;
-    else { slot = ctx->free_slots.back(); ctx->free_slots.pop_back(); }
+    const uint32_t slot = (uint32_t)slot_of[(size_t)i];
     ctx->nodes[node_ids[i]] = NodeEntry{slot, (uint32_t)n, 0u, 0u};
     const size_t row0 = (size_t)slot * (size_t)ctx->cfg.max_keypoints;
     if (n > 0) {
@@ -309,7 +360,7 @@ int rgbdfe_upload_node_keypoints(rgbdfe_ctx* ctx, int32_t node_id, const float* 
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_kp2d, 0, rows * 8, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (this stream only: see rgbdfe_create)
   }
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));  // batches in flight may read the slot
+  if (const int rc = wait_for_pair_lanes(ctx)) return rc;  // batches in flight may read the slot
   if (n > 0)
   {   // (not a NULL-stream copy: refused while another thread of the process has a stream capture open, see orb_host.hip)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_kp2d + (size_t)it->second.slot * (size_t)ctx->cfg.max_keypoints * 2, kp_xy,
@@ -325,8 +376,7 @@ int rgbdfe_release_node(rgbdfe_ctx* ctx, int32_t node_id) {
   std::lock_guard<std::mutex> g(ctx->mu);
   auto it = ctx->nodes.find(node_id);
   if (it == ctx->nodes.end()) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "release of unknown node");
-  // batches in flight may still read this slot
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  if (const int rc = wait_for_pair_lanes(ctx)) return rc;  // batches in flight may still read this slot
   ctx->free_slots.push_back(it->second.slot);
   ctx->nodes.erase(it);
   auto ci = ctx->clouds.find(node_id);

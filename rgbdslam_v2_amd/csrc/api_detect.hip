@@ -2,7 +2,6 @@
 // (one of the host-side translation units of librgbdfe.so; shared declarations: rgbdfe_host.h)
 #include <chrono>
 #include <future>
-#include <unordered_set>
 
 #include "rgbdfe_host.h"
 
@@ -105,14 +104,7 @@ int rgbdfe_sift_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* /*ma
   if (rc != RGBDFE_OK) return fail(ctx, rc, err);
   *n_out = (int32_t)keys.size();
   if ((int32_t)keys.size() > capacity) return fail(ctx, RGBDFE_ERR_CAPACITY, "more SIFT features than the output arrays hold");
-  for (size_t i = 0; i < keys.size(); ++i) {
-    keypoints[i].x = keys[i].x;
-    keypoints[i].y = keys[i].y;
-    keypoints[i].size = (float)(12.0 * keys[i].s);
-    keypoints[i].angle = (float)(keys[i].o * 180.0 / 3.1415927);
-    keypoints[i].response = 0.f;
-    keypoints[i].octave = 0;
-  }
+  for (size_t i = 0; i < keys.size(); ++i) keypoints[i] = sift_key_to_keypoint(keys[i]);
   if (!keys.empty()) memcpy(desc128, desc, keys.size() * 128 * sizeof(float));
   return RGBDFE_OK;
 }
@@ -129,55 +121,38 @@ int rgbdfe_sift_describe(rgbdfe_ctx* ctx, const uint8_t* gray, int32_t rows, int
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   if (n == 0) return RGBDFE_OK;
   std::vector<SiftKey> keys((size_t)n);
-  for (int32_t i = 0; i < n; ++i) {
-    keys[(size_t)i].x = keypoints[i].x;
-    keys[(size_t)i].y = keypoints[i].y;
-    keys[(size_t)i].o = (float)(keypoints[i].angle / 180.0 * 3.1415927);
-    keys[(size_t)i].s = (float)(keypoints[i].size / 12.0);
-  }
+  for (int32_t i = 0; i < n; ++i) keys[(size_t)i] = keypoint_to_sift_key(keypoints[i]);
   const float* desc = nullptr;
   std::string err;
   const int rc = ctx->sift.describe(gray, rows, cols, keys.data(), n, &desc, ctx->stream, err);
   if (rc != RGBDFE_OK) return fail(ctx, rc, err);
   memcpy(desc128, desc, (size_t)n * 128 * sizeof(float));
-  for (int32_t i = 0; i < n; ++i) {
-    keypoints[i].size = (float)(12.0 * keys[(size_t)i].s);
-    keypoints[i].angle = (float)(keys[(size_t)i].o * 180.0 / 3.1415927);
-    keypoints[i].response = 0.f;
-    keypoints[i].octave = 0;
-  }
+  for (int32_t i = 0; i < n; ++i) keypoints[i] = sift_key_to_keypoint(keys[(size_t)i]);   // (x, y: as they came)
   return RGBDFE_OK;
 }
 
-// A run of frames (a recorded sequence): SiftExtractor::kMaxBatch of them share every launch of the pipeline -- the
-// images are independent (SiftGPU keeps no state between them), so frame f's outputs are those of a single call.
-int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, int32_t rows, int32_t cols,
-                             int32_t max_keypoints, int32_t out_stride, rgbdfe_keypoint* keypoints, float* desc128,
-                             int32_t* n_out) {
-  if (!ctx || n_frames < 0 || rows < 1 || cols < 1 || out_stride < 0 ||
-      (n_frames > 0 && (!gray || !n_out || (out_stride > 0 && (!keypoints || !desc128)))))
-    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
-  for (int32_t f = 0; f < n_frames; ++f)
-    if (!gray[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
-  for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
-  bool overflow = false;
-  std::string err;
-  // Three extractors, three streams, a software pipeline over chunks of up to 8 frames.  A chunk passes four steps, each of
-  // which waits for the launches of the one before, does the host's part and enqueues the next launches (sift_extract.hip):
-  //   begin_batch           images staged + uploaded, pyramids, extremum flags, candidate lists     ~1.0 ms of device time
-  //   finish_orientations   feature-count limits -> the orientation launch                          ~0.06 ms
-  //   finish_descriptors    one feature per orientation -> the descriptor launch + 6 MB download    ~0.45 ms
-  //   finish_outputs        keys / descriptor pointers; then the copy into the caller's arrays      host only, ~0.35 ms
-  // One host thread drives all of it, so the ORDER of the steps decides what the device has to do while the host works or
-  // waits: within an iteration the descriptor launch of chunk c goes out first, then chunk c + 2 is begun (its extractor's
-  // device buffers were released by chunk c - 1's last wait; the results of c - 1 sit in host memory begin_batch does not
-  // touch), then chunk c - 1 is copied out -- with two launch chains and a descriptor launch enqueued behind the host's
-  // back -- and only then the host waits: for chunk c + 1's first half (begun a whole iteration ago) and chunk c's
-  // descriptors.  Rounds 3 - 4 ran begin(c + 1) | all of finish(c) | copy-out(c) with two extractors: the device idled
-  // through every copy-out and most waits (profiles/r05_logs/sift_pipeline.txt).
+}  // namespace impl
+
+namespace rgbdfe_host {
+
+// Three extractors, three streams, a software pipeline over chunks of up to 8 frames.  A chunk passes four steps, each of
+// which waits for the launches of the one before, does the host's part and enqueues the next launches (sift_extract.hip):
+//   begin_batch           images staged + uploaded, pyramids, extremum flags, candidate lists     ~1.0 ms of device time
+//   finish_orientations   feature-count limits -> the orientation launch                          ~0.06 ms
+//   finish_descriptors    one feature per orientation -> the descriptor launch + 6 MB download    ~0.45 ms
+//   finish_outputs        keys / descriptor pointers; then the copy into the caller's arrays      host only, ~0.35 ms
+// One host thread drives all of it, so the ORDER of the steps decides what the device has to do while the host works or
+// waits: within an iteration the descriptor launch of chunk c goes out first (with the caller's launches behind it:
+// steps.behind), then chunk c + 2 is begun (its extractor's device buffers were released by chunk c - 1's last wait; the
+// results of c - 1 sit in host memory begin_batch does not touch), then chunk c - 1 is copied out (steps.after) -- with two
+// launch chains and a descriptor launch enqueued behind the host's back -- and only then the host waits: for chunk c + 1's
+// first half (begun a whole iteration ago) and chunk c's descriptors.  Rounds 3 - 4 ran begin(c + 1) | all of finish(c) |
+// copy-out(c) with two extractors: the device idled through every copy-out and most waits
+// (profiles/r05_logs/sift_pipeline.txt).
+int sift_chunk_pipeline(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const float* const* depth, int32_t rows,
+                        int32_t cols, int32_t max_keypoints, const SiftChunkSteps& steps, bool timing) {
   constexpr int B = SiftExtractor::kMaxBatch, D = 3;   // (chunks of 4 or 6 frames measured no faster: 6820 / 6944 vs 6870 frames/s)
+  static_assert(B == kSiftNodeFramesMax, "a chunk is one node launch");
   const int32_t n_chunks = (n_frames + B - 1) / B;
   SiftExtractor* ex[D] = {&ctx->sift, &ctx->sift2, &ctx->sift3};
   // (the chunk streams come from the high-priority class, created back to back: queues of a pool nothing else in the
@@ -187,35 +162,59 @@ int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* c
     if (!ctx->sift_stream2) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream2, +1));
     HIP_TRY(ctx, create_side_stream(&ctx->sift_stream3, +1));
   }
-  hipStream_t st[D] = {ctx->sift_stream1 ? ctx->sift_stream1 : ctx->stream, ctx->sift_stream2 ? ctx->sift_stream2 : ctx->stream,
-                       ctx->sift_stream3 ? ctx->sift_stream3 : ctx->stream};
-  std::vector<SiftKey> keys[D][SiftExtractor::kMaxBatch];
-  const float* desc[D][SiftExtractor::kMaxBatch];
+  const hipStream_t st[D] = {sift_chunk_stream(ctx, 0), sift_chunk_stream(ctx, 1), sift_chunk_stream(ctx, 2)};
+  std::vector<SiftKey> keys[D][B];
+  const float* desc[D][B];
+  std::string err;
+  rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
+  const size_t plane = (size_t)rows * (size_t)cols;
   auto count_of = [&](int32_t c) { return std::min<int32_t>(B, n_frames - c * B); };
-  auto drain = [&]() { for (int i = 0; i < D; ++i) (void)hipStreamSynchronize(st[i]); };
-  auto copy_out = [&](int32_t c) {
-    const int32_t f0 = c * B;
-    const int nf = count_of(c);
-    for (int k = 0; k < nf; ++k) {
-      const std::vector<SiftKey>& K = keys[c % D][k];
-      const int32_t f = f0 + k;
-      n_out[f] = (int32_t)K.size();
-      if ((int32_t)K.size() > out_stride) { overflow = true; continue; }
-      rgbdfe_keypoint* kp = keypoints + (size_t)f * out_stride;
-      for (size_t i = 0; i < K.size(); ++i) {
-        kp[i].x = K[i].x;
-        kp[i].y = K[i].y;
-        kp[i].size = (float)(12.0 * K[i].s);
-        kp[i].angle = (float)(K[i].o * 180.0 / 3.1415927);
-        kp[i].response = 0.f;
-        kp[i].octave = 0;
-      }
-      if (!K.empty()) memcpy(desc128 + (size_t)f * out_stride * 128, desc[c % D][k], K.size() * 128 * sizeof(float));
+  auto chunk = [&](int32_t c) {
+    const int set = c % D;
+    return SiftChunk{c, set, count_of(c), st[set], ex[set], keys[set], desc[set], depth ? sn.d_depth + (size_t)set * B * plane : nullptr};
+  };
+  // helper thread per chunk: the caller's depth images -> pinned set c % D -> device set c % D (depth stream), then the set's
+  // event.  The set's previous copy (chunk c - D) has finished before its pinned images are overwritten: its chunk has been
+  // waited for unless that chunk had no features at all (finish_outputs does not wait then), so the event is waited for here.
+  const int dev = ctx->cfg.device_id;
+  std::future<hipError_t> staged[D];
+  auto stage_depth = [&](int32_t c) {
+    const int set = c % D, nf = count_of(c);
+    const float* const* src = depth + (size_t)c * B;
+    float* h = sn.h_depth + (size_t)set * B * plane;
+    float* d = sn.d_depth + (size_t)set * B * plane;
+    hipStream_t ds = sn.depth_stream;
+    hipEvent_t ev = sn.depth_done[set];
+    const bool reused = c >= D;
+    staged[set] = std::async(std::launch::async, [=]() -> hipError_t {
+      hipError_t e = hipSetDevice(dev);
+      if (e == hipSuccess && reused) e = hipEventSynchronize(ev);
+      for (int k = 0; k < nf; ++k) memcpy(h + (size_t)k * plane, src[k], plane * 4);
+      if (e == hipSuccess) e = hipMemcpyAsync(d, h, (size_t)nf * plane * 4, hipMemcpyHostToDevice, ds);
+      if (e == hipSuccess) e = hipEventRecord(ev, ds);
+      return e;
+    });
+  };
+  auto begin = [&](int32_t c) -> int {
+    if (depth) stage_depth(c);
+    return ex[c % D]->begin_batch(gray + (size_t)c * B, count_of(c), rows, cols, st[c % D], err);
+  };
+  // the caller's launches behind chunk c's descriptor launch, its depth images ordered before them
+  auto behind = [&](int32_t c) -> int {
+    if (depth) {
+      const hipError_t se = staged[c % D].get();
+      if (se != hipSuccess) { err = std::string("depth staging: ") + hipGetErrorString(se); return RGBDFE_ERR_HIP; }
+      if (hipStreamWaitEvent(st[c % D], sn.depth_done[c % D], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
     }
+    return steps.behind ? steps.behind(chunk(c), err) : RGBDFE_OK;
+  };
+  auto drain = [&]() {
+    for (int i = 0; i < D; ++i) if (staged[i].valid()) (void)staged[i].get();
+    for (int i = 0; i < D; ++i) (void)hipStreamSynchronize(st[i]);
+    if (depth) (void)hipStreamSynchronize(sn.depth_stream);
   };
   // RGBDFE_SIFT_TIMING=1: the calling thread's time per step, summed over the call, on stderr (how the order above was found)
-  static const bool timing = getenv("RGBDFE_SIFT_TIMING") && atoi(getenv("RGBDFE_SIFT_TIMING")) != 0;
-  double t_step[5] = {0, 0, 0, 0, 0};   // begin, orientations, descriptors, outputs, copy-out
+  double t_step[5] = {0, 0, 0, 0, 0};   // begin, orientations, descriptors (+ behind), outputs, after (copy-out)
   auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_call = timing ? now() : 0;
   const double stage0 = ctx->sift.stage_us + ctx->sift2.stage_us + ctx->sift3.stage_us;
@@ -226,23 +225,60 @@ int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* c
     if (timing) t_step[slot] += now() - t0_;                  \
     if (rc_ != RGBDFE_OK) { drain(); return fail(ctx, rc_, err); } \
   } while (0)
-  for (int32_t c = 0; c < std::min<int32_t>(2, n_chunks); ++c)
-    SIFT_STEP(0, ex[c % D]->begin_batch(gray + (size_t)c * B, count_of(c), rows, cols, st[c % D], err));
-  if (n_chunks > 0) SIFT_STEP(1, ex[0]->finish_orientations(max_keypoints, st[0], err));
-  for (int32_t c = 0; c < n_chunks; ++c) {
-    SIFT_STEP(2, ex[c % D]->finish_descriptors(st[c % D], err));
-    if (c + 2 < n_chunks)
-      SIFT_STEP(0, ex[(c + 2) % D]->begin_batch(gray + (size_t)(c + 2) * B, count_of(c + 2), rows, cols, st[(c + 2) % D], err));
-    if (c >= 1) { const double t0 = timing ? now() : 0; copy_out(c - 1); if (timing) t_step[4] += now() - t0; }
-    if (c + 1 < n_chunks) SIFT_STEP(1, ex[(c + 1) % D]->finish_orientations(max_keypoints, st[(c + 1) % D], err));
-    SIFT_STEP(3, ex[c % D]->finish_outputs(keys[c % D], desc[c % D], st[c % D], err));
+  // round c: every step for the chunk it belongs to, where that chunk exists (rounds -2 and -1 fill the pipeline, round
+  // n_chunks empties it)
+  auto live = [&](int32_t c) { return c >= 0 && c < n_chunks; };
+  for (int32_t c = -2; c <= n_chunks; ++c) {
+    if (live(c)) {
+      SIFT_STEP(2, ex[c % D]->finish_descriptors(st[c % D], err));
+      SIFT_STEP(2, behind(c));
+    }
+    if (live(c + 2)) SIFT_STEP(0, begin(c + 2));
+    if (live(c - 1)) SIFT_STEP(4, steps.after(chunk(c - 1), err));
+    if (live(c + 1)) SIFT_STEP(1, ex[(c + 1) % D]->finish_orientations(max_keypoints, st[(c + 1) % D], err));
+    if (live(c)) SIFT_STEP(3, ex[c % D]->finish_outputs(keys[c % D], desc[c % D], st[c % D], err));
   }
-  if (n_chunks > 0) { const double t0 = timing ? now() : 0; copy_out(n_chunks - 1); if (timing) t_step[4] += now() - t0; }
 #undef SIFT_STEP
   if (timing)
     fprintf(stderr, "sift_detect_batch %d frames: %.0f us; host us in begin %.0f orientations %.0f descriptors %.0f outputs %.0f copy-out %.0f; of begin, image staging %.0f\n",
             (int)n_frames, now() - t_call, t_step[0], t_step[1], t_step[2], t_step[3], t_step[4],
             ctx->sift.stage_us + ctx->sift2.stage_us + ctx->sift3.stage_us - stage0);
+  return RGBDFE_OK;
+}
+
+}  // namespace rgbdfe_host
+
+namespace impl {
+
+// A run of frames (a recorded sequence): SiftExtractor::kMaxBatch of them share every launch of the pipeline -- the
+// images are independent (SiftGPU keeps no state between them), so frame f's outputs are those of a single call.
+int rgbdfe_sift_detect_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, int32_t rows, int32_t cols,
+                             int32_t max_keypoints, int32_t out_stride, rgbdfe_keypoint* keypoints, float* desc128,
+                             int32_t* n_out) {
+  if (!ctx || n_frames < 0 || rows < 1 || cols < 1 || out_stride < 0 ||
+      (n_frames > 0 && (!gray || !n_out || (out_stride > 0 && (!keypoints || !desc128)))))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  if (!frames_non_null(n_frames, gray)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
+  bool overflow = false;
+  SiftChunkSteps steps;
+  steps.after = [&](const SiftChunk& ch, std::string&) -> int {
+    for (int k = 0; k < ch.nf; ++k) {
+      const std::vector<SiftKey>& K = ch.keys[k];
+      const int32_t f = ch.c * SiftExtractor::kMaxBatch + k;
+      n_out[f] = (int32_t)K.size();
+      if ((int32_t)K.size() > out_stride) { overflow = true; continue; }
+      rgbdfe_keypoint* kp = keypoints + (size_t)f * out_stride;
+      for (size_t i = 0; i < K.size(); ++i) kp[i] = sift_key_to_keypoint(K[i]);
+      if (!K.empty()) memcpy(desc128 + (size_t)f * out_stride * 128, ch.desc[k], K.size() * 128 * sizeof(float));
+    }
+    return RGBDFE_OK;
+  };
+  static const bool timing = getenv("RGBDFE_SIFT_TIMING") && atoi(getenv("RGBDFE_SIFT_TIMING")) != 0;
+  const int rc = sift_chunk_pipeline(ctx, n_frames, gray, nullptr, rows, cols, max_keypoints, steps, timing);
+  if (rc != RGBDFE_OK) return rc;
   if (overflow) return fail(ctx, RGBDFE_ERR_CAPACITY, "more SIFT features in a frame than out_stride rows");
   return RGBDFE_OK;
 }
@@ -294,11 +330,11 @@ int sift_nodes_prepare(rgbdfe_ctx* ctx, size_t plane, bool host_out) {
   return RGBDFE_OK;
 }
 
-// Node::Node's SIFTGPU branch (node.cpp:147-176, 695-769, 1557-1571) for a run of frames, node by node into the slabs: the
-// chunk pipeline of rgbdfe_sift_detect_batch, with the descriptor launch writing device memory only and one sift_nodes launch
-// per chunk behind it (sift_nodes.hip).  The depth images of a chunk are staged by a helper thread and copied on a stream of
-// their own while the chunk is extracted; the node launch waits for them by an event.  The host reads the chunk's node counts
-// (and the host outputs, when asked for) once, after the wait it does for the chunk's keypoints anyway.
+// Node::Node's SIFTGPU branch (node.cpp:147-176, 695-769, 1557-1571) for a run of frames, node by node into the slabs:
+// sift_chunk_pipeline with the descriptor launch writing device memory only and one sift_nodes launch per chunk behind it
+// (sift_nodes.hip).  The depth images of a chunk are staged by the pipeline's helper thread and copied on a stream of their
+// own while the chunk is extracted; the node launch is ordered behind them.  The host reads the chunk's node counts (and the
+// host outputs, when asked for) once, after the wait it does for the chunk's keypoints anyway.
 int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const float* const* depth,
                                    int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double depth_scaling,
                                    int32_t max_keypoints, int32_t use_root_sift, const int32_t* node_ids, int32_t out_stride,
@@ -308,13 +344,7 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   if (max_keypoints < 1 || max_keypoints > ctx->cfg.max_keypoints)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "max_keypoints must lie in [1, the context's max_keypoints (node rows)]");
-  for (int32_t f = 0; f < n_frames; ++f)
-    if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
-  {
-    std::unordered_set<int32_t> seen;
-    for (int32_t f = 0; f < n_frames; ++f)
-      if (node_ids[f] >= 0 && !seen.insert(node_ids[f]).second) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
-  }
+  if (!frames_non_null(n_frames, gray, depth)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
@@ -322,91 +352,29 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
   const bool host_out = keypoints || xyz1 || feature_descriptors;
   int rc = ensure_sift(ctx);
   if (rc == RGBDFE_OK) rc = sift_nodes_prepare(ctx, (size_t)rows * (size_t)cols, host_out);
+  // the node table, all-or-nothing as rgbdfe_detect_describe_batch_nodes: every fresh id takes a slot before any work (a
+  // frame without features becomes an empty node), existing nodes are rewritten in place
+  std::vector<int64_t> slot_of;
+  if (rc == RGBDFE_OK) rc = reserve_node_slots(ctx, n_frames, node_ids, 2u, &slot_of);
   if (rc != RGBDFE_OK) return rc;
-  // the node table, all-or-nothing on capacity as rgbdfe_detect_describe_batch_nodes: every fresh id takes a slot (a frame
-  // without features becomes an empty node), checked before any work; existing nodes are rewritten in place once the pair
-  // lanes that may read them have finished
-  std::vector<int64_t> slot_of((size_t)n_frames, -1);
-  {
-    bool overwrite = false;
-    size_t fresh = 0;
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      if (ctx->nodes.count(node_ids[f]) != 0) overwrite = true;
-      else ++fresh;
-    }
-    if (fresh > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    if (overwrite)
-      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      auto it = ctx->nodes.find(node_ids[f]);
-      if (it != ctx->nodes.end()) { slot_of[(size_t)f] = it->second.slot; continue; }
-      const uint32_t slot = ctx->free_slots.back();
-      ctx->free_slots.pop_back();
-      ctx->nodes[node_ids[f]] = NodeEntry{slot, 0u, 2u, 0u};   // registered before anything can fail: no slot goes missing
-      slot_of[(size_t)f] = slot;
-    }
-  }
   rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
-  constexpr int B = SiftExtractor::kMaxBatch, D = 3;
-  static_assert(B == kSiftNodeFramesMax, "a chunk is one node launch");
-  const int32_t n_chunks = (n_frames + B - 1) / B;
+  constexpr int B = SiftExtractor::kMaxBatch;
   const size_t plane = sn.plane, mk = (size_t)ctx->cfg.max_keypoints;
-  SiftExtractor* ex[D] = {&ctx->sift, &ctx->sift2, &ctx->sift3};
-  if (n_chunks > 1 && !ctx->sift_stream3) {
-    if (!ctx->sift_stream1) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream1, +1));
-    if (!ctx->sift_stream2) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream2, +1));
-    HIP_TRY(ctx, create_side_stream(&ctx->sift_stream3, +1));
-  }
-  hipStream_t st[D] = {ctx->sift_stream1 ? ctx->sift_stream1 : ctx->stream, ctx->sift_stream2 ? ctx->sift_stream2 : ctx->stream,
-                       ctx->sift_stream3 ? ctx->sift_stream3 : ctx->stream};
   struct DeviceDescriptors {   // the extractors hand their descriptors to the node launch for the length of this call
-    SiftExtractor** ex;
-    DeviceDescriptors(SiftExtractor** e) : ex(e) { for (int i = 0; i < D; ++i) ex[i]->desc_device = true; }
-    ~DeviceDescriptors() { for (int i = 0; i < D; ++i) ex[i]->desc_device = false; }
-  } device_descriptors(ex);
-  std::vector<SiftKey> keys[D][B];
-  const float* desc[D][B];
+    SiftExtractor* ex[3];
+    DeviceDescriptors(rgbdfe_ctx* c) : ex{&c->sift, &c->sift2, &c->sift3} { for (SiftExtractor* e : ex) e->desc_device = true; }
+    ~DeviceDescriptors() { for (SiftExtractor* e : ex) e->desc_device = false; }
+  } device_descriptors(ctx);
   bool overflow = false;
-  std::string err;
-  auto count_of = [&](int32_t c) { return std::min<int32_t>(B, n_frames - c * B); };
-  const int dev = ctx->cfg.device_id;
-  // helper thread per chunk: the caller's depth images -> pinned set c % D -> device set c % D (depth stream), then the set's
-  // event.  The set's previous user, chunk c - D, has been waited for (finish_outputs) before chunk c is begun.
-  std::future<hipError_t> staged[D];
-  auto stage_depth = [&](int32_t c) {
-    const int set = c % D, nf = count_of(c);
-    const float* const* src = depth + (size_t)c * B;
-    float* h = sn.h_depth + (size_t)set * B * plane;
-    float* d = sn.d_depth + (size_t)set * B * plane;
-    hipStream_t ds = sn.depth_stream;
-    hipEvent_t ev = sn.depth_done[set];
-    staged[set] = std::async(std::launch::async, [=]() -> hipError_t {
-      hipError_t e = hipSetDevice(dev);
-      for (int k = 0; k < nf; ++k) memcpy(h + (size_t)k * plane, src[k], plane * 4);
-      if (e == hipSuccess) e = hipMemcpyAsync(d, h, (size_t)nf * plane * 4, hipMemcpyHostToDevice, ds);
-      if (e == hipSuccess) e = hipEventRecord(ev, ds);
-      return e;
-    });
-  };
-  auto begin = [&](int32_t c) -> int {
-    stage_depth(c);
-    return ex[c % D]->begin_batch(gray + (size_t)c * B, count_of(c), rows, cols, st[c % D], err);
-  };
+  SiftChunkSteps steps;
   // behind chunk c's descriptor launch: its node launch, then the counts (and host outputs) on their way back
-  auto launch_nodes = [&](int32_t c) -> int {
-    const int set = c % D, nf = count_of(c);
-    const hipError_t se = staged[set].get();
-    if (se != hipSuccess) { err = std::string("depth staging: ") + hipGetErrorString(se); return RGBDFE_ERR_HIP; }
-    hipStream_t s = st[set];
-    if (hipStreamWaitEvent(s, sn.depth_done[set], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
-    const SiftExtractor& X = *ex[set];
+  steps.behind = [&](const SiftChunk& c, std::string& err) -> int {
+    const SiftExtractor& X = *c.ex;
     SiftNodeChunk ch{};
-    ch.n_frames = nf;
-    ch.n_out = sn.d_n + (size_t)set * B;
-    for (int k = 0; k < nf; ++k) {
-      const int32_t f = c * B + k;
+    ch.n_frames = c.nf;
+    ch.n_out = sn.d_n + (size_t)c.set * B;
+    for (int k = 0; k < c.nf; ++k) {
+      const int32_t f = c.c * B + k;
       const SiftExtractor::FrameState& F = X.fs[(size_t)k];
       SiftNodeFrame& o = ch.frame[k];
       o.n_keys = X.fin_grand2 > 0 ? F.total : 0;
@@ -414,22 +382,23 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
         o.keys = X.d_keys + F.base;
         o.desc = reinterpret_cast<const float2*>(X.d_desc + (size_t)F.base * 128);
       }
-      o.depth = sn.d_depth + ((size_t)set * B + k) * plane;
+      o.depth = c.d_depth + (size_t)k * plane;
       if (slot_of[(size_t)f] >= 0) {
         const size_t row0 = (size_t)slot_of[(size_t)f] * mk;
         o.xyz = ctx->d_xyz + row0;
         o.feat = reinterpret_cast<float2*>(ctx->d_sift_f32 + row0 * 128);
       }
-      const size_t r0 = ((size_t)set * B + k) * mk;
+      const size_t r0 = ((size_t)c.set * B + k) * mk;
       if (xyz1) o.xyz_out = sn.d_xyz_out + r0;
       if (feature_descriptors) o.feat_out = reinterpret_cast<float2*>(sn.d_feat_out + r0 * 128);
       if (keypoints) o.kept_out = sn.d_kept_out + r0;
     }
+    hipStream_t s = c.stream;
     launch_sift_nodes(ch, rows, cols, (float)(1. / fx), (float)(1. / fy), (float)cx, (float)cy, depth_scaling, max_keypoints,
                       ctx->feature_min_depth, use_root_sift != 0, s);
     hipError_t e = hipGetLastError();
-    const size_t r0 = (size_t)set * B * mk, nr = (size_t)nf * mk;
-    if (e == hipSuccess) e = hipMemcpyAsync(sn.h_n + (size_t)set * B, ch.n_out, (size_t)nf * 4, hipMemcpyDeviceToHost, s);
+    const size_t r0 = (size_t)c.set * B * mk, nr = (size_t)c.nf * mk;
+    if (e == hipSuccess) e = hipMemcpyAsync(sn.h_n + (size_t)c.set * B, ch.n_out, (size_t)c.nf * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && xyz1) e = hipMemcpyAsync(sn.h_xyz_out + r0, sn.d_xyz_out + r0, nr * 16, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && feature_descriptors)
       e = hipMemcpyAsync(sn.h_feat_out + r0 * 128, sn.d_feat_out + r0 * 128, nr * 512, hipMemcpyDeviceToHost, s);
@@ -437,31 +406,21 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
     if (e != hipSuccess) { err = std::string("SIFT node launch: ") + hipGetErrorString(e); return RGBDFE_ERR_HIP; }
     return RGBDFE_OK;
   };
-  // after chunk c's wait: the node table and the caller's arrays
-  auto finish_nodes = [&](int32_t c) -> int {
-    const int set = c % D, nf = count_of(c);
-    if (hipStreamSynchronize(st[set]) != hipSuccess) { err = "hipStreamSynchronize"; return RGBDFE_ERR_HIP; }
-    for (int k = 0; k < nf; ++k) {
-      const int32_t f = c * B + k;
-      const int32_t n = sn.h_n[(size_t)set * B + k];
+  // after the chunk's wait: the node table and the caller's arrays
+  steps.after = [&](const SiftChunk& c, std::string& err) -> int {
+    if (hipStreamSynchronize(c.stream) != hipSuccess) { err = "hipStreamSynchronize"; return RGBDFE_ERR_HIP; }
+    for (int k = 0; k < c.nf; ++k) {
+      const int32_t f = c.c * B + k;
+      const int32_t n = sn.h_n[(size_t)c.set * B + k];
       n_out[f] = n;
       if (node_ids[f] >= 0) ctx->nodes[node_ids[f]] = NodeEntry{(uint32_t)slot_of[(size_t)f], (uint32_t)n, 2u, 0u};
       if (!host_out) continue;
       if (n > out_stride) { overflow = true; continue; }
-      const size_t r0 = ((size_t)set * B + k) * mk;
+      const size_t r0 = ((size_t)c.set * B + k) * mk;
       if (keypoints) {
-        const std::vector<SiftKey>& K = keys[set][k];
         const int32_t* kept = sn.h_kept_out + r0;
         rgbdfe_keypoint* kp = keypoints + (size_t)f * out_stride;
-        for (int32_t i = 0; i < n; ++i) {
-          const SiftKey& q = K[(size_t)kept[i]];
-          kp[i].x = q.x;
-          kp[i].y = q.y;
-          kp[i].size = (float)(12.0 * q.s);
-          kp[i].angle = (float)(q.o * 180.0 / 3.1415927);
-          kp[i].response = 0.f;
-          kp[i].octave = 0;
-        }
+        for (int32_t i = 0; i < n; ++i) kp[i] = sift_key_to_keypoint(c.keys[k][(size_t)kept[i]]);
       }
       if (xyz1 && n > 0) memcpy(xyz1 + (size_t)f * out_stride * 4, sn.h_xyz_out + r0, (size_t)n * 16);
       if (feature_descriptors && n > 0)
@@ -469,30 +428,8 @@ int rgbdfe_sift_detect_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, const uint
     }
     return RGBDFE_OK;
   };
-  auto drain = [&]() {
-    for (int i = 0; i < D; ++i) if (staged[i].valid()) (void)staged[i].get();
-    for (int i = 0; i < D; ++i) (void)hipStreamSynchronize(st[i]);
-    (void)hipStreamSynchronize(sn.depth_stream);
-  };
-#define SIFT_NODE_STEP(expr)                                       \
-  do {                                                             \
-    const int rc_ = (expr);                                        \
-    if (rc_ != RGBDFE_OK) { drain(); return fail(ctx, rc_, err); } \
-  } while (0)
-  // the order of rgbdfe_sift_detect_batch, with the node launch behind each descriptor launch and the node table / outputs of
-  // chunk c - 1 where that function copies its outputs out
-  for (int32_t c = 0; c < std::min<int32_t>(2, n_chunks); ++c) SIFT_NODE_STEP(begin(c));
-  SIFT_NODE_STEP(ex[0]->finish_orientations(max_keypoints, st[0], err));
-  for (int32_t c = 0; c < n_chunks; ++c) {
-    SIFT_NODE_STEP(ex[c % D]->finish_descriptors(st[c % D], err));
-    SIFT_NODE_STEP(launch_nodes(c));
-    if (c + 2 < n_chunks) SIFT_NODE_STEP(begin(c + 2));
-    if (c >= 1) SIFT_NODE_STEP(finish_nodes(c - 1));
-    if (c + 1 < n_chunks) SIFT_NODE_STEP(ex[(c + 1) % D]->finish_orientations(max_keypoints, st[(c + 1) % D], err));
-    SIFT_NODE_STEP(ex[c % D]->finish_outputs(keys[c % D], desc[c % D], st[c % D], err));
-  }
-  SIFT_NODE_STEP(finish_nodes(n_chunks - 1));
-#undef SIFT_NODE_STEP
+  rc = sift_chunk_pipeline(ctx, n_frames, gray, depth, rows, cols, max_keypoints, steps);
+  if (rc != RGBDFE_OK) return rc;
   if (overflow) return fail(ctx, RGBDFE_ERR_CAPACITY, "more kept SIFT features in a frame than out_stride rows");
   return RGBDFE_OK;
 }
@@ -948,16 +885,9 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
     // the count is exact.
     if (max_kp > ctx->cfg.max_keypoints)
       return fail(ctx, RGBDFE_ERR_CAPACITY, "the detector's max_keypoints exceeds the context's max_keypoints (node rows)");
-    bool overwrite = false;
-    std::unordered_set<int32_t> fresh_ids;
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      if (ctx->nodes.count(node_ids[f]) != 0) overwrite = true;
-      else fresh_ids.insert(node_ids[f]);
-    }
-    if (fresh_ids.size() > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    if (overwrite)  // nodes rewritten in place: wait for pair batches that may still read them
-      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+    // The slots themselves are taken super-frame by super-frame (acquire_node_slot).
+    rc = reserve_node_slots(ctx, n_frames, node_ids, 0u, nullptr);
+    if (rc != RGBDFE_OK) return rc;
   }
   const int S = (n_frames + B - 1) / B;
   // D - 1 device passes are in flight ahead of the super-frame the host is replaying: D image sets / pass slots, D + 1
@@ -1098,14 +1028,8 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
           if (id < 0 || n == 0) continue;
           if (n > ctx->cfg.max_keypoints) { err = "node has more rows than max_keypoints"; return RGBDFE_ERR_CAPACITY; }
           uint32_t slot;
-          auto it = ctx->nodes.find(id);
-          if (it != ctx->nodes.end()) slot = it->second.slot;
-          else {
-            if (ctx->free_slots.empty()) { err = "no free node slot (max_nodes)"; return RGBDFE_ERR_CAPACITY; }
-            slot = ctx->free_slots.back();
-            ctx->free_slots.pop_back();
-            ctx->nodes[id] = NodeEntry{slot, 0u, 0u, 0u};   // registered before anything can fail: no slot goes missing
-          }
+          const int rc_slot = acquire_node_slot(ctx, id, 0u, &slot, true);   // (the lanes: waited for before the first frame)
+          if (rc_slot != RGBDFE_OK) return rc_slot;
           const size_t row0 = (size_t)slot * (size_t)ctx->cfg.max_keypoints;
           const size_t off = (size_t)J[(size_t)k].off;
           if (hipMemcpyAsync(ctx->d_desc + row0 * 8, orb.d_desc + off * 32, (size_t)n * 32, hipMemcpyDeviceToDevice, st2) != hipSuccess ||
@@ -1247,13 +1171,10 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
   if (node_ids)   // frames without features: empty nodes (n = 0), as rgbdfe_upload_node(id, ..., 0) would leave them
     for (int32_t f = 0; f < n_frames; ++f)
       if (node_ids[f] >= 0 && n_out[f] == 0) {
-        auto it = ctx->nodes.find(node_ids[f]);
-        if (it != ctx->nodes.end()) it->second.n = 0;
-        else {
-          if (ctx->free_slots.empty()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-          ctx->nodes[node_ids[f]] = NodeEntry{ctx->free_slots.back(), 0u, 0u, 0u};
-          ctx->free_slots.pop_back();
-        }
+        uint32_t slot;
+        rc = acquire_node_slot(ctx, node_ids[f], 0u, &slot, true);
+        if (rc != RGBDFE_OK) return rc;
+        ctx->nodes[node_ids[f]].n = 0;
       }
   return RGBDFE_OK;
 }
@@ -1280,10 +1201,7 @@ int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_
   // (sensor: a validated run of sensor frames in place of the three plane arrays, which are NULL then; api_sensor.hip)
   if (!ctx || n_frames < 0 || (n_frames > 0 && ((!sensor && (!gray || !depth)) || !n_out)) || rows < 1 || cols < 1)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
-  if (node_ids)
-    for (int32_t f = 0; f < n_frames; ++f)
-      for (int32_t j = 0; j < f; ++j)
-        if (node_ids[f] >= 0 && node_ids[j] == node_ids[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
+  if (node_ids && node_id_twice(n_frames, node_ids)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
   std::lock_guard<std::mutex> g(ctx->mu);
   // (the host outputs may be NULL only where the nodes are the outputs: FAST with node_ids)
   const bool fast = ctx->detector_type == RGBDFE_DETECTOR_FAST;
@@ -1293,8 +1211,7 @@ int rgbdfe_detect_describe_batch(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_
   ensure_detector(ctx);
   if (n_frames > 0 && out_stride < ctx->orb_max_keypoints)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "out_stride must be at least the configured max_keypoints");
-  for (int32_t f = 0; f < n_frames && !sensor; ++f)
-    if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
+  if (!sensor && !frames_non_null(n_frames, gray, depth)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
   if (n_frames == 0) return RGBDFE_OK;
   if (sensor) {
     const int rc_dev = sensor_run_device(ctx, const_cast<SensorRun&>(*sensor));   // the resampling tables

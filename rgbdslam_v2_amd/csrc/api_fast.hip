@@ -16,8 +16,6 @@
 namespace rgbdfe {
 
 namespace {
-constexpr size_t kAlign = 256;
-size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 // frames per chunk: about 10 Mpixel (32 frames at 640 x 480, 8 at 1280 x 960)
 int chunk_frames(int rows, int cols) {
   const double px = (double)rows * (double)cols;
@@ -108,20 +106,19 @@ int FastWorkspace::ensure_slot(int i, int frames, std::string& err) {
   const size_t B = (size_t)frames, cells = (size_t)geom.n_cells;
   if ((size_t)blur_units_per_frame * B > 65535 * 64 || B * plane * 2 + 256 > 0xFFFFFFFFull) { err = "FAST: chunk too large"; return RGBDFE_ERR_CAPACITY; }
   // device
-  size_t o = 0;
-  auto carve = [&o](size_t bytes) { const size_t at = o; o += align_up(bytes); return at; };
-  const size_t o_img = carve(2 * B * plane + 256), o_blur = carve(describe ? B * plane : 0),
-               o_depth = carve(describe ? B * plane * 4 : 0), o_hm = carve(B * 4), o_keep = carve(B * geom.keep_words * 8),
-               o_score = carve(B * geom.score_bytes), o_hist = carve(B * cells * 257 * 4), o_cut = carve(B * cells * sizeof(FastCut)),
-               o_list = carve(B * (size_t)list_cap * sizeof(FastKp)), o_n = carve(B * 4), o_outs = carve(B * sizeof(FastFrameOut)),
-               o_imgs = carve(B * sizeof(ImgDesc)), o_units = carve(B * blur_units_per_frame * sizeof(TileUnit)),
-               o_kp = carve(B * (size_t)out_rows * sizeof(FastKpOut)), o_desc = carve(B * (size_t)out_rows * 32),
-               o_xyz = carve(B * (size_t)out_rows * 16);
-  if (o > s.dev_bytes) {
+  Arena dv;
+  const size_t o_img = dv.carve(2 * B * plane + 256), o_blur = dv.carve(describe ? B * plane : 0),
+               o_depth = dv.carve(describe ? B * plane * 4 : 0), o_hm = dv.carve(B * 4), o_keep = dv.carve(B * geom.keep_words * 8),
+               o_score = dv.carve(B * geom.score_bytes), o_hist = dv.carve(B * cells * 257 * 4), o_cut = dv.carve(B * cells * sizeof(FastCut)),
+               o_list = dv.carve(B * (size_t)list_cap * sizeof(FastKp)), o_n = dv.carve(B * 4), o_outs = dv.carve(B * sizeof(FastFrameOut)),
+               o_imgs = dv.carve(B * sizeof(ImgDesc)), o_units = dv.carve(B * blur_units_per_frame * sizeof(TileUnit)),
+               o_kp = dv.carve(B * (size_t)out_rows * sizeof(FastKpOut)), o_desc = dv.carve(B * (size_t)out_rows * 32),
+               o_xyz = dv.carve(B * (size_t)out_rows * 16);
+  if (dv.size > s.dev_bytes) {
     if (s.dev) (void)hipFree(s.dev);
     s.dev = nullptr; s.dev_bytes = 0; s.version = -1;
-    if (hipMalloc(&s.dev, o) != hipSuccess) { s.dev = nullptr; err = "FAST chunk buffers"; return RGBDFE_ERR_OUT_OF_MEMORY; }
-    s.dev_bytes = o;
+    if (hipMalloc(&s.dev, dv.size) != hipSuccess) { s.dev = nullptr; err = "FAST chunk buffers"; return RGBDFE_ERR_OUT_OF_MEMORY; }
+    s.dev_bytes = dv.size;
   }
   char* d = (char*)s.dev;
   s.d_img = (uint8_t*)(d + o_img); s.d_blur = (uint8_t*)(d + o_blur); s.d_depth = (float*)(d + o_depth);
@@ -131,18 +128,17 @@ int FastWorkspace::ensure_slot(int i, int frames, std::string& err) {
   s.d_outs = (FastFrameOut*)(d + o_outs); s.d_frame_imgs = (ImgDesc*)(d + o_imgs); s.d_blur_units = (TileUnit*)(d + o_units);
   s.d_kp = (FastKpOut*)(d + o_kp); s.d_desc = (uint8_t*)(d + o_desc); s.d_xyz = (float4*)(d + o_xyz);
   // page-locked
-  size_t p = 0;
-  auto pcarve = [&p](size_t bytes) { const size_t at = p; p += align_up(bytes); return at; };
+  Arena pn;
   const size_t rows_out = (size_t)out_rows;
-  const size_t p_img = pcarve(2 * B * plane), p_depth = pcarve(describe ? B * plane * 4 : 0), p_hm = pcarve(B * 4),
-               p_outs = pcarve(B * sizeof(FastFrameOut)), p_n = pcarve(B * 4), p_kp = pcarve(B * rows_out * sizeof(FastKpOut)),
-               p_desc = pcarve(B * rows_out * 32), p_xyz = pcarve(B * rows_out * 16),
-               p_list = pcarve(describe ? 0 : B * (size_t)list_cap * sizeof(FastKp)), p_tab = pcarve(B * sizeof(ImgDesc) + B * blur_units_per_frame * sizeof(TileUnit));
-  if (p > s.pin_bytes) {
+  const size_t p_img = pn.carve(2 * B * plane), p_depth = pn.carve(describe ? B * plane * 4 : 0), p_hm = pn.carve(B * 4),
+               p_outs = pn.carve(B * sizeof(FastFrameOut)), p_n = pn.carve(B * 4), p_kp = pn.carve(B * rows_out * sizeof(FastKpOut)),
+               p_desc = pn.carve(B * rows_out * 32), p_xyz = pn.carve(B * rows_out * 16),
+               p_list = pn.carve(describe ? 0 : B * (size_t)list_cap * sizeof(FastKp)), p_tab = pn.carve(B * sizeof(ImgDesc) + B * blur_units_per_frame * sizeof(TileUnit));
+  if (pn.size > s.pin_bytes) {
     if (s.pin) (void)hipHostFree(s.pin);
     s.pin = nullptr; s.pin_bytes = 0; s.version = -1;
-    if (hipHostMalloc(&s.pin, p, hipHostMallocDefault) != hipSuccess) { s.pin = nullptr; err = "FAST staging buffers"; return RGBDFE_ERR_OUT_OF_MEMORY; }
-    s.pin_bytes = p;
+    if (hipHostMalloc(&s.pin, pn.size, hipHostMallocDefault) != hipSuccess) { s.pin = nullptr; err = "FAST staging buffers"; return RGBDFE_ERR_OUT_OF_MEMORY; }
+    s.pin_bytes = pn.size;
   }
   char* h = (char*)s.pin;
   s.h_img = (uint8_t*)(h + p_img); s.h_depth = (float*)(h + p_depth); s.h_has_mask = (int32_t*)(h + p_hm);
@@ -308,13 +304,8 @@ int FastCall::run(std::string& err) {
         if (xyz1) o.out_xyz = s.d_xyz + r;
         if (node_ids && node_ids[f] >= 0) {
           uint32_t sl;
-          auto it = ctx->nodes.find(node_ids[f]);
-          if (it != ctx->nodes.end()) sl = it->second.slot;
-          else {
-            if (ctx->free_slots.empty()) { err = "no free node slot (max_nodes)"; return RGBDFE_ERR_CAPACITY; }
-            sl = ctx->free_slots.back();
-            ctx->free_slots.pop_back();
-          }
+          const int rc_slot = acquire_node_slot(ctx, node_ids[f], 0u, &sl, true);   // (the lanes: fast_detect_describe waited)
+          if (rc_slot != RGBDFE_OK) { err = ctx->last_error; return rc_slot; }
           ctx->nodes[node_ids[f]] = NodeEntry{sl, 0u, 0u, 0u};
           o.node_desc = ctx->d_desc + (size_t)sl * ms * 8;
           o.node_xyz = ctx->d_xyz + (size_t)sl * ms;
@@ -437,16 +428,8 @@ int fast_detect_describe(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const
   if (node_ids) {  // all-or-nothing on capacity, as the ORB batch (every fresh id counted: empty frames become empty nodes)
     if (max_kp > ctx->cfg.max_keypoints)
       return fail(ctx, RGBDFE_ERR_CAPACITY, "the detector's max_keypoints exceeds the context's max_keypoints (node rows)");
-    bool overwrite = false;
-    std::unordered_set<int32_t> fresh;
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      if (ctx->nodes.count(node_ids[f])) overwrite = true;
-      else fresh.insert(node_ids[f]);
-    }
-    if (fresh.size() > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    if (overwrite)  // nodes rewritten in place: wait for pair batches that may still read them
-      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+    const int rc = reserve_node_slots(ctx, n_frames, node_ids, 0u, nullptr);   // (the slots: taken chunk by chunk)
+    if (rc != RGBDFE_OK) return rc;
   }
   for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
   FastCall call;

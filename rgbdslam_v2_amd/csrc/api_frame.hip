@@ -39,7 +39,7 @@ int rgbdfe_hamming_nn_nodes(rgbdfe_ctx* ctx, int32_t query_id, int32_t train_id,
     return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "node not resident");
   if (q->second.kind != 0u || t->second.kind != 0u)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "rgbdfe_hamming_nn_nodes needs ORB (binary descriptor) nodes");
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
   for (auto& sl : ctx->ring) sl.pending = false;  // every lane is idle now
   rgbdfe_ctx::Slot& slot = ctx->ring[0];
   hipStream_t st = ctx->lanes[0].stream;
@@ -82,7 +82,7 @@ int rgbdfe_place_recognition_batch(rgbdfe_ctx* ctx, const int32_t* query_ids, in
       return fail(ctx, RGBDFE_ERR_INVALID_ARG, "candidate_offsets must ascend within [0, offsets[n_queries]] (<= 65535 candidates per query)");
   }
   if (total == 0 || max_out == 0) return RGBDFE_OK;
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
   for (auto& sl : ctx->ring) sl.pending = false;  // every lane is idle now
   rgbdfe_ctx::Slot& slot = ctx->ring[0];
   rgbdfe_ctx::Lane& lane = ctx->lanes[0];
@@ -497,7 +497,7 @@ int rgbdfe_upload_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* dept
   uint8_t* d_rgb = rgb ? (uint8_t*)ctx->d_scratch + b_depth : nullptr;
   CloudEntry& ce = ctx->clouds[node_id];
   if (ce.d && (ce.ch != ch || ce.cw != cw)) {
-    for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+    if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
     (void)hipFree(ce.d);
     ce.d = nullptr;
   }

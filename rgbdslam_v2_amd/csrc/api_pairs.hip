@@ -36,12 +36,12 @@ int rgbdfe_match_pair_list(rgbdfe_ctx* ctx, const int32_t* query_ids, const int3
       HIP_TRY(ctx, hipMemcpyAsync(ctx->h_results + off, ctx->lanes[li].d_results, sizeof(rgbdfe_match_result) * (size_t)n,
                                   hipMemcpyDeviceToHost, ctx->lanes[li].stream));
     }
-    for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+    if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
     if (out_stride == 1) memcpy(out + super, ctx->h_results, sizeof(rgbdfe_match_result) * (size_t)m);
     else
       for (int32_t i = 0; i < m; ++i) out[(int64_t)(super + i) * out_stride] = ctx->h_results[i];
   }
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
   if (ctx->profiling) drain_pending(ctx);
   return RGBDFE_OK;
 }
@@ -286,15 +286,8 @@ int rgbdfe_upload_sift_node(rgbdfe_ctx* ctx, int32_t node_id, const float* desc1
   int rc = ensure_sift(ctx);
   if (rc != RGBDFE_OK) return rc;
   uint32_t slot;
-  auto it = ctx->nodes.find(node_id);
-  if (it != ctx->nodes.end()) {
-    slot = it->second.slot;
-    for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
-  } else {
-    if (ctx->free_slots.empty()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    slot = ctx->free_slots.back();
-    ctx->free_slots.pop_back();
-  }
+  rc = acquire_node_slot(ctx, node_id, 1u, &slot);
+  if (rc != RGBDFE_OK) return rc;
   const size_t row0 = (size_t)slot * (size_t)ctx->cfg.max_keypoints;
   if (n > 0) {
     float* df = ctx->d_sift_f32 + row0 * 128;
@@ -332,15 +325,8 @@ int rgbdfe_upload_float_node(rgbdfe_ctx* ctx, int32_t node_id, const float* desc
   int rc = ensure_sift(ctx);
   if (rc != RGBDFE_OK) return rc;
   uint32_t slot;
-  auto it = ctx->nodes.find(node_id);
-  if (it != ctx->nodes.end()) {
-    slot = it->second.slot;
-    for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
-  } else {
-    if (ctx->free_slots.empty()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    slot = ctx->free_slots.back();
-    ctx->free_slots.pop_back();
-  }
+  rc = acquire_node_slot(ctx, node_id, 2u, &slot);
+  if (rc != RGBDFE_OK) return rc;
   const size_t row0 = (size_t)slot * (size_t)ctx->cfg.max_keypoints;
   if (n > 0) {
     float* df = ctx->d_sift_f32 + row0 * 128;
@@ -396,7 +382,7 @@ int rgbdfe_match_sift_pair_list(rgbdfe_ctx* ctx, const int32_t* query_ids, const
                                   sizeof(float) * RGBDFE_MAX_MATCHES * (size_t)n, hipMemcpyDeviceToHost,
                                   ctx->lanes[li].stream));
   }
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
   if (ctx->profiling) drain_pending(ctx);
   return RGBDFE_OK;
 }
@@ -422,7 +408,7 @@ int rgbdfe_sift_match_nodes(rgbdfe_ctx* ctx, int32_t query_id, int32_t train_id,
   auto t = ctx->nodes.find(train_id);
   if (q == ctx->nodes.end() || t == ctx->nodes.end()) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "node not resident");
   if (q->second.kind != 1u || t->second.kind != 1u) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "not SIFT nodes");
-  for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+  if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
   for (auto& sl : ctx->ring) sl.pending = false;
   rgbdfe_ctx::Slot& slot = ctx->ring[0];
   rgbdfe_ctx::Lane& lane = ctx->lanes[0];

@@ -214,7 +214,7 @@ int rgbdfe_sensor_clouds(rgbdfe_ctx* ctx, int32_t n_frames, const rgbdfe_sensor_
     const int b = f & 1;   // two buffer sets: frame f + 1 is staged while frame f's copy and launches run
     CloudEntry& ce = ctx->clouds[node_ids[f]];
     if (ce.d && (ce.ch != ch || ce.cw != cw)) {
-      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
+      if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       (void)hipFree(ce.d);
       ce.d = nullptr;

@@ -12,8 +12,6 @@
 //   4. sift_nodes.hip: projectTo3DSiftGPU + RootSIFT into the node slabs and the output rows, one launch for the chunk
 //   5. the counts (and the host outputs, when asked for) come back once
 // With NULL host outputs no descriptor crosses PCIe, except those of empty-list frames.
-#include <unordered_set>
-
 #include "rgbdfe_host.h"
 
 namespace impl {
@@ -22,25 +20,21 @@ namespace {
 
 constexpr int B = kSiftNodeFramesMax;
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the layout of rgbdfe_ctx::sb for frames of `plane` pixels, R kept rows and A aggregate rows per frame
 struct Layout {
   size_t d_agg, d_depth, d_keys, d_rec, d_nkeys, d_rows, d_map, d_n1, d_n, d_xyz, d_feat, d_raw, d_kept, dev_bytes;
   size_t h_agg, h_depth, h_keys, h_rec, h_map, h_n1, h_n, h_xyz, h_feat, h_raw, h_kept, pin_bytes;
   Layout(size_t plane, size_t R, size_t A) {
-    size_t o = 0;
-    auto carve = [&o](size_t b) { const size_t r = o; o += up256(b); return r; };
-    d_agg = carve(B * A * sizeof(rgbdfe_keypoint)); d_depth = carve(B * plane * 4); d_keys = carve(B * R * 16);
-    d_rec = carve(B * R * sizeof(rgbdfe_keypoint)); d_nkeys = carve(B * R * 16); d_rows = carve(B * R * 512);
-    d_map = carve(B * R * 4); d_n1 = carve(B * 4); d_n = carve(B * 4); d_xyz = carve(B * R * 16); d_feat = carve(B * R * 512);
-    d_raw = carve(B * R * 512); d_kept = carve(B * R * 4);
-    dev_bytes = o;
-    o = 0;
-    h_agg = carve(B * A * sizeof(rgbdfe_keypoint)); h_depth = carve(B * plane * 4); h_keys = carve(B * R * 16);
-    h_rec = carve(B * R * sizeof(rgbdfe_keypoint)); h_map = carve(B * R * 4); h_n1 = carve(B * 4); h_n = carve(B * 4);
-    h_xyz = carve(B * R * 16); h_feat = carve(B * R * 512); h_raw = carve(B * R * 512); h_kept = carve(B * R * 4);
-    pin_bytes = o;
+    Arena d, h;
+    d_agg = d.carve(B * A * sizeof(rgbdfe_keypoint)); d_depth = d.carve(B * plane * 4); d_keys = d.carve(B * R * 16);
+    d_rec = d.carve(B * R * sizeof(rgbdfe_keypoint)); d_nkeys = d.carve(B * R * 16); d_rows = d.carve(B * R * 512);
+    d_map = d.carve(B * R * 4); d_n1 = d.carve(B * 4); d_n = d.carve(B * 4); d_xyz = d.carve(B * R * 16);
+    d_feat = d.carve(B * R * 512); d_raw = d.carve(B * R * 512); d_kept = d.carve(B * R * 4);
+    dev_bytes = d.size;
+    h_agg = h.carve(B * A * sizeof(rgbdfe_keypoint)); h_depth = h.carve(B * plane * 4); h_keys = h.carve(B * R * 16);
+    h_rec = h.carve(B * R * sizeof(rgbdfe_keypoint)); h_map = h.carve(B * R * 4); h_n1 = h.carve(B * 4); h_n = h.carve(B * 4);
+    h_xyz = h.carve(B * R * 16); h_feat = h.carve(B * R * 512); h_raw = h.carve(B * R * 512); h_kept = h.carve(B * R * 4);
+    pin_bytes = h.size;
   }
 };
 
@@ -56,8 +50,6 @@ int prepare_bufs(rgbdfe_ctx* ctx, size_t plane, int R, int A) {
   sb.plane = plane; sb.rows_per_frame = R; sb.agg_per_frame = A;
   return RGBDFE_OK;
 }
-
-template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 
 // where a call's outputs go (every pointer may be NULL); row f of the call starts at f * stride
 struct Outputs {
@@ -155,9 +147,8 @@ int run_frames(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, co
         k4.resize(K.size());
         qrec[(size_t)k].resize(K.size());
         for (size_t i = 0; i < K.size(); ++i) {
-          const float size = (float)(12.0 * K[i].s);
-          k4[i] = make_float4(K[i].x, K[i].y, size, 0.f);
-          qrec[(size_t)k][i] = rgbdfe_keypoint{K[i].x, K[i].y, size, (float)(K[i].o * 180.0 / 3.1415927), 0.f, 0};
+          qrec[(size_t)k][i] = sift_key_to_keypoint(K[i]);
+          k4[i] = make_float4(K[i].x, K[i].y, qrec[(size_t)k][i].size, 0.f);
         }
         HIP_TRY(ctx, hipMemcpyAsync(sb.d_qkeys + qoff[(size_t)k], k4.data(), K.size() * 16, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(sb.d_qdesc + qoff[(size_t)k] * 128, qdesc[(size_t)k].data(), K.size() * 512,
@@ -293,13 +284,7 @@ int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, c
                                             rgbdfe_keypoint* keypoints, float* xyz1, float* feature_descriptors, int32_t* n_out) {
   if (!ctx || n_frames < 0 || rows < 1 || cols < 1 || (n_frames > 0 && (!gray || !depth || !node_ids || !n_out)))
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
-  for (int32_t f = 0; f < n_frames; ++f)
-    if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
-  {
-    std::unordered_set<int32_t> seen;
-    for (int32_t f = 0; f < n_frames; ++f)
-      if (node_ids[f] >= 0 && !seen.insert(node_ids[f]).second) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
-  }
+  if (!frames_non_null(n_frames, gray, depth)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   ensure_detector(ctx);
@@ -310,29 +295,9 @@ int rgbdfe_detect_sift_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames, c
   for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
   if (n_frames == 0) return RGBDFE_OK;
   int rc = ensure_sift(ctx);
+  std::vector<int64_t> slot_of;   // all-or-nothing; fresh ids are registered (as empty float nodes) before any work
+  if (rc == RGBDFE_OK) rc = reserve_node_slots(ctx, n_frames, node_ids, 2u, &slot_of);
   if (rc != RGBDFE_OK) return rc;
-  std::vector<int64_t> slot_of((size_t)n_frames, -1);
-  {  // all-or-nothing on capacity; slots are registered before any work, so none goes missing
-    bool overwrite = false;
-    size_t fresh = 0;
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      if (ctx->nodes.count(node_ids[f]) != 0) overwrite = true;
-      else ++fresh;
-    }
-    if (fresh > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    if (overwrite)
-      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      auto it = ctx->nodes.find(node_ids[f]);
-      if (it != ctx->nodes.end()) { slot_of[(size_t)f] = it->second.slot; continue; }
-      const uint32_t slot = ctx->free_slots.back();
-      ctx->free_slots.pop_back();
-      ctx->nodes[node_ids[f]] = NodeEntry{slot, 0u, 2u, 0u};
-      slot_of[(size_t)f] = slot;
-    }
-  }
   Outputs out;
   out.stride = out_stride; out.keypoints = keypoints; out.xyz1 = xyz1; out.feat = feature_descriptors; out.n_out = n_out;
   return run_frames(ctx, n_frames, gray, mask, depth, rows, cols, fx, fy, cx, cy, depth_scaling, use_root_sift != 0, node_ids,

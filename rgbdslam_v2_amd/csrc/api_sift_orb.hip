@@ -2,8 +2,8 @@
 // or a run of frames into resident ORB nodes (one of the host-side translation units of librgbdfe.so; rgbdfe_host.h).
 // DESIGN.md section 4.15.
 //
-// The chunk pipeline of rgbdfe_sift_detect_batch_nodes (three extractors, three chunks of up to 8 frames in flight, the depth
-// images staged by a helper thread and copied on a stream of their own), with the extractors in keys-only mode: the SIFT
+// sift_chunk_pipeline (api_detect.hip: three extractors, three chunks of up to 8 frames in flight, the depth images staged
+// by a helper thread and copied on a stream of their own), with the extractors in keys-only mode: the SIFT
 // pipeline stops after the orientations and leaves the kept features on the device (no descriptor launch, no descriptor
 // read-back).  Behind each chunk, on the chunk's stream:
 //   1. orb_blur_kernel on the chunk's gray images (the extractor's own device copy of them)
@@ -11,9 +11,6 @@
 //   3. sift_orb_brief: rBRIEF into the node slabs and / or the output rows
 //   4. the counts (and the host outputs, when asked for) on their way back
 // After the chunk's wait the host registers the nodes and enqueues their fp4 expansion (hamming_mfma.hip).
-#include <future>
-#include <unordered_set>
-
 #include "rgbdfe_host.h"
 #include "sift_orb.h"
 
@@ -26,8 +23,6 @@ namespace {
 constexpr int B = SiftExtractor::kMaxBatch, D = 3;
 static_assert(B == kSiftNodeFramesMax, "a chunk is one launch of the keypoint kernel");
 
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the layout of rgbdfe_ctx::so: D chunk sets of B frames of `plane` pixels, R rows per frame; the blur's image table and tiles
 // (frame k of a set: gray image at k * plane of the extractor's copy, blurred at k * plane of the set's blur pool)
 struct Layout {
@@ -37,20 +32,16 @@ struct Layout {
   Layout(size_t plane, int rows, int cols, size_t R) {
     const size_t S = (size_t)D * B;
     units_per_frame = ((cols + 63) / 64) * ((rows + 15) / 16);
-    size_t o = 0;
-    auto carve = [&o](size_t b) { const size_t r = o; o += up256(b); return r; };
-    d_blur = carve(S * plane); d_imgs = carve(B * sizeof(ImgDesc)); d_units = carve((size_t)B * units_per_frame * sizeof(TileUnit));
-    d_list = carve(S * R * sizeof(SiftOrbDescKp)); d_kp = carve(S * R * sizeof(rgbdfe_keypoint)); d_desc = carve(S * R * 32);
-    d_xyz = carve(S * R * 16); d_n = carve(S * 4);
-    dev_bytes = o;
-    o = 0;
-    h_kp = carve(S * R * sizeof(rgbdfe_keypoint)); h_desc = carve(S * R * 32); h_xyz = carve(S * R * 16); h_n = carve(S * 4);
-    h_tab = carve(B * sizeof(ImgDesc) + (size_t)B * units_per_frame * sizeof(TileUnit));
-    pin_bytes = o;
+    Arena d, h;
+    d_blur = d.carve(S * plane); d_imgs = d.carve(B * sizeof(ImgDesc)); d_units = d.carve((size_t)B * units_per_frame * sizeof(TileUnit));
+    d_list = d.carve(S * R * sizeof(SiftOrbDescKp)); d_kp = d.carve(S * R * sizeof(rgbdfe_keypoint)); d_desc = d.carve(S * R * 32);
+    d_xyz = d.carve(S * R * 16); d_n = d.carve(S * 4);
+    dev_bytes = d.size;
+    h_kp = h.carve(S * R * sizeof(rgbdfe_keypoint)); h_desc = h.carve(S * R * 32); h_xyz = h.carve(S * R * 16); h_n = h.carve(S * 4);
+    h_tab = h.carve(B * sizeof(ImgDesc) + (size_t)B * units_per_frame * sizeof(TileUnit));
+    pin_bytes = h.size;
   }
 };
-
-template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 
 int prepare_bufs(rgbdfe_ctx* ctx, int rows, int cols) {
   rgbdfe_ctx::SiftOrbBufs& so = ctx->so;
@@ -100,75 +91,34 @@ int run_frames(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, co
   int rc = sift_nodes_prepare(ctx, plane, false);   // the depth staging of rgbdfe_sift_detect_batch_nodes
   if (rc == RGBDFE_OK) rc = prepare_bufs(ctx, rows, cols);
   if (rc != RGBDFE_OK) return rc;
-  rgbdfe_ctx::SiftNodeBufs& sn = ctx->sn;
   rgbdfe_ctx::SiftOrbBufs& so = ctx->so;
   const Layout L(plane, rows, cols, mk);
   void* Dv = so.dev;
   void* P = so.pin;
   const bool host_out = out.keypoints || out.descriptors || out.xyz1;
-  const int32_t n_chunks = (n_frames + B - 1) / B;
-  SiftExtractor* ex[D] = {&ctx->sift, &ctx->sift2, &ctx->sift3};
-  if (n_chunks > 1 && !ctx->sift_stream3) {
-    if (!ctx->sift_stream1) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream1, +1));
-    if (!ctx->sift_stream2) HIP_TRY(ctx, create_side_stream(&ctx->sift_stream2, +1));
-    HIP_TRY(ctx, create_side_stream(&ctx->sift_stream3, +1));
-  }
-  hipStream_t st[D] = {ctx->sift_stream1 ? ctx->sift_stream1 : ctx->stream, ctx->sift_stream2 ? ctx->sift_stream2 : ctx->stream,
-                       ctx->sift_stream3 ? ctx->sift_stream3 : ctx->stream};
   struct KeysOnly {   // the extractors stop after the orientations for the length of this call
-    SiftExtractor** ex;
-    KeysOnly(SiftExtractor** e) : ex(e) { for (int i = 0; i < D; ++i) ex[i]->keys_only = true; }
-    ~KeysOnly() { for (int i = 0; i < D; ++i) ex[i]->keys_only = false; }
-  } keys_only(ex);
-  std::vector<SiftKey> keys[D][B];
-  const float* desc[D][B];
-  std::string err;
-  auto count_of = [&](int32_t c) { return std::min<int32_t>(B, n_frames - c * B); };
-  const int dev = ctx->cfg.device_id;
-  // helper thread per chunk: the caller's depth images -> pinned set c % D -> device set c % D (depth stream), then the set's
-  // event.  The set's previous copy has finished before its pinned images are overwritten.
-  std::future<hipError_t> staged[D];
-  auto stage_depth = [&](int32_t c) {
-    const int set = c % D, nf = count_of(c);
-    const float* const* src = depth + (size_t)c * B;
-    float* h = sn.h_depth + (size_t)set * B * plane;
-    float* d = sn.d_depth + (size_t)set * B * plane;
-    hipStream_t ds = sn.depth_stream;
-    hipEvent_t ev = sn.depth_done[set];
-    const bool reused = c >= D;
-    staged[set] = std::async(std::launch::async, [=]() -> hipError_t {
-      hipError_t e = hipSetDevice(dev);
-      if (e == hipSuccess && reused) e = hipEventSynchronize(ev);
-      for (int k = 0; k < nf; ++k) memcpy(h + (size_t)k * plane, src[k], plane * 4);
-      if (e == hipSuccess) e = hipMemcpyAsync(d, h, (size_t)nf * plane * 4, hipMemcpyHostToDevice, ds);
-      if (e == hipSuccess) e = hipEventRecord(ev, ds);
-      return e;
-    });
-  };
-  auto begin = [&](int32_t c) -> int {
-    stage_depth(c);
-    return ex[c % D]->begin_batch(gray + (size_t)c * B, count_of(c), rows, cols, st[c % D], err);
-  };
+    SiftExtractor* ex[D];
+    KeysOnly(rgbdfe_ctx* c) : ex{&c->sift, &c->sift2, &c->sift3} { for (SiftExtractor* e : ex) e->keys_only = true; }
+    ~KeysOnly() { for (SiftExtractor* e : ex) e->keys_only = false; }
+  } keys_only(ctx);
+  SiftChunkSteps steps;
   // behind chunk c's keys-only step: the blur, the keypoint launch, rBRIEF, then the counts (and host outputs) on their way back
-  auto launch_orb = [&](int32_t c) -> int {
-    const int set = c % D, nf = count_of(c);
-    const hipError_t se = staged[set].get();
-    if (se != hipSuccess) { err = std::string("depth staging: ") + hipGetErrorString(se); return RGBDFE_ERR_HIP; }
-    hipStream_t s = st[set];
-    if (hipStreamWaitEvent(s, sn.depth_done[set], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
-    const SiftExtractor& X = *ex[set];
+  steps.behind = [&](const SiftChunk& c, std::string& err) -> int {
+    const int set = c.set, nf = c.nf;
+    hipStream_t s = c.stream;
+    const SiftExtractor& X = *c.ex;
     uint8_t* blur = at<uint8_t>(Dv, L.d_blur) + (size_t)set * B * plane;
     launch_orb_blur_always(X.d_gray, at<ImgDesc>(Dv, L.d_imgs), at<TileUnit>(Dv, L.d_units), nf * L.units_per_frame, blur, s);
     SiftOrbChunk ch{};
     ch.n_frames = nf;
     ch.n_out = at<int32_t>(Dv, L.d_n) + (size_t)set * B;
     for (int k = 0; k < nf; ++k) {
-      const int32_t f = c * B + k;
+      const int32_t f = c.c * B + k;
       const SiftExtractor::FrameState& F = X.fs[(size_t)k];
       SiftOrbFrame& o = ch.frame[k];
       o.n_keys = X.fin_grand2 > 0 ? F.total : 0;
       if (o.n_keys > 0) o.keys = reinterpret_cast<const SiftOrbKey*>(X.d_keys + (size_t)F.base * 2);
-      o.depth = sn.d_depth + ((size_t)set * B + k) * plane;
+      o.depth = c.d_depth + (size_t)k * plane;
       const size_t r0 = ((size_t)set * B + k) * mk;
       o.list = at<SiftOrbDescKp>(Dv, L.d_list) + r0;
       if (node_ids && slot_of[(size_t)f] >= 0) {
@@ -197,18 +147,18 @@ int run_frames(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, co
     if (e != hipSuccess) { err = std::string("SIFT-ORB launch: ") + hipGetErrorString(e); return RGBDFE_ERR_HIP; }
     return RGBDFE_OK;
   };
-  // after chunk c's wait: the node table, the nodes' expansion for the Hamming matcher, the caller's arrays
-  auto finish_orb = [&](int32_t c) -> int {
-    const int set = c % D, nf = count_of(c);
-    if (hipStreamSynchronize(st[set]) != hipSuccess) { err = "hipStreamSynchronize"; return RGBDFE_ERR_HIP; }
-    for (int k = 0; k < nf; ++k) {
-      const int32_t f = c * B + k;
+  // after the chunk's wait: the node table, the nodes' expansion for the Hamming matcher, the caller's arrays
+  steps.after = [&](const SiftChunk& c, std::string& err) -> int {
+    const int set = c.set;
+    if (hipStreamSynchronize(c.stream) != hipSuccess) { err = "hipStreamSynchronize"; return RGBDFE_ERR_HIP; }
+    for (int k = 0; k < c.nf; ++k) {
+      const int32_t f = c.c * B + k;
       const int32_t n = at<int32_t>(P, L.h_n)[(size_t)set * B + k];
       out.n_out[f] = n;
       if (node_ids && node_ids[f] >= 0) {
         const uint32_t slot = (uint32_t)slot_of[(size_t)f];
         ctx->nodes[node_ids[f]] = NodeEntry{slot, (uint32_t)n, 0u, 0u};
-        launch_hamming_expand(ctx->d_desc + (size_t)slot * mk * 8, ctx->d_desc4, slot, (uint32_t)mk, (uint32_t)n, st[set]);
+        launch_hamming_expand(ctx->d_desc + (size_t)slot * mk * 8, ctx->d_desc4, slot, (uint32_t)mk, (uint32_t)n, c.stream);
         if (hipGetLastError() != hipSuccess) { err = "hamming expand"; return RGBDFE_ERR_HIP; }
       }
       if (!host_out || n == 0) continue;
@@ -219,30 +169,9 @@ int run_frames(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, co
     }
     return RGBDFE_OK;
   };
-  auto drain = [&]() {
-    for (int i = 0; i < D; ++i) if (staged[i].valid()) (void)staged[i].get();
-    for (int i = 0; i < D; ++i) (void)hipStreamSynchronize(st[i]);
-    (void)hipStreamSynchronize(sn.depth_stream);
-  };
-#define SIFT_ORB_STEP(expr)                                        \
-  do {                                                             \
-    const int rc_ = (expr);                                        \
-    if (rc_ != RGBDFE_OK) { drain(); return fail(ctx, rc_, err); } \
-  } while (0)
-  // the order of rgbdfe_sift_detect_batch_nodes, the ORB launches in the place of its node launch
-  for (int32_t c = 0; c < std::min<int32_t>(2, n_chunks); ++c) SIFT_ORB_STEP(begin(c));
-  SIFT_ORB_STEP(ex[0]->finish_orientations(max_keypoints, st[0], err));
-  for (int32_t c = 0; c < n_chunks; ++c) {
-    SIFT_ORB_STEP(ex[c % D]->finish_descriptors(st[c % D], err));
-    SIFT_ORB_STEP(launch_orb(c));
-    if (c + 2 < n_chunks) SIFT_ORB_STEP(begin(c + 2));
-    if (c >= 1) SIFT_ORB_STEP(finish_orb(c - 1));
-    if (c + 1 < n_chunks) SIFT_ORB_STEP(ex[(c + 1) % D]->finish_orientations(max_keypoints, st[(c + 1) % D], err));
-    SIFT_ORB_STEP(ex[c % D]->finish_outputs(keys[c % D], desc[c % D], st[c % D], err));
-  }
-  SIFT_ORB_STEP(finish_orb(n_chunks - 1));
-#undef SIFT_ORB_STEP
-  for (int i = 0; i < D; ++i) HIP_TRY(ctx, hipStreamSynchronize(st[i]));   // the last expansions
+  rc = sift_chunk_pipeline(ctx, n_frames, gray, depth, rows, cols, max_keypoints, steps);
+  if (rc != RGBDFE_OK) return rc;
+  for (int i = 0; i < D; ++i) HIP_TRY(ctx, hipStreamSynchronize(sift_chunk_stream(ctx, i)));   // the last expansions
   return RGBDFE_OK;
 }
 
@@ -288,41 +217,18 @@ int rgbdfe_sift_detect_orb_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frame
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   if (max_keypoints < 1 || max_keypoints > ctx->cfg.max_keypoints)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "max_keypoints must lie in [1, the context's max_keypoints (node rows)]");
-  for (int32_t f = 0; f < n_frames; ++f)
-    if (!gray[f] || !depth[f]) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
-  {
-    std::unordered_set<int32_t> seen;
-    for (int32_t f = 0; f < n_frames; ++f)
-      if (node_ids[f] >= 0 && !seen.insert(node_ids[f]).second) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "a node id appears twice");
-  }
+  if (!frames_non_null(n_frames, gray, depth)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "null frame");
   if (n_frames > 0 && (keypoints || descriptors || xyz1) && out_stride < max_keypoints)
     return fail(ctx, RGBDFE_ERR_CAPACITY, "out_stride below max_keypoints while a host output is asked for");
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   for (int32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
   if (n_frames == 0) return RGBDFE_OK;
-  std::vector<int64_t> slot_of((size_t)n_frames, -1);
-  {  // all-or-nothing on capacity; slots are registered before any work, so none goes missing
-    bool overwrite = false;
-    size_t fresh = 0;
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      if (ctx->nodes.count(node_ids[f]) != 0) overwrite = true;
-      else ++fresh;
-    }
-    if (fresh > ctx->free_slots.size()) return fail(ctx, RGBDFE_ERR_CAPACITY, "no free node slot (max_nodes)");
-    if (overwrite)
-      for (auto& ln : ctx->lanes) HIP_TRY(ctx, hipStreamSynchronize(ln.stream));
-    for (int32_t f = 0; f < n_frames; ++f) {
-      if (node_ids[f] < 0) continue;
-      auto it = ctx->nodes.find(node_ids[f]);
-      if (it != ctx->nodes.end()) { slot_of[(size_t)f] = it->second.slot; continue; }   // (of any kind: an ORB node afterwards)
-      const uint32_t slot = ctx->free_slots.back();
-      ctx->free_slots.pop_back();
-      ctx->nodes[node_ids[f]] = NodeEntry{slot, 0u, 0u, 0u};
-      slot_of[(size_t)f] = slot;
-    }
-  }
+  // all-or-nothing; fresh ids are registered (as empty ORB nodes) before any work, a resident node of any kind keeps its
+  // entry until its frame's final one is written: an ORB node afterwards
+  std::vector<int64_t> slot_of;
+  const int rc = reserve_node_slots(ctx, n_frames, node_ids, 0u, &slot_of);
+  if (rc != RGBDFE_OK) return rc;
   Outputs out;
   out.stride = out_stride; out.keypoints = keypoints; out.descriptors = descriptors; out.xyz1 = xyz1; out.n_out = n_out;
   return run_frames(ctx, n_frames, gray, depth, rows, cols, fx, fy, cx, cy, depth_scaling, max_keypoints, node_ids, slot_of, out);

@@ -385,6 +385,81 @@ int wait_ticket(rgbdfe_ctx* ctx, int64_t ticket, hipStream_t stream);
       return fail(ctx, RGBDFE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
+// ---- the node table (api_context.hip): ctx->nodes and ctx->free_slots change here and in rgbdfe_release_node only.
+// ctx->mu is held.  A slot leaves free_slots together with the entry that names it, so no failure can lose one.
+namespace rgbdfe_host {
+// the pair lanes have finished every batch that may still read a node slot
+int wait_for_pair_lanes(rgbdfe_ctx* ctx);
+// The slot of node_id.  Resident: its own, its entry untouched, after wait_for_pair_lanes (lanes_idle: the caller has waited
+// already).  Fresh: a free slot, registered at once as an empty node of `kind` -- or RGBDFE_ERR_CAPACITY.  The caller writes
+// the final entry (count, kind, flags) once the rows are in place.
+int acquire_node_slot(rgbdfe_ctx* ctx, int32_t node_id, uint32_t kind, uint32_t* slot, bool lanes_idle = false);
+// A batch of ids (negative: no node, where negative_is_none), all or nothing: RGBDFE_ERR_INVALID_ARG with `twice` when an id appears twice,
+// RGBDFE_ERR_CAPACITY when the fresh ids outnumber the free slots; waits for the pair lanes only if some id is resident.
+// slot_of == NULL: a check only, the caller takes the slots one by one (acquire_node_slot with lanes_idle).  Otherwise the
+// fresh ids are registered at once as empty nodes of `kind`, resident entries stay as they are, and slot_of[i] is the slot
+// of node_ids[i] (-1: no node).
+int reserve_node_slots(rgbdfe_ctx* ctx, int32_t n, const int32_t* node_ids, uint32_t kind, std::vector<int64_t>* slot_of,
+                       const char* twice = "a node id appears twice", bool negative_is_none = true);
+bool node_id_twice(int32_t n, const int32_t* node_ids, bool negative_is_none = true);
+
+// frame f of a batch call: every image pointer given
+template <class A, class B = A>
+bool frames_non_null(int32_t n, const A* const* a, const B* const* b = nullptr) {
+  for (int32_t f = 0; f < n; ++f)
+    if (!a[f] || (b && !b[f])) return false;
+  return true;
+}
+
+// SiftGPUWrapper::detect's keypoints (sift_gpu_wrapper.cpp:156-160: size = 12 * scale, angle = orientation in degrees,
+// response = octave = 0) and the way back (:135-138).  Double products, one cast to float: part of parity.
+inline rgbdfe_keypoint sift_key_to_keypoint(const SiftKey& k) {
+  return rgbdfe_keypoint{k.x, k.y, (float)(12.0 * k.s), (float)(k.o * 180.0 / 3.1415927), 0.f, 0};
+}
+inline SiftKey keypoint_to_sift_key(const rgbdfe_keypoint& p) {
+  SiftKey k{};
+  k.x = p.x; k.y = p.y;
+  k.s = (float)(p.size / 12.0);
+  k.o = (float)(p.angle / 180.0 * 3.1415927);
+  return k;
+}
+
+// one allocation carved into 256-byte aligned pieces: carve() hands out offsets, at<T>() turns one into a pointer
+struct Arena {
+  size_t size = 0;
+  size_t carve(size_t bytes) { const size_t off = size; size += (bytes + 255) & ~(size_t)255; return off; }
+};
+template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
+// ---- the SIFT chunk pipeline (api_detect.hip): three extractors (ctx->sift, sift2, sift3), three chunk streams, chunks of
+// SiftExtractor::kMaxBatch frames in the order begin(c + 2) / finish_orientations(c + 1) / finish_descriptors(c) /
+// finish_outputs(c) -- see sift_chunk_pipeline
+struct SiftChunk {
+  int32_t c;          // chunk index: frames c * kMaxBatch .. + nf
+  int set, nf;        // c % 3: the chunk's extractor, stream and buffer set; its frames
+  hipStream_t stream;
+  const SiftExtractor* ex;
+  const std::vector<SiftKey>* keys;   // [nf], filled by finish_outputs (valid in `after`)
+  const float* const* desc;           // [nf]
+  const float* d_depth;               // depth staging: the chunk's nf planes on the device (ordered before `behind`'s launches)
+};
+// the stream of buffer set `set`: the context's main stream until a call with more than one chunk has created the three
+inline hipStream_t sift_chunk_stream(const rgbdfe_ctx* ctx, int set) {
+  const hipStream_t s[3] = {ctx->sift_stream1, ctx->sift_stream2, ctx->sift_stream3};
+  return s[set] ? s[set] : ctx->stream;
+}
+struct SiftChunkSteps {
+  // on the chunk's stream behind its finish_descriptors (may be empty); an error's text goes to `err`
+  std::function<int(const SiftChunk&, std::string& err)> behind;
+  // where rgbdfe_sift_detect_batch copies chunk c - 1 out: behind chunk c's finish_descriptors and chunk c + 2's begin
+  std::function<int(const SiftChunk&, std::string& err)> after;
+};
+// depth != NULL: a helper thread stages each chunk's depth images through ctx->sn (sift_nodes_prepare has run) beside its
+// extraction.  timing: RGBDFE_SIFT_TIMING's line on stderr.  A failure is reported through fail() after the streams drained.
+int sift_chunk_pipeline(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const float* const* depth, int32_t rows,
+                        int32_t cols, int32_t max_keypoints, const SiftChunkSteps& steps, bool timing = false);
+}  // namespace rgbdfe_host
+
 // ---- the single-device implementation of the entry points (api_context / api_pairs / api_detect / api_frame / api_map.hip)
 namespace impl {
 // helpers shared between the implementation files
