@@ -10,6 +10,8 @@ import pytest
 from oracle import pyoracle as po
 from rgbdslam_v2_amd import synth
 
+import sift_match_reference as sr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,30 +25,15 @@ def fe(request):
     f.close()
 
 
-def _xyz(rng, n):
-    return np.concatenate([rng.uniform(-1, 1, (n, 2)), rng.uniform(1, 3, (n, 1)), np.ones((n, 1))], 1).astype(np.float32)
+_xyz, _rand_sift = sr.xyz, sr.rand_sift     # the input builders live in tests/sift_match_reference.py (shared with the
+                                            # kernel-variant worker of tests/test_gpu_sift_variants.py)
 
 
-def _rand_sift(rng, n):
-    v = rng.gamma(0.6, 1.0, (n, 128)).astype(np.float32)
-    v /= np.linalg.norm(v, axis=1, keepdims=True)
-    v = np.minimum(v, 0.2)
-    v /= np.linalg.norm(v, axis=1, keepdims=True)
-    return v.astype(np.float32)
-
-
-@pytest.mark.parametrize("n1,n2", [(1000, 1000), (300, 700), (129, 127), (128, 128), (257, 33), (1, 1), (40, 1), (1, 40)])
+@pytest.mark.parametrize("n1,n2", sr.VS_ORACLE_SIZES)
 def test_sift_match_nodes_vs_oracle(fe, n1, n2):
-    rng = np.random.default_rng(n1 * 31 + n2)
-    d2 = _rand_sift(rng, n2)
-    d1 = _rand_sift(rng, n1)
-    k = min(n1, n2) * 2 // 3
-    src = rng.permutation(n2)[:k]
-    d1[:k] = d2[src] + rng.normal(0, 0.01, (k, 128)).astype(np.float32)
-    d1 = np.abs(d1)
-    d1 /= np.linalg.norm(d1, axis=1, keepdims=True)
-    fe.upload_sift_node(1, d1, _xyz(rng, n1))
-    fe.upload_sift_node(2, d2, _xyz(rng, n2))
+    d1, d2, x1, x2, k = sr.vs_oracle_case(n1, n2)
+    fe.upload_sift_node(1, d1, x1)
+    fe.upload_sift_node(2, d2, x2)
     mq, mt, md = fe.sift_match_nodes(1, 2)
     oq, ot, od = po.sift_match(d1, d2)
     assert np.array_equal(mq, oq) and np.array_equal(mt, ot)
@@ -58,12 +45,12 @@ def test_sift_match_nodes_vs_oracle(fe, n1, n2):
     fe.release_node(2)
 
 
-def _check_nodes(fe, d1, d2, rng):
-    fe.upload_sift_node(1, d1, _xyz(rng, len(d1)))
-    fe.upload_sift_node(2, d2, _xyz(rng, len(d2)))
+def _check_case(fe, c):
+    fe.upload_sift_node(1, c["d1"], c["xyz1"])
+    fe.upload_sift_node(2, c["d2"], c["xyz2"])
     mq, mt, md = fe.sift_match_nodes(1, 2)
-    oq, ot, od = po.sift_match(d1, d2)
-    assert np.array_equal(mq, oq) and np.array_equal(mt, ot) and np.array_equal(md, od)
+    oq, ot, od = po.sift_match(c["d1"], c["d2"])
+    assert np.array_equal(mq, oq) and np.array_equal(mt, ot) and np.array_equal(md, od), c["name"]
     fe.release_node(1)
     fe.release_node(2)
     return len(mq)
@@ -73,55 +60,21 @@ def test_sift_key_paths(fe):
     """The dot-product kernel has two key formats (sift_match.hip): float keys  dot + (31 - seq) / 32  when both nodes
     hold <= 1024 rows and every quantised squared norm is < 2^19, integer keys otherwise.  Same answers from both:
     nodes above 1024 rows, descriptors that are not unit length (one node or both), norms right under the 2^19 limit
-    with duplicated rows (the tie-break bits sit 24 bits under the leading bit there), and saturated u8 values."""
-    rng = np.random.default_rng(77)
-    base = _rand_sift(rng, 1200)
-    noisy = np.abs(base + rng.normal(0, 0.01, base.shape).astype(np.float32))
-    noisy /= np.linalg.norm(noisy, axis=1, keepdims=True)
-    perm = rng.permutation(1200)
-    assert _check_nodes(fe, noisy[perm][:1000], base[:1000], rng) > 300      # float keys
-    assert _check_nodes(fe, noisy[perm][:1100], base[:900], rng) > 300       # > 1024 rows on one side: integer keys
-    assert _check_nodes(fe, noisy[perm][:900], base[:1100], rng) > 300
-    assert _check_nodes(fe, noisy[perm][:1000] * 1.6, base[:1000], rng) > 300   # |d|^2 = 2.56 * 2^18: integer keys
-    _check_nodes(fe, noisy[perm][:1000] * 1.6, base[:1000] * 1.7, rng)   # every angle is acos(1): no match survives
-    # squared norms just under 2^19 (float keys at their upper limit), many exact duplicates -> equal dot products
-    u = np.full((48, 128), 64, np.int32)
-    u[:, 0] = 63
-    for r in range(48):
-        k = rng.integers(1, 128, 6)
-        u[r, k] -= rng.integers(1, 20, 6)
-    assert ((u * u).sum(1) < (1 << 19)).all() and ((u * u).sum(1) > (1 << 19) - 40000).all()
-    f = (u / 512.0).astype(np.float32)
-    d2 = f[rng.integers(0, 48, 1024)]
-    d1 = f[rng.integers(0, 48, 1000)]
-    _check_nodes(fe, d1, d2, rng)
-    d2n = np.abs(d2 + rng.normal(0, 2e-3, d2.shape).astype(np.float32))
-    _check_nodes(fe, d1, np.minimum(d2n, 0.1249), rng)
-    # one row over the limit switches the whole node to integer keys
-    d1b = d1.copy()
-    d1b[500, :] = 0.126
-    _check_nodes(fe, d1b, d2, rng)
-    # saturated / wrapping u8 values (SiftMatchCU.cpp:96-99 stores an unsigned char): 0.6 * 512 = 307 -> 51
-    d1c = _rand_sift(rng, 300)
-    d1c[::7, 3] = 0.6
-    _check_nodes(fe, d1c, base[:400], rng)
+    with duplicated rows (the tie-break bits sit 24 bits under the leading bit there), and saturated u8 values
+    (sift_match_reference.key_path_cases)."""
+    for c in sr.key_path_cases():
+        assert _check_case(fe, c) > c["least"], c["name"]
 
 
 def test_sift_block_shapes(fe):
-    """Float keys run in two block shapes (sift_match.hip, launch_sift_dot): 128-row blocks (32 rows per wave) when the
-    larger side of the batch fits one block, 256-row blocks (64 rows per wave, tiles loaded straight into LDS)
-    otherwise.  Sizes around every boundary of both -- 32 / 64 rows per wave, 128 / 256 rows per block, 128-column tiles
-    (the ragged last tile runs the same pipeline under a column mask), waves without rows -- with duplicated rows so
-    that the tie rules are exercised in every shape."""
-    rng = np.random.default_rng(4242)
-    base = _rand_sift(rng, 1024)
-    base[1::5] = base[0::5][: len(base[1::5])]          # exact duplicates
-    noisy = np.abs(base + rng.normal(0, 0.01, base.shape).astype(np.float32))
-    noisy /= np.linalg.norm(noisy, axis=1, keepdims=True)
-    perm = rng.permutation(1024)
-    for n1, n2 in ((1, 1), (31, 128), (128, 33), (129, 64), (64, 129), (127, 255), (256, 256), (257, 129), (193, 385),
-                   (320, 511), (513, 640), (700, 1023), (1024, 767), (1024, 1024), (65, 1000)):
-        _check_nodes(fe, noisy[perm][:n1], base[:n2], rng)
+    """Float keys run by default in the one-pass kernel's 256-row blocks (sift_match.hip, launch_sift_dot: 64 rows per wave,
+    tiles loaded straight into LDS, a column's partials per row block merged by the finish kernel).  Sizes around every
+    boundary of it -- 32 / 64 rows per wave, 128 / 256 rows per block, 128-column tiles (the ragged last tile runs the same
+    pipeline under a column mask), waves without rows -- with duplicated rows so that the tie rules are exercised in every
+    shape.  The two-pass kernels' 128-row and 256-row block shapes (RGBDFE_SIFT_ONEPASS=0) see the same sizes in
+    tests/test_gpu_sift_variants.py."""
+    for c in sr.block_shape_cases():
+        _check_case(fe, c)
 
 
 def test_sift_tie_rules(fe):
