@@ -461,6 +461,47 @@ int rgbdfe_assemble_map_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* 
 int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_out, int64_t capacity_points,
                                int32_t* rows, int32_t* cols);
 
+/* ---- voxel filter: a cloud reduced to the centroids of its occupied grid cells ----------------------------
+ * rgbdfe_voxel_filter is the pcl::VoxelGrid<point_type> of Node::reducePointCloud (node.cpp:1448-1460; parameter
+ *   "voxelfilter_size", parameter_server.cpp:159) with the filter's defaults: cubic leaf, all fields downsampled, no
+ *   filter field, min_points_per_voxel 0, an input that is not dense.  PCL is not part of the reference tree: the
+ *   statements below are this library's contract (restated, not pinned).  Points are rows of 4 floats
+ *   (x, y, z, rgb bits); all arithmetic is float32 with one rounding per operation.
+ *   L = (float)voxelfilter_size, inv = 1.0f / L; unless L > 0 and inv is finite and non-zero: RGBDFE_ERR_INVALID_ARG.
+ *   A point is valid iff x, y and z are finite; invalid points take part in nothing.  No valid point, or n_in == 0:
+ *   *n_out = 0, RGBDFE_OK.  min_p / max_p = the exact componentwise bounds of the valid points.
+ *   Leaf too small: d[a] = (int64)((max_p[a] - min_p[a]) * inv) + 1; if a float product is >= 2^31 or d0 * d1 * d2 >
+ *   INT32_MAX, the filter hands back its input: *n_out = n_in, out = every input row in order, byte for byte (the
+ *   invalid ones too), *flags has RGBDFE_VOXEL_LEAF_TOO_SMALL, the status is RGBDFE_OK.
+ *   Grid: min_b[a] = (int)floorf(min_p[a] * inv), max_b likewise, div[a] = max_b[a] - min_b[a] + 1, mul = (1, div0,
+ *   div0 * div1) as int32.  Cell of a point: ijk[a] = (int)(floorf(p[a] * inv) - (float)min_b[a]), idx = ijk0 + ijk1 *
+ *   mul1 + ijk2 * mul2 (int32).  One output row per occupied cell, in ascending idx.  With n the cell's member count,
+ *   each of x, y, z is the float sum of the members in ascending input index, starting from the first member's value,
+ *   divided by (float)n (IEEE division); r, g, b (bits 23-16, 15-8, 7-0 of the rgb word) are converted to float,
+ *   summed and divided likewise, truncated with (int), and packed as r << 16 | g << 8 | b (top byte 0).
+ *   PCL's own order inside a cell is what an unstable std::sort leaves; against any order the cells, their order,
+ *   their counts and (while 255 n < 2^24) the rgb words are the same, and x, y, z differ by at most
+ *   2 n 2^-24 max|coordinate|.
+ *   out: capacity rows.  capacity < *n_out: RGBDFE_ERR_CAPACITY with *n_out = the needed size, before the output
+ *   pass; n_in rows always suffice.  n_in >= 2^31: RGBDFE_ERR_CAPACITY.  flags may be NULL.
+ * rgbdfe_voxel_filter_device: the same over device buffers of the context's device (the first device of a
+ *   multi-device handle); no point crosses to the host.  The kernels run on `stream` (NULL: the context's own); the
+ *   call returns when they have finished.  d_out must not overlap d_points (refused where the ranges show it).  n_out
+ *   and flags are host pointers.
+ * rgbdfe_reduce_node_cloud is Node::reducePointCloud: the node's resident cloud is replaced by its filtered cloud,
+ *   unstructured (rgbdfe_download_node_cloud then reports rows 1, cols *n_out; 0 points are a cloud too).  The cached
+ *   samples of the measurement model are dropped, the intrinsics kept; rgbdfe_observation_likelihood answers for such
+ *   a cloud as the reference does for an unstructured one (misc.cpp:835-843: inliers = all = 1; parameter_server.cpp:233
+ *   calls the combination an error), rgbdfe_assemble_map takes it like any other cloud.  With
+ *   RGBDFE_VOXEL_LEAF_TOO_SMALL the cloud stays as it is.  A node without a cloud: RGBDFE_ERR_UNKNOWN_NODE. */
+#define RGBDFE_VOXEL_LEAF_TOO_SMALL 1
+int rgbdfe_voxel_filter(rgbdfe_ctx* ctx, const float* points, int64_t n_in, double voxelfilter_size, float* out,
+                        int64_t capacity, int64_t* n_out, int32_t* flags);
+int rgbdfe_voxel_filter_device(rgbdfe_ctx* ctx, const void* d_points, int64_t n_in, double voxelfilter_size,
+                               void* d_out, int64_t capacity, int64_t* n_out, int32_t* flags, void* stream);
+int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilter_size, int64_t* n_out,
+                             int32_t* flags);
+
 /* ---- candidate selection for loop closure ----------------------------------
  * rgbdfe_potential_edge_targets is GraphManager::getPotentialEdgeTargetsWithDijkstra (graph_manager.cpp:204-324): the
  * ids of the earlier nodes a new node is to be compared with -- `sequential_targets` direct predecessors, then

@@ -312,6 +312,18 @@ class Node {  // the slice of src/node.h the pair path touches
     if (cols) *cols = c;
     return rgbdfe_download_node_cloud(fe_.get(), id_, cloud->data(), (int64_t)r * c, &r, &c) == RGBDFE_OK;
   }
+  // Node::reducePointCloud (src/node.cpp:1448-1460): pc_col becomes its voxel-filtered cloud, unstructured (pointCloud()
+  // then reports 1 row).  Like the reference, vfs <= 0 changes nothing (the reference warns: "Point Clouds can't be reduced
+  // because of invalid voxelfilter_size").  points / flags (optional): the rows of the cloud afterwards, rgbdfe_voxel_filter's flags.
+  bool reducePointCloud(double vfs, int64_t* points = nullptr, int32_t* flags = nullptr) {
+    if (!(vfs > 0.0)) return false;
+    int64_t n = 0;
+    int32_t f = 0;
+    if (rgbdfe_reduce_node_cloud(fe_.get(), id_, vfs, &n, &f) != RGBDFE_OK) return false;
+    if (points) *points = n;
+    if (flags) *flags = f;
+    return true;
+  }
   // feature_locations_2d_ (node.h:160): only the g2o pair refinement reads them (params.g2o_iterations > 0,
   // node.cpp:1222-1268); kp_xy = n x (u, v)
   bool setKeypoints(const float* kp_xy) { return rgbdfe_upload_node_keypoints(fe_.get(), id_, kp_xy, n_) == RGBDFE_OK; }
@@ -408,9 +420,13 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
 // that have no valid estimate; world2cam = n x 16 floats, the column-major Matrix4f of pcl_ros::transformAsMatrix(cam2rgb *
 // eigenTransf2TF(v->estimate())) per node; maximum_depth and preserve_raster_on_save are the parameters of those names.
 // aggregate_cloud = rows of (x, y, z, rgb bits); node_offsets (optional) = the first row of every node, then the row count.
+// voxelfilter_size > 0 (parameter "voxelfilter_size"): the aggregate cloud is voxel-filtered on the device before it is
+// returned (GraphManager::reducePointCloud's filter, applied to the whole map); node_offsets then still describe the
+// unfiltered cloud.  This header knows no device allocator, so the assembled points pass through the host between the two
+// device steps; a caller with device buffers of its own chains rgbdfe_assemble_map_device and voxelFilter instead.
 inline bool assembleAllClouds(const FrontEnd& fe, const std::vector<int32_t>& node_ids, const std::vector<float>& world2cam,
                               double maximum_depth, bool preserve_raster_on_save, std::vector<float>* aggregate_cloud,
-                              std::vector<int64_t>* node_offsets = nullptr) {
+                              std::vector<int64_t>* node_offsets = nullptr, double voxelfilter_size = 0.0) {
   if (world2cam.size() != node_ids.size() * 16) return false;
   std::vector<int64_t> off(node_ids.size() + 1, 0);
   int64_t n = 0;
@@ -425,7 +441,26 @@ inline bool assembleAllClouds(const FrontEnd& fe, const std::vector<int32_t>& no
                           aggregate_cloud->data(), n, &n, off.data()) != RGBDFE_OK)
     return false;
   if (node_offsets) *node_offsets = off;
+  if (voxelfilter_size > 0.0 && n > 0) {
+    std::vector<float> filtered((size_t)n * 4);  // n rows always suffice
+    int64_t kept = 0;
+    if (rgbdfe_voxel_filter(fe.get(), aggregate_cloud->data(), n, voxelfilter_size, filtered.data(), n, &kept, nullptr) != RGBDFE_OK)
+      return false;
+    filtered.resize((size_t)kept * 4);
+    aggregate_cloud->swap(filtered);
+  }
   return true;
+}
+
+// pcl::VoxelGrid with a cubic leaf of voxelfilter_size over a device buffer of n_in rows (x, y, z, rgb bits) into another of
+// `capacity` rows on the context's device (rgbdfe_voxel_filter_device): the consumer of rgbdfe_assemble_map_device's output.
+// Returns the rows written, or -1 (needed: the rows that would have been; flags: RGBDFE_VOXEL_LEAF_TOO_SMALL).
+inline int64_t voxelFilter(const FrontEnd& fe, const void* d_points, int64_t n_in, double voxelfilter_size, void* d_out,
+                           int64_t capacity, int32_t* flags = nullptr, void* stream = nullptr, int64_t* needed = nullptr) {
+  int64_t n = 0;
+  const int rc = rgbdfe_voxel_filter_device(fe.get(), d_points, n_in, voxelfilter_size, d_out, capacity, &n, flags, stream);
+  if (needed) *needed = n;
+  return rc == RGBDFE_OK ? n : -1;
 }
 
 // 4x4 inverse of a column-major float matrix (the reference calls Eigen's Matrix4f::inverse(), node.cpp:1536):

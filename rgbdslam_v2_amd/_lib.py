@@ -302,6 +302,13 @@ def load():
     L.rgbdfe_assemble_map_device.argtypes = [ctx, i32, vp, vp, C.c_double, i32, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]
     L.rgbdfe_download_node_cloud.restype = C.c_int
     L.rgbdfe_download_node_cloud.argtypes = [ctx, i32, vp, C.c_int64, C.POINTER(i32), C.POINTER(i32)]
+    L.rgbdfe_voxel_filter.restype = C.c_int
+    L.rgbdfe_voxel_filter.argtypes = [ctx, vp, C.c_int64, C.c_double, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(i32)]
+    L.rgbdfe_voxel_filter_device.restype = C.c_int
+    L.rgbdfe_voxel_filter_device.argtypes = [ctx, vp, C.c_int64, C.c_double, vp, C.c_int64, C.POINTER(C.c_int64),
+                                             C.POINTER(i32), vp]
+    L.rgbdfe_reduce_node_cloud.restype = C.c_int
+    L.rgbdfe_reduce_node_cloud.argtypes = [ctx, i32, C.c_double, C.POINTER(C.c_int64), C.POINTER(i32)]
     L.rgbdfe_observation_criterion_met.restype = C.c_int
     L.rgbdfe_observation_criterion_met.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                                    C.POINTER(C.c_double)]
@@ -429,6 +436,7 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_host_register", "rgbdfe_host_unregister",
     "rgbdfe_upload_node_cloud", "rgbdfe_release_node_cloud", "rgbdfe_observation_likelihood",
     "rgbdfe_assemble_map", "rgbdfe_assemble_map_device", "rgbdfe_download_node_cloud",
+    "rgbdfe_voxel_filter", "rgbdfe_voxel_filter_device", "rgbdfe_reduce_node_cloud",
     "rgbdfe_observation_criterion_met", "rgbdfe_set_latency_mode", "rgbdfe_set_profiling", "rgbdfe_get_kernel_time",
     "rgbdfe_reset_kernel_time", "rgbdfe_graph_stats", "rgbdfe_set_graph_capture", "rgbdfe_match_pair_list_allgather_inliers", "rgbdfe_pack_inliers", "rgbdfe_sizeof_inlier_header", "rgbdfe_sizeof_match_result", "rgbdfe_abi_version",
     "rgbdfe_pose_graph_create", "rgbdfe_pose_graph_destroy", "rgbdfe_pose_graph_add_node",

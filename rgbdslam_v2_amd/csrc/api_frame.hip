@@ -557,7 +557,12 @@ int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new
       return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "observation likelihood needs the clouds of both nodes");
     const CloudEntry& cn = a->second;
     const CloudEntry& co = b->second;
+    const bool flat = co.ch <= 1 || co.cw <= 1;  // misc.cpp:835: asked of old_pc before the widths are compared (:844)
     if (i == 0) { ch = co.ch; cw = co.cw; cloud_skip = co.cloud_skip; }
+    if (ch <= 1 || cw <= 1) {
+      if (!flat) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "clouds of one batch must share their dimensions");
+      continue;
+    }
     if (cn.ch != ch || cn.cw != cw || co.ch != ch || co.cw != cw || co.cloud_skip != cloud_skip)
       return fail(ctx, RGBDFE_ERR_INVALID_ARG, "clouds of one batch must share their dimensions");  // misc.cpp:845
     if (cn.samples_skip != emm_skip_step) {  // (re)build this node's dense sample array for this skip step

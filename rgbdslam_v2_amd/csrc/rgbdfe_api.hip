@@ -846,6 +846,35 @@ int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_ou
   return RGBDFE_FIRST(ctx, impl::rgbdfe_download_node_cloud(c, node_id, cloud_out, capacity_points, rows, cols));
 }
 
+int rgbdfe_voxel_filter(rgbdfe_ctx* ctx, const float* points, int64_t n_in, double voxelfilter_size, float* out, int64_t capacity,
+                        int64_t* n_out, int32_t* flags) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_voxel_filter(c, points, n_in, voxelfilter_size, out, capacity, n_out, flags));
+}
+
+int rgbdfe_voxel_filter_device(rgbdfe_ctx* ctx, const void* d_points, int64_t n_in, double voxelfilter_size, void* d_out,
+                               int64_t capacity, int64_t* n_out, int32_t* flags, void* stream) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_voxel_filter_device(c, d_points, n_in, voxelfilter_size, d_out, capacity, n_out, flags,
+                                                            stream));
+}
+
+// every device of a group reduces its replica of the cloud: the same kernels on the same bytes; n_out / flags from the first
+int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilter_size, int64_t* n_out, int32_t* flags) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  if (!n_out) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  return RGBDFE_ALL(ctx, [&]() -> int {
+    int64_t n = 0;
+    int32_t f = 0;
+    const int rc = impl::rgbdfe_reduce_node_cloud(c, node_id, voxelfilter_size, &n, &f);
+    if (!RGBDFE_IS_GROUP(ctx) || c == ctx->group->children[0]) {
+      *n_out = n;
+      if (flags) *flags = f;
+    }
+    return rc;
+  }());
+}
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

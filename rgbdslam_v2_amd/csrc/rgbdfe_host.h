@@ -1,6 +1,6 @@
 // rgbdfe_host.h -- what the host-side translation units of librgbdfe.so share: the context (node store, lanes, graph cache,
 // staging), the batch machinery's entry points (api_batches.hip), the single-device implementation of every entry point
-// (namespace impl: api_context / api_pairs / api_detect / api_frame / api_map.hip) and the multi-device group (api_group.hip).
+// (namespace impl: api_context / api_pairs / api_detect / api_frame / api_map / api_voxel.hip) and the multi-device group (api_group.hip).
 // rgbdfe_api.hip holds the extern "C" layer only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -36,7 +36,7 @@ namespace rgbdfe_host {
 // a frame's structured point cloud, resident for the environment measurement model
 struct CloudEntry {
   float4* d = nullptr;  // ch x cw points, followed by the ch x cw depth plane (z only) the EMM gathers from
-  int ch = 0, cw = 0;
+  int ch = 0, cw = 0;   // 1 x n (n >= 0) behind rgbdfe_reduce_node_cloud: unstructured
   float fx = 0, fy = 0, cx = 0, cy = 0;  // as getCameraIntrinsics assigns them (double -> float)
   int cloud_skip = 1;                    // cloud_creation_skip_step the cloud was built with
   float4* d_samples = nullptr;           // the points the EMM visits for emm skip step `samples_skip`, dense
@@ -571,6 +571,9 @@ int rgbdfe_release_node_cloud(rgbdfe_ctx* ctx, int32_t node_id);
 int rgbdfe_assemble_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth, int32_t preserve_raster, float* out, int64_t capacity, int64_t* n_out, int64_t* node_offsets);
 int rgbdfe_assemble_map_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth, int32_t preserve_raster, void* d_out, int64_t capacity, int64_t* n_out, int64_t* node_offsets, void* stream);
 int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_out, int64_t capacity_points, int32_t* rows, int32_t* cols);
+int rgbdfe_voxel_filter(rgbdfe_ctx* ctx, const float* points, int64_t n_in, double voxelfilter_size, float* out, int64_t capacity, int64_t* n_out, int32_t* flags);
+int rgbdfe_voxel_filter_device(rgbdfe_ctx* ctx, const void* d_points, int64_t n_in, double voxelfilter_size, void* d_out, int64_t capacity, int64_t* n_out, int32_t* flags, void* stream);
+int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilter_size, int64_t* n_out, int32_t* flags);
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids, const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out);
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all, double observability_threshold, double* quality);
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);

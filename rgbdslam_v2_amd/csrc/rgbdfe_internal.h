@@ -272,6 +272,35 @@ void launch_map_count_scan(const MapNode* nodes, const uint32_t* tile_node, uint
                            float md2, uint32_t* tile_count, int64_t* tile_first, int64_t* node_first, hipStream_t stream);
 void launch_map_write(const MapNode* nodes, const uint32_t* tile_node, uint32_t n_tiles, const int64_t* tile_first, bool clip,
                       float md2, float4* out, hipStream_t stream);
+// voxel_filter.hip: pcl::VoxelGrid's centroids over a cloud of n < 2^31 points (the stages: the head of that file).  The
+// host reads VoxHeader twice: behind launch_vox_stats (the box, n_valid) and behind launch_vox_heads (n_cells).
+constexpr uint32_t kVoxTile = 1024;      // points (or sorted pairs) of a workgroup in the point and cell passes
+constexpr uint32_t kVoxSortTile = 4096;  // pairs of a workgroup in a sort pass
+struct VoxHeader {
+  float min_p[3], max_p[3];  // the bounding box of the valid points (+inf / -inf when there is none)
+  uint32_t n_valid, n_cells;
+};
+struct VoxGrid {
+  float inv;           // 1.0f / leaf
+  float min_b[3];      // (float)min_b
+  uint32_t mul1, mul2; // div0, div0 * div1 as int32 bits
+  uint32_t flip;       // 0x80000000 when the int32 cell index can be negative (the keys then sort as signed), else 0
+};
+// tile_box: 6 floats per point tile; tile_count: one per point tile; tile_first: one more
+void launch_vox_stats(const float4* pts, uint32_t n, float* tile_box, uint32_t* tile_count, uint32_t* tile_first, VoxHeader* hdr,
+                      hipStream_t stream);
+void launch_vox_keys(const float4* pts, uint32_t n, const VoxGrid& g, const uint32_t* tile_first, uint32_t* keys, uint32_t* idx,
+                     hipStream_t stream);
+// `passes` stable 8-bit passes from the low byte up over n (key, index) pairs, ping-pong between the two buffers; returns
+// the buffer that holds the result.  hist: 256 x (n / kVoxSortTile, rounded up) counters; digit_total: 256
+int launch_vox_sort(uint32_t n, int passes, uint32_t* keys[2], uint32_t* idx[2], uint32_t* hist, uint32_t* digit_total,
+                    hipStream_t stream);
+// cell_start[c] = the first sorted position of cell c, cell_start[n_cells] = n (n + 1 entries suffice); hdr->n_cells
+void launch_vox_heads(const uint32_t* keys, uint32_t n, uint32_t* tile_count, uint32_t* tile_first, uint32_t* cell_start,
+                      VoxHeader* hdr, hipStream_t stream);
+// out[c] = the centroid row of cell c; zplane (may be NULL): its z again, the plane behind a resident cloud
+void launch_vox_centroids(const float4* pts, const uint32_t* idx, const uint32_t* cell_start, uint32_t n_cells, float4* out,
+                          float* zplane, hipStream_t stream);
 void launch_sift_pack(const float* desc_in, const int32_t* kept_idx, const int32_t* n_ptr, int max_rows,
                       bool root_sift, float* raw, float* feat, hipStream_t stream);
 

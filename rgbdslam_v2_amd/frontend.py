@@ -10,6 +10,7 @@ like tests of the reference; all arithmetic happens in librgbdfe.so on the GPU.
 """
 import ctypes as C
 import threading
+import warnings
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -1141,6 +1142,48 @@ class FrontEnd:
             self._ctx, n, node_ids.ctypes.data, T.ctypes.data, float(maximum_depth), int(bool(preserve_raster)),
             out.data_ptr() if out.shape[0] else None, int(out.shape[0]), C.byref(n_out), offsets.ctypes.data, stream))
         return (n_out.value, offsets) if return_offsets else n_out.value
+
+    def voxel_filter(self, points, voxelfilter_size, return_flags=False):
+        """pcl::VoxelGrid with a cubic leaf of voxelfilter_size (Node::reducePointCloud, node.cpp:1448-1460) over points,
+        [n, 4] float32 (x, y, z, rgb bits): one centroid row per occupied cell, in ascending cell index.  return_flags:
+        also the flags (bit 0: the leaf is too small for the cloud's extent and the input came back unchanged)."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        n_out, flags = C.c_int64(0), C.c_int32(0)
+
+        def call(out, cap):
+            return self._L.rgbdfe_voxel_filter(self._ctx, pts.ctypes.data if len(pts) else None, len(pts), float(voxelfilter_size),
+                                               out.ctypes.data if out is not None else None, cap, C.byref(n_out), C.byref(flags))
+        st = call(None, 0)  # the size: RGBDFE_ERR_CAPACITY with n_out set, or OK for an empty result
+        if st != -5:
+            self._check(st)
+        out = np.empty((n_out.value, 4), np.float32)
+        self._check(call(out, len(out)))
+        out = out[:n_out.value]
+        return (out, flags.value) if return_flags else out
+
+    def voxel_filter_device(self, points, voxelfilter_size, out, stream=None, return_flags=False):
+        """voxel_filter from `points` into `out`, contiguous float32 torch tensors [n, 4] and [capacity, 4] on this
+        context's device that do not overlap; no point crosses to the host.  Returns the number of rows written."""
+        for t, name in ((points, "points"), (out, "out")):
+            if not (t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 4 and t.element_size() == 4):
+                raise ValueError("%s must be a contiguous [n, 4] float32 tensor on the device" % name)
+        n_out, flags = C.c_int64(0), C.c_int32(0)
+        self._check(self._L.rgbdfe_voxel_filter_device(
+            self._ctx, points.data_ptr() if points.shape[0] else None, int(points.shape[0]), float(voxelfilter_size),
+            out.data_ptr() if out.shape[0] else None, int(out.shape[0]), C.byref(n_out), C.byref(flags), stream))
+        return (n_out.value, flags.value) if return_flags else n_out.value
+
+    def reduce_node_cloud(self, node_id, voxelfilter_size):
+        """Node::reducePointCloud (node.cpp:1448-1460): the node's resident cloud becomes its voxel-filtered cloud,
+        unstructured (node_cloud() then has the shape (1, n, 4)).  Like the reference, voxelfilter_size <= 0 warns and
+        does nothing (returns None); otherwise returns (rows of the cloud, flags)."""
+        if not voxelfilter_size > 0:
+            warnings.warn("Point Clouds can't be reduced because of invalid voxelfilter_size")  # node.cpp:1458
+            return None
+        n_out, flags = C.c_int64(0), C.c_int32(0)
+        self._check(self._L.rgbdfe_reduce_node_cloud(self._ctx, int(node_id), float(voxelfilter_size), C.byref(n_out),
+                                                     C.byref(flags)))
+        return n_out.value, flags.value
 
     def observation_likelihood(self, new_ids, old_ids, transforms, emm_skip_step=8):
         """observationLikelihood (misc.cpp:814-969) for a batch of directed edges; transforms: n x 4 x 4
