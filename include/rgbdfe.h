@@ -502,6 +502,98 @@ int rgbdfe_voxel_filter_device(rgbdfe_ctx* ctx, const void* d_points, int64_t n_
 int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilter_size, int64_t* n_out,
                              int32_t* flags);
 
+/* ---- occupancy map: node clouds ray-cast into a colour OctoMap on the device ------------------------------
+ * An rgbdfe_octomap is the octree of ColorOctomapServer (ColorOctomapServer.cpp:61-129), fed as
+ *   GraphManager::renderToOctomap / saveOctomapImpl feed it (graph_mgr_io.cpp:253-329): insertPointCloud(cloud, origin,
+ *   max_range, lazy_eval = true) and then averageNodeColor per point, one cloud after another.  Its state is the set of
+ *   leaves, all at depth 16 (lazy insertion, nothing prunes): key, log-odds, colour.  The octomap library is not part
+ *   of the reference tree: the statements below are this library's contract, a restatement of the published 1.6-1.9
+ *   line (restated, not pinned).  One rounding per operation; "float" is binary32, "double" binary64.
+ *   Parameters (rgbdfe_octomap_default_params: parameter_server.cpp:56-64): resolution > 0 and finite with a finite
+ *   inverse, prob_hit / prob_miss / clamping_min / clamping_max inside (0, 1), clamping_min <= clamping_max, else
+ *   RGBDFE_ERR_INVALID_ARG.  logodds(p) = (float)log(p / (1 - p)) (double, then one conversion); occupancy_threshold
+ *   is carried and used by nothing here.
+ *   A cloud = rows of 4 floats (x, y, z, rgb bits) and a column-major Matrix4f (as rgbdfe_assemble_map takes it);
+ *   origin = its translation column (T[12], T[13], T[14]).
+ *   Transform: a row whose x, y and z are finite becomes p[a] = ((R[a][0] * x + R[a][1] * y) + R[a][2] * z) + t[a] in
+ *   float.  A row with a non-finite coordinate before or after the transform contributes nothing, neither to the
+ *   occupancy nor to the colours.
+ *   Key of a coordinate c (float): k = floor((1.0 / resolution) * (double)c) + 32768, valid iff 0 <= k < 65536; a
+ *   point's key is valid iff its three are.  Centre of key k = ((double)(k - 32768) + 0.5) * resolution.
+ *   Range (computeUpdate without a bounding box): d = p - origin in float, norm = sqrt((double)((dx * dx + dy * dy) +
+ *   dz * dz)) with the sum in float.  max_range < 0 or norm <= max_range: the ray origin -> p yields free cells, and
+ *   p's cell, if its key is valid, is occupied.  Otherwise the ray is origin -> origin + (d / (float)norm) *
+ *   (float)max_range, free cells only.  max_range NaN: RGBDFE_ERR_INVALID_ARG; +inf never clips.
+ *   Ray origin -> e (computeRayKeys, Amanatides & Woo): nothing if a key of origin or e is invalid or the two keys are
+ *   equal; otherwise the origin's cell is free.  d = e - origin, length = (float)norm(d) as above, dir = d / length in
+ *   float; step[a] = sign of dir[a].  For step[a] != 0: tMax[a] = ((centre(key[a]) + (double)(float)(step[a] *
+ *   resolution * 0.5)) - (double)origin[a]) / (double)dir[a], tDelta[a] = resolution / fabs((double)dir[a]); DBL_MAX
+ *   both where step[a] == 0.  Each iteration takes a = tMax0 < tMax1 ? (tMax0 < tMax2 ? 0 : 2) : (tMax1 < tMax2 ? 1 : 2)
+ *   (a tie falls to the later axis), then key[a] += step[a] (16-bit, wrapping) and tMax[a] += tDelta[a]; it ends when
+ *   the key equals e's key, or when min(tMax) > (double)length (the library's guard against a missed end cell), in
+ *   both cases without a cell; otherwise the cell is free.  A ray ends after 196608 iterations (no ray between two valid
+ *   keys needs more; the library has no such bound).
+ *   Per cloud: the free and the occupied set are formed over the whole cloud, a cell in both is occupied only, and
+ *   every cell of either set takes exactly one update: a new leaf starts at 0 with colour (255, 255, 255); value =
+ *   value + logodds(prob_hit or prob_miss) in float, then value < logodds(clamping_min) -> that bound, value >
+ *   logodds(clamping_max) -> that bound.
+ *   Colour (averageNodeColor), after the cloud's occupancy update: over the contributing rows in ascending index,
+ *   those beyond max_range included: if the row's key is valid and a leaf (free or occupied) exists there, then with
+ *   r, g, b = bits 23-16, 15-8, 7-0 of the row's rgb word: a leaf whose colour is not (255, 255, 255) takes (prev +
+ *   new) / 2 per channel in integer arithmetic, a leaf whose colour is (255, 255, 255) takes the new colour.  (An
+ *   average that lands on white therefore starts again, as in the library.)
+ *   Clouds are applied strictly one after another in list order: clamping and the colour rule do not commute.
+ *   Inner nodes (updateInnerOccupancy), pruning, the bounding-box branch, occupancyFilter and .ot / .bt files are out
+ *   of scope.
+ * rgbdfe_octomap_create: a map of capacity_cells cells (1 <= capacity_cells < 2^31; 20 bytes each) on the context's
+ *   device (the first device of a multi-device handle); params NULL = the defaults.  Destroy the map before the
+ *   context.  rgbdfe_octomap_reset is ColorOctomapServer::reset (no leaves, same parameters, same capacity).
+ *   rgbdfe_octomap_reserve re-houses the leaves in a table of capacity_cells cells on the device (fewer than the map
+ *   has leaves: RGBDFE_ERR_CAPACITY, nothing changes).
+ * Capacity: the map holds at most capacity_cells leaves and never drops a cell silently.  A cloud fits iff the
+ *   leaves before it plus the new cells of its free and occupied sets are at most capacity_cells.  If a cloud does
+ *   not fit, the call returns RGBDFE_ERR_CAPACITY with *n_done = the number of clouds applied in full, and the map
+ *   equals, leaf for leaf, the map after those clouds; reserve more and go on with the rest of the list.
+ *   The table is open addressing with linear probing: exact up to the last cell, but fast only while the load stays
+ *   well below 1 (the wrappers double the capacity when a cloud does not fit).
+ * rgbdfe_octomap_insert_nodes: node_ids / transforms exactly as rgbdfe_assemble_map takes them (ids may repeat, sizes
+ *   may be mixed, a cloud reduced by rgbdfe_reduce_node_cloud is an ordinary input); max_range is the reference's
+ *   maximum_depth.  An id without a cloud: RGBDFE_ERR_UNKNOWN_NODE before any state changes.  n_done may be NULL.
+ * rgbdfe_octomap_insert_cloud: the same for one host array of n rows (n >= 2^31: RGBDFE_ERR_CAPACITY).
+ * rgbdfe_octomap_leaves: the leaves as 16-byte records in ascending key[0] | key[1] << 16 | key[2] << 32; capacity <
+ *   the number of leaves: RGBDFE_ERR_CAPACITY with *n_out = the needed size, before anything is written.
+ * rgbdfe_octomap_stats: out[0] = capacity_cells, out[1] = leaves, out[2] = kernel launches of the last insert call;
+ *   further entries 0. */
+typedef struct rgbdfe_octomap rgbdfe_octomap;
+typedef struct rgbdfe_octomap_params {
+  double resolution;           /* octomap_resolution, 0.05 */
+  double prob_hit;             /* octomap_prob_hit, 0.9 */
+  double prob_miss;            /* octomap_prob_miss, 0.4 */
+  double clamping_min;         /* octomap_clamping_min, 0.001 */
+  double clamping_max;         /* octomap_clamping_max, 0.999 */
+  double occupancy_threshold;  /* octomap_occupancy_threshold, 0.5: carried, unused */
+} rgbdfe_octomap_params;
+typedef struct rgbdfe_octomap_leaf {
+  uint16_t key[3];
+  uint16_t zero0;
+  float log_odds;
+  uint8_t rgb[3];
+  uint8_t zero1;
+} rgbdfe_octomap_leaf;
+void rgbdfe_octomap_default_params(rgbdfe_octomap_params* params);
+int rgbdfe_octomap_create(rgbdfe_ctx* ctx, const rgbdfe_octomap_params* params, int64_t capacity_cells,
+                          rgbdfe_octomap** map);
+void rgbdfe_octomap_destroy(rgbdfe_octomap* map);
+int rgbdfe_octomap_reset(rgbdfe_octomap* map);
+int rgbdfe_octomap_reserve(rgbdfe_octomap* map, int64_t capacity_cells);
+int rgbdfe_octomap_insert_nodes(rgbdfe_octomap* map, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                                double max_range, int32_t* n_done);
+int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_t n, const float* transform,
+                                double max_range);
+int rgbdfe_octomap_size(rgbdfe_octomap* map, int64_t* n_leaves);
+int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out);
+int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out);
+
 /* ---- candidate selection for loop closure ----------------------------------
  * rgbdfe_potential_edge_targets is GraphManager::getPotentialEdgeTargetsWithDijkstra (graph_manager.cpp:204-324): the
  * ids of the earlier nodes a new node is to be compared with -- `sequential_targets` direct predecessors, then

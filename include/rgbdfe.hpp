@@ -463,6 +463,56 @@ inline int64_t voxelFilter(const FrontEnd& fe, const void* d_points, int64_t n_i
   return rc == RGBDFE_OK ? n : -1;
 }
 
+// ColorOctomapServer (src/ColorOctomapServer.cpp) on the device: the seam of GraphManager::renderToOctomap / saveOctomapImpl
+// (src/graph_mgr_io.cpp:253-329).  insertClouds is the loop over the nodes with a valid estimate: node_ids in graph_ order,
+// world2cam as assembleAllClouds takes it, max_range = the parameter "maximum_depth".  When the table is full it grows (twice
+// the cells) and goes on with the clouds that are not in yet, so a false return is an error, never a dropped cell.
+class OctoMap {
+ public:
+  OctoMap(const FrontEnd& fe, int64_t capacity_cells, const rgbdfe_octomap_params* params = nullptr)
+      : map_(nullptr, rgbdfe_octomap_destroy), capacity_(capacity_cells) {
+    rgbdfe_octomap* m = nullptr;
+    if (rgbdfe_octomap_create(fe.get(), params, capacity_cells, &m) == RGBDFE_OK) map_.reset(m);
+  }
+  bool valid() const { return (bool)map_; }
+  rgbdfe_octomap* get() const { return map_.get(); }
+  bool reset() { return map_ && rgbdfe_octomap_reset(map_.get()) == RGBDFE_OK; }  // ColorOctomapServer::reset
+  bool reserve(int64_t capacity_cells) {
+    if (!map_ || rgbdfe_octomap_reserve(map_.get(), capacity_cells) != RGBDFE_OK) return false;
+    capacity_ = capacity_cells;
+    return true;
+  }
+  bool insertClouds(const std::vector<int32_t>& node_ids, const std::vector<float>& world2cam, double max_range) {
+    if (!map_ || world2cam.size() != node_ids.size() * 16) return false;
+    size_t at = 0;
+    while (at < node_ids.size()) {
+      int32_t done = 0;
+      const int rc = rgbdfe_octomap_insert_nodes(map_.get(), (int32_t)(node_ids.size() - at), node_ids.data() + at,
+                                                 world2cam.data() + at * 16, max_range, &done);
+      if (rc == RGBDFE_OK) return true;
+      if (rc != RGBDFE_ERR_CAPACITY || !reserve(capacity_ * 2)) return false;
+      at += (size_t)done;
+    }
+    return true;
+  }
+  int64_t size() const {
+    int64_t n = 0;
+    return map_ && rgbdfe_octomap_size(map_.get(), &n) == RGBDFE_OK ? n : -1;
+  }
+  // the leaves in ascending key order (key, log-odds, colour)
+  bool leaves(std::vector<rgbdfe_octomap_leaf>* out) const {
+    const int64_t n = size();
+    if (n < 0) return false;
+    out->resize((size_t)n);
+    int64_t got = 0;
+    return rgbdfe_octomap_leaves(map_.get(), out->data(), n, &got) == RGBDFE_OK && got == n;
+  }
+
+ private:
+  std::unique_ptr<rgbdfe_octomap, void (*)(rgbdfe_octomap*)> map_;
+  int64_t capacity_;
+};
+
 // 4x4 inverse of a column-major float matrix (the reference calls Eigen's Matrix4f::inverse(), node.cpp:1536):
 // Gauss-Jordan with partial pivoting in double, rounded to float
 inline std::array<float, 16> inverse4(const std::array<float, 16>& T) {

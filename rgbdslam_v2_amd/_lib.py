@@ -81,6 +81,15 @@ class RgbdfeSensorCloud(C.Structure):   # rgbdfe_sensor_cloud
     _fields_ = [("cloud_skip", C.c_int32), ("encoding_bgr", C.c_int32), ("min_depth", C.c_double)]
 
 
+class OctomapParams(C.Structure):   # rgbdfe_octomap_params
+    _fields_ = [("resolution", C.c_double), ("prob_hit", C.c_double), ("prob_miss", C.c_double),
+                ("clamping_min", C.c_double), ("clamping_max", C.c_double), ("occupancy_threshold", C.c_double)]
+
+
+# rgbdfe_octomap_leaf
+OCTOMAP_LEAF_DTYPE = np.dtype([("key", "<u2", (3,)), ("zero0", "<u2"), ("log_odds", "<f4"), ("rgb", "u1", (3,)),
+                               ("zero1", "u1")])
+
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4")])
 
@@ -309,6 +318,27 @@ def load():
                                              C.POINTER(i32), vp]
     L.rgbdfe_reduce_node_cloud.restype = C.c_int
     L.rgbdfe_reduce_node_cloud.argtypes = [ctx, i32, C.c_double, C.POINTER(C.c_int64), C.POINTER(i32)]
+    omap = vp
+    L.rgbdfe_octomap_default_params.restype = None
+    L.rgbdfe_octomap_default_params.argtypes = [C.POINTER(OctomapParams)]
+    L.rgbdfe_octomap_create.restype = C.c_int
+    L.rgbdfe_octomap_create.argtypes = [ctx, C.POINTER(OctomapParams), C.c_int64, C.POINTER(vp)]
+    L.rgbdfe_octomap_destroy.restype = None
+    L.rgbdfe_octomap_destroy.argtypes = [omap]
+    L.rgbdfe_octomap_reset.restype = C.c_int
+    L.rgbdfe_octomap_reset.argtypes = [omap]
+    L.rgbdfe_octomap_reserve.restype = C.c_int
+    L.rgbdfe_octomap_reserve.argtypes = [omap, C.c_int64]
+    L.rgbdfe_octomap_insert_nodes.restype = C.c_int
+    L.rgbdfe_octomap_insert_nodes.argtypes = [omap, i32, vp, vp, C.c_double, C.POINTER(i32)]
+    L.rgbdfe_octomap_insert_cloud.restype = C.c_int
+    L.rgbdfe_octomap_insert_cloud.argtypes = [omap, vp, C.c_int64, vp, C.c_double]
+    L.rgbdfe_octomap_size.restype = C.c_int
+    L.rgbdfe_octomap_size.argtypes = [omap, C.POINTER(C.c_int64)]
+    L.rgbdfe_octomap_leaves.restype = C.c_int
+    L.rgbdfe_octomap_leaves.argtypes = [omap, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rgbdfe_octomap_stats.restype = C.c_int
+    L.rgbdfe_octomap_stats.argtypes = [omap, vp, i32]
     L.rgbdfe_observation_criterion_met.restype = C.c_int
     L.rgbdfe_observation_criterion_met.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                                    C.POINTER(C.c_double)]
@@ -437,6 +467,9 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_upload_node_cloud", "rgbdfe_release_node_cloud", "rgbdfe_observation_likelihood",
     "rgbdfe_assemble_map", "rgbdfe_assemble_map_device", "rgbdfe_download_node_cloud",
     "rgbdfe_voxel_filter", "rgbdfe_voxel_filter_device", "rgbdfe_reduce_node_cloud",
+    "rgbdfe_octomap_default_params", "rgbdfe_octomap_create", "rgbdfe_octomap_destroy", "rgbdfe_octomap_reset",
+    "rgbdfe_octomap_reserve", "rgbdfe_octomap_insert_nodes", "rgbdfe_octomap_insert_cloud", "rgbdfe_octomap_size",
+    "rgbdfe_octomap_leaves", "rgbdfe_octomap_stats",
     "rgbdfe_observation_criterion_met", "rgbdfe_set_latency_mode", "rgbdfe_set_profiling", "rgbdfe_get_kernel_time",
     "rgbdfe_reset_kernel_time", "rgbdfe_graph_stats", "rgbdfe_set_graph_capture", "rgbdfe_match_pair_list_allgather_inliers", "rgbdfe_pack_inliers", "rgbdfe_sizeof_inlier_header", "rgbdfe_sizeof_match_result", "rgbdfe_abi_version",
     "rgbdfe_pose_graph_create", "rgbdfe_pose_graph_destroy", "rgbdfe_pose_graph_add_node",

@@ -1,0 +1,333 @@
+// api_octomap.hip -- the occupancy map: resident node clouds (or a host cloud) ray-cast one after another into a persistent
+// table of leaves on the device (kernels: octomap.hip); GraphManager::renderToOctomap / saveOctomapImpl
+// (graph_mgr_io.cpp:253-329) over ColorOctomapServer::insertCloudCallback (ColorOctomapServer.cpp:61-129)
+// (one of the host-side translation units of librgbdfe.so; shared declarations: rgbdfe_host.h)
+#include "rgbdfe_host.h"
+
+#include <algorithm>
+
+struct rgbdfe_octomap {
+  rgbdfe_ctx* owner = nullptr;  // the handle the map was created on (a group's, for a multi-device one)
+  rgbdfe_ctx* ctx = nullptr;    // the single-device context its table lives on
+  rgbdfe_octomap_params prm{};
+  OctoTable tb{};
+  void* blob = nullptr;         // the table's one allocation
+  OctoCtl* d_ctl = nullptr;
+  uint32_t epoch = 0;           // of the last cloud
+  int64_t n_leaves = 0;
+  int64_t launches = 0;         // kernel launches of the last insert call (tools/bench_octomap.py)
+};
+
+namespace impl {
+
+namespace {
+
+struct DeviceBuffer {  // staging that lives for one call
+  void* p = nullptr;
+  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+};
+
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// a table of `cap` free slots
+int alloc_table(rgbdfe_ctx* ctx, uint32_t cap, OctoTable* tb, void** blob, hipStream_t st) {
+  const size_t b_key = up256(8 * (size_t)cap), b_f = up256(4 * (size_t)cap);
+  char* p = nullptr;
+  if (hipMalloc((void**)&p, b_key + 3 * b_f) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: table allocation failed");
+  }
+  tb->key = (unsigned long long*)p;
+  tb->value = (float*)(p + b_key);
+  tb->colour = (uint32_t*)(p + b_key + b_f);
+  tb->mark = (uint32_t*)(p + b_key + 2 * b_f);
+  tb->cap = cap;
+  *blob = p;
+  if (hipMemsetAsync(p, 0xff, b_key + 2 * b_f, st) != hipSuccess || hipMemsetAsync(tb->mark, 0, b_f, st) != hipSuccess) {
+    (void)hipFree(p);
+    *blob = nullptr;
+    return fail(ctx, RGBDFE_ERR_HIP, "octomap: clearing the table failed");
+  }
+  return RGBDFE_OK;
+}
+
+bool cap_ok(int64_t capacity_cells) { return capacity_cells >= 1 && capacity_cells < ((int64_t)1 << 31); }
+
+// the leaves into a fresh table of `cap` slots, which becomes the map's.  ctx->mu is held.
+int rehouse(rgbdfe_octomap* map, uint32_t cap) {
+  rgbdfe_ctx* ctx = map->ctx;
+  hipStream_t st = ctx->stream;
+  OctoTable nt{};
+  void* nblob = nullptr;
+  int rc = alloc_table(ctx, cap, &nt, &nblob, st);
+  if (rc != RGBDFE_OK) return rc;
+  OctoCtl ctl{};
+  ctl.n_leaves = (uint32_t)map->n_leaves;
+  hipError_t e = hipMemcpyAsync(map->d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    launch_octo_rehash(map->tb, nt, map->d_ctl, st);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&ctl, map->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess || ctl.overflow != 0) {
+    (void)hipFree(nblob);
+    return fail(ctx, e != hipSuccess ? RGBDFE_ERR_HIP : RGBDFE_ERR_INTERNAL, "octomap: re-housing the leaves failed");
+  }
+  (void)hipFree(map->blob);
+  map->blob = nblob;
+  map->tb = nt;
+  map->epoch = 0;  // the fresh table's marks are 0
+  return RGBDFE_OK;
+}
+
+struct CloudRef { const float4* d; uint32_t n; };
+
+// the clouds one after another; ctx->mu is held and the device is set
+int insert_clouds(rgbdfe_octomap* map, const std::vector<CloudRef>& clouds, const float* transforms, double max_range,
+                  int32_t* n_done) {
+  rgbdfe_ctx* ctx = map->ctx;
+  hipStream_t st = ctx->stream;
+  uint32_t n_max = 0;
+  for (const CloudRef& c : clouds) n_max = std::max(n_max, c.n);
+  const size_t n = n_max, n_tiles = (n + kVoxTile - 1) / kVoxTile, n_sort_tiles = (n + kVoxSortTile - 1) / kVoxSortTile;
+  const size_t b_hdr = 256, b_count = up256(4 * n_tiles), b_first = up256(4 * (n_tiles + 1)), b_pairs = up256(4 * n),
+               b_hist = up256(4 * 256 * n_sort_tiles), b_digits = 1024, b_cells = up256(4 * (n + 1));
+  int rc = ensure_scratch(ctx, b_hdr + b_count + b_first + 4 * b_pairs + b_hist + b_digits + b_cells);
+  if (rc != RGBDFE_OK) return rc;
+  char* at = (char*)ctx->d_scratch;
+  auto take = [&at](size_t b) { char* p = at; at += b; return p; };
+  OctoScratch s{};
+  s.hdr = (VoxHeader*)take(b_hdr);
+  s.tile_count = (uint32_t*)take(b_count);
+  s.tile_first = (uint32_t*)take(b_first);
+  s.keys[0] = (uint32_t*)take(b_pairs); s.keys[1] = (uint32_t*)take(b_pairs);
+  s.idx[0] = (uint32_t*)take(b_pairs); s.idx[1] = (uint32_t*)take(b_pairs);
+  s.hist = (uint32_t*)take(b_hist);
+  s.digits = (uint32_t*)take(b_digits);
+  s.cell_start = (uint32_t*)take(b_cells);
+
+  // the colour rows are sorted by slot, `cap` standing for "no leaf": the passes that cover 0 .. cap
+  int bits = 1;
+  while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)map->tb.cap) ++bits;
+  const int passes = (bits + 7) / 8;
+
+  const rgbdfe_octomap_params& p = map->prm;
+  OctoCloud oc{};
+  oc.res = p.resolution;
+  oc.inv_res = 1.0 / p.resolution;
+  oc.max_range = max_range;
+  oc.hit = (float)log(p.prob_hit / (1.0 - p.prob_hit));
+  oc.miss = (float)log(p.prob_miss / (1.0 - p.prob_miss));
+  oc.clamp_min = (float)log(p.clamping_min / (1.0 - p.clamping_min));
+  oc.clamp_max = (float)log(p.clamping_max / (1.0 - p.clamping_max));
+
+  OctoCtl ctl{};
+  ctl.n_leaves = (uint32_t)map->n_leaves;
+  HIP_TRY(ctx, hipMemcpyAsync(map->d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, st));
+  map->launches = 0;
+  for (size_t k = 0; k < clouds.size(); ++k) {
+    if (map->epoch >= 0x7ffffffeu) {  // 2 * epoch + 1 must fit the mark
+      HIP_TRY(ctx, hipMemsetAsync(map->tb.mark, 0, 4 * (size_t)map->tb.cap, st));
+      map->epoch = 0;
+    }
+    oc.epoch = ++map->epoch;
+    const float* T = transforms + k * 16;  // column-major Matrix4f
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) oc.R[r * 3 + c] = T[c * 4 + r];
+      oc.t[r] = T[12 + r];
+    }
+    launch_octo_cloud(map->tb, map->d_ctl, clouds[k].d, clouds[k].n, oc, passes, s, st);
+    map->launches += clouds[k].n == 0 ? 1 : 7 + 3 * passes;
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&ctl, map->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));  // the one read of the call
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  map->n_leaves = (int64_t)ctl.n_leaves;
+  if (n_done) *n_done = (int32_t)ctl.n_done;
+  if (ctl.overflow != 0) {
+    // the cloud that did not fit left claimed keys without leaves: a fresh table of the same size holds the leaves only
+    rc = rehouse(map, map->tb.cap);
+    if (rc != RGBDFE_OK) return rc;
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: the table is full (the clouds before *n_done are in; reserve more cells)");
+  }
+  return RGBDFE_OK;
+}
+
+bool range_ok(double max_range) { return !std::isnan(max_range); }
+
+}  // namespace
+
+void rgbdfe_octomap_default_params(rgbdfe_octomap_params* p) {
+  if (!p) return;
+  p->resolution = 0.05;            // octomap_resolution (parameter_server.cpp:56)
+  p->prob_hit = 0.9;               // octomap_prob_hit (:63)
+  p->prob_miss = 0.4;              // octomap_prob_miss (:64)
+  p->clamping_min = 0.001;         // octomap_clamping_min (:62)
+  p->clamping_max = 0.999;         // octomap_clamping_max (:61)
+  p->occupancy_threshold = 0.5;    // octomap_occupancy_threshold (:60)
+}
+
+rgbdfe_ctx* octomap_owner(rgbdfe_octomap* map) { return map ? map->owner : nullptr; }
+
+int rgbdfe_octomap_create(rgbdfe_ctx* ctx, rgbdfe_ctx* owner, const rgbdfe_octomap_params* params, int64_t capacity_cells,
+                          rgbdfe_octomap** out) {
+  if (!ctx || !out) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  *out = nullptr;
+  rgbdfe_octomap_params p;
+  impl::rgbdfe_octomap_default_params(&p);
+  if (params) p = *params;
+  auto prob = [](double v) { return v > 0.0 && v < 1.0; };
+  if (!(p.resolution > 0.0) || !std::isfinite(p.resolution) || !std::isfinite(1.0 / p.resolution) || !prob(p.prob_hit) ||
+      !prob(p.prob_miss) || !prob(p.clamping_min) || !prob(p.clamping_max) || !(p.clamping_min <= p.clamping_max))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG,
+                "octomap: resolution must be positive and finite, the probabilities inside (0, 1), clamping_min <= clamping_max");
+  if (!cap_ok(capacity_cells)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: capacity_cells must lie in [1, 2^31)");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  std::unique_ptr<rgbdfe_octomap> map(new rgbdfe_octomap());
+  map->owner = owner;
+  map->ctx = ctx;
+  map->prm = p;
+  if (hipMalloc((void**)&map->d_ctl, sizeof(OctoCtl)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: allocation failed");
+  }
+  int rc = alloc_table(ctx, (uint32_t)capacity_cells, &map->tb, &map->blob, ctx->stream);
+  if (rc == RGBDFE_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, RGBDFE_ERR_HIP, "octomap: clearing the table failed");
+  if (rc != RGBDFE_OK) {
+    if (map->blob) (void)hipFree(map->blob);
+    (void)hipFree(map->d_ctl);
+    return rc;
+  }
+  *out = map.release();
+  return RGBDFE_OK;
+}
+
+void rgbdfe_octomap_destroy(rgbdfe_octomap* map) {
+  if (!map) return;
+  {
+    std::lock_guard<std::mutex> g(map->ctx->mu);
+    (void)hipSetDevice(map->ctx->cfg.device_id);
+    (void)hipStreamSynchronize(map->ctx->stream);
+    if (map->blob) (void)hipFree(map->blob);
+    if (map->d_ctl) (void)hipFree(map->d_ctl);
+  }
+  delete map;
+}
+
+// ColorOctomapServer::reset: an empty tree with the same parameters
+int rgbdfe_octomap_reset(rgbdfe_octomap* map) {
+  rgbdfe_ctx* ctx = map->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  const size_t b_key = up256(8 * (size_t)map->tb.cap), b_f = up256(4 * (size_t)map->tb.cap);
+  HIP_TRY(ctx, hipMemsetAsync(map->blob, 0xff, b_key + 2 * b_f, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(map->tb.mark, 0, b_f, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  map->epoch = 0;
+  map->n_leaves = 0;
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_reserve(rgbdfe_octomap* map, int64_t capacity_cells) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!cap_ok(capacity_cells)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: capacity_cells must lie in [1, 2^31)");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (capacity_cells < map->n_leaves) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: fewer cells than the map has leaves");
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  return rehouse(map, (uint32_t)capacity_cells);
+}
+
+int rgbdfe_octomap_insert_nodes(rgbdfe_octomap* map, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                                double max_range, int32_t* n_done) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (n_done) *n_done = 0;
+  if (n_nodes < 0 || (n_nodes > 0 && (!node_ids || !transforms)) || !range_ok(max_range))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad octomap insertion arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (n_nodes == 0) return RGBDFE_OK;
+  std::vector<CloudRef> clouds((size_t)n_nodes);
+  for (size_t k = 0; k < clouds.size(); ++k) {
+    auto it = ctx->clouds.find(node_ids[k]);
+    if (it == ctx->clouds.end() || !it->second.d) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "octomap: no cloud for a listed node");
+    clouds[k].d = it->second.d;
+    clouds[k].n = (uint32_t)((size_t)it->second.ch * (size_t)it->second.cw);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  return insert_clouds(map, clouds, transforms, max_range, n_done);
+}
+
+int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_t n, const float* transform, double max_range) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (n < 0 || (n > 0 && !points) || !transform || !range_ok(max_range))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad octomap insertion arguments");
+  if (n > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: 2^31 points or more in one cloud");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  DeviceBuffer stage;
+  if (n > 0) {
+    if (hipMalloc(&stage.p, (size_t)n * sizeof(float4)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(stage.p, points, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+  }
+  std::vector<CloudRef> clouds(1);
+  clouds[0].d = (const float4*)stage.p;
+  clouds[0].n = (uint32_t)n;
+  return insert_clouds(map, clouds, transform, max_range, nullptr);  // synchronises before `stage` goes
+}
+
+int rgbdfe_octomap_size(rgbdfe_octomap* map, int64_t* n_leaves) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!n_leaves) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  *n_leaves = map->n_leaves;
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!out || n_out < 0) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const int64_t v[3] = {(int64_t)map->tb.cap, map->n_leaves, map->launches};
+  for (int32_t i = 0; i < n_out; ++i) out[i] = i < 3 ? v[i] : 0;
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!n_out || capacity < 0 || (capacity > 0 && !out)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  *n_out = map->n_leaves;
+  if (capacity < map->n_leaves) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: `out` is too small (*n_out records are needed)");
+  if (map->n_leaves == 0) return RGBDFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  const size_t cap = map->tb.cap;
+  std::vector<unsigned long long> key(cap);
+  std::vector<uint32_t> value(cap), colour(cap);
+  HIP_TRY(ctx, hipMemcpyAsync(key.data(), map->tb.key, 8 * cap, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(value.data(), map->tb.value, 4 * cap, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(colour.data(), map->tb.colour, 4 * cap, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<std::pair<unsigned long long, uint32_t>> order;  // (key, slot) of the leaves
+  order.reserve((size_t)map->n_leaves);
+  for (size_t i = 0; i < cap; ++i)
+    if (key[i] != kOctoEmptyKey && value[i] != kOctoNoLeaf) order.emplace_back(key[i], (uint32_t)i);
+  if ((int64_t)order.size() != map->n_leaves) return fail(ctx, RGBDFE_ERR_INTERNAL, "octomap: the leaf count and the table disagree");
+  std::sort(order.begin(), order.end());
+  for (size_t r = 0; r < order.size(); ++r) {
+    const unsigned long long k = order[r].first;
+    const uint32_t i = order[r].second;
+    rgbdfe_octomap_leaf& o = out[r];
+    o.key[0] = (uint16_t)(k & 0xffffu); o.key[1] = (uint16_t)((k >> 16) & 0xffffu); o.key[2] = (uint16_t)((k >> 32) & 0xffffu);
+    o.zero0 = 0;
+    memcpy(&o.log_odds, &value[i], 4);
+    o.rgb[0] = (uint8_t)((colour[i] >> 16) & 255u); o.rgb[1] = (uint8_t)((colour[i] >> 8) & 255u); o.rgb[2] = (uint8_t)(colour[i] & 255u);
+    o.zero1 = 0;
+  }
+  return RGBDFE_OK;
+}
+
+}  // namespace impl

@@ -875,6 +875,54 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
   }());
 }
 
+// the occupancy map lives on one device (the first of a group, where the clouds are replicated): every call goes there
+void rgbdfe_octomap_default_params(rgbdfe_octomap_params* params) { impl::rgbdfe_octomap_default_params(params); }
+
+int rgbdfe_octomap_create(rgbdfe_ctx* ctx, const rgbdfe_octomap_params* params, int64_t capacity_cells, rgbdfe_octomap** map) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_octomap_create(c, ctx, params, capacity_cells, map));
+}
+
+void rgbdfe_octomap_destroy(rgbdfe_octomap* map) {
+  try {
+    impl::rgbdfe_octomap_destroy(map);
+  } catch (...) {
+  }
+}
+
+#define RGBDFE_ON_MAP(map, call)                       \
+  do {                                                 \
+    if (!(map)) return RGBDFE_ERR_INVALID_ARG;         \
+    rgbdfe_ctx* ctx = impl::octomap_owner(map);        \
+    return RGBDFE_FIRST(ctx, ((void)c, (call)));       \
+  } while (0)
+
+int rgbdfe_octomap_reset(rgbdfe_octomap* map) { RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_reset(map)); }
+
+int rgbdfe_octomap_reserve(rgbdfe_octomap* map, int64_t capacity_cells) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_reserve(map, capacity_cells));
+}
+
+int rgbdfe_octomap_insert_nodes(rgbdfe_octomap* map, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                                double max_range, int32_t* n_done) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_insert_nodes(map, n_nodes, node_ids, transforms, max_range, n_done));
+}
+
+int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_t n, const float* transform, double max_range) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_insert_cloud(map, points, n, transform, max_range));
+}
+
+int rgbdfe_octomap_size(rgbdfe_octomap* map, int64_t* n_leaves) { RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_size(map, n_leaves)); }
+
+int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_leaves(map, out, capacity, n_out));
+}
+
+int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_stats(map, out, n_out));
+}
+#undef RGBDFE_ON_MAP
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

@@ -1,6 +1,6 @@
 // rgbdfe_host.h -- what the host-side translation units of librgbdfe.so share: the context (node store, lanes, graph cache,
 // staging), the batch machinery's entry points (api_batches.hip), the single-device implementation of every entry point
-// (namespace impl: api_context / api_pairs / api_detect / api_frame / api_map / api_voxel.hip) and the multi-device group (api_group.hip).
+// (namespace impl: api_context / api_pairs / api_detect / api_frame / api_map / api_voxel / api_octomap.hip) and the multi-device group (api_group.hip).
 // rgbdfe_api.hip holds the extern "C" layer only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -574,6 +574,18 @@ int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_ou
 int rgbdfe_voxel_filter(rgbdfe_ctx* ctx, const float* points, int64_t n_in, double voxelfilter_size, float* out, int64_t capacity, int64_t* n_out, int32_t* flags);
 int rgbdfe_voxel_filter_device(rgbdfe_ctx* ctx, const void* d_points, int64_t n_in, double voxelfilter_size, void* d_out, int64_t capacity, int64_t* n_out, int32_t* flags, void* stream);
 int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilter_size, int64_t* n_out, int32_t* flags);
+// api_octomap.hip (the map keeps the context it lives on; `owner` is the handle it was created through)
+void rgbdfe_octomap_default_params(rgbdfe_octomap_params* p);
+rgbdfe_ctx* octomap_owner(rgbdfe_octomap* map);
+int rgbdfe_octomap_create(rgbdfe_ctx* ctx, rgbdfe_ctx* owner, const rgbdfe_octomap_params* params, int64_t capacity_cells, rgbdfe_octomap** out);
+void rgbdfe_octomap_destroy(rgbdfe_octomap* map);
+int rgbdfe_octomap_reset(rgbdfe_octomap* map);
+int rgbdfe_octomap_reserve(rgbdfe_octomap* map, int64_t capacity_cells);
+int rgbdfe_octomap_insert_nodes(rgbdfe_octomap* map, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double max_range, int32_t* n_done);
+int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_t n, const float* transform, double max_range);
+int rgbdfe_octomap_size(rgbdfe_octomap* map, int64_t* n_leaves);
+int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out);
+int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out);
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids, const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out);
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all, double observability_threshold, double* quality);
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);

@@ -301,6 +301,44 @@ void launch_vox_heads(const uint32_t* keys, uint32_t n, uint32_t* tile_count, ui
 // out[c] = the centroid row of cell c; zplane (may be NULL): its z again, the plane behind a resident cloud
 void launch_vox_centroids(const float4* pts, const uint32_t* idx, const uint32_t* cell_start, uint32_t n_cells, float4* out,
                           float* zplane, hipStream_t stream);
+// octomap.hip: the occupancy map (include/rgbdfe.h, "occupancy map").  The table is open addressing with linear probing over
+// `cap` slots, one array per field: key (x | y << 16 | z << 32; kOctoEmptyKey: free), value (log-odds; bits kOctoNoLeaf: the
+// key is claimed, the leaf does not exist yet), colour (r << 16 | g << 8 | b), mark (2 * epoch + occupied of the last cloud
+// that touched the slot).  One cloud = launch_octo_cloud with its own epoch (>= 1, ascending).
+constexpr uint64_t kOctoEmptyKey = ~0ull;
+constexpr uint32_t kOctoNoLeaf = 0xffffffffu;
+constexpr uint32_t kOctoMaxSteps = 3u * 65536u;  // no ray between two valid keys takes more steps
+struct OctoTable {
+  unsigned long long* key;
+  float* value;
+  uint32_t* colour;
+  uint32_t* mark;
+  uint32_t cap;
+};
+struct OctoCtl {
+  uint32_t overflow;  // a key found no slot: the cloud that set it and every later cloud of the call change nothing
+  uint32_t n_done;    // clouds of the call that were applied
+  uint32_t n_leaves;
+  uint32_t pad;
+};
+struct OctoCloud {
+  float R[9], t[3];          // as MapNode: row-major rotation, translation = the ray origin
+  double inv_res, res;       // 1.0 / resolution, resolution
+  double max_range;          // < 0: off
+  float hit, miss, clamp_min, clamp_max;
+  uint32_t epoch;
+};
+// scratch of a cloud of n points (all in the context's scratch): as the voxel filter's sort, see api_octomap.hip
+struct OctoScratch {
+  uint32_t* keys[2];
+  uint32_t* idx[2];
+  uint32_t *hist, *digits, *tile_count, *tile_first, *cell_start;
+  VoxHeader* hdr;
+};
+void launch_octo_cloud(const OctoTable& tb, OctoCtl* ctl, const float4* pts, uint32_t n, const OctoCloud& c, int sort_passes,
+                       const OctoScratch& s, hipStream_t stream);
+// every leaf of `from` into the empty table `to` (to.cap >= the leaves of `from`)
+void launch_octo_rehash(const OctoTable& from, const OctoTable& to, OctoCtl* ctl, hipStream_t stream);
 void launch_sift_pack(const float* desc_in, const int32_t* kept_idx, const int32_t* n_ptr, int max_rows,
                       bool root_sift, float* raw, float* feat, hipStream_t stream);
 

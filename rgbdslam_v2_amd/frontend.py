@@ -11,6 +11,7 @@ like tests of the reference; all arithmetic happens in librgbdfe.so on the GPU.
 import ctypes as C
 import threading
 import warnings
+import weakref
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -213,6 +214,10 @@ class FrontEnd:
 
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value:
+            for ref in getattr(self, "_octomaps", []):  # a map goes before the context it lives on
+                m = ref()
+                if m is not None:
+                    m.close()
             self._L.rgbdfe_destroy(self._ctx)
             self._ctx = C.c_void_p()
 
@@ -1185,6 +1190,10 @@ class FrontEnd:
                                                      C.byref(flags)))
         return n_out.value, flags.value
 
+    def octomap(self, capacity_cells, **params):
+        """A persistent occupancy map on this context's device (ColorOctomapServer): see OctoMap."""
+        return OctoMap(self, capacity_cells, **params)
+
     def observation_likelihood(self, new_ids, old_ids, transforms, emm_skip_step=8):
         """observationLikelihood (misc.cpp:814-969) for a batch of directed edges; transforms: n x 4 x 4
         (row-major numpy matrices, new -> old).  Returns an n x 4 uint32 array (inliers, outliers, occluded, all)."""
@@ -1284,3 +1293,111 @@ class GraphManager:
     def nodeComparisons(self, new_node: Node, nodes_to_comp: Sequence[Node]) -> List[MatchingResult]:
         recs = self.frontend.match_node_pairs(new_node.id_, [n.id_ for n in nodes_to_comp])
         return [record_to_matching_result(r) for r in recs]
+
+
+class OctoMap:
+    """ColorOctomapServer on the device (ColorOctomapServer.cpp:61-129; the seam of GraphManager::renderToOctomap /
+    saveOctomapImpl, graph_mgr_io.cpp:253-329): the leaves of a colour OctoMap, fed by ray-casting clouds one after another.
+    params: resolution, prob_hit, prob_miss, clamping_min, clamping_max, occupancy_threshold (defaults:
+    parameter_server.cpp:56-64).  Close the map before its FrontEnd."""
+
+    def __init__(self, fe: "FrontEnd", capacity_cells: int, **params):
+        self._fe, self._L = fe, fe._L
+        self.params = _lib.OctomapParams()
+        self._L.rgbdfe_octomap_default_params(C.byref(self.params))
+        for k, v in params.items():
+            if not hasattr(self.params, k):
+                raise TypeError("unknown octomap parameter %r" % k)
+            setattr(self.params, k, float(v))
+        self._map = C.c_void_p()
+        fe._check(self._L.rgbdfe_octomap_create(fe._ctx, C.byref(self.params), int(capacity_cells), C.byref(self._map)))
+        if not hasattr(fe, "_octomaps"):
+            fe._octomaps = []
+        fe._octomaps.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_map", None) and self._map.value:
+            self._L.rgbdfe_octomap_destroy(self._map)
+            self._map = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self):
+        """ColorOctomapServer::reset: no leaves, the same parameters and capacity."""
+        self._fe._check(self._L.rgbdfe_octomap_reset(self._map))
+
+    def reserve(self, capacity_cells: int):
+        """The leaves re-housed in a table of capacity_cells cells, on the device."""
+        self._fe._check(self._L.rgbdfe_octomap_reserve(self._map, int(capacity_cells)))
+
+    def insert_nodes_status(self, node_ids, transforms, max_range=-1.0):
+        """(status, clouds applied): status -5 (RGBDFE_ERR_CAPACITY) when a cloud did not fit; the map is then the map
+        after the clouds applied.  Other failures raise."""
+        node_ids, T = self._fe._map_args(node_ids, transforms)
+        done = C.c_int32(0)
+        st = self._L.rgbdfe_octomap_insert_nodes(self._map, len(node_ids), node_ids.ctypes.data, T.ctypes.data,
+                                                 float(max_range), C.byref(done))
+        if st != -5:
+            self._fe._check(st)
+        return st, done.value
+
+    def insert_nodes(self, node_ids, transforms, max_range=-1.0, grow=True):
+        """insertCloudCallback for the resident clouds of node_ids, in that order; transforms: n x 4 x 4 (row-major numpy
+        matrices, world2cam per node, as assemble_map takes them); max_range: the parameter maximum_depth (negative: off).
+        grow: a full table is doubled and the remaining clouds follow; otherwise a full table raises with the clouds
+        applied so far in place."""
+        node_ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        T = np.asarray(transforms, np.float32).reshape(-1, 4, 4)
+        at = 0
+        while True:
+            st, done = self.insert_nodes_status(node_ids[at:], T[at:], max_range)
+            if st == 0:
+                return
+            at += done
+            if not grow:
+                self._fe._check(st)
+            self.reserve(2 * self.capacity)
+
+    def insert_cloud(self, points, transform, max_range=-1.0):
+        """The same for one host cloud, [n, 4] float32 (x, y, z, rgb bits), and one row-major 4 x 4 transform."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+        T = np.ascontiguousarray(np.asarray(transform, np.float32).reshape(4, 4).T)  # column-major
+        self._fe._check(self._L.rgbdfe_octomap_insert_cloud(self._map, pts.ctypes.data if len(pts) else None, len(pts),
+                                                            T.ctypes.data, float(max_range)))
+
+    def _stats(self):
+        out = np.zeros(3, np.int64)
+        self._fe._check(self._L.rgbdfe_octomap_stats(self._map, out.ctypes.data, 3))
+        return out
+
+    @property
+    def capacity(self) -> int:
+        return int(self._stats()[0])
+
+    @property
+    def last_launches(self) -> int:
+        """Kernel launches of the last insert call."""
+        return int(self._stats()[2])
+
+    def __len__(self):
+        n = C.c_int64(0)
+        self._fe._check(self._L.rgbdfe_octomap_size(self._map, C.byref(n)))
+        return n.value
+
+    def leaves(self):
+        """The leaves as a structured array (key[3], log_odds, rgb[3]; _lib.OCTOMAP_LEAF_DTYPE), in ascending
+        key[0] | key[1] << 16 | key[2] << 32."""
+        out = np.zeros(len(self), _lib.OCTOMAP_LEAF_DTYPE)
+        n = C.c_int64(0)
+        self._fe._check(self._L.rgbdfe_octomap_leaves(self._map, out.ctypes.data if len(out) else None, len(out), C.byref(n)))
+        return out[:n.value]
