@@ -412,7 +412,13 @@ int rgbdfe_set_hamming_mode(rgbdfe_ctx* ctx, int32_t mode);
  *   jobs per edge, (newer, older, final_trafo) and (older, newer, final_trafo.inverse()), with the counts
  *   summed; matchNodePair then keeps the edge iff rgbdfe_observation_criterion_met(inliers, outliers,
  *   occluded + inliers + outliers, observability_threshold) (node.cpp:1341-1342, misc.cpp:1136-1148).
- *   depth_covariance() is params.depth_cov (the reference's frozen static, misc2.h:30-35). */
+ *   depth_covariance() is params.depth_cov (the reference's frozen static, misc2.h:30-35).
+ *   One batch, one cloud size: every structured cloud named by a call, new or old, must have the dimensions of job 0's
+ *   old cloud, and every old cloud its cloud_skip; otherwise the call returns RGBDFE_ERR_INVALID_ARG and writes nothing to out.
+ *   (The reference returns all-zero counts for one pair of "differing width", misc.cpp:844-847: that result is not
+ *   reproduced; send such pairs in calls of their own size.)  If job 0's old cloud is unstructured (rows or cols
+ *   <= 1, rgbdfe_reduce_node_cloud), every old cloud of the call must be, and every job answers inliers = all = 1
+ *   (misc.cpp:835-843).  emm_skip_step <= 0 answers the same for every job (:831). */
 typedef struct rgbdfe_emm_counts {
   uint32_t inliers, outliers, occluded, all;
 } rgbdfe_emm_counts;

@@ -3,6 +3,7 @@ oracle -- bytes, float bits and integer counts must be identical."""
 import numpy as np
 import pytest
 
+import emm_reference as er
 from oracle import pyoracle as po
 from rgbdslam_v2_amd import synth
 
@@ -124,3 +125,117 @@ def test_pairwise_likelihood_gates_ransac_edges(fe):
     assert list(counts[0]) == list(a + b)
     for f in range(2):
         fe.release_node_cloud(f)
+
+
+# ---- planted scenes, the sample cache, mixed batches (tests/emm_reference.py) ------------------------------------------------
+# The counts must equal, job by job, those of the plain restatement that evaluates math.erf for every sample; its agreement
+# with the oracle and the censuses (every planted sample decides a count) are asserted on the CPU by
+# tests/test_oracle_emm_reference.py.
+_BASE = 1000     # node ids of the scenes' clouds
+
+
+@pytest.mark.parametrize("scene", er.all_scenes(), ids=lambda s: s["name"])
+def test_planted_scenes_match_reference(fe, scene):
+    res, clouds = er.run_scene(scene, po.create_point_cloud)
+    K, kw = scene["K"], dict(min_depth=scene["min_depth"], cloud_skip=scene["cloud_skip"])
+    fe.set_params(depth_cov=scene["depth_cov"])
+    try:
+        for i, d in scene["nodes"].items():
+            got = fe.upload_node_cloud(_BASE + i, d, *K, return_cloud=True, **kw)
+            assert np.array_equal(got.view(np.uint32), clouds[i].view(np.uint32))
+        for c, ((skip_step, jobs), (counts, _)) in enumerate(zip(scene["calls"], res)):
+            got = fe.observation_likelihood([_BASE + j[0] for j in jobs], [_BASE + j[1] for j in jobs],
+                                            np.stack([j[2] for j in jobs]), skip_step)
+            bad = np.flatnonzero((got != counts).any(1))
+            assert len(bad) == 0, (scene["name"], skip_step, bad[:8], got[bad[:8]], counts[bad[:8]])
+            if scene["expect"] is not None:
+                assert np.array_equal(got, np.array(scene["expect"][c], np.uint32))
+    finally:
+        fe.set_params(depth_cov=1e-4)
+        for i in scene["nodes"]:
+            fe.release_node_cloud(_BASE + i)
+
+
+def test_sample_cache_follows_skip_step_and_reupload(fe):
+    """The dense sample array of a node is cached per emm skip step: 3, 8, 3 again, then another depth image of the same
+    size (the cache must not serve the old image), then another size (a batch that mixes sizes is refused)."""
+    rng = np.random.default_rng(21)
+    ch, cw = 16, 17
+    K = (float(cw), float(cw), (cw - 1) / 2, (ch - 1) / 2)
+    depth = {i: er._dense(rng, ch, cw) for i in (0, 1)}
+    T = np.stack([er._wobble(rng), er._wobble(rng, 0.05)])
+    new, old = [_BASE, _BASE + 1], [_BASE + 1, _BASE]
+
+    def check(skip):
+        clouds = {i: po.create_point_cloud(depth[i], *K, min_depth=0.01, cloud_skip=1) for i in (0, 1)}
+        got = fe.observation_likelihood(new, old, T, skip)
+        for g, (n, o), t in zip(got, ((0, 1), (1, 0)), T):
+            ref, _ = er.observation_likelihood(clouds[n], clouds[o], t, *K, 1, skip, fe.params.depth_cov)
+            assert list(g) == list(ref), skip
+        return got
+
+    for i in (0, 1):
+        fe.upload_node_cloud(_BASE + i, depth[i], *K, min_depth=0.01, cloud_skip=1)
+    first = check(3)
+    assert not np.array_equal(check(8), first)
+    assert np.array_equal(check(3), first)
+    depth[0] = er._dense(rng, ch, cw)
+    fe.upload_node_cloud(_BASE, depth[0], *K, min_depth=0.01, cloud_skip=1)
+    assert not np.array_equal(check(3), first)
+    fe.upload_node_cloud(_BASE, er._dense(rng, ch, cw + 1), *K, min_depth=0.01, cloud_skip=1)
+    with pytest.raises(Exception):
+        fe.observation_likelihood(new, old, T, 3)
+    for i in (0, 1):
+        fe.release_node_cloud(_BASE + i)
+
+
+def test_mixed_batches(fe):
+    """One batch, one cloud size: structured clouds of different dimensions are RGBDFE_ERR_INVALID_ARG and `out` is not
+    touched (the reference's "differing width" zero result is not reproduced); an unstructured old cloud (behind
+    reduce_node_cloud) as job 0 answers (1, 0, 0, 1)."""
+    rng = np.random.default_rng(22)
+    K = (16.0, 16.0, 8.0, 8.0)
+    for i, shape in enumerate(((16, 17), (16, 17), (16, 16), (17, 17))):
+        fe.upload_node_cloud(_BASE + i, er._dense(rng, *shape), *K, min_depth=0.01, cloud_skip=1)
+    T = np.ascontiguousarray(np.tile(np.eye(4, dtype=np.float32), (2, 1, 1)))
+    for new, old in (([0, 2], [1, 2]), ([0, 0], [1, 2]), ([0, 2], [1, 1]), ([0, 3], [1, 3]), ([2, 0], [2, 1])):
+        n_ids = np.array([_BASE + k for k in new], np.int32)
+        o_ids = np.array([_BASE + k for k in old], np.int32)
+        out = np.full((2, 4), 0xABABABAB, np.uint32)
+        st = fe._L.rgbdfe_observation_likelihood(fe._ctx, 2, n_ids.ctypes.data, o_ids.ctypes.data, T.ctypes.data, 1,
+                                                 out.ctypes.data)
+        assert st == -1 and np.all(out == 0xABABABAB), (new, old)     # RGBDFE_ERR_INVALID_ARG
+    assert fe.observation_likelihood([_BASE], [_BASE + 1], T[:1], 1)[0, 3] == 16 * 17     # the context still works
+    assert fe.reduce_node_cloud(_BASE + 1, 0.05)[0] > 0
+    assert fe.node_cloud(_BASE + 1).shape[0] == 1
+    assert fe.observation_likelihood([_BASE], [_BASE + 1], T[:1], 1).tolist() == [[1, 0, 0, 1]]
+    assert fe.observation_likelihood([_BASE, _BASE], [_BASE + 1, _BASE + 1], T, 1).tolist() == [[1, 0, 0, 1]] * 2
+    for i in range(4):
+        fe.release_node_cloud(_BASE + i)
+
+
+def test_point_cloud_edges_match_oracle(fe):
+    """createXYZRGBPointCloud at its edges: Z exactly min_depth and its float predecessor, depth_scaling = 0.001 on
+    integer-valued depths (the double product rounds), non-integer cx and cy, a 1 x 1 image."""
+    rng = np.random.default_rng(23)
+    md = np.float32(0.4)
+    cases = []
+    d = rng.uniform(0.3, 0.5, (12, 16)).astype(np.float32)
+    d[0, :4] = [md, np.nextafter(md, np.float32(0)), np.nextafter(md, np.float32(1)), np.nan]
+    d[6, 8] = md; d[7, 9] = np.nextafter(md, np.float32(0))
+    cases.append((d, (13.7, 13.2, 7.31, 5.77), dict(depth_scaling=1.0, min_depth=0.4)))
+    cases.append((d, (13.7, 13.2, 7.31, 5.77), dict(depth_scaling=1.0, min_depth=float(np.nextafter(md, np.float32(1))))))
+    mm = rng.integers(300, 5000, (12, 16)).astype(np.float32)
+    mm[0, :3] = [400, 399, 401]
+    cases.append((mm, (13.7, 13.2, 7.31, 5.77), dict(depth_scaling=0.001, min_depth=0.4)))
+    cases.append((np.array([[1.25]], np.float32), (1.5, 1.5, 0.25, -0.25), dict(depth_scaling=1.0, min_depth=0.1)))
+    cases.append((np.array([[np.nan]], np.float32), (1.5, 1.5, 0.25, -0.25), dict(depth_scaling=1.0, min_depth=0.1)))
+    for depth, K, kw in cases:
+        for s in (1, 2) if depth.shape[0] > 1 else (1,):
+            got = fe.upload_node_cloud(_BASE, depth, *K, cloud_skip=s, return_cloud=True, **kw)
+            ref = po.create_point_cloud(depth, *K, cloud_skip=s, **kw)
+            assert got.shape == ref.shape and np.array_equal(got.view(np.uint32), ref.view(np.uint32))
+            if depth.shape[0] > 1 and kw["depth_scaling"] == 1.0 and s == 1:   # the planted pixels sit either side of :525
+                assert np.isfinite(got[0, 0, 2]) == (np.float32(kw["min_depth"]) <= md) and np.isnan(got[0, 1, 2])
+                assert np.isfinite(got[0, 2, 2])
+    fe.release_node_cloud(_BASE)

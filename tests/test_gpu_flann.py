@@ -2,9 +2,13 @@
 l2_knn2_kernel / l2_ratio_kernel behind rgbdfe_match_flann_pair_list -- against oracle/rgbd_oracle.c::orc_flann_match /
 orc_match_float_node_pair.  The squared distances are float sums in flann::L2's order: neighbours, ratios, match
 lists, inlier sets and pose bits are identical."""
+import re
+from pathlib import Path
+
 import numpy as np
 import pytest
 
+import flann_reference as fr
 from oracle import pyoracle as po
 from rgbdslam_v2_amd import synth
 from rgbdslam_v2_amd.frontend import inlier_indices
@@ -101,3 +105,92 @@ def test_wrong_node_kind_is_refused():
     with pytest.raises(RgbdfeError):
         fe.upload_float_node(3, np.zeros((4, 30), np.float32), x[:4])   # dim not a multiple of 4
     fe.close()
+
+
+# ---- planted families, one ragged batch, one node at capacity (tests/flann_reference.py) ------------------------------------
+# Every comparison below is == on counts, indices and float bits against the plain numpy reference, whose agreement with
+# the oracle and whose censuses (the inputs decide the outcome) tests/test_oracle_flann_reference.py asserts on the CPU.
+_XYZ = np.tile(np.array([[0, 0, 2, 1]], np.float32), (768, 1))
+
+
+def _assert_record(rec, ratio_row, q, t, ratio, max_matches=300, expected=None):
+    kq, kt, kd = expected if expected is not None else fr.expected_record(q, t, ratio, max_matches)
+    n = int(rec["n_all"])
+    assert n == len(kq)
+    assert np.array_equal(rec["all_q"][:n], kq) and np.array_equal(rec["all_t"][:n], kt)
+    assert np.array_equal(ratio_row[:n].view(np.uint32), kd.view(np.uint32))
+
+
+@pytest.fixture(scope="module")
+def fe768():
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    f = FrontEnd(device_id=0, max_nodes=16, max_keypoints=768, max_pairs_per_batch=16, min_matches=0)
+    yield f
+    f.close()
+
+
+@pytest.mark.parametrize("mode", [0, 1 << 20], ids=["one_wave_per_pair", "record_replay"])
+@pytest.mark.parametrize("fam", fr.all_families(), ids=lambda f: f["name"])
+def test_flann_planted_families(fe768, fam, mode):
+    fe = fe768
+    fe.set_latency_mode(mode, 0)
+    q, t = fam["q"], fam["t"]
+    fe.upload_float_node(1, q, _XYZ[:len(q)])
+    fe.upload_float_node(2, t, _XYZ[:len(t)])
+    for ratio in fam["ratios"]:
+        out, dist = fe.match_flann_pair_list([1], [2], ratio)
+        _assert_record(out[0], dist[0], q, t, ratio)
+    if fam["name"] == "cap":      # the record's full capacity: 320 of the 450 accepted matches
+        fe.set_params(max_matches=320)
+        try:
+            out, dist = fe.match_flann_pair_list([1], [2], 0.95)
+            assert out[0]["n_all"] == 320
+            _assert_record(out[0], dist[0], q, t, 0.95, max_matches=320)
+        finally:
+            fe.set_params(max_matches=300)
+
+
+def _lanes():
+    """RGBDFE_LANES of the build (csrc/rgbdfe_host.h): consecutive calls take the lanes' scratch buffers in turn."""
+    import rgbdslam_v2_amd
+    src = (Path(rgbdslam_v2_amd.__file__).parent / "csrc" / "rgbdfe_host.h").read_text()
+    return int(re.search(r"#define RGBDFE_LANES (\d+)", src).group(1))
+
+
+def test_flann_ragged_batch_and_scratch_reuse():
+    """One call of 11 pairs whose sizes sit either side of the 256-query tile, with nq = 0, nt < 2 and the node capacity;
+    then the reversed list, so that every pair slot of a lane's scratch (knn rows, claims, match lists) holds a smaller pair
+    than the call before: each lane sees forward, reversed, forward."""
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    fe = FrontEnd(device_id=0, max_nodes=16, max_keypoints=768, max_pairs_per_batch=16, min_matches=0)
+    nodes = fr.ragged_nodes()
+    node_id = {n: 20 + k for k, n in enumerate(fr.RAGGED_ROWS)}
+    for n, d in nodes.items():
+        fe.upload_float_node(node_id[n], d, _XYZ[:n])
+        assert fe.node_count(node_id[n]) == n
+    ref = {p: fr.expected_record(nodes[p[0]], nodes[p[1]], 0.95) for p in fr.RAGGED_PAIRS}
+    assert all((len(ref[p][0]) == 0) == (p[0] == 0 or p[1] < 2) for p in fr.RAGGED_PAIRS)
+    fwd, rev = list(fr.RAGGED_PAIRS), list(fr.RAGGED_PAIRS)[::-1]
+    L = _lanes()
+    for pairs in [fwd] * L + [rev] * L + [fwd] * L + [rev]:
+        out, dist = fe.match_flann_pair_list([node_id[a] for a, _ in pairs], [node_id[b] for _, b in pairs], 0.95)
+        for rec, row, p in zip(out, dist, pairs):
+            _assert_record(rec, row, None, None, 0.95, expected=ref[p])
+    fe.close()
+
+
+def test_flann_node_at_capacity(fe768):
+    """nq = nt = max_keypoints: against itself every query has ratio +0.0 and the record keeps queries 0..299; against a
+    permuted copy the train indices are the permutation."""
+    fe = fe768
+    rng = np.random.default_rng(5)
+    d = fr.root_sift(rng, 768)
+    perm = rng.permutation(768)
+    fe.upload_float_node(1, d, _XYZ)
+    fe.upload_float_node(2, d[perm], _XYZ)
+    out, dist = fe.match_flann_pair_list([1, 1, 2], [1, 2, 1], 0.95)
+    assert out[0]["n_all"] == 300 and np.array_equal(out[0]["all_q"][:300], np.arange(300))
+    assert np.array_equal(out[0]["all_t"][:300], np.arange(300)) and not dist[0][:300].view(np.uint32).any()
+    assert np.array_equal(perm[out[1]["all_t"][:300]], np.arange(300))
+    for rec, row, (a, b) in zip(out, dist, ((d, d), (d, d[perm]), (d[perm], d))):
+        _assert_record(rec, row, a, b, 0.95)
