@@ -549,8 +549,8 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
  *   new) / 2 per channel in integer arithmetic, a leaf whose colour is (255, 255, 255) takes the new colour.  (An
  *   average that lands on white therefore starts again, as in the library.)
  *   Clouds are applied strictly one after another in list order: clamping and the colour rule do not commute.
- *   Inner nodes (updateInnerOccupancy), pruning, the bounding-box branch, occupancyFilter and .ot / .bt files are out
- *   of scope.
+ *   Pruning, the bounding-box branch, occupancyFilter and .bt files are out of scope; inner nodes
+ *   (updateInnerOccupancy), depth queries and .ot files: the next block.
  * rgbdfe_octomap_create: a map of capacity_cells cells (1 <= capacity_cells < 2^31; 20 bytes each) on the context's
  *   device (the first device of a multi-device handle); params NULL = the defaults.  Destroy the map before the
  *   context.  rgbdfe_octomap_reset is ColorOctomapServer::reset (no leaves, same parameters, same capacity).
@@ -568,8 +568,8 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
  * rgbdfe_octomap_insert_cloud: the same for one host array of n rows (n >= 2^31: RGBDFE_ERR_CAPACITY).
  * rgbdfe_octomap_leaves: the leaves as 16-byte records in ascending key[0] | key[1] << 16 | key[2] << 32; capacity <
  *   the number of leaves: RGBDFE_ERR_CAPACITY with *n_out = the needed size, before anything is written.
- * rgbdfe_octomap_stats: out[0] = capacity_cells, out[1] = leaves, out[2] = kernel launches of the last insert call;
- *   further entries 0. */
+ * rgbdfe_octomap_stats: out[0] = capacity_cells, out[1] = leaves, out[2] = kernel launches of the last insert call,
+ *   out[3] = kernel launches of the last tree / tree_device / nodes_at_depth / write call; further entries 0. */
 typedef struct rgbdfe_octomap rgbdfe_octomap;
 typedef struct rgbdfe_octomap_params {
   double resolution;           /* octomap_resolution, 0.05 */
@@ -599,6 +599,71 @@ int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_
 int rgbdfe_octomap_size(rgbdfe_octomap* map, int64_t* n_leaves);
 int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out);
 int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out);
+
+/* ---- occupancy map: the tree of a leaf set -- inner nodes, one depth, .ot files ---------------------------------
+ * What ColorOctomapServer::save (ColorOctomapServer.cpp:38-58: updateInnerOccupancy is :128, then AbstractOcTree::write)
+ *   and ColorOctomapServer::render (:187-268, the nodes of octomap_display_level) need beyond the leaves, built on the
+ *   device from the leaves of an rgbdfe_octomap.  As above, the contract is this library's restatement of the published
+ *   octomap 1.6-1.9 line (restated, not pinned).
+ *   Shape and order: all leaves are at depth 16, the root at depth 0.  On the way down the child index at depth d
+ *   (1 .. 16) is taken from bit b = 16 - d of the key (computeChildIdx): ((k0 >> b) & 1) | ((k1 >> b) & 1) << 1 |
+ *   ((k2 >> b) & 1) << 2.  A leaf's path code is the 48-bit number of its 16 child indices, the depth-1 index most
+ *   significant.  Depth-first pre-order with the children in ascending index = the nodes ordered by (path code of their
+ *   first leaf, depth); every file and query order below is that order.
+ *   The tree is a pure function of the leaf set (lazy insertion creates inner nodes and never reads them, nothing
+ *   prunes, updateInnerOccupancy overwrites every inner value).  An empty map has no nodes, not even a root; otherwise
+ *   the root exists.
+ *   Inner node values, bottom-up from the final children (updateOccupancyChildren, updateColorChildren /
+ *   getAverageChildColor): log_odds = the float maximum over the existing children, starting from -FLT_MAX (a subtree
+ *   of free cells has a negative value).  Colour: over the existing children whose colour is not (255, 255, 255), c
+ *   their number, each channel = the integer sum divided by c, truncated; c = 0: (255, 255, 255).  The average is
+ *   hierarchical (a parent averages its children's already truncated colours, not the leaves below), and an inner node
+ *   that comes out white counts as unset one level up (the library's rule: reproduced, not mended).
+ *   Node record (rgbdfe_octomap_node, 8 bytes, the bytes ColorOcTreeNode writes): float log_odds (little endian),
+ *   uint8_t rgb[3], uint8_t children (bit i set iff child i exists; 0 for a leaf).
+ *   .ot file (AbstractOcTree::write): the lines "# Octomap OcTree file", "# (feel free to add / change comments, but
+ *   leave the first line as it is!)", "#", "id ColorOcTree", "size <number of nodes>", "res <resolution as printf %g>",
+ *   "data", each ended by '\n', then the node records in pre-order.  An empty map: "size 0" and no data.
+ * rgbdfe_octomap_tree: the records in pre-order to host memory.  capacity < the number of nodes: RGBDFE_ERR_CAPACITY
+ *   with *n_nodes = the needed size, before anything is written.  rgbdfe_octomap_tree_device: the same into device
+ *   memory of the map's device (`stream` NULL: the context's stream; the call returns when the records are in place).
+ *   A map with more than (2^32 - 1) / 17 leaves is refused by every call of this block (RGBDFE_ERR_CAPACITY): node
+ *   positions are 32-bit on the device.
+ * rgbdfe_octomap_nodes_at_depth: the nodes of one depth (0 .. 16) whose log_odds >= min_log_odds by float comparison,
+ *   in tree order, as rgbdfe_octomap_leaf records whose key is the first cell's key with the low 16 - depth bits
+ *   cleared (the key keyToCoord(key, depth) takes); -INFINITY returns every node of the depth.  NaN or a depth outside
+ *   0 .. 16: RGBDFE_ERR_INVALID_ARG; capacity as above with *n_out.  This is the set render() walks at
+ *   octomap_display_level.  With s = 16 - depth, a node's edge is resolution * 2^s (getNodeSize(depth)) and its centre
+ *   on axis a is keyToCoord(key[a], depth) = (floor(((double)key[a] - 32768) / 2^s) + 0.5) * (resolution * 2^s); the
+ *   division is exact for the keys returned here.  "occupancy >= thr" corresponds to log_odds >= log(thr / (1 - thr));
+ *   that conversion and render()'s alpha byte stay with the caller (exp in double is not bit-reproducible between the
+ *   device and a host libm, and this interface does not need it).
+ * rgbdfe_octomap_write: ColorOctomapServer::save: the header on the host, the payload built on the device.  A file
+ *   that cannot be opened: RGBDFE_ERR_INVALID_ARG; a write that fails: RGBDFE_ERR_INTERNAL and the file is removed,
+ *   so that nothing partial stays behind under the name.
+ * rgbdfe_octomap_set_leaves: the map's contents replaced by these n leaves (any order), parameters and capacity
+ *   unchanged.  n above the capacity: RGBDFE_ERR_CAPACITY, nothing changes.  A repeated key, a non-zero padding field
+ *   or a non-finite log-odds: RGBDFE_ERR_INVALID_ARG, the map is left empty.
+ * rgbdfe_octomap_read: an .ot file parsed on the host, then rgbdfe_octomap_set_leaves.  Inner values in the file are
+ *   ignored (they are a function of the leaves).  Refused with RGBDFE_ERR_INVALID_ARG and a message that says which
+ *   (the map is unchanged): a first line other than the format's, an id other than ColorOcTree, a res whose %g text
+ *   differs from the map's, a truncated file, a size that does not match the records (or bytes behind them), a node
+ *   above depth 16 without children (a pruned file from elsewhere) or one of depth 16 with children.
+ * None of these calls changes the leaves except the last two; a tree call between two inserts does not alter what the
+ *   later insert produces.  Nothing is cached: every call works from the leaves as they are.  The calls' workspace
+ *   (about 76 bytes per leaf) belongs to the map and goes with rgbdfe_octomap_destroy. */
+typedef struct rgbdfe_octomap_node {
+  float log_odds;
+  uint8_t rgb[3];
+  uint8_t children;
+} rgbdfe_octomap_node;
+int rgbdfe_octomap_tree(rgbdfe_octomap* map, rgbdfe_octomap_node* out, int64_t capacity, int64_t* n_nodes);
+int rgbdfe_octomap_tree_device(rgbdfe_octomap* map, void* d_out, int64_t capacity, int64_t* n_nodes, void* stream);
+int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_log_odds, rgbdfe_octomap_leaf* out,
+                                  int64_t capacity, int64_t* n_out);
+int rgbdfe_octomap_write(rgbdfe_octomap* map, const char* path);
+int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n);
+int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path);
 
 /* ---- candidate selection for loop closure ----------------------------------
  * rgbdfe_potential_edge_targets is GraphManager::getPotentialEdgeTargetsWithDijkstra (graph_manager.cpp:204-324): the

@@ -507,6 +507,44 @@ class OctoMap {
     int64_t got = 0;
     return rgbdfe_octomap_leaves(map_.get(), out->data(), n, &got) == RGBDFE_OK && got == n;
   }
+  // every node of the octree over the leaves, inner values as updateInnerOccupancy leaves them, in depth-first pre-order
+  // (the payload of an .ot file); an empty map has no nodes
+  bool tree(std::vector<rgbdfe_octomap_node>* out) const {
+    if (!map_) return false;
+    out->clear();
+    int64_t n = 0;
+    int rc = rgbdfe_octomap_tree(map_.get(), nullptr, 0, &n);  // the size: RGBDFE_ERR_CAPACITY, or OK for an empty map
+    if (rc == RGBDFE_OK) return true;
+    if (rc != RGBDFE_ERR_CAPACITY) return false;
+    out->resize((size_t)n);
+    int64_t got = 0;
+    return rgbdfe_octomap_tree(map_.get(), out->data(), n, &got) == RGBDFE_OK && got == n;
+  }
+  // the same records into device memory (room for `capacity` of them); the number of nodes, -1 on failure
+  int64_t treeDevice(void* d_out, int64_t capacity, void* stream = nullptr) const {
+    int64_t n = 0;
+    return map_ && rgbdfe_octomap_tree_device(map_.get(), d_out, capacity, &n, stream) == RGBDFE_OK ? n : -1;
+  }
+  // ColorOctomapServer::render's set: the nodes of octomap_display_level `depth` with log_odds >= min_log_odds
+  // (-INFINITY: all of them), in tree order; key = the node's first cell, edge = resolution * 2^(16 - depth)
+  bool nodesAtDepth(int32_t depth, float min_log_odds, std::vector<rgbdfe_octomap_leaf>* out) const {
+    if (!map_) return false;
+    out->clear();
+    int64_t n = 0;
+    int rc = rgbdfe_octomap_nodes_at_depth(map_.get(), depth, min_log_odds, nullptr, 0, &n);
+    if (rc == RGBDFE_OK) return true;
+    if (rc != RGBDFE_ERR_CAPACITY) return false;
+    out->resize((size_t)n);
+    int64_t got = 0;
+    return rgbdfe_octomap_nodes_at_depth(map_.get(), depth, min_log_odds, out->data(), n, &got) == RGBDFE_OK && got == n;
+  }
+  bool write(const std::string& path) const {  // ColorOctomapServer::save
+    return map_ && rgbdfe_octomap_write(map_.get(), path.c_str()) == RGBDFE_OK;
+  }
+  bool read(const std::string& path) { return map_ && rgbdfe_octomap_read(map_.get(), path.c_str()) == RGBDFE_OK; }
+  bool setLeaves(const std::vector<rgbdfe_octomap_leaf>& leaves) {
+    return map_ && rgbdfe_octomap_set_leaves(map_.get(), leaves.data(), (int64_t)leaves.size()) == RGBDFE_OK;
+  }
 
  private:
   std::unique_ptr<rgbdfe_octomap, void (*)(rgbdfe_octomap*)> map_;

@@ -90,6 +90,9 @@ class OctomapParams(C.Structure):   # rgbdfe_octomap_params
 OCTOMAP_LEAF_DTYPE = np.dtype([("key", "<u2", (3,)), ("zero0", "<u2"), ("log_odds", "<f4"), ("rgb", "u1", (3,)),
                                ("zero1", "u1")])
 
+# rgbdfe_octomap_node: the 8 bytes of a node in an .ot file
+OCTOMAP_NODE_DTYPE = np.dtype([("log_odds", "<f4"), ("rgb", "u1", (3,)), ("children", "u1")])
+
 KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                            ("response", "<f4"), ("octave", "<i4")])
 
@@ -339,6 +342,18 @@ def load():
     L.rgbdfe_octomap_leaves.argtypes = [omap, vp, C.c_int64, C.POINTER(C.c_int64)]
     L.rgbdfe_octomap_stats.restype = C.c_int
     L.rgbdfe_octomap_stats.argtypes = [omap, vp, i32]
+    L.rgbdfe_octomap_tree.restype = C.c_int
+    L.rgbdfe_octomap_tree.argtypes = [omap, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rgbdfe_octomap_tree_device.restype = C.c_int
+    L.rgbdfe_octomap_tree_device.argtypes = [omap, vp, C.c_int64, C.POINTER(C.c_int64), vp]
+    L.rgbdfe_octomap_nodes_at_depth.restype = C.c_int
+    L.rgbdfe_octomap_nodes_at_depth.argtypes = [omap, i32, C.c_float, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rgbdfe_octomap_write.restype = C.c_int
+    L.rgbdfe_octomap_write.argtypes = [omap, C.c_char_p]
+    L.rgbdfe_octomap_set_leaves.restype = C.c_int
+    L.rgbdfe_octomap_set_leaves.argtypes = [omap, vp, C.c_int64]
+    L.rgbdfe_octomap_read.restype = C.c_int
+    L.rgbdfe_octomap_read.argtypes = [omap, C.c_char_p]
     L.rgbdfe_observation_criterion_met.restype = C.c_int
     L.rgbdfe_observation_criterion_met.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                                    C.POINTER(C.c_double)]
@@ -470,6 +485,8 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_octomap_default_params", "rgbdfe_octomap_create", "rgbdfe_octomap_destroy", "rgbdfe_octomap_reset",
     "rgbdfe_octomap_reserve", "rgbdfe_octomap_insert_nodes", "rgbdfe_octomap_insert_cloud", "rgbdfe_octomap_size",
     "rgbdfe_octomap_leaves", "rgbdfe_octomap_stats",
+    "rgbdfe_octomap_tree", "rgbdfe_octomap_tree_device", "rgbdfe_octomap_nodes_at_depth", "rgbdfe_octomap_write",
+    "rgbdfe_octomap_set_leaves", "rgbdfe_octomap_read",
     "rgbdfe_observation_criterion_met", "rgbdfe_set_latency_mode", "rgbdfe_set_profiling", "rgbdfe_get_kernel_time",
     "rgbdfe_reset_kernel_time", "rgbdfe_graph_stats", "rgbdfe_set_graph_capture", "rgbdfe_match_pair_list_allgather_inliers", "rgbdfe_pack_inliers", "rgbdfe_sizeof_inlier_header", "rgbdfe_sizeof_match_result", "rgbdfe_abi_version",
     "rgbdfe_pose_graph_create", "rgbdfe_pose_graph_destroy", "rgbdfe_pose_graph_add_node",

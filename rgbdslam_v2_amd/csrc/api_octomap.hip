@@ -3,6 +3,7 @@
 // (graph_mgr_io.cpp:253-329) over ColorOctomapServer::insertCloudCallback (ColorOctomapServer.cpp:61-129)
 // (one of the host-side translation units of librgbdfe.so; shared declarations: rgbdfe_host.h)
 #include "rgbdfe_host.h"
+#include "ot_parse.h"
 
 #include <algorithm>
 
@@ -16,6 +17,10 @@ struct rgbdfe_octomap {
   uint32_t epoch = 0;           // of the last cloud
   int64_t n_leaves = 0;
   int64_t launches = 0;         // kernel launches of the last insert call (tools/bench_octomap.py)
+  // the tree calls' workspace (octomap_tree.hip): one allocation, grown when a call needs more, freed with the map
+  void* tree_ws = nullptr;
+  size_t tree_ws_bytes = 0;
+  int64_t tree_launches = 0;    // kernel launches of the last tree / depth / write call (tools/bench_octomap_tree.py)
 };
 
 namespace impl {
@@ -212,15 +217,14 @@ void rgbdfe_octomap_destroy(rgbdfe_octomap* map) {
     (void)hipStreamSynchronize(map->ctx->stream);
     if (map->blob) (void)hipFree(map->blob);
     if (map->d_ctl) (void)hipFree(map->d_ctl);
+    if (map->tree_ws) (void)hipFree(map->tree_ws);
   }
   delete map;
 }
 
-// ColorOctomapServer::reset: an empty tree with the same parameters
-int rgbdfe_octomap_reset(rgbdfe_octomap* map) {
+// no leaves, the same table; ctx->mu is held and the device is set
+static int clear_map(rgbdfe_octomap* map) {
   rgbdfe_ctx* ctx = map->ctx;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   const size_t b_key = up256(8 * (size_t)map->tb.cap), b_f = up256(4 * (size_t)map->tb.cap);
   HIP_TRY(ctx, hipMemsetAsync(map->blob, 0xff, b_key + 2 * b_f, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(map->tb.mark, 0, b_f, ctx->stream));
@@ -228,6 +232,14 @@ int rgbdfe_octomap_reset(rgbdfe_octomap* map) {
   map->epoch = 0;
   map->n_leaves = 0;
   return RGBDFE_OK;
+}
+
+// ColorOctomapServer::reset: an empty tree with the same parameters
+int rgbdfe_octomap_reset(rgbdfe_octomap* map) {
+  rgbdfe_ctx* ctx = map->ctx;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  return clear_map(map);
 }
 
 int rgbdfe_octomap_reserve(rgbdfe_octomap* map, int64_t capacity_cells) {
@@ -291,8 +303,8 @@ int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out) {
   rgbdfe_ctx* ctx = map->ctx;
   if (!out || n_out < 0) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const int64_t v[3] = {(int64_t)map->tb.cap, map->n_leaves, map->launches};
-  for (int32_t i = 0; i < n_out; ++i) out[i] = i < 3 ? v[i] : 0;
+  const int64_t v[4] = {(int64_t)map->tb.cap, map->n_leaves, map->launches, map->tree_launches};
+  for (int32_t i = 0; i < n_out; ++i) out[i] = i < 4 ? v[i] : 0;
   return RGBDFE_OK;
 }
 
@@ -328,6 +340,263 @@ int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t
     o.zero1 = 0;
   }
   return RGBDFE_OK;
+}
+
+// ---- the tree of the leaf set: inner nodes, one depth, .ot files (kernels: octomap_tree.hip) ------------------------------
+
+namespace {
+
+// the workspace of a tree call over the map as it is; ctx->mu is held and the device is set
+int tree_workspace(rgbdfe_octomap* map, TreeScratch* t) {
+  rgbdfe_ctx* ctx = map->ctx;
+  const size_t n = (size_t)map->n_leaves, cap = map->tb.cap;
+  if (17 * (uint64_t)n > (uint64_t)UINT32_MAX)
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: the tree of this map may have 2^32 nodes or more");
+  const size_t tiles = (std::max(n, cap) + kTreeTile - 1) / kTreeTile, sort_tiles = (n + kVoxSortTile - 1) / kVoxSortTile;
+  const size_t b_hdr = 256, b8 = up256(8 * n), b4 = up256(4 * n), b_hist = up256(4 * 256 * sort_tiles), b_digits = 1024,
+               b_count = up256(4 * tiles), b_first = up256(4 * (tiles + 1));
+  const size_t bytes = b_hdr + 2 * b8 + 13 * b4 + b_hist + b_digits + b_count + b_first;
+  if (bytes > map->tree_ws_bytes) {
+    if (map->tree_ws) (void)hipFree(map->tree_ws);
+    map->tree_ws = nullptr;
+    map->tree_ws_bytes = 0;
+    if (hipMalloc(&map->tree_ws, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      map->tree_ws = nullptr;
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: tree workspace allocation failed");
+    }
+    map->tree_ws_bytes = bytes;
+  }
+  char* at = (char*)map->tree_ws;
+  auto take = [&at](size_t b) { char* p = at; at += b; return p; };
+  t->hdr = (TreeHdr*)take(b_hdr);
+  t->code = (unsigned long long*)take(b8);
+  t->scode = (unsigned long long*)take(b8);
+  t->slot = (uint32_t*)take(b4);
+  t->keys[0] = (uint32_t*)take(b4); t->keys[1] = (uint32_t*)take(b4);
+  t->idx[0] = (uint32_t*)take(b4); t->idx[1] = (uint32_t*)take(b4);
+  t->top = (uint32_t*)take(b4);
+  t->off = (uint32_t*)take(b4);
+  for (int l = 0; l < 2; ++l) {
+    t->level[l].value = (float*)take(b4);
+    t->level[l].colour = (uint32_t*)take(b4);
+    t->level[l].first = (uint32_t*)take(b4);
+  }
+  t->hist = (uint32_t*)take(b_hist);
+  t->digits = (uint32_t*)take(b_digits);
+  t->tile_count = (uint32_t*)take(b_count);
+  t->tile_first = (uint32_t*)take(b_first);
+  return RGBDFE_OK;
+}
+
+// the records of the whole tree to host (h_out) or device (d_out) memory; ctx->mu is held
+// (or, with `vec`, to a vector that takes the size the tree needs)
+int tree_common(rgbdfe_octomap* map, rgbdfe_octomap_node* h_out, void* d_out, bool to_device, int64_t capacity, int64_t* n_nodes,
+                void* stream, std::vector<rgbdfe_octomap_node>* vec = nullptr) {
+  rgbdfe_ctx* ctx = map->ctx;
+  *n_nodes = 0;
+  map->tree_launches = 0;
+  if (map->n_leaves == 0) return RGBDFE_OK;  // an empty map has no node, not even a root
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  TreeScratch t{};
+  int rc = tree_workspace(map, &t);
+  if (rc != RGBDFE_OK) return rc;
+  const uint32_t n = (uint32_t)map->n_leaves;
+  HIP_TRY(ctx, hipMemsetAsync(t.hdr, 0, sizeof(TreeHdr), st));
+  int launches = launch_tree_leaves(map->tb, n, t, st);
+  launches += launch_tree_chain(n, t, st);
+  HIP_TRY(ctx, hipGetLastError());
+  TreeHdr h{};
+  HIP_TRY(ctx, hipMemcpyAsync(&h, t.hdr, sizeof(h), hipMemcpyDeviceToHost, st));  // the one read before the capacity check
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  map->tree_launches = launches;
+  if ((int64_t)h.cnt[16] != map->n_leaves) return fail(ctx, RGBDFE_ERR_INTERNAL, "octomap: the leaf count and the table disagree");
+  const int64_t total = (int64_t)h.n_nodes;
+  *n_nodes = total;
+  if (vec) {
+    vec->resize((size_t)total);
+    h_out = vec->data();
+  } else if (capacity < total) {
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: `out` is too small (*n_nodes records are needed)");
+  }
+  DeviceBuffer stage;
+  void* d_rec = d_out;
+  if (!to_device) {
+    if (hipMalloc(&stage.p, (size_t)total * sizeof(rgbdfe_octomap_node)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
+    }
+    d_rec = stage.p;
+  }
+  launches += launch_tree_levels(n, 0u, t, d_rec, st);
+  HIP_TRY(ctx, hipGetLastError());
+  if (!to_device)
+    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_rec, (size_t)total * sizeof(rgbdfe_octomap_node), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  map->tree_launches = launches;
+  return RGBDFE_OK;
+}
+
+std::string ot_header(const rgbdfe_octomap* map, int64_t n_nodes) {
+  char res[64], size[64];
+  snprintf(res, sizeof(res), "%g", map->prm.resolution);
+  snprintf(size, sizeof(size), "%lld", (long long)n_nodes);
+  return std::string("# Octomap OcTree file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n"
+                     "id ColorOcTree\nsize ") + size + "\nres " + res + "\ndata\n";
+}
+
+// `leaves` become the map's contents; ctx->mu is held
+int set_leaves_locked(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (n > (int64_t)map->tb.cap) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: more leaves than the map has cells (nothing changed)");
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = ctx->stream;
+  int rc = clear_map(map);
+  if (rc != RGBDFE_OK || n == 0) return rc;
+  std::vector<OctoLeafIn> in((size_t)n);
+  for (size_t i = 0; i < in.size(); ++i) {
+    const rgbdfe_octomap_leaf& l = leaves[i];
+    if (l.zero0 != 0 || l.zero1 != 0 || !std::isfinite(l.log_odds))
+      return fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: a leaf with non-zero padding or a non-finite log-odds (the map is empty)");
+    in[i].key = (unsigned long long)l.key[0] | ((unsigned long long)l.key[1] << 16) | ((unsigned long long)l.key[2] << 32);
+    in[i].value = l.log_odds;
+    in[i].colour = ((uint32_t)l.rgb[0] << 16) | ((uint32_t)l.rgb[1] << 8) | (uint32_t)l.rgb[2];
+  }
+  DeviceBuffer stage;
+  const size_t b_in = up256(in.size() * sizeof(OctoLeafIn));
+  if (hipMalloc(&stage.p, b_in + 256) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
+  }
+  uint32_t* d_dup = (uint32_t*)((char*)stage.p + b_in);
+  OctoCtl ctl{};
+  uint32_t dup = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(stage.p, in.data(), in.size() * sizeof(OctoLeafIn), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(d_dup, 0, 4, st));
+  HIP_TRY(ctx, hipMemcpyAsync(map->d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, st));
+  launch_octo_set_leaves((const OctoLeafIn*)stage.p, (uint32_t)n, map->tb, map->d_ctl, d_dup, st);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&ctl, map->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&dup, d_dup, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (dup != 0 || ctl.overflow != 0) {
+    rc = clear_map(map);
+    if (rc != RGBDFE_OK) return rc;
+    return dup != 0 ? fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: a key is repeated among the leaves (the map is empty)")
+                    : fail(ctx, RGBDFE_ERR_INTERNAL, "octomap: a leaf found no slot");
+  }
+  map->n_leaves = n;
+  return RGBDFE_OK;
+}
+
+}  // namespace
+
+int rgbdfe_octomap_tree(rgbdfe_octomap* map, rgbdfe_octomap_node* out, int64_t capacity, int64_t* n_nodes) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!n_nodes || capacity < 0 || (capacity > 0 && !out)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return tree_common(map, out, nullptr, false, capacity, n_nodes, nullptr);
+}
+
+int rgbdfe_octomap_tree_device(rgbdfe_octomap* map, void* d_out, int64_t capacity, int64_t* n_nodes, void* stream) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!n_nodes || capacity < 0 || (capacity > 0 && !d_out)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return tree_common(map, nullptr, d_out, true, capacity, n_nodes, stream);
+}
+
+int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_log_odds, rgbdfe_octomap_leaf* out, int64_t capacity,
+                                  int64_t* n_out) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!n_out || capacity < 0 || (capacity > 0 && !out) || depth < 0 || depth > 16 || std::isnan(min_log_odds))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: bad depth query arguments (depth 0 .. 16, min_log_odds not NaN)");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  *n_out = 0;
+  map->tree_launches = 0;
+  if (map->n_leaves == 0) return RGBDFE_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = ctx->stream;
+  TreeScratch t{};
+  int rc = tree_workspace(map, &t);
+  if (rc != RGBDFE_OK) return rc;
+  const uint32_t n = (uint32_t)map->n_leaves;
+  // the nodes of a depth are at most min(leaves, 8^depth): the staging is sized before anything runs
+  const uint64_t bound = depth >= 11 ? (uint64_t)n : std::min<uint64_t>(n, (uint64_t)1 << (3 * depth));
+  DeviceBuffer stage;
+  if (hipMalloc(&stage.p, (size_t)bound * sizeof(rgbdfe_octomap_leaf)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
+  }
+  HIP_TRY(ctx, hipMemsetAsync(t.hdr, 0, sizeof(TreeHdr), st));
+  int launches = launch_tree_leaves(map->tb, n, t, st);
+  launches += launch_tree_levels(n, (uint32_t)depth, t, nullptr, st);
+  launches += launch_tree_filter(n, (uint32_t)depth, min_log_odds, t, stage.p, st);
+  HIP_TRY(ctx, hipGetLastError());
+  TreeHdr h{};
+  HIP_TRY(ctx, hipMemcpyAsync(&h, t.hdr, sizeof(h), hipMemcpyDeviceToHost, st));  // the one read before the capacity check
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  map->tree_launches = launches;
+  if ((int64_t)h.cnt[16] != map->n_leaves) return fail(ctx, RGBDFE_ERR_INTERNAL, "octomap: the leaf count and the table disagree");
+  *n_out = (int64_t)h.n_out;
+  if (capacity < *n_out) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: `out` is too small (*n_out records are needed)");
+  if (h.n_out > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(out, stage.p, (size_t)h.n_out * sizeof(rgbdfe_octomap_leaf), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_write(rgbdfe_octomap* map, const char* path) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!path) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  // the payload first: a failure on the device leaves no file behind
+  std::vector<rgbdfe_octomap_node> rec;
+  int64_t n_nodes = 0;
+  const int rc = tree_common(map, nullptr, nullptr, false, 0, &n_nodes, nullptr, &rec);
+  if (rc != RGBDFE_OK) return rc;
+  const std::string head = ot_header(map, n_nodes);
+  FILE* f = fopen(path, "wb");
+  if (!f) return fail(ctx, RGBDFE_ERR_INVALID_ARG, std::string("octomap: cannot open for writing: ") + path);
+  bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
+  if (ok && !rec.empty()) ok = fwrite(rec.data(), sizeof(rgbdfe_octomap_node), rec.size(), f) == rec.size();
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) {
+    (void)remove(path);  // nothing partial stays behind under the name
+    return fail(ctx, RGBDFE_ERR_INTERNAL, std::string("octomap: writing failed (the file was removed): ") + path);
+  }
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (n < 0 || (n > 0 && !leaves)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return set_leaves_locked(map, leaves, n);
+}
+
+int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!path) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::vector<uint8_t> bytes;
+  {
+    FILE* f = fopen(path, "rb");
+    if (!f) return fail(ctx, RGBDFE_ERR_INVALID_ARG, std::string("octomap: cannot open for reading: ") + path);
+    uint8_t buf[65536];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof(buf), f)) > 0) bytes.insert(bytes.end(), buf, buf + got);
+    const bool bad = ferror(f) != 0;
+    fclose(f);
+    if (bad) return fail(ctx, RGBDFE_ERR_INTERNAL, std::string("octomap: reading failed: ") + path);
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  char res[64];
+  snprintf(res, sizeof(res), "%g", map->prm.resolution);
+  std::vector<rgbdfe_octomap_leaf> leaves;
+  std::string err;
+  if (!ot_parse(bytes.data(), bytes.size(), res, &leaves, &err)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: " + err);
+  return set_leaves_locked(map, leaves.data(), (int64_t)leaves.size());
 }
 
 }  // namespace impl

@@ -244,6 +244,33 @@ __global__ __launch_bounds__(256) void octo_rehash_kernel(OctoTable from, OctoTa
   to.colour[s] = from.colour[i];
 }
 
+// rgbdfe_octomap_set_leaves: a claim pass as octo_rehash_kernel over given leaves.  `to` holds no key when it starts, so a
+// key that is met in the table is a repeated one, whichever of its lanes comes second.
+__global__ __launch_bounds__(256) void octo_set_leaves_kernel(const OctoLeafIn* __restrict__ src, uint32_t n, OctoTable to,
+                                                             OctoCtl* __restrict__ ctl, uint32_t* __restrict__ dup) {
+  const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= n) return;
+  const OctoLeafIn in = src[r];
+  uint32_t i = home_slot(in.key, to.cap);
+  for (uint32_t probe = 0; probe < to.cap; ++probe) {
+    unsigned long long k = __hip_atomic_load(&to.key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (k == kOctoEmptyKey) {
+      k = atomicCAS(&to.key[i], kOctoEmptyKey, in.key);
+      if (k == kOctoEmptyKey) {  // claimed: the slot is this lane's
+        to.value[i] = in.value;
+        to.colour[i] = in.colour;
+        return;
+      }
+    }
+    if (k == in.key) {
+      atomicMax(dup, 1u);
+      return;
+    }
+    i = i + 1u == to.cap ? 0u : i + 1u;
+  }
+  atomicMax(&ctl->overflow, 1u);
+}
+
 inline uint32_t blocks_of(uint32_t n) { return (uint32_t)(((uint64_t)n + 255u) / 256u); }
 
 }  // namespace
@@ -264,6 +291,10 @@ void launch_octo_cloud(const OctoTable& tb, OctoCtl* ctl, const float4* pts, uin
 
 void launch_octo_rehash(const OctoTable& from, const OctoTable& to, OctoCtl* ctl, hipStream_t stream) {
   hipLaunchKernelGGL(octo_rehash_kernel, dim3(blocks_of(from.cap)), dim3(256), 0, stream, from, to, ctl);
+}
+
+void launch_octo_set_leaves(const OctoLeafIn* src, uint32_t n, const OctoTable& to, OctoCtl* ctl, uint32_t* dup, hipStream_t stream) {
+  if (n > 0) hipLaunchKernelGGL(octo_set_leaves_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, src, n, to, ctl, dup);
 }
 
 }  // namespace rgbdfe

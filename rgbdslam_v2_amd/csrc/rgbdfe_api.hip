@@ -921,6 +921,27 @@ int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t
 int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out) {
   RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_stats(map, out, n_out));
 }
+
+int rgbdfe_octomap_tree(rgbdfe_octomap* map, rgbdfe_octomap_node* out, int64_t capacity, int64_t* n_nodes) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_tree(map, out, capacity, n_nodes));
+}
+
+int rgbdfe_octomap_tree_device(rgbdfe_octomap* map, void* d_out, int64_t capacity, int64_t* n_nodes, void* stream) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_tree_device(map, d_out, capacity, n_nodes, stream));
+}
+
+int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_log_odds, rgbdfe_octomap_leaf* out,
+                                  int64_t capacity, int64_t* n_out) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_nodes_at_depth(map, depth, min_log_odds, out, capacity, n_out));
+}
+
+int rgbdfe_octomap_write(rgbdfe_octomap* map, const char* path) { RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_write(map, path)); }
+
+int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_set_leaves(map, leaves, n));
+}
+
+int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path) { RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_read(map, path)); }
 #undef RGBDFE_ON_MAP
 
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,

@@ -586,6 +586,12 @@ int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_
 int rgbdfe_octomap_size(rgbdfe_octomap* map, int64_t* n_leaves);
 int rgbdfe_octomap_leaves(rgbdfe_octomap* map, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out);
 int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out);
+int rgbdfe_octomap_tree(rgbdfe_octomap* map, rgbdfe_octomap_node* out, int64_t capacity, int64_t* n_nodes);
+int rgbdfe_octomap_tree_device(rgbdfe_octomap* map, void* d_out, int64_t capacity, int64_t* n_nodes, void* stream);
+int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_log_odds, rgbdfe_octomap_leaf* out, int64_t capacity, int64_t* n_out);
+int rgbdfe_octomap_write(rgbdfe_octomap* map, const char* path);
+int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n);
+int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path);
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids, const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out);
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all, double observability_threshold, double* quality);
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);

@@ -339,6 +339,47 @@ void launch_octo_cloud(const OctoTable& tb, OctoCtl* ctl, const float4* pts, uin
                        const OctoScratch& s, hipStream_t stream);
 // every leaf of `from` into the empty table `to` (to.cap >= the leaves of `from`)
 void launch_octo_rehash(const OctoTable& from, const OctoTable& to, OctoCtl* ctl, hipStream_t stream);
+// every leaf of `src` (n records: key as the table packs it, log-odds, r << 16 | g << 8 | b) into the empty table `to`
+// (to.cap >= n); a key that is already there raises *dup
+struct OctoLeafIn {
+  unsigned long long key;
+  float value;
+  uint32_t colour;
+};
+void launch_octo_set_leaves(const OctoLeafIn* src, uint32_t n, const OctoTable& to, OctoCtl* ctl, uint32_t* dup, hipStream_t stream);
+// octomap_tree.hip: the octree of a map's leaves (include/rgbdfe.h, "the tree of a leaf set"; the stages: the head of that
+// file).  Workspace of a map of n leaves in a table of cap slots: see api_octomap_tree.hip.
+constexpr uint32_t kTreeTile = 1024;  // elements of a workgroup in a count / write pass
+struct TreeHdr {
+  uint32_t cnt[17];  // nodes of depth d (cnt[16] = leaves), as far as the passes went
+  uint32_t n_nodes;  // all nodes: the sum the chain scan leaves
+  uint32_t n_out;    // records of the depth filter
+  uint32_t dup;      // rgbdfe_octomap_set_leaves: a key came twice
+  uint32_t pad[4];
+};
+struct TreeLevel {   // the nodes of one depth in tree order
+  float* value;
+  uint32_t* colour;  // r << 16 | g << 8 | b | child mask << 24
+  uint32_t* first;   // the sorted index of the node's first leaf
+};
+struct TreeScratch {
+  TreeHdr* hdr;
+  unsigned long long *code, *scode;  // path codes: of the leaves in slot order, in tree order
+  uint32_t* slot;
+  uint32_t* keys[2];
+  uint32_t* idx[2];
+  uint32_t *hist, *digits, *tile_count, *tile_first;
+  uint32_t *top, *off;
+  TreeLevel level[2];
+};
+// each returns its number of kernel launches.  leaves: gather, sort, arrange (hdr->cnt[16]; level[0] = depth 16);
+// chain: off, hdr->n_nodes; levels: depth 15 down to `down_to`, the records of every node into d_records unless NULL
+// (needs chain); filter: the nodes of `depth` (the levels must have gone down to it) with value >= min_log_odds as
+// rgbdfe_octomap_leaf records, hdr->n_out
+int launch_tree_leaves(const OctoTable& tb, uint32_t n_leaves, const TreeScratch& t, hipStream_t stream);
+int launch_tree_chain(uint32_t n_leaves, const TreeScratch& t, hipStream_t stream);
+int launch_tree_levels(uint32_t n_leaves, uint32_t down_to, const TreeScratch& t, void* d_records, hipStream_t stream);
+int launch_tree_filter(uint32_t n_leaves, uint32_t depth, float min_log_odds, const TreeScratch& t, void* d_out, hipStream_t stream);
 void launch_sift_pack(const float* desc_in, const int32_t* kept_idx, const int32_t* n_ptr, int max_rows,
                       bool root_sift, float* raw, float* feat, hipStream_t stream);
 

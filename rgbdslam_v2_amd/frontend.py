@@ -9,6 +9,7 @@ This module keeps those names and argument meanings so the parity tests read
 like tests of the reference; all arithmetic happens in librgbdfe.so on the GPU.
 """
 import ctypes as C
+import os
 import threading
 import warnings
 import weakref
@@ -1299,7 +1300,9 @@ class OctoMap:
     """ColorOctomapServer on the device (ColorOctomapServer.cpp:61-129; the seam of GraphManager::renderToOctomap /
     saveOctomapImpl, graph_mgr_io.cpp:253-329): the leaves of a colour OctoMap, fed by ray-casting clouds one after another.
     params: resolution, prob_hit, prob_miss, clamping_min, clamping_max, occupancy_threshold (defaults:
-    parameter_server.cpp:56-64).  Close the map before its FrontEnd."""
+    parameter_server.cpp:56-64).  tree / tree_device / nodes_at_depth / write / read / set_leaves: the octree over the leaves
+    (updateInnerOccupancy), the node set of render() and the .ot file of save(), built on the device.  Close the map before
+    its FrontEnd."""
 
     def __init__(self, fe: "FrontEnd", capacity_cells: int, **params):
         self._fe, self._L = fe, fe._L
@@ -1401,3 +1404,65 @@ class OctoMap:
         n = C.c_int64(0)
         self._fe._check(self._L.rgbdfe_octomap_leaves(self._map, out.ctypes.data if len(out) else None, len(out), C.byref(n)))
         return out[:n.value]
+
+    @property
+    def last_tree_launches(self) -> int:
+        """Kernel launches of the last tree / tree_device / nodes_at_depth / write call."""
+        out = np.zeros(4, np.int64)
+        self._fe._check(self._L.rgbdfe_octomap_stats(self._map, out.ctypes.data, 4))
+        return int(out[3])
+
+    def tree_status(self, out):
+        """(status, nodes needed) of rgbdfe_octomap_tree into `out` (a _lib.OCTOMAP_NODE_DTYPE array): status -5
+        (RGBDFE_ERR_CAPACITY) when `out` is too short, and nothing is written then.  Other failures raise."""
+        n = C.c_int64(0)
+        st = self._L.rgbdfe_octomap_tree(self._map, out.ctypes.data if len(out) else None, len(out), C.byref(n))
+        if st != -5:
+            self._fe._check(st)
+        return st, n.value
+
+    def tree(self):
+        """Every node of the octree over the leaves (inner values as updateInnerOccupancy leaves them) in depth-first
+        pre-order, children in ascending index: a structured array (log_odds, rgb[3], children;
+        _lib.OCTOMAP_NODE_DTYPE), the payload of an .ot file.  An empty map has no nodes."""
+        out = np.zeros(0, _lib.OCTOMAP_NODE_DTYPE)
+        st, n = self.tree_status(out)
+        if st == 0:
+            return out
+        out = np.zeros(n, _lib.OCTOMAP_NODE_DTYPE)
+        self._fe._check(self.tree_status(out)[0])
+        return out
+
+    def tree_device(self, out, stream=None):
+        """The same records into `out`, a contiguous uint8 torch tensor [capacity, 8] on the map's device; no record
+        crosses to the host.  Returns the number of nodes; raises when the room is too small."""
+        if not (out.is_cuda and out.is_contiguous() and out.dim() == 2 and out.shape[1] == 8 and out.element_size() == 1):
+            raise ValueError("out must be a contiguous [capacity, 8] uint8 tensor on the device")
+        n = C.c_int64(0)
+        self._fe._check(self._L.rgbdfe_octomap_tree_device(self._map, out.data_ptr() if out.shape[0] else None,
+                                                           int(out.shape[0]), C.byref(n), stream))
+        return n.value
+
+    def nodes_at_depth(self, depth, min_log_odds=-np.inf):
+        """The nodes of one depth (0 .. 16) with log_odds >= min_log_odds, in tree order, as leaf records
+        (_lib.OCTOMAP_LEAF_DTYPE) whose key is the node's first cell with the low 16 - depth bits cleared: what
+        ColorOctomapServer::render walks at octomap_display_level.  A node's edge is resolution * 2 ** (16 - depth)."""
+        bound = len(self) if depth >= 11 else min(len(self), 8 ** max(int(depth), 0))
+        out = np.zeros(bound, _lib.OCTOMAP_LEAF_DTYPE)
+        n = C.c_int64(0)
+        self._fe._check(self._L.rgbdfe_octomap_nodes_at_depth(self._map, int(depth), float(min_log_odds),
+                                                              out.ctypes.data if len(out) else None, len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def write(self, path):
+        """ColorOctomapServer::save: the map as an .ot file (id ColorOcTree)."""
+        self._fe._check(self._L.rgbdfe_octomap_write(self._map, os.fsencode(path)))
+
+    def read(self, path):
+        """The leaves of an .ot file written with the same resolution become the map's contents."""
+        self._fe._check(self._L.rgbdfe_octomap_read(self._map, os.fsencode(path)))
+
+    def set_leaves(self, leaves):
+        """The map's contents replaced by these leaves (_lib.OCTOMAP_LEAF_DTYPE records, any order)."""
+        lv = np.ascontiguousarray(leaves, _lib.OCTOMAP_LEAF_DTYPE).reshape(-1)
+        self._fe._check(self._L.rgbdfe_octomap_set_leaves(self._map, lv.ctypes.data if len(lv) else None, len(lv)))
