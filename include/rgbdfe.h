@@ -692,6 +692,98 @@ int rgbdfe_potential_edge_targets(const rgbdfe_pose_graph* g, int32_t sequential
                                   int32_t include_predecessor, rgbdfe_rand_fn rand_fn, void* rand_state, uint32_t seed,
                                   int32_t* ids_out, int32_t capacity, int32_t* n_out);
 
+/* ---- pose-graph optimisation (GraphManager::optimizeGraphImpl, graph_manager.cpp:938-1066) ----------
+ * The stage between the edges of rgbdfe_match_node_pairs and the `transforms` of rgbdfe_assemble_map /
+ * rgbdfe_octomap_insert_nodes: Levenberg-Marquardt over g2o::EdgeSE3 with a Huber kernel, solved by block-Jacobi
+ * preconditioned conjugate gradients (backend_solver "pcg"), on the device.  g2o is not part of the reference tree: the
+ * contract is this library's restatement (restated, not pinned), tests/pose_graph_oracle.py states it
+ * literally and the device gives its bytes.  Everything is double; the only operations are + - * / sqrt and comparisons.
+ *
+ *   Vertices: the nodes of the graph object in ascending node id, each an SE(3) estimate (identity until set) and a
+ *     `fixed` flag (pose_relative_to = first / previous / largest_loop: the caller sets flags, fixationOfVertices :911-937).
+ *     Free vertices are numbered in that order.  No fixed vertex at all is legal.
+ *   Edges: those added with rgbdfe_pose_graph_add_edge_se3, in insertion order: measurement Z and a 6x6 information
+ *     matrix O (row-major; any symmetric matrix).  Edges of rgbdfe_pose_graph_add_edge carry no measurement: ignored.
+ *   Sums of three products are (a0 b0 + a1 b1) + a2 b2; longer ones run left to right.
+ *   Error  e = toVectorMQT(Z^-1 Xi^-1 Xj): A = Xi^-1 Xj (Ra = Ri' Rj, ta = Ri'(tj - ti)), D = Z^-1 A (RD = Rz' Ra,
+ *     tD = Rz'(ta - tz)); e = (tD, x, y, z of the quaternion of RD).  Matrix -> quaternion: trace > 0: s = sqrt(trace + 1),
+ *     w = s / 2, (x, y, z) = (R21 - R12, R02 - R20, R10 - R01) * (0.5 / s); otherwise i = the largest diagonal entry (i = 0;
+ *     R11 > R00: 1; R22 > Rii: 2), j, k cyclic, s = sqrt(Rii - Rjj - Rkk + 1), q_i = s / 2, w = (Rkj - Rjk) * (0.5 / s),
+ *     q_j = (Rji + Rij) * (0.5 / s), q_k = (Rki + Rik) * (0.5 / s); then divided by its norm, all four signs flipped when w < 0.
+ *   Update  X <- X * fromVectorMQT(d): translation d[0..2]; rotation from v = d[3..5]: w = 1 - |v|^2, w < 0: identity,
+ *     else the matrix of the quaternion (v, sqrt(w)).  The rotation block is never re-orthogonalised (g2o does so every
+ *     1000 updates); the error's quaternion is normalised instead.
+ *   Jacobians at a zero update, with Q = w I + [u]x of the error quaternion (u, w):
+ *     de/dXj = [RD 0; 0 Q],  de/dXi = [-Rz'  2 Rz'[ta]x; 0  -Q Ra'].
+ *   Huber, delta 1: chi2 = e'Oe; chi2 <= 1: rho = chi2, w = 1; else rho = 2 sqrt(chi2) - 1, w = 1 / sqrt(chi2).  An edge
+ *     contributes w J'OJ and -w J'Oe (OJ first, then J'(OJ), then times w); the graph's chi2 is the sum of rho.
+ *   H and b: a vertex's diagonal block and part of b add its edges' contributions in insertion order; the off-diagonal
+ *     blocks are the distinct pairs of free vertices in the order the edges first join them, stored with row < column (an
+ *     edge whose first vertex has the larger free index contributes transposed), adding their edges in insertion order.
+ *   Sums over edges (chi2) and vertices (dot products) go through one tree: leaves of 64 consecutive values (zero
+ *     padded) halved 32, 16 .. 1; leaf k is added into accumulator k % 64 in ascending k; the 64 accumulators are halved
+ *     the same way.  A dot product's value per vertex is its six products left to right.
+ *   PCG on (H + lambda I) x = b: M = the diagonal blocks of H + lambda I, applied through their Cholesky factors;
+ *     x = 0, r = b, z = M^-1 r, p = z; while not r'z <= 1e-6 (absolute) and fewer than 6 * (free vertices) iterations:
+ *     q = A p (per row: the diagonal block's terms, then the vertex's off-diagonal blocks in block order),
+ *     alpha = r'z / p'q, x += alpha p, r -= alpha q, z = M^-1 r, beta = r'z_new / r'z, p = z + beta p.
+ *   Levenberg-Marquardt as g2o's OptimizationAlgorithmLevenberg: per rgbdfe_pose_graph_optimize call lambda = 1e-5 *
+ *     max |diag H| of the first linearisation, ni = 2.  An iteration linearises, then tries up to 10 times: solve, apply to
+ *     a copy of the estimates, gain = (chi2 - chi2_trial) / (dx'(lambda dx + b) + 1e-3); gain > 0 and chi2_trial finite:
+ *     keep, lambda *= clamp(1 - (2 gain - 1)^3, 1/3, 2/3), ni = 2; otherwise drop the copy, lambda *= ni, ni *= 2.  Trials
+ *     go on while gain < 0.  After 10 trials, or at gain == 0 (g2o's released code: neither accepted nor retried), the call
+ *     ends; that iteration counts as done, as in SparseOptimizer::optimize.
+ *
+ * rgbdfe_pose_graph_set_estimate / get_estimate: 16 doubles, a column-major 4x4 (rotation and translation are kept).
+ * rgbdfe_pose_graph_add_edge_se3: also registers the topology as rgbdfe_pose_graph_add_edge does; set_estimate != 0:
+ *   X2 = X1 * Z (addEdgeToG2O :858,864).  node_id1 == node_id2: RGBDFE_ERR_INVALID_ARG.
+ * rgbdfe_pose_graph_chi2: the sum of rho at the current estimates (0 without a measured edge).
+ * rgbdfe_pose_graph_linearize: one linearisation to host arrays: errors (6 per edge) and weights (w per edge) in
+ *   insertion order; free_ids (node ids), h_diag (36 per free vertex, row-major), b (6 per free vertex); off_rows /
+ *   off_cols (free indices) and h_off (36 per block); *chi2.  Any array may be NULL.  A capacity below the count:
+ *   RGBDFE_ERR_CAPACITY with the three counts set.
+ * rgbdfe_pose_graph_optimize: SparseOptimizer::optimize(iterations).  rgbdfe_pose_graph_optimize_graph: the loop of
+ *   optimizeGraphImpl (:996-1014): break_criterion >= 1: optimize(ceil(c / 10)) until c iterations are done or a call
+ *   does none; otherwise optimize(5) while chi2 / chi2_prev < 1 - c (first chi2_prev: DBL_MAX).  Every measured edge
+ *   takes part.  A graph with no measured edge or no free vertex: 0 iterations, estimates untouched.
+ *   report (may be NULL): iterations done and the final chi2; for the first RGBDFE_POSE_GRAPH_REPORT_ITERATIONS
+ *   iterations (of all calls of the loop) the trials, each trial's PCG iterations, chi2 before and after, lambda after;
+ *   kernel launches, read-backs, seconds spent building and uploading the plan, seconds in all.
+ * rgbdfe_pose_graph_transforms: the estimates of node_ids as column-major Matrix4f rows (float), what rgbdfe_assemble_map
+ *   and rgbdfe_octomap_insert_nodes take; composing with cam2rgb stays with the caller.
+ * Errors: an unknown node id: RGBDFE_ERR_UNKNOWN_NODE before any state changes; a non-finite input: RGBDFE_ERR_INVALID_ARG.
+ * The device buffers belong to the graph object and go with rgbdfe_pose_graph_destroy. */
+#define RGBDFE_POSE_GRAPH_REPORT_ITERATIONS 64
+#define RGBDFE_POSE_GRAPH_MAX_TRIALS 10
+typedef struct rgbdfe_pose_graph_iteration {
+  int32_t trials;
+  int32_t pcg_iterations[RGBDFE_POSE_GRAPH_MAX_TRIALS];
+  int32_t pad;
+  double chi2_before, chi2_after, lambda;
+} rgbdfe_pose_graph_iteration;
+typedef struct rgbdfe_pose_graph_report {
+  int32_t iterations;   /* Levenberg-Marquardt iterations done */
+  int32_t recorded;     /* entries of it[] */
+  double chi2;
+  int64_t launches, readbacks;
+  double upload_seconds, total_seconds;
+  rgbdfe_pose_graph_iteration it[RGBDFE_POSE_GRAPH_REPORT_ITERATIONS];
+} rgbdfe_pose_graph_report;
+int rgbdfe_pose_graph_set_estimate(rgbdfe_pose_graph* g, int32_t node_id, const double* transform);
+int rgbdfe_pose_graph_get_estimate(const rgbdfe_pose_graph* g, int32_t node_id, double* transform);
+int rgbdfe_pose_graph_set_fixed(rgbdfe_pose_graph* g, int32_t node_id, int32_t fixed);
+int rgbdfe_pose_graph_add_edge_se3(rgbdfe_pose_graph* g, int32_t node_id1, int32_t node_id2, const double* transform,
+                                   const double* information, int32_t set_estimate);
+int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2);
+int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* errors, double* weights, int32_t edge_capacity,
+                                int32_t* n_edges, int32_t* free_ids, double* h_diag, double* b, int32_t vertex_capacity,
+                                int32_t* n_free, int32_t* off_rows, int32_t* off_cols, double* h_off, int32_t block_capacity,
+                                int32_t* n_blocks, double* chi2);
+int rgbdfe_pose_graph_optimize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, int32_t iterations, rgbdfe_pose_graph_report* report);
+int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double break_criterion,
+                                     rgbdfe_pose_graph_report* report);
+int rgbdfe_pose_graph_transforms(const rgbdfe_pose_graph* g, int32_t n, const int32_t* node_ids, float* out);
+
 /* GPU prefilter in front of the pair path (second half): what loop_closing.cpp's
  * GraphManager::getNeighbours (:190-277, behind DO_LOOP_CLOSING, never wired into nodeComparisons) sketched -- every
  * descriptor of the new node votes `k_neighbours - rank` (:241) for the nodes holding its k nearest descriptors, a

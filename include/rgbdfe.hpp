@@ -358,6 +358,32 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
     rgbdfe_pose_graph_add_node(topology_.get(), n->id_, vertex_id, n->matchable_ ? 1 : 0, keyframe ? 1 : 0);
   }
   void edgeAdded(int id1, int id2) { rgbdfe_pose_graph_add_edge(topology_.get(), id1, id2); }
+  // GraphManager::addEdgeToG2O (graph_manager.cpp:811-909): the edge with its measurement enters the optimizer (and the
+  // topology candidate selection reads); set_estimate: the second node's estimate becomes X1 * transform (:858,864)
+  bool addEdgeToG2O(const LoadedEdge3D& edge, bool set_estimate = false) {
+    double info[36] = {0};
+    for (int k = 0; k < 6; ++k) info[7 * k] = edge.informationScale;
+    return rgbdfe_pose_graph_add_edge_se3(topology_.get(), edge.id1, edge.id2, edge.transform.data(), info,
+                                          set_estimate ? 1 : 0) == RGBDFE_OK;
+  }
+  // pose_relative_to (fixationOfVertices, :911-937): the caller fixes the vertices of its choice
+  bool setFixed(int node_id, bool fixed = true) {
+    return rgbdfe_pose_graph_set_fixed(topology_.get(), node_id, fixed ? 1 : 0) == RGBDFE_OK;
+  }
+  // double GraphManager::optimizeGraph(double break_criterion) (:938-1066; optimizer_iterations, default 0.01): Levenberg-
+  // Marquardt + PCG on the device; returns chi2, negative on failure.  report (optional): iterations, trials, PCG counts.
+  double optimizeGraph(double break_criterion = 0.01, rgbdfe_pose_graph_report* report = nullptr) {
+    rgbdfe_pose_graph_report local;
+    rgbdfe_pose_graph_report* rep = report ? report : &local;
+    if (rgbdfe_pose_graph_optimize_graph(fe_.get(), topology_.get(), break_criterion, rep) != RGBDFE_OK) return -1.0;
+    return rep->chi2;
+  }
+  // the estimates of node_ids as n x 16 floats (column-major Matrix4f): the world2cam of assembleMap / the OctoMap calls
+  std::vector<float> transforms(const std::vector<int32_t>& node_ids) const {
+    std::vector<float> out(16 * node_ids.size());
+    if (rgbdfe_pose_graph_transforms(topology_.get(), (int32_t)node_ids.size(), node_ids.data(), out.data()) != RGBDFE_OK) return {};
+    return out;
+  }
   // QList<int> GraphManager::getPotentialEdgeTargetsWithDijkstra(new_node, sequential_targets, geodesic_targets,
   // sampled_targets, predecessor_id, include_predecessor); geodesic_depth is the parameter server's "geodesic_depth".
   // rand_fn == nullptr: reproducible draws from `seed` instead of rand().

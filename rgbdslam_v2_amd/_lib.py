@@ -86,6 +86,21 @@ class OctomapParams(C.Structure):   # rgbdfe_octomap_params
                 ("clamping_min", C.c_double), ("clamping_max", C.c_double), ("occupancy_threshold", C.c_double)]
 
 
+POSE_GRAPH_REPORT_ITERATIONS = 64
+POSE_GRAPH_MAX_TRIALS = 10
+
+
+class PoseGraphIteration(C.Structure):   # rgbdfe_pose_graph_iteration
+    _fields_ = [("trials", C.c_int32), ("pcg_iterations", C.c_int32 * POSE_GRAPH_MAX_TRIALS), ("pad", C.c_int32),
+                ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("lam", C.c_double)]
+
+
+class PoseGraphReport(C.Structure):   # rgbdfe_pose_graph_report
+    _fields_ = [("iterations", C.c_int32), ("recorded", C.c_int32), ("chi2", C.c_double), ("launches", C.c_int64),
+                ("readbacks", C.c_int64), ("upload_seconds", C.c_double), ("total_seconds", C.c_double),
+                ("it", PoseGraphIteration * POSE_GRAPH_REPORT_ITERATIONS)]
+
+
 # rgbdfe_octomap_leaf
 OCTOMAP_LEAF_DTYPE = np.dtype([("key", "<u2", (3,)), ("zero0", "<u2"), ("log_odds", "<f4"), ("rgb", "u1", (3,)),
                                ("zero1", "u1")])
@@ -460,6 +475,25 @@ def load():
     L.rgbdfe_pose_graph_add_edge.argtypes = [vp, i32, i32]
     L.rgbdfe_pose_graph_set_matchable.restype = C.c_int
     L.rgbdfe_pose_graph_set_matchable.argtypes = [vp, i32, i32]
+    L.rgbdfe_pose_graph_set_estimate.restype = C.c_int
+    L.rgbdfe_pose_graph_set_estimate.argtypes = [vp, i32, vp]
+    L.rgbdfe_pose_graph_get_estimate.restype = C.c_int
+    L.rgbdfe_pose_graph_get_estimate.argtypes = [vp, i32, vp]
+    L.rgbdfe_pose_graph_set_fixed.restype = C.c_int
+    L.rgbdfe_pose_graph_set_fixed.argtypes = [vp, i32, i32]
+    L.rgbdfe_pose_graph_add_edge_se3.restype = C.c_int
+    L.rgbdfe_pose_graph_add_edge_se3.argtypes = [vp, i32, i32, vp, vp, i32]
+    L.rgbdfe_pose_graph_chi2.restype = C.c_int
+    L.rgbdfe_pose_graph_chi2.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    L.rgbdfe_pose_graph_linearize.restype = C.c_int
+    L.rgbdfe_pose_graph_linearize.argtypes = [vp, vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp, i32, C.POINTER(i32), vp, vp, vp,
+                                              i32, C.POINTER(i32), C.POINTER(C.c_double)]
+    L.rgbdfe_pose_graph_optimize.restype = C.c_int
+    L.rgbdfe_pose_graph_optimize.argtypes = [vp, vp, i32, C.POINTER(PoseGraphReport)]
+    L.rgbdfe_pose_graph_optimize_graph.restype = C.c_int
+    L.rgbdfe_pose_graph_optimize_graph.argtypes = [vp, vp, C.c_double, C.POINTER(PoseGraphReport)]
+    L.rgbdfe_pose_graph_transforms.restype = C.c_int
+    L.rgbdfe_pose_graph_transforms.argtypes = [vp, i32, vp, vp]
     L.rgbdfe_potential_edge_targets.restype = C.c_int
     L.rgbdfe_potential_edge_targets.argtypes = [vp, i32, i32, i32, i32, i32, i32, RAND_FN, vp, C.c_uint32, vp, i32,
                                                 C.POINTER(i32)]
@@ -491,6 +525,9 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_reset_kernel_time", "rgbdfe_graph_stats", "rgbdfe_set_graph_capture", "rgbdfe_match_pair_list_allgather_inliers", "rgbdfe_pack_inliers", "rgbdfe_sizeof_inlier_header", "rgbdfe_sizeof_match_result", "rgbdfe_abi_version",
     "rgbdfe_pose_graph_create", "rgbdfe_pose_graph_destroy", "rgbdfe_pose_graph_add_node",
     "rgbdfe_pose_graph_add_edge", "rgbdfe_pose_graph_set_matchable", "rgbdfe_potential_edge_targets",
+    "rgbdfe_pose_graph_set_estimate", "rgbdfe_pose_graph_get_estimate", "rgbdfe_pose_graph_set_fixed",
+    "rgbdfe_pose_graph_add_edge_se3", "rgbdfe_pose_graph_chi2", "rgbdfe_pose_graph_linearize",
+    "rgbdfe_pose_graph_optimize", "rgbdfe_pose_graph_optimize_graph", "rgbdfe_pose_graph_transforms",
     "rgbdfe_create_multi", "rgbdfe_device_count", "rgbdfe_device_context", "rgbdfe_match_pair_list_allgather",
     "rgbdfe_gather_transport", "rgbdfe_gather_exchanges", "rgbdfe_set_hamming_mode", "rgbdfe_project_to_3d_cloud", "rgbdfe_detect_describe_cloud",
     "rgbdfe_detect_describe_batch", "rgbdfe_detect_describe_batch_nodes", "rgbdfe_match_pair_list_allgather_edges",

@@ -40,6 +40,83 @@ class PoseGraph:
         """An edge entering the optimizer (GraphManager::addEdgeToG2O, graph_manager.cpp:811)."""
         self._check(self._L.rgbdfe_pose_graph_add_edge(self._g, int(id1), int(id2)))
 
+    # ---- the optimiser (include/rgbdfe.h, "pose-graph optimisation") ----
+    @staticmethod
+    def _ctx(front_end):
+        return getattr(front_end, "_ctx", front_end)
+
+    @staticmethod
+    def _report(rep):
+        its = [dict(trials=int(r.trials), pcg=[int(v) for v in r.pcg_iterations[:r.trials]], chi2_before=float(r.chi2_before),
+                    chi2_after=float(r.chi2_after), lam=float(r.lam)) for r in rep.it[:rep.recorded]]
+        return dict(iterations=int(rep.iterations), chi2=float(rep.chi2), its=its, launches=int(rep.launches),
+                    readbacks=int(rep.readbacks), upload_seconds=float(rep.upload_seconds),
+                    total_seconds=float(rep.total_seconds))
+
+    def set_estimate(self, node_id, transform):
+        """The vertex's estimate: a 4x4 (row, column) array."""
+        t = np.ascontiguousarray(np.asarray(transform, np.float64).reshape(4, 4).T)
+        self._check(self._L.rgbdfe_pose_graph_set_estimate(self._g, int(node_id), t.ctypes.data))
+
+    def get_estimate(self, node_id):
+        t = np.zeros((4, 4), np.float64)
+        self._check(self._L.rgbdfe_pose_graph_get_estimate(self._g, int(node_id), t.ctypes.data))
+        return t.T.copy()
+
+    def set_fixed(self, node_id, fixed=True):
+        self._check(self._L.rgbdfe_pose_graph_set_fixed(self._g, int(node_id), int(bool(fixed))))
+
+    def add_edge_se3(self, id1, id2, transform, information, set_estimate=False):
+        """An edge with its measurement entering the optimizer (GraphManager::addEdgeToG2O, graph_manager.cpp:811-909):
+        transform 4x4, information 6x6 (or a scalar: I * information, matchNodePair's)."""
+        t = np.ascontiguousarray(np.asarray(transform, np.float64).reshape(4, 4).T)
+        info = np.asarray(information, np.float64)
+        info = np.ascontiguousarray(np.eye(6) * float(info) if info.ndim == 0 else info.reshape(6, 6))
+        self._check(self._L.rgbdfe_pose_graph_add_edge_se3(self._g, int(id1), int(id2), t.ctypes.data, info.ctypes.data,
+                                                           int(bool(set_estimate))))
+
+    def chi2(self, front_end):
+        out = C.c_double(0)
+        self._check(self._L.rgbdfe_pose_graph_chi2(self._ctx(front_end), self._g, C.byref(out)))
+        return out.value
+
+    def linearize(self, front_end):
+        """One linearisation: dict(e[E,6], w[E], free_ids, Hd[nf,6,6], b[nf,6], rows, cols, B[nb,6,6], chi2)."""
+        ne, nf, nb = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        chi2 = C.c_double(0)
+        rc = self._L.rgbdfe_pose_graph_linearize(self._ctx(front_end), self._g, None, None, 0, C.byref(ne), None, None, None, 0,
+                                                 C.byref(nf), None, None, None, 0, C.byref(nb), C.byref(chi2))
+        if rc not in (0, -5):  # RGBDFE_ERR_CAPACITY: the counts are set
+            self._check(rc)
+        e, w = np.zeros((ne.value, 6)), np.zeros(ne.value)
+        ids, Hd, b = np.zeros(nf.value, np.int32), np.zeros((nf.value, 6, 6)), np.zeros((nf.value, 6))
+        rows, cols, B = np.zeros(nb.value, np.int32), np.zeros(nb.value, np.int32), np.zeros((nb.value, 6, 6))
+        self._check(self._L.rgbdfe_pose_graph_linearize(
+            self._ctx(front_end), self._g, e.ctypes.data, w.ctypes.data, ne.value, C.byref(ne), ids.ctypes.data, Hd.ctypes.data,
+            b.ctypes.data, nf.value, C.byref(nf), rows.ctypes.data, cols.ctypes.data, B.ctypes.data, nb.value, C.byref(nb),
+            C.byref(chi2)))
+        return dict(e=e, w=w, free_ids=ids, Hd=Hd, b=b, rows=rows, cols=cols, B=B, chi2=chi2.value)
+
+    def optimize(self, front_end, iterations):
+        """SparseOptimizer::optimize(iterations); the report as a dict."""
+        rep = _lib.PoseGraphReport()
+        self._check(self._L.rgbdfe_pose_graph_optimize(self._ctx(front_end), self._g, int(iterations), C.byref(rep)))
+        return self._report(rep)
+
+    def optimize_graph(self, front_end, break_criterion=0.01):
+        """The loop of GraphManager::optimizeGraphImpl (optimizer_iterations = 0.01 by default); the report as a dict."""
+        rep = _lib.PoseGraphReport()
+        self._check(self._L.rgbdfe_pose_graph_optimize_graph(self._ctx(front_end), self._g, float(break_criterion), C.byref(rep)))
+        return self._report(rep)
+
+    def transforms(self, node_ids):
+        """The estimates as n x 4 x 4 float32 (row, column) matrices: the `transforms` of FrontEnd.assemble_map and
+        OctoMap.insert_nodes."""
+        ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        out = np.zeros((len(ids), 16), np.float32)  # column-major rows, as the C ABI gives them
+        self._check(self._L.rgbdfe_pose_graph_transforms(self._g, len(ids), ids.ctypes.data, out.ctypes.data))
+        return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+
     def set_matchable(self, node_id, matchable):
         self._check(self._L.rgbdfe_pose_graph_set_matchable(self._g, int(node_id), int(bool(matchable))))
 

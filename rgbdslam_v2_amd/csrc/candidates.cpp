@@ -21,17 +21,7 @@
 #include <vector>
 
 #include "rgbdfe.h"
-
-struct rgbdfe_pose_graph {
-  struct NodeInfo {
-    int32_t vertex_id;
-    bool matchable;
-  };
-  std::map<int32_t, NodeInfo> nodes;                 // node id -> node (graph_)
-  std::set<int32_t> camera_vertices;                 // vertex ids
-  std::map<int32_t, std::set<int32_t>> adjacency;    // vertex id -> vertex ids joined by an edge
-  std::deque<int32_t> keyframes;
-};
+#include "pose_graph_host.h"
 
 namespace {
 
@@ -84,12 +74,17 @@ extern "C" {
 
 rgbdfe_pose_graph* rgbdfe_pose_graph_create(void) { return new (std::nothrow) rgbdfe_pose_graph(); }
 
-void rgbdfe_pose_graph_destroy(rgbdfe_pose_graph* g) { delete g; }
+void rgbdfe_pose_graph_destroy(rgbdfe_pose_graph* g) {
+  if (g && g->device && g->device_free) g->device_free(g->device);  // the optimiser's device buffers
+  delete g;
+}
 
 int rgbdfe_pose_graph_add_node(rgbdfe_pose_graph* g, int32_t node_id, int32_t vertex_id, int32_t matchable,
                                int32_t keyframe) try {
   if (!g || node_id < 0 || vertex_id < 0) return RGBDFE_ERR_INVALID_ARG;
-  g->nodes[node_id] = rgbdfe_pose_graph::NodeInfo{vertex_id, matchable != 0};
+  rgbdfe_pose_graph::NodeInfo& nd = g->nodes[node_id];  // a node added again keeps its estimate and its fixed flag
+  nd.vertex_id = vertex_id;
+  nd.matchable = matchable != 0;
   g->camera_vertices.insert(vertex_id);
   g->adjacency[vertex_id];
   if (keyframe) g->keyframes.push_back(node_id);
@@ -210,6 +205,106 @@ int rgbdfe_potential_edge_targets(const rgbdfe_pose_graph* g, int32_t sequential
   return RGBDFE_OK;
 } catch (const std::bad_alloc&) {
   return RGBDFE_ERR_OUT_OF_MEMORY;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+// ---- the optimiser's vertices and edges (the device work: api_pose_graph.hip) ----------------------------------------
+namespace {
+bool all_finite(const double* v, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!(v[i] - v[i] == 0.0)) return false;
+  return true;
+}
+void pose_from_matrix(const double* m, double* est) {  // column-major 4x4 -> rotation row-major, translation
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) est[3 * r + c] = m[4 * c + r];
+    est[9 + r] = m[12 + r];
+  }
+}
+double dot3(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+}  // namespace
+
+int rgbdfe_pose_graph_set_estimate(rgbdfe_pose_graph* g, int32_t node_id, const double* transform) try {
+  if (!g || !transform || !all_finite(transform, 16)) return RGBDFE_ERR_INVALID_ARG;
+  const auto a = g->nodes.find(node_id);
+  if (a == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;
+  pose_from_matrix(transform, a->second.est);
+  return RGBDFE_OK;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_get_estimate(const rgbdfe_pose_graph* g, int32_t node_id, double* transform) try {
+  if (!g || !transform) return RGBDFE_ERR_INVALID_ARG;
+  const auto a = g->nodes.find(node_id);
+  if (a == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;
+  const double* est = a->second.est;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) transform[4 * c + r] = est[3 * r + c];
+    transform[12 + r] = est[9 + r];
+    transform[4 * r + 3] = 0.0;
+  }
+  transform[15] = 1.0;
+  return RGBDFE_OK;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_set_fixed(rgbdfe_pose_graph* g, int32_t node_id, int32_t fixed) try {
+  if (!g) return RGBDFE_ERR_INVALID_ARG;
+  const auto a = g->nodes.find(node_id);
+  if (a == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;
+  a->second.fixed = fixed != 0;
+  return RGBDFE_OK;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_add_edge_se3(rgbdfe_pose_graph* g, int32_t node_id1, int32_t node_id2, const double* transform,
+                                   const double* information, int32_t set_estimate) try {
+  if (!g || !transform || !information || node_id1 == node_id2 || !all_finite(transform, 16) || !all_finite(information, 36))
+    return RGBDFE_ERR_INVALID_ARG;
+  const auto a = g->nodes.find(node_id1), b = g->nodes.find(node_id2);
+  if (a == g->nodes.end() || b == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;
+  rgbdfe_pose_graph::MeasuredEdge m;
+  m.id1 = node_id1;
+  m.id2 = node_id2;
+  pose_from_matrix(transform, m.z);
+  for (int k = 0; k < 36; ++k) m.info[k] = information[k];
+  g->edges.push_back(m);
+  g->adjacency[a->second.vertex_id].insert(b->second.vertex_id);
+  g->adjacency[b->second.vertex_id].insert(a->second.vertex_id);
+  if (set_estimate) {  // X2 = X1 * Z (addEdgeToG2O, graph_manager.cpp:858,864)
+    const double* x = a->second.est;
+    double* y = b->second.est;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) y[3 * r + c] = dot3(x[3 * r], x[3 * r + 1], x[3 * r + 2], m.z[c], m.z[3 + c], m.z[6 + c]);
+      y[9 + r] = dot3(x[3 * r], x[3 * r + 1], x[3 * r + 2], m.z[9], m.z[10], m.z[11]) + x[9 + r];
+    }
+  }
+  return RGBDFE_OK;
+} catch (const std::bad_alloc&) {
+  return RGBDFE_ERR_OUT_OF_MEMORY;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_transforms(const rgbdfe_pose_graph* g, int32_t n, const int32_t* node_ids, float* out) try {
+  if (!g || n < 0 || (n > 0 && (!node_ids || !out))) return RGBDFE_ERR_INVALID_ARG;
+  for (int32_t i = 0; i < n; ++i)
+    if (g->nodes.find(node_ids[i]) == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;  // before anything is written
+  for (int32_t i = 0; i < n; ++i) {
+    const double* est = g->nodes.find(node_ids[i])->second.est;
+    float* m = out + 16 * (size_t)i;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) m[4 * c + r] = (float)est[3 * r + c];
+      m[12 + r] = (float)est[9 + r];
+      m[4 * r + 3] = 0.0f;
+    }
+    m[15] = 1.0f;
+  }
+  return RGBDFE_OK;
 } catch (...) {
   return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
 }

@@ -944,6 +944,33 @@ int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* le
 int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path) { RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_read(map, path)); }
 #undef RGBDFE_ON_MAP
 
+// pose-graph optimisation runs on one device (the first of a group)
+int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_chi2(c, g, chi2));
+}
+
+int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* errors, double* weights, int32_t edge_capacity,
+                                int32_t* n_edges, int32_t* free_ids, double* h_diag, double* b, int32_t vertex_capacity,
+                                int32_t* n_free, int32_t* off_rows, int32_t* off_cols, double* h_off, int32_t block_capacity,
+                                int32_t* n_blocks, double* chi2) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_linearize(c, g, errors, weights, edge_capacity, n_edges, free_ids, h_diag, b,
+                                                             vertex_capacity, n_free, off_rows, off_cols, h_off, block_capacity,
+                                                             n_blocks, chi2));
+}
+
+int rgbdfe_pose_graph_optimize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, int32_t iterations, rgbdfe_pose_graph_report* report) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_optimize(c, g, iterations, report));
+}
+
+int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double break_criterion,
+                                     rgbdfe_pose_graph_report* report) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_optimize_graph(c, g, break_criterion, report));
+}
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

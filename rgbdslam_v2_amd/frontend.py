@@ -1286,10 +1286,26 @@ class Node:
 
 
 class GraphManager:
-    """Only the fan-out of GraphManager::nodeComparisons (src/graph_manager.cpp:531-583)."""
+    """The fan-out of GraphManager::nodeComparisons (src/graph_manager.cpp:531-583) and, over a candidates.PoseGraph,
+    addEdgeToG2O (:811-909) and optimizeGraph (:938-1066)."""
 
-    def __init__(self, frontend: FrontEnd):
+    def __init__(self, frontend: FrontEnd, pose_graph=None):
         self.frontend = frontend
+        self.pose_graph = pose_graph
+
+    def _graph(self):
+        if self.pose_graph is None:
+            from .candidates import PoseGraph
+            self.pose_graph = PoseGraph()
+        return self.pose_graph
+
+    def addEdgeToG2O(self, edge, set_estimate: bool = False):
+        """edge: a LoadedEdge3D (MatchingResult.edge); both nodes must be in the pose graph."""
+        self._graph().add_edge_se3(edge.id1, edge.id2, edge.transform, edge.informationMatrix, set_estimate)
+
+    def optimize_graph(self, break_criterion: float = 0.01):
+        """optimizeGraph with optimizer_iterations = break_criterion; the report (its "chi2" is what the reference returns)."""
+        return self._graph().optimize_graph(self.frontend, break_criterion)
 
     def nodeComparisons(self, new_node: Node, nodes_to_comp: Sequence[Node]) -> List[MatchingResult]:
         recs = self.frontend.match_node_pairs(new_node.id_, [n.id_ for n in nodes_to_comp])
