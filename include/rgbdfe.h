@@ -388,10 +388,17 @@ int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_it
  *                LDS reads of the next train tile sit between the MFMAs of the other accumulator; train tiles arrive by
  *                global_load_lds through three LDS buffers);
  *   2            as 1, the row index added by the VALU instead of the matrix core's C operand;
- *   0            xor + popcount on the VALU (hamming_nn.hip) -- also what nodes with max_keypoints > 32768 get.
- * RGBDFE_HAMMING_MODE_DEFAULT is the mode of a new context; environment variable RGBDFE_HAMMING_MODE overrides it. */
+ *   0            xor + popcount on the VALU (hamming_nn.hip) -- also what nodes with max_keypoints > 32768 get;
+ *   4            mode 3's kernel with 512 instead of 256 queries per block (four query tiles per wave), whatever the batch.
+ * RGBDFE_HAMMING_MODE_DEFAULT is the mode of a new context; environment variable RGBDFE_HAMMING_MODE overrides it.
+ * A context left at mode 3 picks the block width per batch: 512 queries where the batch fills the chip many times over
+ * without splitting the train rows, 256 otherwise (every live-SLAM batch); environment variable RGBDFE_HAMMING_WIDE = 0 / 1
+ * (read by rgbdfe_create) fixes it, and rgbdfe_set_hamming_mode(ctx, 3) asks for 256-query blocks by name.
+ * rgbdfe_hamming_wide_last: 1 = the latest Hamming launch of the context ran 512-query blocks, 0 = it did not, -1 = there
+ * was none yet. */
 #define RGBDFE_HAMMING_MODE_DEFAULT 3
 int rgbdfe_set_hamming_mode(rgbdfe_ctx* ctx, int32_t mode);
+int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx);
 
 /* ---- frame-level data either side of the pair path ----------------
  * rgbdfe_depth_to_mono8: depthToCV8UC1 (misc.cpp:414-430), the detection mask the listener derives from

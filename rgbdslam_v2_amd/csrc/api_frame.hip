@@ -642,10 +642,17 @@ int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_it
 }
 
 int rgbdfe_set_hamming_mode(rgbdfe_ctx* ctx, int32_t mode) {
-  if (!ctx || mode < 0 || mode > 3) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "hamming mode must be 0, 1, 2 or 3");
+  if (!ctx || mode < 0 || mode > 4) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "hamming mode must be 0, 1, 2, 3 or 4");
   std::lock_guard<std::mutex> g(ctx->mu);
   ctx->hamming_mode = mode;
+  if (mode == 3) ctx->hamming_wide = 0;   // asked for by name: the 256-query kernel, whatever the batch
   return RGBDFE_OK;
+}
+
+int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return ctx->hamming_wide_last;
 }
 
 int rgbdfe_set_profiling(rgbdfe_ctx* ctx, int enable) {

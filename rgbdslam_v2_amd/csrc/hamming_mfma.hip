@@ -65,6 +65,7 @@ namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
+typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 #ifndef RGBDFE_HAMMING_QT
@@ -110,6 +111,13 @@ __global__ __launch_bounds__(256) void hamming_expand_kernel(const uint32_t* __r
 __device__ __forceinline__ v8i as_operand(uint4 v) {
   v8i o;
   o[0] = (int)v.x; o[1] = (int)v.y; o[2] = (int)v.z; o[3] = (int)v.w;
+  o[4] = 0; o[5] = 0; o[6] = 0; o[7] = 0;
+  return o;
+}
+
+__device__ __forceinline__ v8i op8(v4i v) {
+  v8i o;
+  o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
   o[4] = 0; o[5] = 0; o[6] = 0; o[7] = 0;
   return o;
 }
@@ -318,7 +326,18 @@ __global__ __launch_bounds__(kThreads) void hamming_mfma_kernel(const uint4* __r
 //     the excluded rows in that one stage), missing tiles are phantoms: they read some valid tile and add a base of
 //     2^22, which no real key reaches (real keys are < 1024).
 // Keys are those of the other kernels, bit for bit (tests/test_gpu_hamming.py runs all four).
+//
+// The kernel is a template over QT, the 32-query operand tiles a wave holds.  QT = 2 (256 queries per block) is the stream
+// described above.  QT = 4 (512 queries per block, "wide") walks the same stages with FOUR units per train tile: per MFMA it
+// needs half the LDS reads, half the L2 -> LDS traffic, half the block prologues and half the barriers.  The two
+// accumulators still alternate unit by unit and there are four running minima.  Its 64 query-operand registers leave room,
+// at three waves per SIMD (168 VGPRs), for neither a second A operand set nor `c3`: the one A operand set is refilled in
+// place by the last unit of every tile, and the ragged tile's rows that do not take part are overwritten in LDS (see the
+// QT = 4 stream below).  hamming_mfma_geometry picks QT per batch.
 // ------------------------------------------------------------------------------------------------
+#ifndef RGBDFE_HAMMING_PIPE_QT
+#define RGBDFE_HAMMING_PIPE_QT 0             // 0: both forms, chosen per batch; 2 / 4: the automatic choice always takes that one
+#endif                                       // (diagnostics, tools/build_hamming_pipe_variants.sh; modes 3 and 4 still force theirs)
 #ifndef RGBDFE_HAMMING_PIPE_BURST
 #define RGBDFE_HAMMING_PIPE_BURST 0
 #endif
@@ -341,7 +360,7 @@ constexpr float kRowUnitPerTile = 32.0f / 16384.0f;  // the tile's first row, in
 #define HP_SGB(MASK, N) __builtin_amdgcn_sched_group_barrier(MASK, N, 0);
 #define HP_FENCE() __builtin_amdgcn_sched_barrier(0);
 
-template <bool SPLIT>
+template <int QT, bool SPLIT>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RGBDFE_HAMMING_PIPE_WAVES, RGBDFE_HAMMING_PIPE_WAVES)))
 void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
                                                                      const PairWork* __restrict__ work,
@@ -351,6 +370,8 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
   // three stage buffers [slot][fragment order of a tile] as three VARIABLES: the compiler tells LDS objects apart by
   // variable, and only then does it let the LDS reads of one buffer pass the global_load_lds towards another
   __shared__ uint4 lds0[kPipeStage][256], lds1[kPipeStage][256], lds2[kPipeStage][256];
+  static_assert((QT == 2 || QT == 4) && kPipeStage == 4, "the unrolled streams are written for two or four query tiles and four-tile stages");
+  constexpr uint32_t kQPB = 4u * QT * 32u;  // queries per block
   const uint32_t L = blockIdx.x;
   const uint32_t xcd = L & 7u;
   const uint32_t j = L >> 3;
@@ -363,7 +384,7 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
 
   const PairWork w = work[pair];
   const uint32_t nq = w.nq;
-  if (qblock * kQueriesPerBlock >= nq) return;
+  if (qblock * kQPB >= nq) return;
   // this block's tiles as slots: the full tiles first, phantoms, the ragged tile (if it is this block's) in the last slot
   const HammingSlots slots = HammingSlots::make(w.nt, SPLIT ? tsplit : 1u, SPLIT ? split : 0u, kPipeStage);
   const uint32_t nt_search = slots.nt_search, n_stages = slots.n_stages;
@@ -374,10 +395,10 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t half = lane >> 5;
 
-  v8i bq[kQT][4];
+  v8i bq[QT][4];
 #pragma unroll
-  for (int t = 0; t < kQT; ++t) {
-    uint32_t qt = qblock * (kQueriesPerBlock / 32) + wave * kQT + t;
+  for (int t = 0; t < QT; ++t) {
+    uint32_t qt = qblock * (kQPB / 32u) + wave * QT + t;
     qt = min(qt, tiles_per_slot - 1u);
     const uint4* __restrict__ qs = slab + ((size_t)w.q_slot * tiles_per_slot + qt) * 256u;
 #pragma unroll
@@ -388,7 +409,7 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
     }
   }
 
-  v16f crow, c3;
+  v16f crow, c3;   // (c3: QT = 2 only)
 #pragma unroll
   for (int r = 0; r < 16; ++r) crow[r] = kBias + (float)((r & 3) + 8 * (r >> 2) + 4 * (int)half) * kRowUnit;
   c3 = crow;
@@ -402,8 +423,8 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
       c3[r] = row < nts ? crow[r] : kNone;
     }
   };
-
   uint32_t best0 = __float_as_uint(kNone), best1 = __float_as_uint(kNone);
+  uint32_t best2 = __float_as_uint(kNone), best3 = __float_as_uint(kNone);   // (QT = 4)
 
   const uint32_t last_tile = tiles_per_slot - 1u;
   const char* __restrict__ ts = reinterpret_cast<const char*>(slab + (size_t)w.t_slot * tiles_per_slot * 256u);
@@ -427,7 +448,6 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
   };
 
   if (n_stages > 0) {
-    static_assert(kQT == 2 && kPipeStage == 4, "the unrolled stream is written for two query tiles and four-tile stages");
     load_stage(0, lds0);
     if (n_stages > 1) load_stage(1, lds1);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
@@ -460,15 +480,26 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
     HP_SGB(0x008, 1) HP_SGB(0x002, RGBDFE_HAMMING_PIPE_VALU_GROUPS / 10 % 10)                        \
     HP_SGB(0x008, 1) HP_SGB(0x002, RGBDFE_HAMMING_PIPE_VALU_GROUPS % 10)
 #endif
-#define HP_UNIT(ACC, A, Q, C, PACC, PBEST, PBASE, R0, R1)                                           \
+    // (a unit without LDS reads, QT = 4: the same order without the read group)
+#if RGBDFE_HAMMING_PIPE_BURST
+#define HP_UNIT_SCHED0() HP_SGB(0x008, 4) HP_SGB(0x002, 12)
+#else
+#define HP_UNIT_SCHED0()                                                                            \
+    HP_SGB(0x008, 1)                                                                                \
+    HP_SGB(0x008, 1) HP_SGB(0x002, RGBDFE_HAMMING_PIPE_VALU_GROUPS / 100)                            \
+    HP_SGB(0x008, 1) HP_SGB(0x002, RGBDFE_HAMMING_PIPE_VALU_GROUPS / 10 % 10)                        \
+    HP_SGB(0x008, 1) HP_SGB(0x002, RGBDFE_HAMMING_PIPE_VALU_GROUPS % 10)
+#endif
+#define HP_UNIT_X(ACC, A, Q, C, PACC, PBEST, PBASE, READS, SCHED)                                   \
     HP_MFMA(ACC, A[0], bq[Q][0], C)                                                                 \
-    R0 R1                                                                                           \
+    READS                                                                                           \
     HP_MFMA(ACC, A[1], bq[Q][1], ACC)                                                               \
     HP_EPI(PACC, PBEST, PBASE)                                                                      \
     HP_MFMA(ACC, A[2], bq[Q][2], ACC)                                                               \
     HP_MFMA(ACC, A[3], bq[Q][3], ACC)                                                               \
-    HP_UNIT_SCHED()                                                                                 \
+    SCHED()                                                                                         \
     HP_FENCE()
+#define HP_UNIT(ACC, A, Q, C, PACC, PBEST, PBASE, R0, R1) HP_UNIT_X(ACC, A, Q, C, PACC, PBEST, PBASE, R0 R1, HP_UNIT_SCHED)
     // A stage out of buffer CUR in two halves; the barrier between them publishes the NEXT stage (this wave's
     // global_load_lds of it was issued a whole stage ago) and frees the buffer of the PREVIOUS one for the stage after the
     // next.  The loop below turns at that barrier, where nothing is in flight (the compiler's bookkeeping of what an LDS
@@ -551,51 +582,165 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
     }
 
 #endif
-    HP_READ(aA, 0, 0, 0) HP_READ(aA, 0, 0, 1) HP_READ(aA, 0, 0, 2) HP_READ(aA, 0, 0, 3)
-#if RGBDFE_HAMMING_PIPE_ALT4
-    v16f acc0, acc1, acc2 = crow, acc3 = crow;
+    // QT = 4: four units per train tile (query tiles 0..3 of the wave), the accumulators alternate as above.  64 registers
+    // of query operands leave room for ONE A operand set, and only if the next tile's operand lands in the registers of
+    // the current one -- which the register allocator does not do by itself (it scatters the new values and spills the
+    // query operands).  So this stream reads LDS with its own ds_read_b128 (`a4[s]` is input and output of the statement:
+    // the same four registers) and counts its own waits:
+    //   * the tile's last unit reads the next tile's k-step s right behind its own MFMA of k-step s; the other three units
+    //     carry no read;
+    //   * LDS reads return in order, so the next tile's first unit waits for lgkmcnt(3 - s) in front of its MFMA of k-step
+    //     s -- nothing else in the loop counts on lgkmcnt (the stage loads are LDS-DMA: vmcnt); a fence behind every wait
+    //     keeps the MFMA behind it, and one between an MFMA and the read that replaces its operand keeps that order.
+    //     (The compiler folds neighbouring waits into the stricter one: lgkmcnt(2) and lgkmcnt(0) per tile in the ISA.)
+    // Unit q reduces unit q - 1 (q = 0: the previous tile's unit 3).
+    // There is no second C operand either (`c3` above; a changed `crow` would have to live beside the unchanged one).  The
+    // ragged tile is excluded in LDS instead: once its stage has been published, every row of it that does not take part
+    // is overwritten with the tile's FIRST row, which always takes part.  A copy has that row's distance and a larger row
+    // index, so its key is larger than the original's and it can never be the minimum.  One LDS read and one LDS write per
+    // thread and block, between the barrier that publishes the last stage and the next one (which comes before the last
+    // slot of any stage is read).
+#if RGBDFE_HAMMING_PIPE_DIAG & 2
+#define HP4_READ(BUF, SLOT, S) asm volatile("" : "+v"(a4[S]));
 #else
-    v16f acc0, acc1 = crow;
+#define HP4_READ(BUF, SLOT, S)                                                                                       \
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(a4[S]) : "v"(rd##BUF), "n"((SLOT) * 4096 + (S) * 1024) : "memory");
 #endif
-    float pend = 4.0e6f;  // acc1 = the row terms (>= 256), + 4e6: a phantom for the first unit's reduction slot
-    float b0, b1;
-    uint32_t st = 0;
-    HP_HALF_A(0)
-    for (;;) {
-      HP_HALF_B(0, 1, 2)
-      if (++st == n_stages) break;
-      HP_HALF_A(1)
-      HP_HALF_B(1, 2, 0)
-      if (++st == n_stages) break;
-      HP_HALF_A(2)
-      HP_HALF_B(2, 0, 1)
-      if (++st == n_stages) break;
-      HP_HALF_A(0)
+#define HP4_WAIT(N) __builtin_amdgcn_s_waitcnt(0xC07F | ((N) << 8)); HP_FENCE()   /* lgkmcnt(N) alone */
+#define HP4_A(S) op8(a4[S])
+    // (the tile bases are block-uniform: kept in scalar registers here, five vector registers less)
+#define HP4_BASE(SLOT) __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(HP_BASE(SLOT))))
+#define HP4_UNIT0(ACC, Q, C, PACC, PBEST, PBASE)                                                                     \
+      HP_MFMA(ACC, HP4_A(0), bq[Q][0], C)                                                                            \
+      HP_MFMA(ACC, HP4_A(1), bq[Q][1], ACC)                                                                          \
+      HP_EPI(PACC, PBEST, PBASE)                                                                                     \
+      HP_MFMA(ACC, HP4_A(2), bq[Q][2], ACC)                                                                          \
+      HP_MFMA(ACC, HP4_A(3), bq[Q][3], ACC)                                                                          \
+      HP_UNIT_SCHED0()                                                                                               \
+      HP_FENCE()
+#define HP4_TILE(C, PB, B, RSLOT, RBUF)                                                                              \
+      HP4_WAIT(3) HP_MFMA(acc0, HP4_A(0), bq[0][0], C)                                                               \
+      HP4_WAIT(2) HP_MFMA(acc0, HP4_A(1), bq[0][1], acc0)                                                            \
+      HP_EPI(acc1, best3, PB)                                                                                        \
+      HP4_WAIT(1) HP_MFMA(acc0, HP4_A(2), bq[0][2], acc0)                                                            \
+      HP4_WAIT(0) HP_MFMA(acc0, HP4_A(3), bq[0][3], acc0)                                                            \
+      HP_FENCE()                                                                                                     \
+      HP4_UNIT0(acc1, 1, C, acc0, best0, B)                                                                          \
+      HP4_UNIT0(acc0, 2, C, acc1, best1, B)                                                                          \
+      HP_MFMA(acc1, HP4_A(0), bq[3][0], C)                                                                           \
+      HP_FENCE() HP4_READ(RBUF, RSLOT, 0)                                                                            \
+      HP_MFMA(acc1, HP4_A(1), bq[3][1], acc1)                                                                        \
+      HP_FENCE() HP4_READ(RBUF, RSLOT, 1)                                                                            \
+      HP_EPI(acc0, best2, B)                                                                                         \
+      HP_MFMA(acc1, HP4_A(2), bq[3][2], acc1)                                                                        \
+      HP_FENCE() HP4_READ(RBUF, RSLOT, 2)                                                                            \
+      HP_MFMA(acc1, HP4_A(3), bq[3][3], acc1)                                                                        \
+      HP_FENCE() HP4_READ(RBUF, RSLOT, 3)                                                                            \
+      HP_FENCE()
+#define HP4_HALF_A(CUR, NXT)                                                                                         \
+    {                                                                                                                \
+      b0 = HP4_BASE(0); b1 = HP4_BASE(1);                                                                            \
+      HP_FENCE()                                                                                                     \
+      HP4_TILE(crow, pend, b0, 1, CUR)                                                                               \
+      HP4_TILE(crow, b0, b1, 2, CUR)                                                                                 \
+      HP_TURN()                                                                                                      \
+      if (has_ragged && st + 2u == n_stages) patch_ragged(lds##NXT);   /* the next stage is the last one */           \
     }
+#define HP4_HALF_B(CUR, NXT, NN)                                                                                     \
+    {                                                                                                                \
+      if (HP_LOADS && st + 2u < n_stages) load_stage(st + 2u, lds##NN);                                              \
+      const float b2 = HP4_BASE(2), b3 = HP4_BASE(3);                                                                \
+      HP_FENCE()                                                                                                     \
+      HP4_TILE(crow, b1, b2, 3, CUR)                                                                                 \
+      HP_FENCE()                                                                                                     \
+      HP4_TILE(crow, b2, b3, 0, NXT)                                                                                 \
+      pend = b3;                                                                                                     \
+    }
+    if constexpr (QT == 2) {
+      HP_READ(aA, 0, 0, 0) HP_READ(aA, 0, 0, 1) HP_READ(aA, 0, 0, 2) HP_READ(aA, 0, 0, 3)
 #if RGBDFE_HAMMING_PIPE_ALT4
-    HP_EPI(acc2, best0, pend)
-    HP_EPI(acc3, best1, pend)
+      v16f acc0, acc1, acc2 = crow, acc3 = crow;
 #else
-    HP_EPI(acc1, best1, pend)
+      v16f acc0, acc1 = crow;
 #endif
+      float pend = 4.0e6f;  // acc1 = the row terms (>= 256), + 4e6: a phantom for the first unit's reduction slot
+      float b0, b1;
+      uint32_t st = 0;
+      HP_HALF_A(0)
+      for (;;) {
+        HP_HALF_B(0, 1, 2)
+        if (++st == n_stages) break;
+        HP_HALF_A(1)
+        HP_HALF_B(1, 2, 0)
+        if (++st == n_stages) break;
+        HP_HALF_A(2)
+        HP_HALF_B(2, 0, 1)
+        if (++st == n_stages) break;
+        HP_HALF_A(0)
+      }
+#if RGBDFE_HAMMING_PIPE_ALT4
+      HP_EPI(acc2, best0, pend)
+      HP_EPI(acc3, best1, pend)
+#else
+      HP_EPI(acc1, best1, pend)
+#endif
+    } else {
+      // this lane's 16 bytes of (slot 0, k-step 0) in each stage buffer, as LDS addresses
+      const uint32_t rd0 = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)&lds0[0][0] + lane * 16u;
+      const uint32_t rd1 = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)&lds1[0][0] + lane * 16u;
+      const uint32_t rd2 = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)&lds2[0][0] + lane * 16u;
+      v4i a4[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+      auto patch_ragged = [&](uint4 (*buf)[256]) {   // (thread = one 16-byte piece of the tile: k-step, row half, row)
+        const uint32_t t = threadIdx.x;
+        if ((t & 31u) >= (nt_search & 31u)) buf[kPipeStage - 1][t] = buf[kPipeStage - 1][t & ~31u];
+      };
+      if (has_ragged && n_stages <= 2u) patch_ragged(n_stages == 1u ? lds0 : lds1);   // published by the barrier above
+      HP4_READ(0, 0, 0) HP4_READ(0, 0, 1) HP4_READ(0, 0, 2) HP4_READ(0, 0, 3)
+      v16f acc0, acc1 = crow;
+      float pend = 4.0e6f;  // (as above: the first unit reduces a phantom)
+      float b0, b1;
+      uint32_t st = 0;
+      HP4_HALF_A(0, 1)
+      for (;;) {
+        HP4_HALF_B(0, 1, 2)
+        if (++st == n_stages) break;
+        HP4_HALF_A(1, 2)
+        HP4_HALF_B(1, 2, 0)
+        if (++st == n_stages) break;
+        HP4_HALF_A(2, 0)
+        HP4_HALF_B(2, 0, 1)
+        if (++st == n_stages) break;
+        HP4_HALF_A(0, 1)
+      }
+      HP_EPI(acc1, best3, pend)
+    }
+#undef HP4_TILE
+#undef HP4_UNIT0
+#undef HP4_BASE
+#undef HP4_A
+#undef HP4_WAIT
+#undef HP4_READ
+#undef HP4_HALF_A
+#undef HP4_HALF_B
 #undef HP_HALF_A
 #undef HP_HALF_B
 #undef HP_TURN
 #undef HP_LOADS
 #undef HP_UNIT
+#undef HP_UNIT_X
 #undef HP_EPI
 #undef HP_BASE
 #undef HP_READ
   }
 
   uint32_t* kout = keys + ((size_t)pair * tsplit + split) * max_kp;
-  const uint32_t bests[2] = {best0, best1};
+  const uint32_t bests[4] = {best0, best1, best2, best3};
 #pragma unroll
-  for (int t = 0; t < kQT; ++t) {
+  for (int t = 0; t < QT; ++t) {
     uint32_t bb = bests[t];
     bb = min(bb, (uint32_t)__shfl_xor((int)bb, 32));
     const float b = __uint_as_float(bb);
-    const uint32_t qi = qblock * kQueriesPerBlock + (wave * kQT + (uint32_t)t) * 32u + (lane & 31u);
+    const uint32_t qi = qblock * kQPB + (wave * QT + (uint32_t)t) * 32u + (lane & 31u);
     if (half == 0 && qi < nq) {
       uint32_t key = kNoMatchKey;
       if (RGBDFE_HAMMING_PIPE_DIAG ? b < -1.0f : b < 1024.0f) {  // real keys: 2*hd + row / 2^14 < 514; phantoms and excluded rows are >= 2^22
@@ -643,22 +788,53 @@ void launch_hamming_expand(const uint32_t* node_rows, uint32_t* slab, uint32_t s
   hipLaunchKernelGGL(hamming_expand_kernel, dim3(tiles), dim3(256), 0, stream, node_rows, dst, n);
 }
 
-HammingGeometry hamming_mfma_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_t max_nt, uint32_t key_planes_capacity) {
-  HammingGeometry g{0, 1};
+// The wide (512-query) form of the pipelined kernel halves the blocks of a batch and doubles their length.  The automatic
+// choice takes it only where that costs nothing: the train rows are not split (a batch that needs splits to fill the chip has
+// no blocks to spare: live SLAM, ~20 pairs), and the batch is still at least kWideMinBlocksPerSlot blocks deep on every one of
+// the chip's block slots (256 CUs x 3 blocks of 48 KB LDS).  A launch ends with a partly idle chip for about one block's
+// length; a wide block is two narrow ones long, so the wide form adds one narrow block's length of tail to a launch that is
+// 2 x depth of them long: 1 / (2 x 10) = 5 % at the threshold in the worst case (a last round of one block), about half of
+// that on average and less for deeper batches -- against the 3-4 % the wide form gains where it was measured, at 8000 blocks
+// of equal length.  Below the threshold nothing is known to be gained, so nothing changes there.
+constexpr uint32_t kHammingBlockSlots = 256u * 3u;
+constexpr uint32_t kWideMinBlocksPerSlot = 10u;
+
+// pipe_wide: -1 = choose (the pipelined kernel only), 0 = 256-query blocks, 1 = 512-query blocks
+HammingGeometry hamming_mfma_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_t max_nt, uint32_t key_planes_capacity,
+                                      int pipe_wide) {
+  HammingGeometry g{0, 1, 0};
   if (n_pairs == 0 || max_nq == 0) return g;
-  g.qblocks = (max_nq + kQueriesPerBlock - 1) / kQueriesPerBlock;
-  // small batches (live SLAM: ~20 pairs per frame) split the train tiles over several blocks, one key plane each
-  const uint32_t blocks1 = n_pairs * g.qblocks;
   const uint32_t ttiles = (max_nt + 31u) / 32u;
-  if (blocks1 < 1024 && ttiles > kStage) {
-    uint32_t tsplit = (1024 + blocks1 - 1) / blocks1;
-    const uint32_t max_split = (ttiles + kStage - 1) / kStage;  // at least one LDS stage per block
-    if (tsplit > max_split) tsplit = max_split;
-    if (tsplit > 32) tsplit = 32;
-    const uint32_t fit = key_planes_capacity / n_pairs;
-    if (tsplit > fit) tsplit = fit;
-    if (tsplit < 1) tsplit = 1;
-    g.tsplit = tsplit;
+  auto shape = [&](uint32_t queries_per_block) {
+    HammingGeometry h{(max_nq + queries_per_block - 1u) / queries_per_block, 1, 0};
+    // small batches (live SLAM: ~20 pairs per frame) split the train tiles over several blocks, one key plane each
+    const uint32_t blocks1 = n_pairs * h.qblocks;
+    if (blocks1 < 1024 && ttiles > kStage) {
+      uint32_t tsplit = (1024 + blocks1 - 1) / blocks1;
+      const uint32_t max_split = (ttiles + kStage - 1) / kStage;  // at least one LDS stage per block
+      if (tsplit > max_split) tsplit = max_split;
+      if (tsplit > 32) tsplit = 32;
+      const uint32_t fit = key_planes_capacity / n_pairs;
+      if (tsplit > fit) tsplit = fit;
+      if (tsplit < 1) tsplit = 1;
+      h.tsplit = tsplit;
+    }
+    return h;
+  };
+  g = shape(kQueriesPerBlock);
+  if (pipe_wide < 0) {
+#if RGBDFE_HAMMING_PIPE_QT == 4
+    pipe_wide = 1;
+#elif RGBDFE_HAMMING_PIPE_QT == 2
+    pipe_wide = 0;
+#else
+    const uint64_t wide_blocks = (uint64_t)n_pairs * ((max_nq + 2u * kQueriesPerBlock - 1u) / (2u * kQueriesPerBlock));
+    pipe_wide = g.tsplit == 1u && wide_blocks >= (uint64_t)kHammingBlockSlots * kWideMinBlocksPerSlot ? 1 : 0;
+#endif
+  }
+  if (pipe_wide > 0) {
+    g = shape(2u * kQueriesPerBlock);
+    g.wide = 1;
   }
   return g;
 }
@@ -674,18 +850,21 @@ uint32_t launch_hamming_mfma(const uint32_t* slab, const PairWork* work, uint32_
 #define RGBDFE_LAUNCH_HM(M, S)                                                                                   \
   hipLaunchKernelGGL((hamming_mfma_kernel<M, S>), dim3(grid), dim3(kThreads), 0, stream, s4, work, keys, max_kp, \
                      tiles_per_slot, n_pairs, qblocks, tsplit)
-  if (mode == 3) {
-    if (tsplit > 1)
-      hipLaunchKernelGGL((hamming_mfma_pipe_kernel<true>), dim3(grid), dim3(kThreads), 0, stream, s4, work, keys, max_kp,
-                         tiles_per_slot, n_pairs, qblocks, tsplit);
-    else
-      hipLaunchKernelGGL((hamming_mfma_pipe_kernel<false>), dim3(grid), dim3(kThreads), 0, stream, s4, work, keys, max_kp,
-                         tiles_per_slot, n_pairs, qblocks, tsplit);
+#define RGBDFE_LAUNCH_HP(QT, S)                                                                                        \
+  hipLaunchKernelGGL((hamming_mfma_pipe_kernel<QT, S>), dim3(grid), dim3(kThreads), 0, stream, s4, work, keys, max_kp, \
+                     tiles_per_slot, n_pairs, qblocks, tsplit)
+  if (mode == 3 || mode == 4) {   // the geometry says which form (mode 4's is always wide, an explicit mode 3's never)
+    if (geom.wide) {
+      if (tsplit > 1) RGBDFE_LAUNCH_HP(4, true); else RGBDFE_LAUNCH_HP(4, false);
+    } else {
+      if (tsplit > 1) RGBDFE_LAUNCH_HP(2, true); else RGBDFE_LAUNCH_HP(2, false);
+    }
   } else if (mode == 2) {
     if (tsplit > 1) RGBDFE_LAUNCH_HM(2, true); else RGBDFE_LAUNCH_HM(2, false);
   } else {
     if (tsplit > 1) RGBDFE_LAUNCH_HM(1, true); else RGBDFE_LAUNCH_HM(1, false);
   }
+#undef RGBDFE_LAUNCH_HP
 #undef RGBDFE_LAUNCH_HM
   return tsplit;
 }

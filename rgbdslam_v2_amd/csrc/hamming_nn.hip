@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kHamThreads) void hamming_nn_kernel(
 }
 
 HammingGeometry hamming_nn_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_t max_nt, uint32_t key_planes_capacity) {
-  HammingGeometry g{0, 1};
+  HammingGeometry g{0, 1, 0};
   if (n_pairs == 0 || max_nq == 0) return g;
   g.qblocks = (max_nq + kQueriesPerBlock - 1) / kQueriesPerBlock;
   // Enough blocks to fill 256 CUs several times over; split the train rows when the

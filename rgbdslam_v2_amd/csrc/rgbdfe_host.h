@@ -176,7 +176,10 @@ struct rgbdfe_ctx {
   hipEvent_t orb_describe_done[OrbWorkspace::kSets] = {};  // frame f's description has left its image set
   bool feature_min_depth = false;  // "use_feature_min_depth" (parameter_server.cpp:90): rgbdfe_set_feature_min_depth
   bool sift_fast = true;       // sift_match.hip's float keys where a pair qualifies (RGBDFE_SIFT_FAST_KEYS=0: never)
-  int hamming_mode = RGBDFE_HAMMING_MODE_DEFAULT;   // rgbdfe.h: 0 = popcount kernel (hamming_nn.hip), 1 / 2 / 3 = fp4 MFMA kernels (hamming_mfma.hip)
+  int hamming_mode = RGBDFE_HAMMING_MODE_DEFAULT;   // rgbdfe.h: 0 = popcount kernel (hamming_nn.hip), 1 / 2 / 3 / 4 = fp4 MFMA kernels (hamming_mfma.hip)
+  int hamming_wide = -1;       // mode 3: -1 = 256- or 512-query blocks per batch (hamming_mfma_geometry), 0 / 1 = always that one
+                               // (RGBDFE_HAMMING_WIDE at rgbdfe_create; rgbdfe_set_hamming_mode(3) sets 0, mode 4 is always wide)
+  int hamming_wide_last = -1;  // the latest Hamming launch: 1 = 512-query blocks, 0 = any other kernel, -1 = none yet
   // Batches run on kLanes internal HIP streams ("lanes"), each with its own keys / results
   // staging, so that batch k+1's Hamming kernel fills the SIMDs that batch k's RANSAC tail
   // leaves idle.  The pair lists go through a ring of pinned buffers so the host can prepare
@@ -601,6 +604,7 @@ int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all, double observability_threshold, double* quality);
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);
 int rgbdfe_set_hamming_mode(rgbdfe_ctx* ctx, int32_t mode);
+int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx);
 int rgbdfe_set_profiling(rgbdfe_ctx* ctx, int enable);
 int rgbdfe_get_kernel_time(rgbdfe_ctx* ctx, int which, double* total_ms, int64_t* launches, int64_t* pairs);
 int rgbdfe_reset_kernel_time(rgbdfe_ctx* ctx);

@@ -113,9 +113,15 @@ class FrontEnd:
 
     def set_hamming_mode(self, mode: int):
         """0 = popcount kernel, 1 = fp4 MFMA kernel, 2 = MFMA kernel with the VALU row term, 3 = the MFMA kernel as a
-        software pipeline inside every wave (include/rgbdfe.h; _lib.DEFAULT_HAMMING_MODE is what a new context uses)."""
+        software pipeline inside every wave with 256 queries per block, 4 = that kernel with 512 queries per block
+        (include/rgbdfe.h; _lib.DEFAULT_HAMMING_MODE is what a new context uses: mode 3 with the block width chosen per batch)."""
         self._check(self._L.rgbdfe_set_hamming_mode(self._ctx, mode))
         self._hamming_mode = int(mode)
+
+    @property
+    def hamming_wide_last(self) -> int:
+        """1 = the latest Hamming launch ran the pipelined kernel's 512-query blocks, 0 = it did not, -1 = none yet."""
+        return int(self._L.rgbdfe_hamming_wide_last(self._ctx))
 
     @property
     def hamming_mode(self) -> int:
@@ -127,7 +133,7 @@ class FrontEnd:
                 m = int(os.environ.get("RGBDFE_HAMMING_MODE", str(DEFAULT_HAMMING_MODE)))
             except ValueError:
                 m = DEFAULT_HAMMING_MODE
-            m = m if 0 <= m <= 3 else DEFAULT_HAMMING_MODE
+            m = m if 0 <= m <= 4 else DEFAULT_HAMMING_MODE
         return 0 if self.cfg.max_keypoints > 32768 else m
 
     def group_submit_us(self) -> float:

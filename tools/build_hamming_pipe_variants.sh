@@ -7,6 +7,10 @@ build() {  # name, extra flags
   OBJS=$(ls *.o | grep -v "^hamming_mfma.o$" | grep -v prof | grep -v _wd | tr '\n' ' ')
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../librgbdfe_hp_$1.so $OBJS /tmp/hp_$1.o
 }
+# HAMMING_QT: the automatic choice between 256-query blocks (two query tiles per wave) and 512-query blocks (four) pinned
+# to one of them -- A/B of the two forms at every batch size without touching the mode
+build qt2 "-DRGBDFE_HAMMING_PIPE_QT=2"
+build qt4 "-DRGBDFE_HAMMING_PIPE_QT=4"
 build w2 "-DRGBDFE_HAMMING_PIPE_WAVES=2"
 build burst "-DRGBDFE_HAMMING_PIPE_BURST=1"
 build alt4 "-DRGBDFE_HAMMING_PIPE_ALT4=1 -DRGBDFE_HAMMING_PIPE_WAVES=2"
