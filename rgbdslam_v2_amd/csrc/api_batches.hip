@@ -99,9 +99,8 @@ void drain_pending(rgbdfe_ctx* ctx) {
   ctx->pending.clear();
 }
 
-// Decides whether a batch of n pairs takes the record / replay latency path and makes sure the lane's record buffer
-// is large enough (falls back to the one-wave-per-pair kernel when it cannot be allocated).
-// the error pool of the select+RANSAC launches of a lane: one region per wave of the largest grid
+// the error pool of the select+RANSAC launches of a lane: one region per pair of the largest batch (the one-wave kernel,
+// the result waves and the g2o refinement each run one wave per pair; the refinement kernel keeps its errors in LDS)
 int ensure_ec_pool(rgbdfe_ctx* ctx, rgbdfe_ctx::Lane& lane, size_t regions, hipStream_t stream) {
   if (regions <= lane.ec_regions) return RGBDFE_OK;
   HIP_TRY(ctx, hipStreamSynchronize(stream));
@@ -112,17 +111,19 @@ int ensure_ec_pool(rgbdfe_ctx* ctx, rgbdfe_ctx::Lane& lane, size_t regions, hipS
   lane.ec_regions = regions;
   return RGBDFE_OK;
 }
+// Decides whether a batch of n pairs takes the record / replay latency path and makes sure the lane's record buffer
+// is large enough (falls back to the one-wave-per-pair kernel when it cannot be allocated).
 int want_latency_path(rgbdfe_ctx* ctx, rgbdfe_ctx::Lane& lane, int32_t n, hipStream_t stream, bool* use, int* chunk_out,
                       PhasePlan* plan) {
   const size_t need_recs = (size_t)n * (size_t)(ctx->rc.ransac_iterations > 0 ? ctx->rc.ransac_iterations : 0);
   const bool force_phases = ctx->latency_chunk_iters < 0;  // testing aid: the phased schedule for any batch size
   const int chunk_cfg = force_phases ? -ctx->latency_chunk_iters : ctx->latency_chunk_iters;
-  // automatic: small batches want many short waves (latency), large ones long waves (a wave refills its 7 slots from
-  // its own share of iterations, so longer shares keep the batched rounds fuller); tools/bench_batch_sweep.py
+  // `chunk` is scheduling, not memory: launch_record_replay derives from it the share of a pair's iteration range that one
+  // unit of the refinement launch records (small batches want many short shares for latency, large ones long shares;
+  // tools/bench_batch_sweep.py).  That includes the kMaxEcRegions loop below, which lengthens the shares of very large
+  // batches; the error pool is sized by pairs alone (the end of this function).
   int chunk = chunk_cfg > 0 ? chunk_cfg : (n <= 64 ? 4 : (n <= 640 ? 7 : (n <= 1280 ? 14 : 28)));
-  // every recording wave owns a region of the error pool: keep the largest grid (a phase is at most all iterations)
-  // within kMaxEcRegions by recording more iterations per wave
-  // (a batch of more than kMaxEcRegions pairs cannot get below one region per pair: it takes the one-wave kernel)
+  // (a batch of more than kMaxEcRegions pairs takes the one-wave kernel)
   const int I_all = ctx->rc.ransac_iterations > 0 ? ctx->rc.ransac_iterations : 0;
   const bool too_many_pairs = (size_t)n > kMaxEcRegions;
   while (!too_many_pairs && chunk < I_all && (size_t)n * (size_t)((I_all + chunk - 1) / chunk) > kMaxEcRegions) ++chunk;
@@ -144,22 +145,10 @@ int want_latency_path(rgbdfe_ctx* ctx, rgbdfe_ctx::Lane& lane, int32_t n, hipStr
     lane.d_walk = nullptr;
     latency = false;
   }
-  // Up to 256 pairs one phase (full speculation, lowest latency); above, four phases so that recording stops
-  // where the reference's bookkeeping stops iterating.
+  // Up to 256 pairs one phase (full speculation, lowest latency); above, up to four windows per pair so that recording
+  // stops where the reference's bookkeeping stops iterating (what else was measured for 257 .. 1280 pairs).
   const int I = ctx->rc.ransac_iterations;
-  static const int env_phases = getenv("RGBDFE_PHASES") ? atoi(getenv("RGBDFE_PHASES")) : 0;  // experiments only
-  // (round 6, measured and kept as a switch only -- RGBDFE_MID_PLAN: a phased plan's unit is a whole pair whose windows follow each
-  // other inside one workgroup; with 257 .. 1280 pairs, fewer than the launch has unit buffers, a HARD pair -- one that needs
-  // nearly all of its iterations and passes the pre-screen with most of them, 0.002 z^2 -- is one workgroup's chain of 160
-  // refinements while others idle: 512 such pairs take 2.7 ms phased and 1.8 ms with full speculation in shares (= 1).  But an
-  // EASY pair, the usual case between neighbouring frames, ends its loop inside the first 14 iterations and speculation records
-  // all 200: the front-end sub-record's 2030 pairs, matched as two halves, take 6.3 ms instead of 3.3.  Two windows, [0, 14) and
-  // the rest (= 2), help neither.  Default 0: phased from 257 pairs on, as before.)
-  static const int mid_plan = getenv("RGBDFE_MID_PLAN") ? atoi(getenv("RGBDFE_MID_PLAN")) : 0;
-  const bool mid = n > 256 && n <= 1280 && !force_phases && env_phases == 0;
-  if ((n <= 256 && !force_phases) || env_phases == 1 || (mid && mid_plan == 1)) { plan->n_phases = 1; plan->ends[0] = I; }
-  else if (mid && mid_plan == 2 && I > 14) { plan->n_phases = 2; plan->ends[0] = 14; plan->ends[1] = I; }
-  else if (env_phases == 2) { plan->n_phases = 2; plan->ends[0] = ((I * 7 / 20) / 7) * 7 > 0 ? ((I * 7 / 20) / 7) * 7 : I; plan->ends[1] = I; if (plan->ends[0] >= I) plan->n_phases = 1; }
+  if (n <= 256 && !force_phases) { plan->n_phases = 1; plan->ends[0] = I; }
   else {
     const int cand[4] = {14, ((I * 7 / 20) / 7) * 7, ((I * 14 / 20) / 7) * 7, I};
     int k = 0, last = 0;
@@ -168,20 +157,8 @@ int want_latency_path(rgbdfe_ctx* ctx, rgbdfe_ctx::Lane& lane, int32_t n, hipStr
     plan->n_phases = k;
   }
   *use = latency;
-  size_t regions = (size_t)n;
-  if (latency) {
-    int begin = 0;
-    for (int p = 0; p < plan->n_phases; ++p) {
-      size_t chunks = (size_t)((plan->ends[p] - begin + chunk - 1) / chunk);
-      if (plan->n_phases > 2 && p == 1)  // launch_record_replay: the second phase covers all that is left, two sub-grids
-        chunks += (size_t)((I - begin + 63) / 64);
-      if ((size_t)n * chunks > regions) regions = (size_t)n * chunks;
-      begin = plan->ends[p];
-    }
-  }
-  // recording grids: 8 segments x ceil(n / 8) pairs x shares per pair (one region per launched wave)
-  regions = regions / (size_t)(n > 0 ? n : 1) * (((size_t)n + 7) / 8 * 8);
-  return ensure_ec_pool(ctx, lane, regions + 8, stream);
+  // one region per pair, for the one-wave kernel as for the result waves
+  return ensure_ec_pool(ctx, lane, ((size_t)n + 7) / 8 * 8 + 8, stream);
 }
 
 // The Hamming stage of an ORB batch: the fp4 MFMA kernel by default, the popcount kernel when asked for
@@ -266,7 +243,7 @@ int enqueue_pairs(rgbdfe_ctx* ctx, const int32_t* qids, const int32_t* tids, int
   // Everything that can fail without leaving work behind (scratch allocations, the schedule) comes first; the ticket
   // is committed only once the batch is on its stream.
   // A batch whose record / replay scratch would be too large (pairs x iterations records, one error-pool region per
-  // recording wave) is run as several pieces, one after the other on the same stream with the same scratch: every piece
+  // pair) is run as several pieces, one after the other on the same stream with the same scratch: every piece
   // takes the record / replay schedule.  (The one-wave-per-pair kernel runs only when it is asked for,
   // rgbdfe_set_latency_mode(ctx, 0, 0).)
   int32_t piece = n;

@@ -697,14 +697,4 @@ __device__ __forceinline__ void walk_records(WalkRegs& w, int recorded_end, int 
 #endif
 constexpr int kClass2Num = RGBDFE_CLASS2_NUM, kClass2Den = RGBDFE_CLASS2_DEN;
 
-// The class a pair is treated as from the second phase on.  WalkState::speculate: 0 = `it` has jumped ahead, 1 = no
-// jump and mostly valid hypotheses, 2 = no jump and junk-heavy.  Class 1 behaves like class 0 (phase by phase) unless the
-// batch has very few such pairs (walk[n_pairs].state counts them, < 1/64 of the batch): then keeping the third and fourth
-// phase's launches alive for a handful of long waves costs more than recording those pairs to the end like class 2.
-__device__ __forceinline__ int effective_class(const WalkState* __restrict__ walk, uint32_t pair, uint32_t n_pairs) {
-  const int c = walk[pair].speculate;
-  if (c != 1) return c;
-  return ((uint32_t)walk[n_pairs].state * 64u <= n_pairs) ? 2 : 0;
-}
-
 }  // namespace rgbdfe

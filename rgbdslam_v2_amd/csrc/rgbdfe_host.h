@@ -195,7 +195,7 @@ struct rgbdfe_ctx {
     size_t recs_capacity = 0;               // in records
     WalkState* d_walk = nullptr;            // record / replay: per pair progress (max_pairs)
     PairPrep* d_prep = nullptr;             // selected matches of every pair of the batch (max_pairs)
-    double* d_ec = nullptr;                 // error pool of select+RANSAC: one region per launched wave
+    double* d_ec = nullptr;                 // error pool of select+RANSAC: one region per pair of a piece
     size_t ec_regions = 0;
     uint32_t* d_keys = nullptr;             // max_pairs x max_kp
     rgbdfe_match_result* d_results = nullptr;  // staging for the host-output entry points
@@ -364,7 +364,7 @@ using namespace rgbdfe_host;
 // ---- batch machinery (api_batches.hip)
 namespace rgbdfe_host {
 struct PhasePlan { int ends[4]; int n_phases; };
-constexpr size_t kMaxEcRegions = (size_t)1 << 16;  // 1.2 GB
+constexpr size_t kMaxEcRegions = (size_t)1 << 16;  // pairs of a record / replay piece at most (1.2 GB of error pool)
 int fail(rgbdfe_ctx* ctx, int code, const std::string& msg);
 void fill_ransac_const(rgbdfe_ctx* ctx);
 int validate_params(rgbdfe_ctx* ctx, const rgbdfe_params& p);

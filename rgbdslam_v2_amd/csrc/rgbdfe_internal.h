@@ -90,37 +90,29 @@ struct alignas(16) PairPrep {
   uint32_t fast_alpha;                    // every weight inside the window of the unscaled float division
   uint32_t pad;
 };
-// per-pair progress of the record / replay schedule: the reference's in-order bookkeeping (node.cpp:1171-1190),
-// resumed phase by phase by replay_walk_kernel
+// per-pair progress of the record / replay schedule: the reference's in-order bookkeeping (node.cpp:1171-1190) as far as
+// the refinement kernel (ransac_split.hip) had to run it -- between two windows of a pair of a phased plan; a pair recorded
+// in one window, or in shares, keeps the start values the hypothesis kernel wrote.  The result waves
+// (select_ransac_kernel<kReplay>) resume the walk at real_iterations and run it to the end of the recorded range.
+// walk[n_pairs] holds the batch's counters instead (zeroed by the hypothesis kernel; `it` = the refinement launch's unit
+// counter).
 struct WalkState {
   int32_t state;             // >= 0: upper bound of the iterations that may still be needed; < 0: the loop has ended
   int32_t it, real_iterations, valid_iterations;
   int32_t best_idx;          // iteration whose record is the best hypothesis so far, -1 = none
   int32_t best_n;
   float rmse;
-  int32_t speculate;         // class of the pair, set by the walk of the first phase: 0 = `it` has jumped ahead (a hypothesis
-                             // with more than half of the matches as inliers: the loop may end early); 1 = no jump yet: the
-                             // pair will most likely run all its iterations, the next recording launch records ALL of them;
-                             // 2 = ... and at most 1/4 of the iterations produced a refined hypothesis ("junk-heavy")
+  int32_t speculate;         // end of the pair's recorded range: the result wave walks [real_iterations, speculate)
 };
-// parameters of one record / replay phase (select_ransac.hip)
+// what the one-wave kernel and the result waves (select_ransac_kernel<kWhole / kReplay>, select_ransac.hip) are given
 struct RecordPlan {
-  IterRec* recs = nullptr;   // [pair][iteration]
-  IterSum* sums = nullptr;   // [pair][iteration], behind the records in the same allocation
-  WalkState* walk = nullptr; // [pair]
-  uint32_t n_chunks = 1;     // recording waves per pair in this phase
-  int chunk_iters = 0;       // iterations per recording wave
-  int phase_begin = 0, phase_end = 0;
-  int spec_end = 0;          // the launch's waves cover [phase_begin, spec_end); pairs of class 1 / 2 record beyond phase_end
-  uint32_t n_chunks_b = 0;   // sub-grid B (class-2 pairs): recording waves per pair, in shares of chunk_iters_b iterations
-  int chunk_iters_b = 0;
-  int n_phases_total = 0;    // phases of the whole plan
-  const PairPrep* prep = nullptr;  // [pair], every mode
-  double* ec_pool = nullptr;  // every mode: select_ransac_ec_region_bytes() per launched wave (the inlier errors of
-                              // a refinement round's scorings, read back lane = slot by the sequential error sums)
-  // result waves of the split path: the walk over [WalkState::real_iterations, WalkState::speculate) is theirs
-  int final_walk = 0;
-  const uint64_t* vmask = nullptr;  // [pair][vmask_words]: SplitPlan::vmask
+  IterRec* recs = nullptr;   // [pair][iteration] (kReplay)
+  IterSum* sums = nullptr;   // [pair][iteration], behind the records in the same allocation (kReplay)
+  WalkState* walk = nullptr; // [pair] (kReplay)
+  const PairPrep* prep = nullptr;  // [pair]
+  double* ec_pool = nullptr;  // select_ransac_ec_region_bytes() per pair (the inlier errors of a refinement round's
+                              // scorings, read back lane = slot by the sequential error sums)
+  const uint64_t* vmask = nullptr;  // [pair][vmask_words]: SplitPlan::vmask (kReplay)
   int vmask_words = 0;
 };
 size_t select_ransac_ec_region_bytes();

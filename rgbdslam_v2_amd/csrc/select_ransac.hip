@@ -13,7 +13,9 @@
 //                       hd, wave prefix scan, then a stable placement pass that ranks equal-hd lanes of a 64-query
 //                       chunk with __ballot bit-matching (SIFT: the head of the list sift_sort_kernel ordered); the
 //                       matched points become 7-word records (from.xyz, to.xyz, weight) in the pair's PairPrep block.
-//   select_ransac_kernel<MODE>  the RANSAC work (12.9 KB LDS, 168 VGPRs: 12 waves per CU), see MODE below:
+//   select_ransac_kernel<MODE>  (MODE: see below) kReplay: the result wave of a pair whose iterations ransac_split.hip
+//                       has recorded.  kWhole: a pair's whole RANSAC work in one wave (12.9 KB LDS, 168 VGPRs: 12 waves
+//                       per CU):
 //     * hypothesis generation: LANE = RANSAC ITERATION.  64 iterations' 4-point samples, weighted fits and 3x3
 //       Jacobi SVDs are computed at once (the counter-based generator makes iteration k's sample a pure function
 //       of k, D1);
@@ -26,7 +28,7 @@
 //       side by side from the wave's rows of the error pool;
 //     * refits (per round): the PCL weighted-mean recurrences of all active slots share one 63-lane loop (9 state
 //       elements per slot), followed by one batched SVD (LANE = SLOT).
-//   replay_walk_kernel  the reference's in-order bookkeeping (`it += 10/20`, the 80 % exit) over recorded iterations.
+//   g2o_refine_kernel   the optional two-view refinement of a pair's result (node.cpp:1222-1268).
 //   The float/double operation order is the oracle's (oracle/rgbd_oracle.c), which restates the reference and is
 //   pinned on the reference's own compiled code (oracle/_ref/libref_ransac.so): sequential weighted-mean recurrence,
 //   sequential error sum.  Compiled with -ffp-contract=off the results are bit-identical to the CPU restatement, so
@@ -129,8 +131,6 @@ struct __attribute__((aligned(16))) RansacLds {
 // Optional phase timers (librgbdfe_prof.so, -DRGBDFE_PROFILE_PHASES): wall cycles per phase are
 // written over the head of all_q of each result.  Never enabled in the product build.
 #ifdef RGBDFE_PROFILE_PHASES
-// totals over the recording waves of all launches since the last reset (slot 16 = waves); rgbdfe_debug_phase_totals
-__device__ unsigned long long g_phase_totals[24];
 #define PH_DECL uint64_t ph_t0 = __builtin_readcyclecounter(); uint64_t ph[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #define PH_MARK(i) { uint64_t ph_t1 = __builtin_readcyclecounter(); ph[i] += ph_t1 - ph_t0; ph_t0 = ph_t1; }
 #define PH_COUNT(i) { ph[i] += 1; }
@@ -474,15 +474,16 @@ __global__ __launch_bounds__(kSortThreads) void sift_sort_kernel(uint16_t* __res
   }
 }
 
-// MODE selects what a wave does with a pair's RANSAC iterations ("record / replay"):
-//   kWhole   the whole pair: windows of iterations refined side by side, replayed in order (one wave per pair)
-//   kRecord  a share of the iterations of a phase: refine them (7 slots, refilled as iterations finish) and write each
-//            iteration's outcome (IterRec) to memory -- several waves share one pair; no bookkeeping, no result
-//   kReplay  the result of a pair whose in-order bookkeeping replay_walk_kernel has run over the records: adopt the best
-//            record, the identity fallback, the result POD
-// kRecord + replay_walk_kernel + kReplay give the same result as kWhole (an iteration's refinement is a pure function of
-// its index, D1) with the refinement work of one pair spread over many waves.
-constexpr int kWhole = 0, kRecord = 1, kReplay = 2;
+// MODE selects what a wave does for its pair ("record / replay"):
+//   kWhole   the whole pair: windows of iterations refined side by side, replayed in order.  The library's path when it is
+//            asked for (rgbdfe_set_latency_mode(ctx, 0, 0)) or the record buffer cannot be allocated, and the byte reference
+//            of the tests
+//   kReplay  the result of a pair whose iterations the hypothesis + refinement kernels (ransac_split.hip) have recorded:
+//            the rest of the in-order bookkeeping over the records, adopt the best record, the identity fallback, the
+//            result POD
+// Recording + kReplay give the same result as kWhole (an iteration's refinement is a pure function of its index, D1) with
+// the refinement work of one pair spread over many waves.
+constexpr int kWhole = 0, kReplay = 1;
 
 // ---------------------------------------------------------------------------------
 // Once per pair, before any select+RANSAC wave: the <= max_matches strongest matches in the reference's order
@@ -665,58 +666,14 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) v
     const PairWork* __restrict__ work, rgbdfe_match_result* __restrict__ results, uint32_t n_pairs,
     const RansacConst rc, const RecordPlan plan) {
   __shared__ RansacLds lds;
-  // Recording waves: the workgroups of a launch go round-robin over the 8 XCDs, each with its own L2.  The grid is
-  // walked in 8 contiguous segments, segment = blockIdx % 8, and a segment owns a contiguous range of pairs, so that the
-  // waves sharing a pair (its PairPrep block, its records) run on one XCD.  The long shares of sub-grid B are ordered
-  // share-major inside a segment (share 0 of all its pairs, then share 1, ...): consecutive workgroups -- which the
-  // dispatcher spreads over the CUs -- then do the same kind of work instead of clustering a pair's long waves on a CU.
-  // A recording launch has two sub-grids per pair: n_chunks shares of chunk_iters iterations (sub-grid A) and n_chunks_b
-  // shares of a whole hypothesis batch (sub-grid B; only the second phase of a phased plan has one).  Which sub-grid
-  // works for a pair, and how far, is the pair's class:
-  //   WalkState::speculate 0  the first phase has moved `it` ahead (a hypothesis with > 50 % inliers): the loop may
-  //                           end early -> sub-grid A up to the phase's nominal end, phase by phase;
-  //                           (also: most iterations give a refined hypothesis, more than 9/14 of them -- such a pair
-  //                           finds its > 50 % hypothesis soon: recording ahead of the walk would be wasted)
-  //                        2  no jump so far and at most 9/14 of the iterations gave a refined hypothesis: the pair will
-  //                           most likely run all its iterations -> sub-grid B records ALL that is left at once, in long
-  //                           shares and with the hypothesis pre-screen (no further phases, no launch tails for it).
-  //                        (a class "record all that is left, in short shares and without the pre-screen" was measured
-  //                           and is slower than class 0 for the pairs it would apply to)
-  const uint32_t per_pair = plan.n_chunks + plan.n_chunks_b;
-  const uint32_t pps = (n_pairs + 7u) / 8u;  // pairs per segment
-  const uint32_t seg = blockIdx.x % 8u, in_seg = blockIdx.x / 8u;
-  // sub-grid A first, pair-major (a pair's short shares next to each other: its PairPrep block is read once into L2 and
-  // the ordinary phases keep the locality they were tuned with); then sub-grid B, share-major
-  const uint32_t units_a = pps * plan.n_chunks;
-  const bool in_b = MODE == kRecord && in_seg >= units_a;
-  const uint32_t pair = MODE != kRecord ? blockIdx.x
-                        : seg * pps + (in_b ? (in_seg - units_a) % pps : (plan.n_chunks ? in_seg / plan.n_chunks : 0u));
-  const uint32_t in_pair = MODE != kRecord ? 0u
-                           : (in_b ? plan.n_chunks + (in_seg - units_a) / pps : (plan.n_chunks ? in_seg % plan.n_chunks : 0u));
-  if (MODE == kRecord && (in_pair >= per_pair || pair >= seg * pps + pps)) return;
-  const bool sub_b = MODE == kRecord && in_pair >= plan.n_chunks;
-  const uint32_t unit = sub_b ? in_pair - plan.n_chunks : in_pair;  // share index inside the pair's sub-grid
+  const uint32_t pair = blockIdx.x;
   if (pair >= n_pairs) return;
-  // record / replay bookkeeping: walk[pair].state >= 0 is an upper bound of the iterations the pair can still need,
-  // < 0 means its loop has ended
-  const int pair_state = MODE != kRecord ? 0 : (plan.phase_begin == 0 ? rc.ransac_iterations : plan.walk[pair].state);
-  if (MODE == kRecord && pair_state < 0) return;
-  const int pair_class = (MODE == kRecord && plan.phase_begin != 0) ? effective_class(plan.walk, pair, n_pairs) : 0;
-  if (MODE == kRecord && (pair_class == 2) != sub_b) return;  // the other sub-grid works for this pair
-  const int my_chunk_iters = sub_b ? plan.chunk_iters_b : plan.chunk_iters;
-  const int recorded_end = MODE == kRecord ? min(sub_b ? plan.spec_end : plan.phase_end, pair_state) : 0;
-  // the pre-screen pays where many hypotheses are junk: for the pairs the first phase's walk has put into class 2 (the
-  // first phase itself, 14 of 200 iterations, runs without it: a pair of mostly valid hypotheses would only pay for it)
-  const bool prescreen = MODE != kRecord || pair_class == 2 || plan.n_phases_total == 1;
-  const int k_begin = MODE == kRecord ? plan.phase_begin + (int)unit * my_chunk_iters : 0;
-  const int k_end = MODE == kRecord ? min(k_begin + my_chunk_iters, recorded_end) : 0;
-  if (MODE == kRecord && k_begin >= k_end) return;  // nothing of this chunk is needed (any more)
   IterRec* __restrict__ rec_pair = MODE == kWhole ? nullptr : plan.recs + (size_t)pair * (size_t)rc.ransac_iterations;
   IterSum* __restrict__ sum_pair = MODE == kWhole ? nullptr : plan.sums + (size_t)pair * (size_t)rc.ransac_iterations;
   const int lane = threadIdx.x;
   const PairWork w = work[pair];
   rgbdfe_match_result* __restrict__ out = results + pair;
-  double* __restrict__ ec_region = plan.ec_pool + (size_t)blockIdx.x * kEcRegion;  // this wave's rows of the error pool
+  double* __restrict__ ec_region = plan.ec_pool + (size_t)pair * kEcRegion;  // this wave's rows of the error pool
   PH_DECL
 
   // ------------------------------------------------- the pair's matches (pair_prep_kernel) -> LDS
@@ -738,8 +695,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) v
     }
     wave_sync();
   };
-  // no RANSAC for this pair (node.cpp:1087, :1130): a recording wave has nothing to record
-  if (MODE == kRecord && !(n_all > rc.min_matches && n_all >= 4)) return;
   if (MODE != kReplay) load_points();  // a result wave needs them for the identity fallback only
 
   PH_MARK(1)
@@ -818,18 +773,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) v
         // is provably above the threshold; NaN counts).  Every lane walks all matches for ITS hypothesis -- the match
         // record is the same LDS address for all lanes (broadcast) -- which costs ~1/4 of a slot's pass-1 scoring per
         // hypothesis and spares a junk iteration the whole slot machinery (open, score, bookkeeping round, close).
-        if (!prescreen) {  // (wave-uniform) every finite hypothesis takes a slot
-          hyp_viable = !hyp_nan;
-        } else {
-          hyp_viable = !hyp_nan && prescreen_may_pass(hypR, hypt, lds.M, n_all, pmax, rc) >= thr;
-        }
+        hyp_viable = !hyp_nan && prescreen_may_pass(hypR, hypt, lds.M, n_all, pmax, rc) >= thr;
         viable_mask = __ballot(hyp_viable);
         PH_MARK(2)
     };
     // slot g <- iteration k: first transform = its 4-point hypothesis
     auto open_slot = [&](int g, int k) {
-      // (recording waves get here through next_viable(), which has generated the batch that holds k)
-      if (MODE != kRecord && (hyp_base < 0 || k < hyp_base || k >= hyp_base + kWave)) gen_hypotheses(k);
+      if (hyp_base < 0 || k < hyp_base || k >= hyp_base + kWave) gen_hypotheses(k);
       const int hl = k - hyp_base;
       float R0[9], t0[3];
 #pragma unroll
@@ -990,85 +940,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) v
     wave_sync();
 
     int it = 0;
-    if (MODE == kRecord) {
-      // Recording: the iterations of the chunk are independent and their outcomes are addressed by iteration index,
-      // so a slot whose iteration has left its refinement loop is written out and refilled with the next
-      // iteration at once -- the batched rounds stay full instead of waiting for a window's slowest slot.
-      int k_next = k_begin;
-      // next viable iteration of the chunk (or -1); generates hypothesis batches as needed and writes the (empty)
-      // records of their junk iterations, 64 at a time, lane = iteration
-      auto next_viable = [&]() -> int {
-        while (k_next < k_end) {
-          if (hyp_base < 0 || k_next < hyp_base || k_next >= hyp_base + kWave) {
-            gen_hypotheses(k_next);
-            const int k = hyp_base + lane;
-            if (k < k_end && !hyp_viable) sum_pair[k] = IterSum{1e6, 0, 0};  // refined_matches stays empty (:1133-1134)
-          }
-          const int off0 = k_next - hyp_base;
-          const uint64_t rest = viable_mask >> off0;
-          if (rest == 0ull) { k_next = min(k_end, hyp_base + kWave); continue; }
-          const int k = k_next + (int)__builtin_ctzll(rest);
-          if (k >= k_end) { k_next = k_end; break; }
-          k_next = k + 1;
-          return k;
-        }
-        return -1;
-      };
-      while (n_all >= 4) {
-        if (lane < kSlots) {
-          Slot& sl = lds.slot[lane];
-          if (sl.iter >= 0 && !sl.active) {
-            IterRec& r = rec_pair[sl.iter];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) r.rR[i] = sl.rR[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) r.rt[i] = sl.rt[i];
-#pragma unroll
-            for (int q = 0; q < kRounds; ++q) r.rmask[q] = sl.rmask[q];
-            r.rerr = sl.rerr;
-            r.rn = sl.rn;
-            r.pad = 0;
-            sum_pair[sl.iter] = IterSum{sl.rerr, sl.rn, 0};
-            sl.iter = -1;
-          }
-        }
-        wave_sync();
-        bool occupied = false;
-        for (int g = 0; g < kSlots; ++g) {
-          int it_g = __builtin_amdgcn_readfirstlane(lds.slot[g].iter);
-          if (it_g < 0) {
-            const int k = next_viable();
-            if (k >= 0) {
-              open_slot(g, k);
-              it_g = k;
-            }
-          }
-          occupied |= it_g >= 0;
-        }
-        wave_sync();
-        if (!occupied) break;
-        refine_round();
-      }
-#ifdef RGBDFE_PROFILE_PHASES
-      PH_MARK(5)
-      if (lane == 0) {
-        for (int i = 0; i < 16; ++i) atomicAdd(&g_phase_totals[i], (unsigned long long)ph[i]);
-        atomicAdd(&g_phase_totals[16], 1ull);
-        atomicAdd(&g_phase_totals[17], (unsigned long long)(k_end - k_begin));
-        atomicAdd(&g_phase_totals[18], (unsigned long long)ph[18]);
-        atomicAdd(&g_phase_totals[19], (unsigned long long)ph[19]);
-        atomicAdd(&g_phase_totals[20], (unsigned long long)ph[20]);
-        atomicAdd(&g_phase_totals[21], (unsigned long long)ph[21]);
-      }
-#endif
-    } else if (MODE == kReplay) {
-      // the in-order bookkeeping: adopt its outcome and the record of the best iteration.  One-kernel recording stage: it
-      // ran in replay_walk_kernel, phase by phase.  Split path (plan.final_walk): the refinement kernel has walked what it
-      // had to know between a pair's windows (nothing at all for a pair recorded in one window) and left the end of the
-      // pair's recorded range in WalkState::speculate; the rest of the walk is this wave's.
+    if (MODE == kReplay) {
+      // the in-order bookkeeping: adopt its outcome and the record of the best iteration.  The refinement kernel has walked
+      // what it had to know between a pair's windows (nothing at all for a pair recorded in one window) and left the end of
+      // the pair's recorded range in WalkState::speculate; the rest of the walk is this wave's.
       const WalkState ws = plan.walk[pair];
       WalkRegs wr{ws.it, ws.real_iterations, ws.valid_iterations, ws.best_idx, ws.best_n, ws.rmse, ws.state < 0};
-      if (plan.final_walk && n_all >= 4) {
+      if (n_all >= 4) {
         const uint64_t* __restrict__ vm_pair = plan.vmask + (size_t)pair * (size_t)plan.vmask_words;
         walk_records<false>(wr, min(ws.speculate, rc.ransac_iterations), rc.ransac_iterations, n_all, thr, sum_pair,
                             [&](int k) { return ((vm_pair[k >> 6] >> (k & 63)) & 1ull) != 0ull; }, lane);
@@ -1141,7 +1019,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) v
       }
     }
     }  // kWhole
-    if (MODE != kRecord && valid_iterations == 0) {  // :1192 identity hypothesis
+    if (valid_iterations == 0) {  // :1192 identity hypothesis
       if (MODE == kReplay) load_points();
       uint64_t inl_mask[kRounds];
       int n_inl;
@@ -1159,7 +1037,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(3, 3))) v
   wave_sync();
 
   // ------------------------------------------------------------------ result POD
-  if (MODE != kRecord && lane == 0) {
+  if (lane == 0) {
     const Hyp& b = lds.best;
     out->n_all = n_all;
     out->n_inl = best_n;
@@ -1238,187 +1116,57 @@ void launch_select_ransac_sift(const float4* xyz_pool, const PairWork* work, uin
                      plan);
 }
 
-// The reference's in-order bookkeeping (node.cpp:1130-1191: `it += 10 / 20`, the 80 % exit, best-so-far) over the records
-// of iterations [real_iterations, min(phase_end, state)): one wave per pair, 64 records fetched per step, the sequential
-// decisions on wave-uniform values.  Leaves either "finished" (state < 0) or a tighter bound on the iterations the pair
-// can still need; resumes where the previous phase stopped.
-__global__ __launch_bounds__(kWave) void replay_walk_kernel(const IterSum* __restrict__ sums, WalkState* __restrict__ walk,
-                                                            const PairPrep* __restrict__ prep, uint32_t n_pairs,
-                                                            const RansacConst rc, int phase_begin, int phase_end,
-                                                            int spec_end, int may_speculate,
-                                                            const uint8_t* __restrict__ preclass, int phase_index,
-                                                            const uint64_t* __restrict__ vmask, int vmask_words) {
-  const uint32_t pair = blockIdx.x;
-  if (pair >= n_pairs) return;
-  const int lane = threadIdx.x;
-  WalkState ws = walk[pair];
-  const int I = rc.ransac_iterations;
-  if (phase_begin == 0) {
-    ws.state = I;
-    ws.it = 0; ws.real_iterations = 0; ws.valid_iterations = 0;
-    ws.best_idx = -1; ws.best_n = 0;
-    ws.rmse = 1e6f;  // :1112
-    ws.speculate = 0;
-  } else if (ws.state < 0) {
-    return;
-  }
-  const int n_all = prep[pair].n_all;
-  // the records of a speculating pair reach as far as its recording waves were allowed to go
-  // (first phase of a split plan: the pairs the hypothesis kernel has pre-classified junk-heavy were recorded to the end)
-  const bool to_spec_end = spec_end > phase_end && (phase_begin != 0 ? effective_class(walk, pair, n_pairs) == 2
-                                                                     : (preclass != nullptr && preclass[pair] == 2));
-  const int recorded_end = min(to_spec_end ? spec_end : phase_end, ws.state);
-  uint32_t thr = (uint32_t)rc.min_matches;                                         // :1094
-  if ((double)thr > 0.75 * (double)n_all) thr = (uint32_t)(0.75 * (double)n_all);  // :1095-1098
-  const IterSum* __restrict__ sum_pair = sums + (size_t)pair * (size_t)(I > 0 ? I : 0);
-  WalkRegs wr{ws.it, ws.real_iterations, ws.valid_iterations, ws.best_idx, ws.best_n, ws.rmse, false};
-  const bool runs = n_all > rc.min_matches && n_all >= 4;  // :1087, :1130
-  // split path: an iteration the pre-screen rejected has no summary at all -- the pair's viable mask says so (its bit is
-  // clear) and it counts as {1e6, 0} (the hypothesis kernel used to write 16 bytes for every one of them: 12.8 MB per batch
-  // of configs[1] written and read back up to four times)
-  const uint64_t* __restrict__ vm_pair = vmask != nullptr ? vmask + (size_t)pair * (size_t)vmask_words : nullptr;
-  if (runs)
-    walk_records<false>(wr, recorded_end, I, n_all, thr, sum_pair,
-                        [&](int k) { return vm_pair == nullptr || ((vm_pair[k >> 6] >> (k & 63)) & 1ull) != 0ull; }, lane);
-  const int it = wr.it, real_iterations = wr.real_iterations, valid_iterations = wr.valid_iterations;
-  const int best_idx = wr.best_idx, best_n = wr.best_n;
-  const float rmse = wr.rmse;
-  const bool done = wr.done;
-  if (lane == 0) {
-    // records ran out before the loop ended: at most (I - it) more iterations can follow
-    ws.state = (runs && !done && it < I) ? real_iterations + (I - it) : -1;
-    // after the first phase: nothing has jumped `it` ahead yet -> record the rest of this pair in one go
-    // class of the pair for the rest of the plan (see select_ransac_kernel): 1 = no jump so far, 2 = ... and junk-heavy
-#ifdef RGBDFE_NO_CLASS2  // diagnostics build
-    may_speculate = 0;
-#endif
-    if (may_speculate) {
-      const bool no_jump = ws.state >= 0 && it == real_iterations;
-      const bool junk_heavy = valid_iterations * kClass2Den <= real_iterations * kClass2Num;
-      ws.speculate = no_jump ? (junk_heavy ? 2 : 1) : 0;
-      // class-1 pairs of the batch are counted: when there are only a few of them they are recorded like class 2
-      // (see effective_class) instead of keeping the later phases' launches alive for a handful of long waves
-      if (ws.speculate == 1) atomicAdd(&walk[n_pairs].state, 1);
-    }
-    ws.it = it; ws.real_iterations = real_iterations; ws.valid_iterations = valid_iterations;
-    ws.best_idx = best_idx; ws.best_n = best_n; ws.rmse = rmse;
-    walk[pair] = ws;
-    // "a pair is still running after phase phase_index": the next refinement launch ends at once when nobody says so
-    if (ws.state >= 0) walk[n_pairs].best_n = phase_index + 1;
-  }
-}
-
-// Which recording stage a batch takes.  ransac_split.hip's hypothesis + refinement kernels (bit-identical to the
-// one-kernel stage select_ransac_kernel<kRecord>) are the default for every record / replay plan; the refinement kernel's
-// waves synchronise through one hardware barrier per half-round and nothing else, so there is no batch shape it has to be
-// kept away from (round 4's streaming version, with LDS spin locks, stalled on small batches and was gated to phased plans).
-//   RGBDFE_RANSAC_SPLIT unset or = 1: the split path; = 0: the one-kernel stage (A/B runs).
-static int ransac_split_mode() {
-  static const int mode = getenv("RGBDFE_RANSAC_SPLIT") ? (atoi(getenv("RGBDFE_RANSAC_SPLIT")) != 0 ? 1 : 0) : -1;
-  return mode;
-}
-
-// Record / replay schedule.  The iteration range is covered in `n_phases` phases ending at phase_ends[]: each phase
-// launches the recording waves (the phase in equal shares of at most chunk_iters iterations per wave; waves of finished
-// pairs and waves beyond a pair's remaining need return at once) and the walk (one small wave per pair), which either
-// ends the pair's loop or tightens the bound on the iterations it can still need.  One launch of result waves follows
-// the last phase.  One phase = full speculation (lowest latency); several phases stop recording where the reference's
-// bookkeeping stops iterating.  recs: n_pairs x rc.ransac_iterations records; walk: n_pairs states; prep: filled.
+// Record / replay schedule: the hypothesis kernel (every iteration's 4-point fit + pre-screen, all pairs, lane = iteration),
+// ONE refinement launch over the viable iterations of the whole batch (ransac_split.hip) and one launch of result waves,
+// which finish the in-order walk.  phase_ends[0 .. n_phases): one phase = full speculation (small batches, lowest latency);
+// several = the windows in which the refinement kernel records a pair, so that recording stops where the reference's
+// bookkeeping stops iterating.  recs: n_pairs x rc.ransac_iterations records (+ summaries, masks, order buckets behind
+// them); walk: n_pairs states + the batch's counters; prep: filled.
 static void launch_record_replay(const PairWork* work, rgbdfe_match_result* results, uint32_t n_pairs,
                                  const RansacConst& rc, const PairPrep* prep, IterRec* recs, WalkState* walk,
                                  double* ec_pool, int chunk_iters, const int* phase_ends, int n_phases,
                                  hipStream_t stream) {
-  int begin = 0;
-  RecordPlan plan{};
-  plan.recs = recs; plan.walk = walk; plan.prep = prep; plan.ec_pool = ec_pool;
-  const size_t n_recs = (size_t)n_pairs * (size_t)(rc.ransac_iterations > 0 ? rc.ransac_iterations : 0);
-  plan.sums = reinterpret_cast<IterSum*>(recs + n_recs);
-  plan.n_phases_total = n_phases;  // a single-phase plan (small batches: full speculation) always pre-screens
   const int I = rc.ransac_iterations;
-  const int split_mode = ransac_split_mode();
-  const bool split = split_mode != 0;
-  // walk[n_pairs]: the batch's counters (class-1 pairs; split path: unit counters, "still running" flag), zero at the start
-  // (the split path's hypothesis kernel does it itself)
-  if (!split) (void)hipMemsetAsync(walk + n_pairs, 0, sizeof(WalkState), stream);
+  const size_t n_recs = (size_t)n_pairs * (size_t)(I > 0 ? I : 0);
   SplitPlan sp{};
-  if (split) {
-    // every iteration's hypothesis + pre-screen, all pairs, one launch (lane = iteration); the phases below refine the
-    // viable ones
-    sp.recs = recs; sp.sums = plan.sums; sp.walk = walk; sp.prep = prep;
-    sp.vmask = reinterpret_cast<uint64_t*>(plan.sums + n_recs);
-    sp.vmask_words = ransac_split_words_per_pair(I);
-    sp.preclass = reinterpret_cast<uint8_t*>(sp.vmask + (size_t)n_pairs * (size_t)sp.vmask_words);
-    sp.order_cnt = ransac_split_order_cnt(recs, n_pairs, I);
-    sp.order = sp.order_cnt + kOrderBuckets;
-    // phased plans: pairs the pre-screen alone shows to be junk-heavy skip the first phase's launch + walk and record
-    // everything at once (the classes only schedule the recording: the walk decides the outcome either way)
-    static const bool no_pre = getenv("RGBDFE_NO_PRECLASS") && atoi(getenv("RGBDFE_NO_PRECLASS")) != 0;  // A/B runs
-    sp.preclass_iters = (n_phases > 1 && !no_pre) ? phase_ends[0] : 0;
-    // ONE refinement launch for the whole batch.  Phased plans: a unit is a pair, whose range the kernel records in windows
-    // with the in-order walk between them (SplitPlan); latency batches (one phase, full speculation): a pair's range in
-    // shares of 4 x chunk_iters iterations so that a handful of pairs still fills the chip.  The result waves below finish
-    // the walk.
-    sp.phased = n_phases > 1 ? 1 : 0;
-    sp.n_phases = n_phases < 4 ? n_phases : 4;
-    for (int p = 0; p < 4; ++p) sp.phase_ends[p] = p < sp.n_phases ? (p == sp.n_phases - 1 ? I : phase_ends[p]) : I;
-    // Full speculation: a pair's range in shares of 4 x chunk_iters iterations so that a handful of pairs still fills the chip
-    // -- but no more shares than it takes to give every unit buffer of the launch (workgroups x resident units) a unit: a
-    // pair cut into shares is loaded once per share, a pair in one piece is one workgroup's chain of passes (0.002 z^2, 512
-    // pairs: whole pairs 2.66 ms, shares of 28 1.83 ms; 0.01 z^2: 0.397 / 0.427 ms).
-    int share = chunk_iters >= 28 ? (I > 0 ? I : 1) : chunk_iters * 4;
-    {
-      const int buffers = ransac_split_wgs() * 4;
-      const int want = (int)((buffers + (int)n_pairs - 1) / (int)(n_pairs > 0 ? n_pairs : 1));   // shares per pair that fill them
-      const int by_want = I > 0 ? (I + want - 1) / (want > 0 ? want : 1) : 1;
-      if (by_want > share) share = by_want;
-    }
-    if (share > ransac_split_max_share()) share = ransac_split_max_share();   // (a unit's list of viable iterations)
-    sp.n_shares = sp.phased ? 1 : (I > 0 ? (I + share - 1) / share : 1);
-    sp.share_iters = sp.phased ? I : (I > 0 ? (I + sp.n_shares - 1) / sp.n_shares : share);
-    // (the launch's unit counter: a spare word of walk[n_pairs], zeroed by the hypothesis kernel)
-    sp.unit_counter = reinterpret_cast<uint32_t*>(&walk[n_pairs].it);
-    launch_ransac_hyp(work, n_pairs, rc, sp, stream);
-    if (I > 0) launch_ransac_refine(n_pairs, rc, sp, stream);
-    plan.final_walk = 1;
-    plan.vmask = sp.vmask;
-    plan.vmask_words = sp.vmask_words;
-  } else {
-  for (int p = 0; p < n_phases; ++p) {
-    const int end = phase_ends[p];
-    // The second phase of a phased plan covers everything that is left for the pairs of class 2 (see replay_walk_kernel);
-    // waves that have nothing to do for their pair return at once.
-#ifdef RGBDFE_NO_SUBGRID_B  // diagnostics build
-    const bool spec = false;
-#else
-    const bool spec = n_phases > 2 && p == 1 && I > end;
-#endif
-    const int cover = spec ? I : end;
-    {
-      // the one-kernel recording launch of this phase
-      // sub-grid A: the phase in ceil(length / chunk) equal shares (a short last wave would be the launch's straggler)
-      const int n_chunks = (end - begin + chunk_iters - 1) / chunk_iters;
-      plan.n_chunks = (uint32_t)n_chunks;
-      plan.chunk_iters = n_chunks > 0 ? (end - begin + n_chunks - 1) / n_chunks : chunk_iters;
-      const int cover_rec = spec ? I : end;
-      const int n_chunks_b = spec ? (cover_rec - begin + kWave - 1) / kWave : 0;
-      plan.n_chunks_b = (uint32_t)n_chunks_b;
-      plan.chunk_iters_b = n_chunks_b > 0 ? (cover_rec - begin + n_chunks_b - 1) / n_chunks_b : kWave;
-      plan.phase_begin = begin;
-      plan.phase_end = end;
-      plan.spec_end = cover_rec;
-      if (cover_rec > begin)
-        hipLaunchKernelGGL(select_ransac_kernel<kRecord>,
-                           dim3(8u * ((n_pairs + 7u) / 8u) * (plan.n_chunks + plan.n_chunks_b)), dim3(kWave), 0, stream, work,
-                           results, n_pairs, rc, plan);  // 8 XCD segments x pairs per segment x shares per pair
-    }
-    hipLaunchKernelGGL(replay_walk_kernel, dim3(n_pairs), dim3(kWave), 0, stream, plan.sums, walk, prep, n_pairs, rc, begin,
-                       end, cover, (n_phases > 2 && p == 0) ? 1 : 0, (const uint8_t*)nullptr, p,
-                       (const uint64_t*)nullptr, 0);
-    begin = end;
+  sp.recs = recs; sp.walk = walk; sp.prep = prep;
+  sp.sums = reinterpret_cast<IterSum*>(recs + n_recs);
+  sp.vmask = reinterpret_cast<uint64_t*>(sp.sums + n_recs);
+  sp.vmask_words = ransac_split_words_per_pair(I);
+  sp.preclass = reinterpret_cast<uint8_t*>(sp.vmask + (size_t)n_pairs * (size_t)sp.vmask_words);
+  sp.order_cnt = ransac_split_order_cnt(recs, n_pairs, I);
+  sp.order = sp.order_cnt + kOrderBuckets;
+  // phased plans: pairs the pre-screen alone shows to be junk-heavy skip the first window and record everything at once
+  // (the classes only schedule the recording: the walk decides the outcome either way)
+  static const bool no_pre = getenv("RGBDFE_NO_PRECLASS") && atoi(getenv("RGBDFE_NO_PRECLASS")) != 0;  // A/B runs
+  sp.preclass_iters = (n_phases > 1 && !no_pre) ? phase_ends[0] : 0;
+  // Phased plans: a unit is a pair, whose range the kernel records in windows with the in-order walk between them
+  // (SplitPlan); latency batches (one phase, full speculation): a unit is a share of a pair's range.
+  sp.phased = n_phases > 1 ? 1 : 0;
+  sp.n_phases = n_phases < 4 ? n_phases : 4;
+  for (int p = 0; p < 4; ++p) sp.phase_ends[p] = p < sp.n_phases ? (p == sp.n_phases - 1 ? I : phase_ends[p]) : I;
+  // Full speculation: a pair's range in shares of 4 x chunk_iters iterations so that a handful of pairs still fills the chip
+  // -- but no more shares than it takes to give every unit buffer of the launch (workgroups x resident units) a unit: a
+  // pair cut into shares is loaded once per share, a pair in one piece is one workgroup's chain of passes (0.002 z^2, 512
+  // pairs: whole pairs 2.66 ms, shares of 28 1.83 ms; 0.01 z^2: 0.397 / 0.427 ms).
+  int share = chunk_iters >= 28 ? (I > 0 ? I : 1) : chunk_iters * 4;
+  {
+    const int buffers = ransac_split_wgs() * 4;
+    const int want = (int)((buffers + (int)n_pairs - 1) / (int)(n_pairs > 0 ? n_pairs : 1));   // shares per pair that fill them
+    const int by_want = I > 0 ? (I + want - 1) / (want > 0 ? want : 1) : 1;
+    if (by_want > share) share = by_want;
   }
-  }
-  plan.n_chunks = 1;
-  plan.n_chunks_b = 0;
+  if (share > ransac_split_max_share()) share = ransac_split_max_share();   // (a unit's list of viable iterations)
+  sp.n_shares = sp.phased ? 1 : (I > 0 ? (I + share - 1) / share : 1);
+  sp.share_iters = sp.phased ? I : (I > 0 ? (I + sp.n_shares - 1) / sp.n_shares : share);
+  // (the launch's unit counter: a spare word of walk[n_pairs], the batch's counters, which the hypothesis kernel zeroes)
+  sp.unit_counter = reinterpret_cast<uint32_t*>(&walk[n_pairs].it);
+  launch_ransac_hyp(work, n_pairs, rc, sp, stream);
+  if (I > 0) launch_ransac_refine(n_pairs, rc, sp, stream);
+  RecordPlan plan{};
+  plan.recs = recs; plan.sums = sp.sums; plan.walk = walk; plan.prep = prep; plan.ec_pool = ec_pool;
+  plan.vmask = sp.vmask;
+  plan.vmask_words = sp.vmask_words;
   hipLaunchKernelGGL(select_ransac_kernel<kReplay>, dim3(n_pairs), dim3(kWave), 0, stream, work, results, n_pairs, rc,
                      plan);
 }
@@ -1875,13 +1623,3 @@ void launch_g2o_refine(const PairWork* work, rgbdfe_match_result* results, uint3
 size_t select_ransac_ec_region_bytes() { return sizeof(double) * (size_t)kEcRegion; }
 
 }  // namespace rgbdfe
-
-#ifdef RGBDFE_PROFILE_PHASES
-// diagnostics build only (librgbdfe_prof.so): wall cycles per phase summed over the recording waves
-extern "C" int rgbdfe_debug_phase_totals(unsigned long long* out20, int reset) {
-  unsigned long long zero[24] = {0};
-  if (out20 && hipMemcpyFromSymbol(out20, HIP_SYMBOL(rgbdfe::g_phase_totals), sizeof(zero)) != hipSuccess) return -1;
-  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(rgbdfe::g_phase_totals), zero, sizeof(zero)) != hipSuccess) return -1;
-  return 0;
-}
-#endif

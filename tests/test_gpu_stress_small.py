@@ -17,7 +17,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_small_batches_beside_context_churn():
     env = dict(os.environ)
-    env.pop("RGBDFE_RANSAC_SPLIT", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stress_small_batches.py"), "6000", "2", "single", "20", "3"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -1,5 +1,5 @@
 """GPU box: bench.py's front_end sub-record alone (detect + describe + resident nodes, then every node against its 20
-predecessors): one JSON line.  For A/B runs of library variants or switches (RGBDFE_LIB, RGBDFE_MID_PLAN ...)."""
+predecessors): one JSON line.  For A/B runs of library variants or switches (RGBDFE_LIB, RGBDFE_NO_PRECLASS ...)."""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
