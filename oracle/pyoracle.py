@@ -746,20 +746,152 @@ def match_sift_node_pair(qdesc, qxyz1, qid, tdesc, txyz1, tid, params=None):
     return r
 
 
-def match_node_pair_g2o(qdesc, qxyz1, qkp, qid, tdesc, txyz1, tkp, tid, g2o_iterations, params=None):
-    """matchNodePair with g2o_transformation_refinement = g2o_iterations (node.cpp:1222-1268)."""
+class G2oTrace(C.Structure):
+    _fields_ = [("quat_branch", C.c_int32), ("pivot_failed_at", C.c_int32), ("ww_negative", C.c_int32), ("nsel", C.c_int32)]
+
+
+class G2oBlockTrace(C.Structure):
+    _fields_ = [("outcome", C.c_int32), ("entered_by_error", C.c_int32), ("n_calls", C.c_int32), ("n_inl_first", C.c_int32),
+                ("thr", C.c_int32), ("thr_clipped", C.c_int32), ("n_inl_ransac", C.c_int32), ("call", G2oTrace * 2)]
+
+
+G2O_QUAT_TRACE = 3   # quat_branch: trace > 0; 0, 1, 2: the largest diagonal element
+G2O_NOT_RUN, G2O_REJECTED, G2O_ENTERED_NOT_ADOPTED, G2O_ADOPTED, G2O_ADOPTED_AFTER_SECOND = range(5)
+G2O_OUTCOMES = ("not_run", "rejected", "entered_not_adopted", "adopted", "adopted_after_second")
+
+
+def _trace_to_dict(t):
+    return dict(quat_branch=t.quat_branch, pivot_failed_at=t.pivot_failed_at, ww_negative=t.ww_negative, nsel=t.nsel)
+
+
+def _block_trace_to_dict(t):
+    return dict(outcome=t.outcome, entered_by_error=t.entered_by_error, n_calls=t.n_calls, n_inl_first=t.n_inl_first,
+                thr=t.thr, thr_clipped=t.thr_clipped, n_inl_ransac=t.n_inl_ransac,
+                calls=[_trace_to_dict(t.call[i]) for i in range(t.n_calls)])
+
+
+def _g2o_lib():
+    L = lib()
+    if not getattr(L, "_g2o_bound", False):
+        vp = C.c_void_p
+        L.orc_g2o_refine.restype = C.c_int
+        L.orc_g2o_refine.argtypes = [vp] * 7 + [C.c_int, vp, C.c_int, C.c_double]
+        L.orc_g2o_refine_traced.restype = C.c_int
+        L.orc_g2o_refine_traced.argtypes = L.orc_g2o_refine.argtypes + [C.POINTER(G2oTrace)]
+        blk = [vp] * 6 + [C.c_int, C.POINTER(OrcParams), C.c_int, vp, C.POINTER(C.c_float), vp, C.POINTER(C.c_int),
+                          C.POINTER(C.c_int)]
+        L.orc_g2o_block.restype = C.c_int
+        L.orc_g2o_block.argtypes = blk
+        L.orc_g2o_block_traced.restype = C.c_int
+        L.orc_g2o_block_traced.argtypes = blk + [C.POINTER(G2oBlockTrace)]
+        pair = [vp, vp, vp, C.c_uint32, C.c_int32, vp, vp, vp, C.c_uint32, C.c_int32, C.POINTER(OrcParams), C.c_int,
+                C.POINTER(OrcResult)]
+        L.orc_match_node_pair_g2o.restype = None
+        L.orc_match_node_pair_g2o.argtypes = pair
+        L.orc_match_node_pair_g2o_traced.restype = None
+        L.orc_match_node_pair_g2o_traced.argtypes = pair + [C.POINTER(G2oBlockTrace)]
+        L.orc_match_float_node_pair_g2o.restype = None
+        L.orc_match_float_node_pair_g2o.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int32, vp, vp, vp, C.c_int, C.c_int32,
+                                                    C.c_int, C.c_double, C.POINTER(OrcParams), C.c_int, C.POINTER(OrcResult),
+                                                    vp, C.POINTER(G2oBlockTrace)]
+        L._g2o_bound = True
+    return L
+
+
+def _g2o_arrays(qxyz1, txyz1, qkp, tkp, mq, mt):
+    return [np.ascontiguousarray(a, dt) for a, dt in ((qxyz1, np.float32), (txyz1, np.float32), (qkp, np.float32),
+                                                      (tkp, np.float32), (mq, np.int32), (mt, np.int32))]
+
+
+def g2o_refine(qxyz1, txyz1, qkp, tkp, mq, mt, sel, T, iterations, depth_cov=1e-4, trace=False):
+    """getTransformFromMatchesG2O (transformation_estimation.cpp:37-170) over the matches sel of (mq, mt), started at the
+    4x4 T: (ok, refined T), and with trace=True the path taken as a third element (orc_g2o_refine_traced)."""
+    L = _g2o_lib()
+    a = _g2o_arrays(qxyz1, txyz1, qkp, tkp, mq, mt)
+    sel = np.ascontiguousarray(sel, np.int32)
+    Tc = np.ascontiguousarray(np.asarray(T, np.float32).T).copy()      # column-major storage
+    args = [_p(x) for x in a] + [_p(sel), len(sel), _p(Tc), int(iterations), float(depth_cov)]
+    if not trace:
+        ok = L.orc_g2o_refine(*args)
+        return ok, Tc.reshape(4, 4).T.copy()
+    tr = G2oTrace()
+    ok = L.orc_g2o_refine_traced(*args, C.byref(tr))
+    return ok, Tc.reshape(4, 4).T.copy(), _trace_to_dict(tr)
+
+
+def compute_inliers_and_error(qxyz1, txyz1, mq, mt, T, max_dist_for_inliers, depth_cov):
+    """Node::computeInliersAndError (node.cpp:968-1020) with the caller's squared float threshold: (inlier positions, error)."""
+    a = _g2o_arrays(qxyz1, txyz1, np.zeros((0, 2)), np.zeros((0, 2)), mq, mt)
+    Tc = np.ascontiguousarray(np.asarray(T, np.float32).T).copy()
+    inl = np.zeros(max(len(a[4]), 1), np.int32)
+    err = C.c_double(0.0)
+    md = np.float32(max_dist_for_inliers)
+    n = lib().orc_compute_inliers_and_error(_p(a[0]), _p(a[1]), _p(a[4]), _p(a[5]), len(a[4]), _p(Tc), float(md * md),
+                                            float(depth_cov), _p(inl), C.byref(err))
+    return inl[:n].copy(), err.value
+
+
+def g2o_block(qxyz1, txyz1, qkp, tkp, mq, mt, T, rmse, matches, valid_iterations, g2o_iterations, params=None, trace=False):
+    """The refinement block of getRelativeTransformationTo (node.cpp:1222-1268, :1275) on what RANSAC left (T, rmse, the
+    inlier positions `matches`, valid_iterations): dict(found, T, rmse, matches, valid_iterations[, trace])."""
+    params = params or default_params()
+    L = _g2o_lib()
+    a = _g2o_arrays(qxyz1, txyz1, qkp, tkp, mq, mt)
+    Tc = np.ascontiguousarray(np.asarray(T, np.float32).T).copy()
+    m = np.zeros(ORC_MAX_MATCHES, np.int32)
+    m[: len(matches)] = matches
+    r, nm, vi = C.c_float(rmse), C.c_int(len(matches)), C.c_int(valid_iterations)
+    args = [_p(x) for x in a] + [len(a[4]), C.byref(params), int(g2o_iterations), _p(Tc), C.byref(r), _p(m), C.byref(nm),
+                                 C.byref(vi)]
+    if trace:
+        tr = G2oBlockTrace()
+        found = L.orc_g2o_block_traced(*args, C.byref(tr))
+    else:
+        found = L.orc_g2o_block(*args)
+    out = dict(found=found, T=Tc.reshape(4, 4).T.copy(), rmse=np.float32(r.value), matches=m[: nm.value].copy(),
+               valid_iterations=vi.value)
+    if trace:
+        out["trace"] = _block_trace_to_dict(tr)
+    return out
+
+
+def match_node_pair_g2o(qdesc, qxyz1, qkp, qid, tdesc, txyz1, tkp, tid, g2o_iterations, params=None, trace=False):
+    """matchNodePair with g2o_transformation_refinement = g2o_iterations (node.cpp:1222-1268); trace=True adds the
+    block's path under "trace" (orc_match_node_pair_g2o_traced)."""
     params = params or default_params()
     arrs = [np.ascontiguousarray(a, dt) for a, dt in ((qdesc, np.uint8), (qxyz1, np.float32), (qkp, np.float32),
                                                       (tdesc, np.uint8), (txyz1, np.float32), (tkp, np.float32))]
     out = OrcResult()
-    L = lib()
-    vp = C.c_void_p
-    L.orc_match_node_pair_g2o.restype = None
-    L.orc_match_node_pair_g2o.argtypes = [vp, vp, vp, C.c_uint32, C.c_int32, vp, vp, vp, C.c_uint32, C.c_int32,
-                                          C.POINTER(OrcParams), C.c_int, C.POINTER(OrcResult)]
-    L.orc_match_node_pair_g2o(_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), arrs[0].shape[0], qid, _p(arrs[3]), _p(arrs[4]),
-                              _p(arrs[5]), arrs[3].shape[0], tid, C.byref(params), g2o_iterations, C.byref(out))
-    return result_to_dict(out)
+    L = _g2o_lib()
+    args = [_p(arrs[0]), _p(arrs[1]), _p(arrs[2]), arrs[0].shape[0], qid, _p(arrs[3]), _p(arrs[4]), _p(arrs[5]),
+            arrs[3].shape[0], tid, C.byref(params), g2o_iterations, C.byref(out)]
+    if not trace:
+        L.orc_match_node_pair_g2o(*args)
+        return result_to_dict(out)
+    tr = G2oBlockTrace()
+    L.orc_match_node_pair_g2o_traced(*args, C.byref(tr))
+    r = result_to_dict(out)
+    r["trace"] = _block_trace_to_dict(tr)
+    return r
+
+
+def match_float_node_pair_g2o(matcher, qdesc, qxyz1, qkp, qid, tdesc, txyz1, tkp, tid, g2o_iterations,
+                              nn_distance_ratio=0.95, params=None):
+    """A float-descriptor pair -- matcher "sift" (orc_match_sift_node_pair) or "flann" (orc_match_float_node_pair) --
+    followed by the refinement block on its match list, as orc_match_node_pair_g2o does for ORB; with "all_dist" and "trace"."""
+    params = params or default_params()
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (qdesc, qxyz1, qkp, tdesc, txyz1, tkp)]
+    out = OrcResult()
+    dist = np.zeros(ORC_MAX_MATCHES, np.float32)
+    tr = G2oBlockTrace()
+    _g2o_lib().orc_match_float_node_pair_g2o({"sift": 1, "flann": 2}[matcher], _p(arrs[0]), _p(arrs[1]), _p(arrs[2]),
+                                             arrs[0].shape[0], qid, _p(arrs[3]), _p(arrs[4]), _p(arrs[5]), arrs[3].shape[0],
+                                             tid, arrs[0].shape[1], nn_distance_ratio, C.byref(params), g2o_iterations,
+                                             C.byref(out), _p(dist), C.byref(tr))
+    r = result_to_dict(out)
+    r["all_dist"] = dist[: r["n_all"]].copy()
+    r["trace"] = _block_trace_to_dict(tr)
+    return r
 
 
 def flann_match(qdesc, tdesc, nn_distance_ratio=0.95):

@@ -542,9 +542,11 @@ static int orc_has_nan16(const float* T) {
 /* oracle agree to the bit.                                                                                        */
 /* sel: positions (into mq/mt) of the matches to use.  qkp/tkp: pixel coordinates (x, y) per keypoint.              */
 /* ------------------------------------------------------------------------- */
-static void gn_rot_from_matrix_via_quaternion(const double Rin[9], double Rout[9]) {
+/* returns the branch taken: ORC_G2O_QUAT_TRACE, or the largest diagonal element 0, 1 or 2 */
+static int gn_rot_from_matrix_via_quaternion(const double Rin[9], double Rout[9]) {
   /* Eigen::Quaterniond(Matrix3d) (Shoemake), normalised by g2o::SE3Quat, back to a rotation matrix */
   double q[4]; /* x y z w */
+  int branch = ORC_G2O_QUAT_TRACE;
   const double t = Rin[0] + Rin[4] + Rin[8];
   if (t > 0.0) {
     double tt = sqrt(t + 1.0);
@@ -564,6 +566,7 @@ static void gn_rot_from_matrix_via_quaternion(const double Rin[9], double Rout[9
     q[3] = (Rin[k * 3 + j] - Rin[j * 3 + k]) * tt;
     q[j] = (Rin[j * 3 + i] + Rin[i * 3 + j]) * tt;
     q[k] = (Rin[k * 3 + i] + Rin[i * 3 + k]) * tt;
+    branch = i;
   }
   const double nrm = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
   for (int i = 0; i < 4; ++i) q[i] = q[i] / nrm;
@@ -575,6 +578,7 @@ static void gn_rot_from_matrix_via_quaternion(const double Rin[9], double Rout[9
   Rout[0] = 1.0 - (tyy + tzz); Rout[1] = txy - twz;          Rout[2] = txz + twy;
   Rout[3] = txy + twz;          Rout[4] = 1.0 - (txx + tzz); Rout[5] = tyz - twx;
   Rout[6] = txz - twy;          Rout[7] = tyz + twx;          Rout[8] = 1.0 - (txx + tyy);
+  return branch;
 }
 
 /* projection Jacobian d(u, v, depth)/dY at camera coordinates Y, K = (fx, fy) */
@@ -667,9 +671,11 @@ static void gn_match_terms(const double X[3], const double R1[9], const double t
   for (int a = 0; a < 6; ++a) acc[21 + a] += bc[a] - ((W[a * 3 + 0] * bp[0] + W[a * 3 + 1] * bp[1]) + W[a * 3 + 2] * bp[2]);
 }
 
-/* returns 1 when every step solved (positive pivots), 0 when the solver stopped early */
-int orc_g2o_refine(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
-                   const int32_t* mt, const int32_t* sel, int nsel, float T[16], int iterations, double depth_cov) {
+/* returns 1 when every step solved (positive pivots), 0 when the solver stopped early; tr (may be NULL): which path */
+int orc_g2o_refine_traced(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
+                          const int32_t* mt, const int32_t* sel, int nsel, float T[16], int iterations, double depth_cov,
+                          orc_g2o_trace* tr) {
+  if (tr) { tr->quat_branch = -1; tr->pivot_failed_at = -1; tr->ww_negative = 0; tr->nsel = nsel; }
   if (nsel <= 0 || nsel > ORC_MAX_MATCHES) return 0;
   const double wz = 1.0 / depth_cov; /* misc2.h:44 with the frozen depth_covariance (D3) */
   double (*X)[3] = malloc(sizeof(double) * 3 * (size_t)nsel);
@@ -695,7 +701,8 @@ int orc_g2o_refine(const float* qxyz1, const float* txyz1, const float* qkp, con
     for (int c = 0; c < 3; ++c) Rin[r * 3 + c] = (double)T[c * 4 + r];
     t1[r] = (double)T[12 + r];
   }
-  gn_rot_from_matrix_via_quaternion(Rin, R1);
+  const int branch = gn_rot_from_matrix_via_quaternion(Rin, R1);
+  if (tr) tr->quat_branch = branch;
   int ok = 1;
   for (int it = 0; it < iterations; ++it) {
     /* lane l accumulates its matches l, l+64, ...; then the xor butterfly */
@@ -727,7 +734,10 @@ int orc_g2o_refine(const float* qxyz1, const float* txyz1, const float* qkp, con
         L[i * 6 + j] = v / L[j * 6 + j];
       }
     }
-    if (!ok) break; /* the linear solver failed: g2o stops optimising */
+    if (!ok) { /* the linear solver failed: g2o stops optimising */
+      if (tr) tr->pivot_failed_at = it;
+      break;
+    }
     for (int i = 0; i < 6; ++i) {
       double v = -g[i];
       for (int kk = 0; kk < i; ++kk) v -= L[i * 6 + kk] * y[kk];
@@ -767,6 +777,8 @@ int orc_g2o_refine(const float* qxyz1, const float* txyz1, const float* qkp, con
         Rd[0] = 1.0 - (tyy + tzz); Rd[1] = txy - twz;          Rd[2] = txz + twy;
         Rd[3] = txy + twz;          Rd[4] = 1.0 - (txx + tzz); Rd[5] = tyz - twx;
         Rd[6] = txz - twy;          Rd[7] = tyz + twx;          Rd[8] = 1.0 - (txx + tyy);
+      } else if (tr) {
+        tr->ww_negative++;
       }
       double tn[3], Rn[9];
       for (int r = 0; r < 3; ++r) tn[r] = t1[r] + ((R1[r * 3 + 0] * dc[0] + R1[r * 3 + 1] * dc[1]) + R1[r * 3 + 2] * dc[2]);
@@ -789,6 +801,11 @@ int orc_g2o_refine(const float* qxyz1, const float* txyz1, const float* qkp, con
   T[15] = 1.0f;
   free(X); free(M1); free(M2);
   return ok;
+}
+
+int orc_g2o_refine(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
+                   const int32_t* mt, const int32_t* sel, int nsel, float T[16], int iterations, double depth_cov) {
+  return orc_g2o_refine_traced(qxyz1, txyz1, qkp, tkp, mq, mt, sel, nsel, T, iterations, depth_cov, NULL);
 }
 
 /* Sensitivity harness: which inlier set the adopted transform was FITTED from (the final inlier set is what that
@@ -901,9 +918,10 @@ int orc_ransac(const float* qxyz1, const float* txyz1, const int32_t* mq,
 /* inliers as before (:1252-1260).  Runs only for g2o_iterations > 0 and more inliers than min_inlier_threshold (:1226). */
 /* Returns the new `found` (:1275).                                                                                      */
 /* ------------------------------------------------------------------------- */
-int orc_g2o_block(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
-                  const int32_t* mt, int n, const orc_params* prm, int g2o_iterations, float T[16], float* rmse_io,
-                  int32_t* matches, int* n_matches_io, int* valid_iterations_io) {
+int orc_g2o_block_traced(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
+                         const int32_t* mt, int n, const orc_params* prm, int g2o_iterations, float T[16], float* rmse_io,
+                         int32_t* matches, int* n_matches_io, int* valid_iterations_io, orc_g2o_block_trace* tr) {
+  if (tr) { memset(tr, 0, sizeof(*tr)); tr->outcome = ORC_G2O_NOT_RUN; }
   unsigned int min_inlier_threshold = (unsigned int)prm->min_matches;
   if ((double)min_inlier_threshold > 0.75 * (double)n) min_inlier_threshold = (unsigned int)(0.75 * (double)n);
   const float max_dist_m = (float)(double)prm->max_dist_for_inliers;
@@ -913,16 +931,29 @@ int orc_g2o_block(const float* qxyz1, const float* txyz1, const float* qkp, cons
   if (g2o_iterations > 0 && (unsigned int)n_matches > min_inlier_threshold) { /* :1226 */
     float Tn[16];
     memcpy(Tn, T, sizeof(Tn)); /* :1228 */
-    orc_g2o_refine(qxyz1, txyz1, qkp, tkp, mq, mt, matches, n_matches, Tn, g2o_iterations, prm->depth_cov); /* :1229 */
+    orc_g2o_refine_traced(qxyz1, txyz1, qkp, tkp, mq, mt, matches, n_matches, Tn, g2o_iterations, prm->depth_cov,
+                          tr ? &tr->call[0] : NULL); /* :1229 */
     int32_t inlier[ORC_MAX_MATCHES];
     double inlier_error;
     int n_inl = orc_compute_inliers_and_error(qxyz1, txyz1, mq, mt, n, Tn, sq_max, prm->depth_cov, inlier, &inlier_error); /* :1233 */
+    if (tr) {
+      tr->n_calls = 1;
+      tr->n_inl_first = n_inl;
+      tr->outcome = ORC_G2O_REJECTED;
+    }
     if (n_inl >= n_matches || ((unsigned int)n_inl >= min_inlier_threshold && inlier_error < (double)rmse)) { /* :1239 */
+      if (tr) {
+        tr->outcome = ORC_G2O_ENTERED_NOT_ADOPTED;
+        tr->entered_by_error = !(n_inl >= n_matches);
+      }
       if (n_inl > n_matches) { /* :1241 */
-        orc_g2o_refine(qxyz1, txyz1, qkp, tkp, mq, mt, inlier, n_inl, Tn, g2o_iterations, prm->depth_cov); /* :1243 */
+        orc_g2o_refine_traced(qxyz1, txyz1, qkp, tkp, mq, mt, inlier, n_inl, Tn, g2o_iterations, prm->depth_cov,
+                              tr ? &tr->call[1] : NULL); /* :1243 */
         n_inl = orc_compute_inliers_and_error(qxyz1, txyz1, mq, mt, n, Tn, sq_max, prm->depth_cov, inlier, &inlier_error); /* :1244 */
+        if (tr) tr->n_calls = 2;
       }
       if (n_inl >= n_matches) { /* :1252 */
+        if (tr) tr->outcome = tr->n_calls == 2 ? ORC_G2O_ADOPTED_AFTER_SECOND : ORC_G2O_ADOPTED;
         memcpy(T, Tn, sizeof(Tn));                                   /* :1256 */
         memcpy(matches, inlier, sizeof(int32_t) * (size_t)n_inl);    /* :1257 */
         n_matches = n_inl;
@@ -936,14 +967,35 @@ int orc_g2o_block(const float* qxyz1, const float* txyz1, const float* qkp, cons
   return (unsigned int)n_matches >= min_inlier_threshold; /* :1275 */
 }
 
-/* matchNodePair with g2o_transformation_refinement = g2o_iterations; qkp / tkp: KeyPoint.pt of the two nodes */
-void orc_match_node_pair_g2o(const uint8_t* qdesc, const float* qxyz1, const float* qkp, uint32_t nq, int32_t qid,
-                             const uint8_t* tdesc, const float* txyz1, const float* tkp, uint32_t nt, int32_t tid,
-                             const orc_params* prm, int g2o_iterations, orc_result* out) {
-  orc_match_node_pair(qdesc, qxyz1, nq, qid, tdesc, txyz1, nt, tid, prm, out);
+int orc_g2o_block(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
+                  const int32_t* mt, int n, const orc_params* prm, int g2o_iterations, float T[16], float* rmse_io,
+                  int32_t* matches, int* n_matches_io, int* valid_iterations_io) {
+  return orc_g2o_block_traced(qxyz1, txyz1, qkp, tkp, mq, mt, n, prm, g2o_iterations, T, rmse_io, matches, n_matches_io,
+                              valid_iterations_io, NULL);
+}
+
+/* the refinement block on a finished pair record (ORB or float matcher): what matchNodePair does after :1324 */
+static void orc_result_g2o(const float* qxyz1, const float* qkp, int32_t qid, const float* txyz1, const float* tkp,
+                           int32_t tid, const orc_params* prm, int g2o_iterations, orc_result* out,
+                           orc_g2o_block_trace* tr) {
+  if (tr) { memset(tr, 0, sizeof(*tr)); tr->outcome = ORC_G2O_NOT_RUN; }
   if (g2o_iterations <= 0 || out->n_all < prm->min_matches || out->n_all <= prm->min_matches) return; /* no RANSAC ran (:1319, :1087) */
-  const int found = orc_g2o_block(qxyz1, txyz1, qkp, tkp, out->all_q, out->all_t, out->n_all, prm, g2o_iterations, out->T,
-                                  &out->rmse, out->inl_idx, &out->n_inl, &out->valid_iterations);
+  if (tr) { /* what the RANSAC loop left, for the threshold edges of :1226 */
+    unsigned int thr = (unsigned int)prm->min_matches;
+    if ((double)thr > 0.75 * (double)out->n_all) thr = (unsigned int)(0.75 * (double)out->n_all);
+    tr->thr = (int32_t)thr;
+    tr->thr_clipped = thr != (unsigned int)prm->min_matches;
+    tr->n_inl_ransac = out->n_inl;
+  }
+  orc_g2o_block_trace blk;
+  const int found = orc_g2o_block_traced(qxyz1, txyz1, qkp, tkp, out->all_q, out->all_t, out->n_all, prm, g2o_iterations,
+                                         out->T, &out->rmse, out->inl_idx, &out->n_inl, &out->valid_iterations,
+                                         tr ? &blk : NULL);
+  if (tr) {
+    const int32_t thr = tr->thr, clipped = tr->thr_clipped, n0 = tr->n_inl_ransac;
+    *tr = blk;
+    tr->thr = thr; tr->thr_clipped = clipped; tr->n_inl_ransac = n0;
+  }
   if (found) {
     out->info_scale = (double)((float)out->n_inl / (out->rmse * out->rmse)); /* node.cpp:1335 */
     out->id1 = tid;
@@ -952,6 +1004,30 @@ void orc_match_node_pair_g2o(const uint8_t* qdesc, const float* qxyz1, const flo
     out->id1 = out->id2 = -1;
     out->info_scale = 0.0;
   }
+}
+
+/* matchNodePair with g2o_transformation_refinement = g2o_iterations; qkp / tkp: KeyPoint.pt of the two nodes */
+void orc_match_node_pair_g2o_traced(const uint8_t* qdesc, const float* qxyz1, const float* qkp, uint32_t nq, int32_t qid,
+                                    const uint8_t* tdesc, const float* txyz1, const float* tkp, uint32_t nt, int32_t tid,
+                                    const orc_params* prm, int g2o_iterations, orc_result* out, orc_g2o_block_trace* tr) {
+  orc_match_node_pair(qdesc, qxyz1, nq, qid, tdesc, txyz1, nt, tid, prm, out);
+  orc_result_g2o(qxyz1, qkp, qid, txyz1, tkp, tid, prm, g2o_iterations, out, tr);
+}
+
+/* the same behind the float matchers: matcher 1 = SiftGPU (orc_match_sift_node_pair), 2 = FLANN (orc_match_float_node_pair) */
+void orc_match_float_node_pair_g2o(int matcher, const float* qdesc, const float* qxyz1, const float* qkp, int nq, int32_t qid,
+                                   const float* tdesc, const float* txyz1, const float* tkp, int nt, int32_t tid, int dim,
+                                   double nn_distance_ratio, const orc_params* prm, int g2o_iterations, orc_result* out,
+                                   float* all_dist, orc_g2o_block_trace* tr) {
+  if (matcher == 1) orc_match_sift_node_pair(qdesc, qxyz1, nq, qid, tdesc, txyz1, nt, tid, prm, out, all_dist);
+  else orc_match_float_node_pair(qdesc, qxyz1, nq, qid, tdesc, txyz1, nt, tid, dim, nn_distance_ratio, prm, out, all_dist);
+  orc_result_g2o(qxyz1, qkp, qid, txyz1, tkp, tid, prm, g2o_iterations, out, tr);
+}
+
+void orc_match_node_pair_g2o(const uint8_t* qdesc, const float* qxyz1, const float* qkp, uint32_t nq, int32_t qid,
+                             const uint8_t* tdesc, const float* txyz1, const float* tkp, uint32_t nt, int32_t tid,
+                             const orc_params* prm, int g2o_iterations, orc_result* out) {
+  orc_match_node_pair_g2o_traced(qdesc, qxyz1, qkp, nq, qid, tdesc, txyz1, tkp, nt, tid, prm, g2o_iterations, out, NULL);
 }
 
 /* ------------------------------------------------------------------------- */

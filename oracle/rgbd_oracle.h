@@ -133,6 +133,44 @@ int orc_g2o_block(const float* qxyz1, const float* txyz1, const float* qkp, cons
 void orc_match_node_pair_g2o(const uint8_t* qdesc, const float* qxyz1, const float* qkp, uint32_t nq, int32_t qid,
                              const uint8_t* tdesc, const float* txyz1, const float* tkp, uint32_t nt, int32_t tid,
                              const orc_params* prm, int g2o_iterations, orc_result* out);
+/* Which path a refinement took (tests assert that a planted case visits what it names). */
+#define ORC_G2O_QUAT_TRACE 3 /* quat_branch: trace > 0; 0, 1, 2 = the largest diagonal element */
+typedef struct {
+  int32_t quat_branch;     /* branch of Eigen::Quaterniond(Matrix3d) for the start estimate; -1: nothing ran */
+  int32_t pivot_failed_at; /* iteration at which a Cholesky pivot was not positive (the solver stopped); -1: none */
+  int32_t ww_negative;     /* iterations whose pose update had |dq| > 1 (the rotation increment stays the identity) */
+  int32_t nsel;            /* matches the refinement ran on */
+} orc_g2o_trace;
+enum {
+  ORC_G2O_NOT_RUN = 0,              /* :1226 false (or no RANSAC ran) */
+  ORC_G2O_REJECTED = 1,             /* :1239 false */
+  ORC_G2O_ENTERED_NOT_ADOPTED = 2,  /* :1239 true, :1252 false */
+  ORC_G2O_ADOPTED = 3,              /* :1252 true, no second refinement */
+  ORC_G2O_ADOPTED_AFTER_SECOND = 4  /* :1241 true, :1252 true */
+};
+typedef struct {
+  int32_t outcome;          /* ORC_G2O_* */
+  int32_t entered_by_error; /* :1239 held through its second clause only */
+  int32_t n_calls;          /* refinements run: 0, 1 or 2 */
+  int32_t n_inl_first;      /* inliers of the first refinement's pose (:1233) */
+  int32_t thr, thr_clipped, n_inl_ransac; /* filled by the pair functions: min_inlier_threshold, whether 0.75 n clipped it, RANSAC's inliers */
+  orc_g2o_trace call[2];
+} orc_g2o_block_trace;
+/* the same results as the untraced functions, byte for byte; tr may be NULL */
+int orc_g2o_refine_traced(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
+                          const int32_t* mt, const int32_t* sel, int nsel, float T[16], int iterations, double depth_cov,
+                          orc_g2o_trace* tr);
+int orc_g2o_block_traced(const float* qxyz1, const float* txyz1, const float* qkp, const float* tkp, const int32_t* mq,
+                         const int32_t* mt, int n, const orc_params* prm, int g2o_iterations, float T[16], float* rmse_io,
+                         int32_t* matches, int* n_matches_io, int* valid_iterations_io, orc_g2o_block_trace* tr);
+void orc_match_node_pair_g2o_traced(const uint8_t* qdesc, const float* qxyz1, const float* qkp, uint32_t nq, int32_t qid,
+                                    const uint8_t* tdesc, const float* txyz1, const float* tkp, uint32_t nt, int32_t tid,
+                                    const orc_params* prm, int g2o_iterations, orc_result* out, orc_g2o_block_trace* tr);
+/* matcher 1 = orc_match_sift_node_pair, 2 = orc_match_float_node_pair, then the refinement block on its all_q / all_t */
+void orc_match_float_node_pair_g2o(int matcher, const float* qdesc, const float* qxyz1, const float* qkp, int nq, int32_t qid,
+                                   const float* tdesc, const float* txyz1, const float* tkp, int nt, int32_t tid, int dim,
+                                   double nn_distance_ratio, const orc_params* prm, int g2o_iterations, orc_result* out,
+                                   float* all_dist, orc_g2o_block_trace* tr);
 int orc_flann_match(const float* qdesc, int nq, const float* tdesc, int nt, int dim, double nn_distance_ratio,
                     int32_t* mq, int32_t* mt, float* md);
 void orc_match_float_node_pair(const float* qdesc, const float* qxyz1, int nq, int32_t qid, const float* tdesc,

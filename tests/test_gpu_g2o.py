@@ -99,3 +99,178 @@ def test_g2o_needs_keypoints():
     fe.set_params(g2o_iterations=0)
     assert fe.match_pair_list([1], [0])["n_all"][0] > 0
     fe.close()
+
+
+# ---- the planted cases of tests/g2o_cases.py, the fuzz, the float matchers, the submission paths ----------------------
+import g2o_cases as gc  # noqa: E402
+
+SCHEDULES = [((0, 0), "one_wave_per_pair"), ((1 << 20, 0), "record_replay")]
+LEFT_ALONE = (po.G2O_NOT_RUN, po.G2O_REJECTED, po.G2O_ENTERED_NOT_ADOPTED)
+
+
+@pytest.fixture(scope="module")
+def fe_small():
+    """The smallest context that holds every planted case: 8 nodes of up to 400 rows (capacity 448, a whole number of 64-row tiles), up to 24 pairs."""
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    f = FrontEnd(device_id=0, max_nodes=8, max_keypoints=448, max_pairs_per_batch=24)
+    yield f
+    f.close()
+
+
+def _upload(fe, nodes):
+    for k, (d, x, kp) in enumerate(nodes):
+        fe.upload_node(k, d, x)
+        fe.upload_node_keypoints(k, kp)
+
+
+def _run_case(fe, c):
+    """The case's pairs on both schedules and with the refinement off: (records per schedule, RANSAC-only records)."""
+    pq = np.array([p[0] for p in c["pairs"]], np.int32)
+    pt = np.array([p[1] for p in c["pairs"]], np.int32)
+    try:
+        _upload(fe, c["nodes"])
+        outs = []
+        for mode, _ in SCHEDULES:
+            fe.set_latency_mode(*mode)
+            fe.set_params(g2o_iterations=c["iters"], **c["params"])
+            outs.append(fe.match_pair_list(pq, pt))
+        fe.set_params(g2o_iterations=0)
+        plain = fe.match_pair_list(pq, pt)
+        return outs, plain
+    finally:
+        fe.set_params(g2o_iterations=0, **gc.DEFAULTS)
+        for k in range(len(c["nodes"])):
+            fe.release_node(k)
+
+
+@pytest.mark.parametrize("name", list(gc.CASES))
+def test_planted_cases_match_oracle(fe_small, name):
+    """Every pair of every planted case (tests/g2o_cases.py; what each is for: DESIGN.md, "Two-view refinement: branches and
+    the cases that reach them") against the oracle's full record, bit for bit, on both schedules; a pair whose refinement
+    is not adopted -- a NaN pose included -- keeps the RANSAC record byte for byte."""
+    c = gc.get(name)
+    refs = gc.oracle_records(name)
+    outs, plain = _run_case(fe_small, c)
+    for out, (_, schedule) in zip(outs, SCHEDULES):
+        for rec, base, ref, pair in zip(out, plain, refs, c["pairs"]):
+            try:
+                gc.check_record(rec, ref)
+            except AssertionError as e:
+                raise AssertionError("%s %s pair %s: %s" % (name, schedule, pair, e)) from e
+            if ref["trace"]["outcome"] in LEFT_ALONE:
+                assert rec.tobytes() == base.tobytes(), (name, schedule, pair)
+            else:
+                assert rec["valid_iterations"] == base["valid_iterations"] + 1
+    assert outs[0].tobytes() == outs[1].tobytes()
+
+
+def test_randomised_nodes_and_parameters_with_refinement():
+    """test_randomised_nodes_and_parameters_match_oracle's fuzz with the refinement on (gc.fuzz_trials: node sizes from 0 to
+    400, NaN / zero depths, unrelated and duplicated descriptors, keypoints 0 / 0.2 / 2 pixels off, 1 / 3 / 8 steps, random
+    matching and RANSAC parameters): every pair equals the oracle bit for bit on both schedules, and the phased plan forced
+    onto the batch gives the same bytes."""
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    fe = FrontEnd(device_id=0, max_nodes=8, max_keypoints=448, max_pairs_per_batch=24)
+    try:
+        refined = 0
+        for trial, c in enumerate(gc.fuzz_trials()):
+            refs = gc.records_of(c)
+            pq = np.array([p[0] for p in c["pairs"]], np.int32)
+            pt = np.array([p[1] for p in c["pairs"]], np.int32)
+            _upload(fe, c["nodes"])
+            fe.set_params(g2o_iterations=c["iters"], **c["params"])
+            outs = []
+            for mode in ((0, 0), (1 << 20, 0), (1 << 30, -5)):
+                fe.set_latency_mode(*mode)
+                outs.append(fe.match_pair_list(pq, pt))
+            for out in outs[:2]:
+                for rec, ref, pair in zip(out, refs, c["pairs"]):
+                    try:
+                        gc.check_record(rec, ref)
+                    except AssertionError as e:
+                        raise AssertionError("trial %d pair %s %s: %s" % (trial, pair, c["params"], e)) from e
+            assert outs[2].tobytes() == outs[0].tobytes() == outs[1].tobytes(), trial
+            refined += sum(r["trace"]["n_calls"] for r in refs)
+            for k in range(len(c["nodes"])):
+                fe.release_node(k)
+        assert refined >= 10
+    finally:
+        fe.close()
+
+
+@pytest.mark.parametrize("matcher", ["sift", "flann"])
+def test_refinement_behind_the_float_matchers(matcher):
+    """launch_g2o_refine after launch_select_ransac_sift / ..._sift_latency (api_batches.hip: the float matchers' branch): the
+    PairPrep that the refinement reads is written by the list path's prep.  Resident SIFT nodes and FLANN float nodes with
+    keypoints, 3 steps, records and distance lists against the oracle's float pair followed by its refinement block."""
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    c = gc.float_case()
+    refs = gc.float_records(matcher, c)
+    outcomes = [r["trace"]["outcome"] for r in refs]
+    assert any(o >= po.G2O_ADOPTED for o in outcomes) and any(o in (po.G2O_REJECTED, po.G2O_ENTERED_NOT_ADOPTED) for o in outcomes)
+    assert outcomes[-2:] == [po.G2O_NOT_RUN] * 2                                   # the unrelated frame
+    pq = np.array([p[0] for p in c["pairs"]], np.int32)
+    pt = np.array([p[1] for p in c["pairs"]], np.int32)
+    fe = FrontEnd(device_id=0, max_nodes=8, max_keypoints=320, max_pairs_per_batch=16, g2o_iterations=c["iters"])
+    try:
+        for k, (d, x, kp) in enumerate(c["nodes"]):
+            (fe.upload_sift_node if matcher == "sift" else fe.upload_float_node)(k, d, x)
+            fe.upload_node_keypoints(k, kp)
+        run = fe.match_sift_pair_list if matcher == "sift" else fe.match_flann_pair_list
+        results = []
+        for mode, schedule in SCHEDULES:
+            fe.set_latency_mode(*mode)
+            out, dist = run(pq, pt)
+            for rec, dd, ref, pair in zip(out, dist, refs, c["pairs"]):
+                try:
+                    gc.check_record(rec, ref, hd=False)
+                    assert np.array_equal(dd[: ref["n_all"]], ref["all_dist"])
+                except AssertionError as e:
+                    raise AssertionError("%s %s pair %s: %s" % (matcher, schedule, pair, e)) from e
+            results.append(out.tobytes() + dist.tobytes())
+        assert results[0] == results[1]
+        fe.set_params(g2o_iterations=0)
+        plain, _ = run(pq, pt)
+        for rec, base, o in zip(out, plain, outcomes):
+            assert (rec.tobytes() == base.tobytes()) == (o in LEFT_ALONE)
+    finally:
+        fe.close()
+
+
+def test_refinement_through_tickets_and_with_graph_capture(monkeypatch):
+    """With the refinement on, two submit_pair_list batches in flight give the bytes of the synchronous call; and a context
+    created with RGBDFE_GRAPHS=1 gives them again while capturing nothing: `graphable` requires g2o_iterations == 0, so the
+    chain goes out as plain launches."""
+    import torch
+    from rgbdslam_v2_amd.frontend import FrontEnd, RESULT_DTYPE
+    c = gc.get("adopt_mix_a")
+    refs = gc.oracle_records("adopt_mix_a")
+    pq = np.array([p[0] for p in c["pairs"]], np.int32)
+    pt = np.array([p[1] for p in c["pairs"]], np.int32)
+
+    def run(graphs):
+        monkeypatch.setenv("RGBDFE_GRAPHS", "1" if graphs else "0")
+        fe = FrontEnd(device_id=0, max_nodes=8, max_keypoints=320, max_pairs_per_batch=24, g2o_iterations=c["iters"])
+        try:
+            assert fe.graph_stats()["enabled"] == (1 if graphs else 0)
+            _upload(fe, c["nodes"])
+            sync = fe.match_pair_list(pq, pt)
+            bufs = [torch.zeros(len(pq) * RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda") for _ in range(2)]
+            tickets = [fe.submit_pair_list(pq, pt, b.data_ptr()) for b in bufs]
+            outs = []
+            for tk, b in zip(tickets, bufs):
+                fe.wait_ticket(tk, None)
+                outs.append(b.cpu().numpy().tobytes())
+            again = fe.match_pair_list(pq, pt)
+            return sync, outs, again, fe.graph_stats()
+        finally:
+            fe.close()
+
+    sync, outs, again, st = run(False)
+    for rec, ref in zip(sync, refs):
+        gc.check_record(rec, ref)
+    assert outs[0] == outs[1] == sync.tobytes() == again.tobytes()
+    g_sync, g_outs, g_again, g_st = run(True)
+    assert g_sync.tobytes() == sync.tobytes() and g_outs[0] == g_outs[1] == sync.tobytes() == g_again.tobytes()
+    assert g_st["enabled"] == 1 and g_st["launches"] == 0 and g_st["captures"] == 0, g_st
+    assert sum(r["trace"]["outcome"] >= po.G2O_ADOPTED for r in refs) >= 5
