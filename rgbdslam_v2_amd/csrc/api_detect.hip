@@ -4,6 +4,7 @@
 #include <future>
 
 #include "rgbdfe_host.h"
+#include "staging_ring.h"
 
 namespace impl {
 
@@ -55,12 +56,12 @@ int rgbdfe_orb_detect(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
   std::string err;
   int rc = ctx->orb.prepare(cols, rows, false, err);
   if (rc == RGBDFE_OK) rc = ctx->orb.upload_and_build(gray, mask, ctx->stream, err);
-  std::vector<std::vector<KpOut>> out(1);
-  if (rc == RGBDFE_OK) rc = ctx->orb.detect_pass({1}, {fast_threshold}, out, ctx->stream, err);
+  std::vector<KpOut> out;
+  if (rc == RGBDFE_OK) rc = ctx->orb.detect_pass(fast_threshold, out, ctx->stream, err);
   if (rc != RGBDFE_OK) return fail(ctx, rc, err);
-  *n_out = (int32_t)out[0].size();
-  if ((int)out[0].size() > capacity) return fail(ctx, RGBDFE_ERR_CAPACITY, "more ORB keypoints than the output array holds");
-  kp_to_abi(out[0], keypoints);
+  *n_out = (int32_t)out.size();
+  if ((int)out.size() > capacity) return fail(ctx, RGBDFE_ERR_CAPACITY, "more ORB keypoints than the output array holds");
+  kp_to_abi(out, keypoints);
   return RGBDFE_OK;
 }
 
@@ -473,6 +474,24 @@ int rgbdfe_sift_geometry(rgbdfe_ctx* ctx, int32_t* octave_min, int32_t* octave_n
   return RGBDFE_OK;
 }
 
+// hasNonZero(sub_mask) (feature_adjuster.cpp:175-183) of n cells for one frame: a sensor frame's mask, the caller's, or none
+static void frame_mask_flags(const SensorRun* sensor, int sframe, const uint8_t* mask, int cols, const GridCell* cells, int n,
+                             char* flags) {
+  if (sensor) cell_mask_flags(cells, n, flags, [&](const GridCell& ce) { return sensor->mask_nonzero(sframe, ce.x0, ce.y0, ce.w, ce.h); });
+  else if (mask) cell_mask_flags(cells, n, flags, [&](const GridCell& ce) { return mask_nonzero(mask, cols, ce); });
+  else std::fill(flags, flags + n, (char)1);
+}
+
+// the batch pipelines' side streams and the events that order them, created by the first batch call
+static int ensure_orb_streams(rgbdfe_ctx* ctx) {
+  if (ctx->orb_upload_stream) return RGBDFE_OK;
+  HIP_TRY(ctx, create_side_stream(&ctx->orb_upload_stream, -1));   // uploads + pyramids: behind everything else
+  HIP_TRY(ctx, create_side_stream(&ctx->orb_compute_stream, +1));  // descriptions: short, the host waits for them
+  for (hipEvent_t& e : ctx->orb_upload_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (hipEvent_t& e : ctx->orb_describe_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return RGBDFE_OK;
+}
+
 // One frame of Node::Node's feature path in three stages; the caller holds the lock.
 //   detect()            detector grid + threshold adaptation (node.cpp:160) on ctx->stream: the frame's keypoints
 //   describe_enqueue()  removeDepthless, retainBest, cv::ORB::compute and projectTo3D (:186-210) enqueued on a stream
@@ -514,24 +533,8 @@ struct DetectFrame {
     tq = tm ? orb_now_us() : 0;
     int rc = orb.prepare(cols, rows, true, err);
     if (rc != RGBDFE_OK) return fail(ctx, rc, err);
-    // hasNonZero(sub_mask) per cell (feature_adjuster.cpp:175-183)
-    orb.cell_mask_nonzero.assign((size_t)orb.n_cells, (mask || sensor) ? 0 : 1);
-    if (sensor)
-      for (int c = 0; c < orb.n_cells; ++c) {
-        const OrbWorkspace::Cell& ce = orb.cells[c];
-        orb.cell_mask_nonzero[c] = sensor->mask_nonzero(sframe, ce.x0, ce.y0, ce.w, ce.h) ? 1 : 0;
-      }
-    else if (mask)
-      for (int c = 0; c < orb.n_cells; ++c) {
-        const OrbWorkspace::Cell& ce = orb.cells[c];
-        char nz = 0;
-        for (int y = 0; y < ce.h && !nz; ++y) {
-          const uint8_t* r = mask + (size_t)(ce.y0 + y) * cols + ce.x0;
-          for (int x = 0; x < ce.w; ++x)
-            if (r[x]) { nz = 1; break; }
-        }
-        orb.cell_mask_nonzero[c] = nz;
-      }
+    orb.cell_mask_nonzero.resize((size_t)orb.n_cells);
+    frame_mask_flags(sensor, sframe, mask, cols, orb.cells.data(), orb.n_cells, orb.cell_mask_nonzero.data());
     // the depth image stays on the host: removeDepthless and projectTo3D look at one pixel per keypoint
     lap(0);
     if (!uploaded && sensor) {  // raw bytes up, the ingest kernel writes [gray | mask] into the pool (and the depth plane)
@@ -591,57 +594,17 @@ struct DetectFrame {
       HIP_TRY(ctx, hipMemcpyAsync(zmin.data(), d_z, (size_t)n0 * 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(ctx, hipStreamSynchronize(st));
     }
-    if (min_depth) {  // removeDepthless with the neighbourhood depth (node.cpp:82)
-      size_t m = 0;
-      for (size_t i = 0; i < kps.size(); ++i) {
-        const KpOut& k = kps[i];
-        if (k.x >= (float)cols || k.x < 0 || k.y >= (float)rows || k.y < 0 || std::isnan(k.x) || std::isnan(k.y)) continue;
-        if (std::isnan(zmin[i])) continue;
-        zmin[m] = zmin[i];
-        kps[m++] = k;
-      }
-      kps.resize(m);
-      zmin.resize(m);
-    } else {  // removeDepthless (node.cpp:67-97, :186)
-      // one scattered read of the 1.2 MB depth image per keypoint: issue them all before the first is needed (the loop
-      // below otherwise pays a cache miss per keypoint, ~100 us per frame)
-      for (const KpOut& k : kps) {
-        if (sensor) break;
-        if (!(k.x >= 0 && k.x < (float)cols && k.y >= 0 && k.y < (float)rows)) continue;
-        int r = (int)roundf(k.y), c = (int)roundf(k.x);
-        r = r >= rows ? rows - 1 : r;
-        c = c >= cols ? cols - 1 : c;
-        __builtin_prefetch(depth + (size_t)r * cols + c, 0, 1);
-      }
-      size_t m = 0;
-      for (const KpOut& k : kps) {
-        if (k.x >= (float)cols || k.x < 0 || k.y >= (float)rows || k.y < 0 || std::isnan(k.x) || std::isnan(k.y)) continue;
-        int r = (int)roundf(k.y), c = (int)roundf(k.x);
-        r = r >= rows ? rows - 1 : r;
-        c = c >= cols ? cols - 1 : c;
-        if (std::isnan(depth_px(r, c))) continue;
-        kps[m++] = k;
-      }
-      kps.resize(m);
+    // one scattered read of the 1.2 MB depth image per keypoint: issue them all before the first is needed (removeDepthless
+    // otherwise pays a cache miss per keypoint, ~100 us per frame)
+    for (const KpOut& k : kps) {
+      if (min_depth || sensor) break;
+      if (!(k.x >= 0 && k.x < (float)cols && k.y >= 0 && k.y < (float)rows)) continue;
+      int r, c;
+      depth_pixel(k, rows, cols, r, c);
+      __builtin_prefetch(depth + (size_t)r * cols + c, 0, 1);
     }
-    if ((int)kps.size() > max_kp) {  // retainBest(max_keypoints) + resize (node.cpp:188-191)
-      // the max_kp first of the order (response descending, position ascending), in their original order: a selection
-      std::vector<std::pair<float, int>> r(kps.size());
-      for (size_t i = 0; i < kps.size(); ++i) r[i] = std::make_pair(kps[i].response, (int)i);
-      auto before = [](const std::pair<float, int>& a, const std::pair<float, int>& b) {
-        return a.first > b.first || (a.first == b.first && a.second < b.second);
-      };
-      std::nth_element(r.begin(), r.begin() + (max_kp - 1), r.end(), before);
-      const std::pair<float, int> cut = r[(size_t)max_kp - 1];
-      size_t m = 0;
-      for (size_t i = 0; i < kps.size(); ++i)
-        if (!before(cut, std::make_pair(kps[i].response, (int)i))) {
-          if (min_depth) zmin[m] = zmin[i];
-          kps[m++] = kps[i];
-        }
-      kps.resize(m);
-      if (min_depth) zmin.resize(m);
-    }
+    auto depth_at = [this](int r, int c) { return depth_px(r, c); };
+    remove_depthless_and_cut(kps, min_depth ? &zmin : nullptr, depth_at, rows, cols, max_kp);  // node.cpp:186-191
     // cv::ORB::compute (node.cpp:202) drops border keypoints and regroups the rest by octave, so projectTo3D
     // (node.cpp:210) is enqueued from inside compute_enqueue(), once the final keypoint list exists: both ride on one
     // synchronisation.  xy (2n floats) + depth.at<float>(round(y), round(x)) (n floats, node.cpp:942): 12 bytes per
@@ -655,18 +618,7 @@ struct DetectFrame {
         xyz_in_big.resize((size_t)n * 3); xyz_out_big.resize((size_t)n * 4);
         xyz_in = xyz_in_big.data(); xyz_out = xyz_out_big.data();
       }
-      for (int i = 0; i < n; ++i) {
-        xyz_in[2 * i] = kps[i].x;
-        xyz_in[2 * i + 1] = kps[i].y;
-        if (min_depth) {  // node.cpp:940-941: the same neighbourhood depth as in removeDepthless
-          xyz_in[(size_t)2 * n + i] = zmin[(size_t)order[(size_t)i]];
-          continue;
-        }
-        int r = (int)roundf(kps[i].y), c = (int)roundf(kps[i].x);
-        r = r >= rows ? rows - 1 : r;
-        c = c >= cols ? cols - 1 : c;
-        xyz_in[(size_t)2 * n + i] = depth_px(r, c);
-      }
+      depth_lookups(kps, min_depth ? &zmin : nullptr, order, depth_at, rows, cols, xyz_in);
       if (hipMemcpyAsync(orb.d_kpxy, xyz_in, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess)
         return RGBDFE_ERR_HIP;
       launch_project_to_3d(orb.d_kpxy, n, nullptr, rows, cols, (float)(1. / fx), (float)(1. / fy), (float)cx,
@@ -703,6 +655,17 @@ struct DetectFrame {
     if (tm) orb.timing.frames++;
     return RGBDFE_OK;
   }
+
+  // a single call: the three stages back to back on the context's stream (the images are set already)
+  int run_alone(rgbdfe_ctx* c, double fx_, double fy_, double cx_, double cy_, double scaling, rgbdfe_keypoint* kp_out,
+                uint8_t* desc_out, float* xyz_out_, int32_t* n) {
+    ctx = c; fx = fx_; fy = fy_; cx = cx_; cy = cy_; depth_scaling = scaling;
+    keypoints = kp_out; descriptors = desc_out; xyz1 = xyz_out_; n_out = n;
+    int rc = detect(false, nullptr);
+    if (rc == RGBDFE_OK) rc = describe_enqueue(ctx->stream);
+    if (rc == RGBDFE_OK) rc = finish(ctx->stream);
+    return rc;
+  }
 };
 
 int rgbdfe_detect_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, const float* depth,
@@ -718,13 +681,8 @@ int rgbdfe_detect_describe(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* 
     return fast_detect_describe(ctx, 1, &gray, &mask, &depth, rows, cols, fx, fy, cx, cy, depth_scaling, ctx->orb_max_keypoints,
                                 keypoints, descriptors, xyz1, n_out, nullptr);
   DetectFrame fr;
-  fr.ctx = ctx; fr.gray = gray; fr.mask = mask; fr.depth = depth; fr.rows = rows; fr.cols = cols;
-  fr.fx = fx; fr.fy = fy; fr.cx = cx; fr.cy = cy; fr.depth_scaling = depth_scaling;
-  fr.keypoints = keypoints; fr.descriptors = descriptors; fr.xyz1 = xyz1; fr.n_out = n_out;
-  int rc = fr.detect(false, nullptr);
-  if (rc == RGBDFE_OK) rc = fr.describe_enqueue(ctx->stream);
-  if (rc == RGBDFE_OK) rc = fr.finish(ctx->stream);
-  return rc;
+  fr.gray = gray; fr.mask = mask; fr.depth = depth; fr.rows = rows; fr.cols = cols;
+  return fr.run_alone(ctx, fx, fy, cx, cy, depth_scaling, keypoints, descriptors, xyz1, n_out);
 }
 
 // rgbdfe_detect_describe on frame 0 of a sensor run (the ORB type; the caller holds the lock, has set the device, ensured
@@ -733,13 +691,8 @@ int detect_describe_sensor_frame(rgbdfe_ctx* ctx, const SensorRun& run, double f
                                  double depth_scaling, rgbdfe_keypoint* keypoints, uint8_t* descriptors, float* xyz1,
                                  int32_t* n_out) {
   DetectFrame fr;
-  fr.ctx = ctx; fr.sensor = &run; fr.sframe = 0; fr.depth_set = 0; fr.rows = run.H; fr.cols = run.W;
-  fr.fx = fx; fr.fy = fy; fr.cx = cx; fr.cy = cy; fr.depth_scaling = depth_scaling;
-  fr.keypoints = keypoints; fr.descriptors = descriptors; fr.xyz1 = xyz1; fr.n_out = n_out;
-  int rc = fr.detect(false, nullptr);
-  if (rc == RGBDFE_OK) rc = fr.describe_enqueue(ctx->stream);
-  if (rc == RGBDFE_OK) rc = fr.finish(ctx->stream);
-  return rc;
+  fr.sensor = &run; fr.sframe = 0; fr.depth_set = 0; fr.rows = run.H; fr.cols = run.W;
+  return fr.run_alone(ctx, fx, fy, cx, cy, depth_scaling, keypoints, descriptors, xyz1, n_out);
 }
 
 int detect_aggregate(rgbdfe_ctx* ctx, const uint8_t* gray, const uint8_t* mask, int32_t rows, int32_t cols,
@@ -781,16 +734,17 @@ constexpr int kSuperFrames = 7;   // frames per super-frame at least (large fram
 // B = 64 / grid^2 (7 for the 3 x 3 grid) frames share every launch: one upload, one pyramid chain (7 launches), one blur,
 // one detection pass (FAST score -> NMS count -> scan -> emit -> measure) over 7 x 72 images, one rBRIEF launch -- a frame
 // alone is 1.7 M pixels and cannot fill 256 CUs, and its 27 dependent device operations cost 5-15 us each whatever their
-// size.  Frames stay sequentially dependent through the per-cell FAST thresholds: OrbWorkspace::super_detect runs the
-// device pass at a floor threshold and replays the reference's adjuster over the scored corners frame by frame (identical
-// keypoints: see select_pass).  The per-frame CPU work that does not touch the HIP runtime (removeDepthless, retainBest,
+// size.  Frames stay sequentially dependent through the per-cell FAST thresholds: the device pass runs at a floor threshold
+// and OrbWorkspace::super_replay replays the reference's adjuster over the scored corners frame by frame (identical
+// keypoints: see orb_replay.h select_cell).  The per-frame CPU work that does not touch the HIP runtime (removeDepthless, retainBest,
 // cv::ORB::compute's border filter / regroup / descriptor records, the depth look-ups) runs on worker threads while the
 // calling thread drives the next super-frame's pass.
 namespace {
 
 struct SuperFrameJob {  // one frame of a super-frame, between detection and copy-out
   bool deferred = false;              // the frame's keypoints are still to be selected from the pass's corners (select_frame)
-  OrbWorkspace::PassView pv;
+  GridDetector det;                   // ... of this detector (its mask flags are the calling thread's: not read here)
+  PassView pv;
   std::vector<int> thr;               // every (frame, cell)'s final threshold of the super-frame
   std::vector<KpOut> kps;
   std::vector<int> order;
@@ -803,43 +757,12 @@ struct SuperFrameJob {  // one frame of a super-frame, between detection and cop
 // projectTo3D's depth look-ups (node.cpp:942) for one frame: DetectFrame::describe_enqueue's host work, no HIP calls
 void super_describe_prepare(const OrbWorkspace& orb, SuperFrameJob& j, int frame_in_super, const float* depth, int rows,
                             int cols, int max_kp, const SensorRun* sensor = nullptr, int sframe = 0) {
-  std::vector<KpOut>& kps = j.kps;
   auto depth_px = [&](int r, int c) { return sensor ? sensor->depth_at(sframe, r, c) : depth[(size_t)r * cols + c]; };
-  if (j.deferred) orb.select_frame(j.pv, frame_in_super, j.thr.data(), kps);
-  size_t m = 0;
-  for (const KpOut& k : kps) {
-    if (k.x >= (float)cols || k.x < 0 || k.y >= (float)rows || k.y < 0 || std::isnan(k.x) || std::isnan(k.y)) continue;
-    int r = (int)roundf(k.y), c = (int)roundf(k.x);
-    r = r >= rows ? rows - 1 : r;
-    c = c >= cols ? cols - 1 : c;
-    if (std::isnan(depth_px(r, c))) continue;
-    kps[m++] = k;
-  }
-  kps.resize(m);
-  if ((int)kps.size() > max_kp) {  // the max_kp first of the order (response descending, position ascending), in place
-    std::vector<std::pair<float, int>> r(kps.size());
-    for (size_t i = 0; i < kps.size(); ++i) r[i] = std::make_pair(kps[i].response, (int)i);
-    auto before = [](const std::pair<float, int>& a, const std::pair<float, int>& b) {
-      return a.first > b.first || (a.first == b.first && a.second < b.second);
-    };
-    std::nth_element(r.begin(), r.begin() + (max_kp - 1), r.end(), before);
-    const std::pair<float, int> cut = r[(size_t)max_kp - 1];
-    m = 0;
-    for (size_t i = 0; i < kps.size(); ++i)
-      if (!before(cut, std::make_pair(kps[i].response, (int)i))) kps[m++] = kps[i];
-    kps.resize(m);
-  }
-  orb.compute_prepare(kps, frame_in_super, j.order, j.dk);
-  const int n = (int)kps.size();
-  j.xyz_in.resize((size_t)n * 3);
-  for (int i = 0; i < n; ++i) {
-    j.xyz_in[(size_t)2 * i] = kps[i].x;
-    j.xyz_in[(size_t)2 * i + 1] = kps[i].y;
-    int r = (int)roundf(kps[i].y), c = (int)roundf(kps[i].x);
-    r = r >= rows ? rows - 1 : r;
-    c = c >= cols ? cols - 1 : c;
-    j.xyz_in[(size_t)2 * n + i] = depth_px(r, c);
-  }
+  if (j.deferred) select_frame(j.det, j.pv, frame_in_super, j.thr.data(), j.kps);
+  remove_depthless_and_cut(j.kps, nullptr, depth_px, rows, cols, max_kp);
+  orb.compute_prepare(j.kps, frame_in_super, j.order, j.dk);
+  j.xyz_in.resize(j.kps.size() * 3);
+  depth_lookups(j.kps, nullptr, j.order, depth_px, rows, cols, j.xyz_in.data());
 }
 
 int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t* const* gray, const uint8_t* const* mask,
@@ -870,12 +793,7 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
     rc = sensor_ensure(ctx, OrbWorkspace::kStages, OrbWorkspace::kSets, sensor->frame_bytes * (size_t)B, 0, 0);
     if (rc != RGBDFE_OK) return rc;
   }
-  if (!ctx->orb_upload_stream) {
-    HIP_TRY(ctx, create_side_stream(&ctx->orb_upload_stream, -1));   // uploads + pyramids: behind everything else
-    HIP_TRY(ctx, create_side_stream(&ctx->orb_compute_stream, +1));  // descriptions: short, the host waits for them
-    for (hipEvent_t& e : ctx->orb_upload_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (hipEvent_t& e : ctx->orb_describe_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  if ((rc = ensure_orb_streams(ctx)) != RGBDFE_OK) return rc;
   hipStream_t up = ctx->orb_upload_stream, st2 = ctx->orb_compute_stream;
   const int max_kp = ctx->orb_max_keypoints;
   if (node_ids) {
@@ -901,69 +819,31 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
   // s - NS (the buffer's previous user) has been detected (its upload from that buffer is complete then)
   const int NS = std::max(D + 1, std::min((int)OrbWorkspace::kStages,
                                           getenv("RGBDFE_SUPER_STAGES") ? atoi(getenv("RGBDFE_SUPER_STAGES")) : (int)OrbWorkspace::kStages));
-  std::mutex m;
-  std::condition_variable cv;
-  int staged = 0, detected = 0;
-  bool stop = false;
-  static const int stage_threads = getenv("RGBDFE_STAGE_THREADS") ? std::max(1, atoi(getenv("RGBDFE_STAGE_THREADS"))) : 4;
-  if (!ctx->stage_pool) ctx->stage_pool.reset(new TaskPool(stage_threads));
   // (the frames' CPU halves: a worker per frame up to RGBDFE_DETECT_WORKERS workers, the frames queue behind them)
   static const int max_workers = getenv("RGBDFE_DETECT_WORKERS") ? std::max(1, atoi(getenv("RGBDFE_DETECT_WORKERS"))) : 14;   // (a worker per frame of a 14-frame super-frame; 7 / 12 / 14 workers: 20.6 / 20.3 / 21.2 k frames/s, four alternating runs each)
   const int n_workers = std::min(B, max_workers);
   if (!ctx->detect_pool || ctx->detect_pool->size() != n_workers) ctx->detect_pool.reset(new TaskPool(n_workers));
-  TaskPool& stage_pool = *ctx->stage_pool;
+  TaskPool& copy_pool = stage_pool(ctx);
   TaskPool& pool = *ctx->detect_pool;
   pool.failed_ = false;
-  std::thread helper([&]() {
-    for (int s = 0; s < S; ++s) {
-      {
-        std::unique_lock<std::mutex> l(m);
-        cv.wait(l, [&] { return stop || detected >= s - NS + 1; });
-        if (stop) return;
+  StagingRing ring(S, NS, [&](int s) {
+    // (2 W H bytes per frame through one core's memcpy would bound the whole pipeline: 75 us per 640 x 480 frame)
+    for (int k = 0; k < count_of(s); ++k) {
+      const int f = first_of(s) + k;
+      if (sensor) {  // the raw bytes, nothing else: the ingest kernel behind the upload makes the planes
+        uint8_t* dst = ctx->sensor.h_raw[s % NS] + (size_t)k * sensor->frame_bytes;
+        copy_pool.submit([sensor, f, dst] { sensor->stage(f, dst); });
+        continue;
       }
-      // (2 W H bytes per frame through one core's memcpy would bound the whole pipeline: 75 us per 640 x 480 frame)
-      for (int k = 0; k < count_of(s); ++k) {
-        const int f = first_of(s) + k;
-        if (sensor) {  // the raw bytes, nothing else: the ingest kernel behind the upload makes the planes
-          uint8_t* dst = ctx->sensor.h_raw[s % NS] + (size_t)k * sensor->frame_bytes;
-          stage_pool.submit([sensor, f, dst] { sensor->stage(f, dst); });
-          continue;
-        }
-        stage_pool.submit([&orb, &gray, &mask, f, s, k, NS] { orb.stage_image_at(gray[f], mask ? mask[f] : nullptr, s % NS, k); });
-      }
-      stage_pool.wait_all();
-      std::lock_guard<std::mutex> l(m);
-      staged = s + 1;
-      cv.notify_all();
+      copy_pool.submit([&orb, &gray, &mask, f, s, k, NS] { orb.stage_image_at(gray[f], mask ? mask[f] : nullptr, s % NS, k); });
     }
+    copy_pool.wait_all();
   });
-  struct HelperJoin {
-    std::thread& th; std::mutex& m; std::condition_variable& cv; bool& stop;
-    ~HelperJoin() {
-      { std::lock_guard<std::mutex> l(m); stop = true; }
-      cv.notify_all();
-      if (th.joinable()) th.join();
-    }
-  } helper_join{helper, m, cv, stop};
-  // how the host replays the adjuster over a super-frame's scored corners: 1 (default) from counts on the calling thread, the
-  // selections themselves inside the frames' description jobs; 2 = per-cell chains + per-frame merges on the worker pool
-  // while the calling thread waits; 0 = the sequential loop
-  static const int replay_mode = getenv("RGBDFE_SUPER_PARALLEL_REPLAY") ? atoi(getenv("RGBDFE_SUPER_PARALLEL_REPLAY")) : 1;
-  static const bool par_replay = replay_mode == 2;
-  struct ParallelForGuard {  // the workspace outlives the pool
-    OrbWorkspace& o;
-    ~ParallelForGuard() { o.parallel_for = nullptr; }
-  } pf_guard{orb};
-  if (par_replay) orb.parallel_for = [&pool](int n, const std::function<void(int)>& fn) { pool.parallel_for(n, fn); };
-  else orb.parallel_for = nullptr;
   std::vector<SuperFrameJob> jobs[2];
   jobs[0].resize((size_t)B); jobs[1].resize((size_t)B);
   int n_tot[2] = {0, 0};
   auto enqueue_upload = [&](int s) -> int {
-    {
-      std::unique_lock<std::mutex> l(m);
-      cv.wait(l, [&] { return staged > s; });
-    }
+    ring.wait_staged(s);
     if (s >= D && hipStreamWaitEvent(up, ctx->orb_describe_done[s % D], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
     int r;
     if (sensor) {  // frame k's [gray | mask] pair at k * 2WH of the set's pool (orb_host.hip enqueue_staged_super)
@@ -1064,11 +944,11 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
     return RGBDFE_OK;
   };
   static const bool tm = getenv("RGBDFE_DETECT_TIMING") && atoi(getenv("RGBDFE_DETECT_TIMING")) != 0;
-  double t_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // mask scan, super_detect, hook: describe enqueue, hook: upload enqueue, finish, prepare start, pool wait
+  double t_us[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // mask scan, replay, hook: describe enqueue, hook: upload enqueue, finish, prepare start, pool wait
   double tq = tm ? orb_now_us() : 0;
   auto lap = [&](int i) { if (tm) { const double now = orb_now_us(); t_us[i] += now - tq; tq = now; } };
   orb.timing.on = tm;
-  const long passes0 = orb.super_passes;
+  const long passes0 = orb.device_passes;
   // Software pipeline: the device pass of super-frame s + 1 is enqueued BEFORE the host replays the adjuster over
   // super-frame s (its floors come from the thresholds of that moment; a cell that falls below its floor is re-run by
   // super_replay), so the device works on s + 1 while the host selects keypoints of s; description of s - 1 and the
@@ -1093,57 +973,33 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
       if (rc != RGBDFE_OK) break;
     }
     lap(3);
-    // hasNonZero(sub_mask) per (frame, cell) (feature_adjuster.cpp:175-183)
     orb.cell_mask_nonzero.assign((size_t)orb.n_cells, 1);
-    for (int k = 0; k < nf; ++k) {
-      if (sensor) {
-        for (int c9 = 0; c9 < pc; ++c9) {
-          const OrbWorkspace::Cell& ce = orb.cells[(size_t)k * pc + c9];
-          orb.cell_mask_nonzero[(size_t)k * pc + c9] = sensor->mask_nonzero(first_of(s) + k, ce.x0, ce.y0, ce.w, ce.h) ? 1 : 0;
-        }
-        continue;
-      }
-      const uint8_t* mk = mask ? mask[first_of(s) + k] : nullptr;
-      if (!mk) continue;
-      for (int c9 = 0; c9 < pc; ++c9) {
-        const OrbWorkspace::Cell& ce = orb.cells[(size_t)k * pc + c9];
-        char nz = 0;
-        for (int y = 0; y < ce.h && !nz; ++y) {
-          const uint8_t* r = mk + (size_t)(ce.y0 + y) * cols + ce.x0;
-          for (int x = 0; x < ce.w; ++x)
-            if (r[x]) { nz = 1; break; }
-        }
-        orb.cell_mask_nonzero[(size_t)k * pc + c9] = nz;
-      }
-    }
+    for (int k = 0; k < nf; ++k)
+      frame_mask_flags(sensor, first_of(s) + k, mask ? mask[first_of(s) + k] : nullptr, cols, orb.cells.data() + (size_t)k * pc, pc,
+                       orb.cell_mask_nonzero.data() + (size_t)k * pc);
     lap(0);
     std::vector<std::vector<KpOut>> kps;
     OrbWorkspace::Deferred def;
-    rc = orb.super_replay(nf, s % D, s % D, kps, ctx->stream, err, replay_mode == 1 ? &def : nullptr);
+    rc = orb.super_replay(nf, s % D, s % D, kps, ctx->stream, err, def);
     if (rc != RGBDFE_OK) break;
-    {
-      std::lock_guard<std::mutex> l(m);
-      detected = s + 1;
-    }
-    cv.notify_all();
+    ring.mark_consumed(s);   // (its upload from the staging buffer is complete)
     lap(1);
     if (s > 0) { rc = finish(s - 1); if (rc != RGBDFE_OK) break; }
     lap(4);
     for (int k = 0; k < nf; ++k) {
       SuperFrameJob& j = jobs[s & 1][(size_t)k];
       j.deferred = def.valid;
-      if (def.valid) { j.pv = def.pv; j.thr = def.thr_final; j.kps.clear(); }
+      if (def.valid) { j.det = orb.detector(); j.pv = def.pv; j.thr = def.thr_final; j.kps.clear(); }
       else j.kps.swap(kps[(size_t)k]);
     }
     start_prepare(s);
     lap(5);
   }
   if (tm) {
-    fprintf(stderr, "[rgbdfe super-frame timing] depth %d, replay mode %d (sequential fallbacks: %ld); ", D, replay_mode,
-            orb.replay_fallbacks);
+    fprintf(stderr, "[rgbdfe super-frame timing] depth %d (sequential fallbacks: %ld); ", D, orb.replay_fallbacks);
     fprintf(stderr, "[rgbdfe super-frame timing] %d frames in %d super-frames, %ld device passes; per frame (us): mask scan %.1f, "
             "replay incl. wait for its pass %.1f, describe enqueue %.1f, upload + next pass enqueue %.1f (re-passes: enqueue %.1f, "
-            "wait %.1f; selections %.1f), finish %.1f, prepare start %.1f\n", (int)n_frames, S, orb.super_passes - passes0,
+            "wait %.1f; selections %.1f), finish %.1f, prepare start %.1f\n", (int)n_frames, S, orb.device_passes - passes0,
             t_us[0] / n_frames, t_us[1] / n_frames, t_us[2] / n_frames, t_us[3] / n_frames, orb.timing.us[2] / n_frames,
             orb.timing.us[3] / n_frames, orb.timing.us[4] / n_frames, t_us[4] / n_frames, t_us[5] / n_frames);
     for (double& u : orb.timing.us) u = 0;
@@ -1157,12 +1013,7 @@ int detect_describe_batch_super(rgbdfe_ctx* ctx, int32_t n_frames, const uint8_t
   lap(7);
   if (tm) fprintf(stderr, "[rgbdfe super-frame timing] whole call (us): filling the pipeline (staging + upload + pass enqueue of the first "
                           "%d super-frames) %.0f, draining it (the last super-frame's description) %.0f\n", D - 1, t_us[6], t_us[7]);
-  {
-    std::lock_guard<std::mutex> l(m);
-    stop = true;
-    cv.notify_all();
-  }
-  if (helper.joinable()) helper.join();
+  ring.stop();
   (void)hipStreamSynchronize(up);
   (void)hipStreamSynchronize(ctx->stream);
   orb.use_set(0);
@@ -1250,12 +1101,7 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
   int rc = orb.prepare(cols, rows, true, err);
   if (rc == RGBDFE_OK) rc = orb.ensure_alt(err);
   if (rc != RGBDFE_OK) return fail(ctx, rc, err);
-  if (!ctx->orb_upload_stream) {
-    HIP_TRY(ctx, create_side_stream(&ctx->orb_upload_stream, -1));   // uploads + pyramids: behind everything else
-    HIP_TRY(ctx, create_side_stream(&ctx->orb_compute_stream, +1));  // descriptions: short, the host waits for them
-    for (hipEvent_t& e : ctx->orb_upload_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (hipEvent_t& e : ctx->orb_describe_done) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  if ((rc = ensure_orb_streams(ctx)) != RGBDFE_OK) return rc;
   hipStream_t up = ctx->orb_upload_stream;
   if (sensor) {  // frame f's raw bytes and float depth plane live in set f & 1 too
     rc = sensor_ensure(ctx, 2, 2, sensor->frame_bytes, ctx->feature_min_depth ? 2 : 0, (size_t)rows * cols);
@@ -1267,33 +1113,10 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
   // the calling thread's launches are the critical path.  The calling thread enqueues the device half of frame f + 2's
   // upload (one copy + the pyramid launches, on a second stream) from the hook of frame f + 1's detection pass, behind
   // frame f's description, which reads the same set.
-  std::mutex m;
-  std::condition_variable cv;
-  int staged = 0, detected = 0;  // frames staged by the helper / detected by the caller
-  bool stop = false;
-  std::thread helper([&]() {
-    for (int32_t f = 0; f < n_frames; ++f) {
-      {
-        std::unique_lock<std::mutex> l(m);
-        cv.wait(l, [&] { return stop || detected >= f - 1; });
-        if (stop) return;
-      }
-      if (sensor) sensor->stage(f, ctx->sensor.h_raw[f & 1]);
-      else orb.stage_images(gray[f], mask ? mask[f] : nullptr, f & 1);
-      std::lock_guard<std::mutex> l(m);
-      staged = f + 1;
-      cv.notify_all();
-    }
+  StagingRing ring(n_frames, 2, [&](int f) {
+    if (sensor) sensor->stage(f, ctx->sensor.h_raw[f & 1]);
+    else orb.stage_images(gray[f], mask ? mask[f] : nullptr, f & 1);
   });
-  // whatever happens below (an exception on its way to the ABI barrier included): the helper is told to stop and joined
-  struct HelperJoin {
-    std::thread& th; std::mutex& m; std::condition_variable& cv; bool& stop;
-    ~HelperJoin() {
-      { std::lock_guard<std::mutex> l(m); stop = true; }
-      cv.notify_all();
-      if (th.joinable()) th.join();
-    }
-  } helper_join{helper, m, cv, stop};
   // The calling thread: frame f + 1 is detected on ctx->stream (set (f + 1) & 1) while frame f is described on the second
   // stream (set f & 1) -- describe_enqueue(f) runs as the `before_wait` hook of frame f + 1's first detection pass, i.e.
   // its host work (removeDepthless, retainBest, the descriptor records) overlaps that pass's device time.
@@ -1309,10 +1132,7 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
     d.xyz1 = xyz1 + (size_t)f * out_stride * 4; d.n_out = n_out + f;
   };
   auto enqueue_upload = [&](int32_t f) -> int {  // the device half of frame f's upload, on `up`
-    {
-      std::unique_lock<std::mutex> l(m);
-      cv.wait(l, [&] { return staged > f; });
-    }
+    ring.wait_staged(f);
     // the set was frame f - 2's: its description (second stream) reads the pyramid this upload overwrites
     if (f >= 2 && hipStreamWaitEvent(up, ctx->orb_describe_done[f & 1], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
     int r;
@@ -1332,11 +1152,6 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
     if (hipStreamWaitEvent(ctx->stream, ctx->orb_upload_done[f & 1], 0) != hipSuccess) { err = "hipStreamWaitEvent"; return RGBDFE_ERR_HIP; }
     return RGBDFE_OK;
   };
-  auto mark_detected = [&](int32_t f) {
-    std::lock_guard<std::mutex> l(m);
-    detected = f + 1;
-    cv.notify_all();
-  };
   auto describe = [&](int32_t f) -> int {  // enqueue frame f's description on the second stream, from its own image set
     orb.use_set(f & 1);
     if (hipStreamWaitEvent(st2, ctx->orb_upload_done[f & 1], 0) != hipSuccess) return RGBDFE_ERR_HIP;
@@ -1353,7 +1168,7 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
     rc = fr[0].detect(true, n_frames > 1 ? std::function<int()>([&]() -> int { rc_up = enqueue_upload(1); return rc_up; })
                                          : std::function<int()>());
     if (rc != RGBDFE_OK && rc_up == RGBDFE_OK) err.clear();  // reported through fail()
-    if (rc == RGBDFE_OK) mark_detected(0);
+    if (rc == RGBDFE_OK) ring.mark_consumed(0);
   }
   for (int32_t f = 0; f < n_frames && rc == RGBDFE_OK; ++f) {
     if (f + 1 < n_frames) {
@@ -1361,16 +1176,10 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
       if (rc != RGBDFE_OK) break;
       init(fr[(size_t)((f + 1) & 1)], f + 1);
       orb.use_set((f + 1) & 1);
-      static const bool overlap = !(getenv("RGBDFE_DETECT_OVERLAP") && atoi(getenv("RGBDFE_DETECT_OVERLAP")) == 0);  // A/B switch
-      if (!overlap) {
-        rc = describe(f);
-        if (rc != RGBDFE_OK) { err.clear(); break; }
-        orb.use_set((f + 1) & 1);
-      }
       int rc_hook = RGBDFE_OK;
       bool hook_err_is_mine = false;
       rc = fr[(size_t)((f + 1) & 1)].detect(true, [&, f]() -> int {
-        if (overlap) rc_hook = describe(f);
+        rc_hook = describe(f);
         if (rc_hook == RGBDFE_OK && f + 2 < n_frames) {
           rc_hook = enqueue_upload(f + 2);
           hook_err_is_mine = rc_hook != RGBDFE_OK;
@@ -1379,7 +1188,7 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
         return rc_hook;
       });
       if (rc != RGBDFE_OK) { if (!hook_err_is_mine) err.clear(); break; }
-      mark_detected(f + 1);
+      ring.mark_consumed(f + 1);
     } else {
       rc = describe(f);
       if (rc != RGBDFE_OK) { err.clear(); break; }
@@ -1388,12 +1197,7 @@ static int detect_describe_batch_frames(rgbdfe_ctx* ctx, int32_t n_frames, const
     if (rc != RGBDFE_OK) { err.clear(); break; }
   }
   (void)hipStreamSynchronize(st2);
-  {
-    std::lock_guard<std::mutex> l(m);
-    stop = true;
-    cv.notify_all();
-  }
-  if (helper.joinable()) helper.join();
+  ring.stop();
   (void)hipStreamSynchronize(up);
   orb.use_set(0);
   if (rc != RGBDFE_OK) return err.empty() ? rc : fail(ctx, rc, err);

@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "rgbdfe_host.h"
+#include "staging_ring.h"
 
 #include "orb_pattern.inc"  // kOrbBitPattern31
 
@@ -249,48 +250,15 @@ int FastCall::run(std::string& err) {
     }
     if (pool) pool->wait_all();
   };
-  // helper thread (runs of several chunks): stages chunk c once chunk c - K has been collected (its slot is free then)
-  std::mutex m;
-  std::condition_variable cv;
-  int staged = 0, collected = 0;
-  bool stop = false;
-  std::thread helper;
-  if (n_chunks > 1) {
-    static const int stage_threads = getenv("RGBDFE_STAGE_THREADS") ? std::max(1, atoi(getenv("RGBDFE_STAGE_THREADS"))) : 4;
-    if (!ctx->stage_pool) ctx->stage_pool.reset(new TaskPool(stage_threads));
-    TaskPool* pool = ctx->stage_pool.get();
-    helper = std::thread([&, pool]() {
-      for (int c = 0; c < n_chunks; ++c) {
-        {
-          std::unique_lock<std::mutex> l(m);
-          cv.wait(l, [&] { return stop || collected >= c - K + 1; });
-          if (stop) return;
-        }
-        stage(c, pool);
-        std::lock_guard<std::mutex> l(m);
-        staged = c + 1;
-        cv.notify_all();
-      }
-    });
-  }
-  struct HelperJoin {
-    std::thread& th; std::mutex& m; std::condition_variable& cv; bool& stop;
-    ~HelperJoin() {
-      { std::lock_guard<std::mutex> l(m); stop = true; }
-      cv.notify_all();
-      if (th.joinable()) th.join();
-    }
-  } helper_join{helper, m, cv, stop};
+  // runs of several chunks: a helper thread stages chunk c once chunk c - K has been collected (its slot is free then)
+  TaskPool* const copy_pool = n_chunks > 1 ? &stage_pool(ctx) : nullptr;
+  StagingRing ring(n_chunks > 1 ? n_chunks : 0, K, [&](int c) { stage(c, copy_pool); });
   const size_t ms = (size_t)ctx->cfg.max_keypoints;
   auto enqueue = [&](int c) -> int {
     FastWorkspace::Slot& s = fw.slot[c % K];
     const int nf = count_of(c), f0 = first_of(c);
-    if (n_chunks > 1) {
-      std::unique_lock<std::mutex> l(m);
-      cv.wait(l, [&] { return staged > c; });
-    } else {
-      stage(c, nullptr);
-    }
+    if (n_chunks > 1) ring.wait_staged(c);
+    else stage(c, nullptr);
     bool any_mask = false;
     for (int k = 0; k < nf; ++k) any_mask = any_mask || s.h_has_mask[k];
     // where the outputs go; nodes are registered before anything can fail (no slot goes missing), their counts at collect()
@@ -387,9 +355,7 @@ int FastCall::run(std::string& err) {
       }
       if (hipGetLastError() != hipSuccess) { err = "hamming expand"; return RGBDFE_ERR_HIP; }
     }
-    std::lock_guard<std::mutex> l(m);
-    collected = c + 1;
-    cv.notify_all();
+    ring.mark_consumed(c);
     return RGBDFE_OK;
   };
   for (int c = 0; c < n_chunks && rc == RGBDFE_OK; ++c) {
@@ -397,12 +363,7 @@ int FastCall::run(std::string& err) {
     if (rc == RGBDFE_OK) rc = enqueue(c);
   }
   for (int c = std::max(0, n_chunks - K); c < n_chunks && rc == RGBDFE_OK; ++c) rc = collect(c);
-  {
-    std::lock_guard<std::mutex> l(m);
-    stop = true;
-    cv.notify_all();
-  }
-  if (helper.joinable()) helper.join();
+  ring.stop();
   (void)hipStreamSynchronize(up);
   (void)hipStreamSynchronize(st);
   if (rc != RGBDFE_OK) return rc;

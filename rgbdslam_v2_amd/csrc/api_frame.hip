@@ -352,18 +352,10 @@ int rgbdfe_detect_describe_cloud(rgbdfe_ctx* ctx, const uint8_t* gray, const uin
   } else {
     rc = orb.prepare(cols, rows, true, err);
     if (rc != RGBDFE_OK) return fail(ctx, rc, err);
-    orb.cell_mask_nonzero.assign((size_t)orb.n_cells, mask ? 0 : 1);
-    if (mask)
-      for (int c = 0; c < orb.n_cells; ++c) {
-        const OrbWorkspace::Cell& ce = orb.cells[c];
-        char nz = 0;
-        for (int y = 0; y < ce.h && !nz; ++y) {
-          const uint8_t* r = mask + (size_t)(ce.y0 + y) * cols + ce.x0;
-          for (int x = 0; x < ce.w; ++x)
-            if (r[x]) { nz = 1; break; }
-        }
-        orb.cell_mask_nonzero[c] = nz;
-      }
+    orb.cell_mask_nonzero.assign((size_t)orb.n_cells, 1);
+    if (mask)  // hasNonZero(sub_mask) per cell (feature_adjuster.cpp:175-183)
+      cell_mask_flags(orb.cells.data(), orb.n_cells, orb.cell_mask_nonzero.data(),
+                      [&](const GridCell& ce) { return mask_nonzero(mask, cols, ce); });
     rc = orb.upload_and_build(gray, mask, ctx->stream, err);
     if (rc == RGBDFE_OK) rc = orb.grid_detect(kps, ctx->stream, err);
     if (rc != RGBDFE_OK) return fail(ctx, rc, err);

@@ -5,19 +5,15 @@
 #include <vector>
 
 #include "orb_internal.h"
+#include "orb_replay.h"
 
 namespace rgbdfe {
 
-struct KpOut {  // cv::KeyPoint fields in use
-  float x, y, size, angle, response;
-  int octave;
-};
-
 struct OrbWorkspace {
-  struct Cell { int x0, y0, w, h; };
-  // the read-back of one detection pass: per-image counts, their prefix, the scored corners
-  struct PassView { const int* totals = nullptr; const int* base = nullptr; const RawKp* raw = nullptr; };
-  // (see replay_counts)
+  using Cell = GridCell;
+  // a super-frame replayed from counts (orb_replay.h replay_counts): the pass and every (frame, cell)'s final threshold, from
+  // which whoever prepares a frame's description selects its keypoints (select_frame, any thread); !valid: the sequential
+  // loop ran instead and the keypoints are in kps_per_frame
   struct Deferred { bool valid = false; PassView pv; std::vector<int> thr_final; };
   ~OrbWorkspace();
   void release();
@@ -45,23 +41,22 @@ struct OrbWorkspace {
   bool blur_pending = false;        // upload_and_build left the blur to the first detection pass (single-call path)
   hipEvent_t ev_readback = nullptr;
   // A detection pass = gpu_pass (FAST + NMS + Harris + angle for every corner at the cells' thresholds, one round trip)
-  // + select_pass (orb.cpp computeKeyPoints' per-level selections on the host).  select_pass may ask for HIGHER thresholds
-  // than the gpu_pass ran with: the corners at threshold t are exactly the corners at any floor f <= t whose FAST score
-  // is >= t (see select_pass), which lets grid_detect serve two adjuster iterations from one round trip.
+  // + select_cell (orb.cpp computeKeyPoints' per-level selections on the host, orb_replay.h).  The selection may ask for
+  // HIGHER thresholds than the gpu_pass ran with: the corners at threshold t are exactly the corners at any floor f <= t
+  // whose FAST score is >= t (see select_cell), which lets one round trip serve two adjuster iterations, or several frames.
   int gpu_pass(const std::vector<int>& active, const std::vector<int>& thr, hipStream_t s, std::string& err);
-  void select_pass(const std::vector<int>& active, const std::vector<int>& thr, std::vector<std::vector<KpOut>>& out);
-  int detect_pass(const std::vector<int>& active, const std::vector<int>& thr,
-                  std::vector<std::vector<KpOut>>& out, hipStream_t s, std::string& err);
-  int grid_detect(std::vector<KpOut>& kps, hipStream_t s, std::string& err);
-  // super-frame workspace: the frames [0, nf) of the current image set in order (cell_mask_nonzero holds nf * grid^2 flags)
-  int super_detect(int nf, std::vector<std::vector<KpOut>>& kps_per_frame, hipStream_t s, std::string& err,
-                   const std::vector<int>* covered_floors = nullptr, Deferred* deferred = nullptr);
+  int detect_pass(int thr, std::vector<KpOut>& out, hipStream_t s, std::string& err);  // cv::ORB::detect on the one-cell workspace
+  // the detector over the frames [0, nf) of the current image set in order (cell_mask_nonzero holds nf * grid^2 flags):
+  // device passes as the adjuster needs them (orb_replay.h detect_frames; the floors and cells of a pass: orb_host.hip)
+  int detect_frames(int nf, std::vector<std::vector<KpOut>>& kps_per_frame, hipStream_t s, std::string& err, double floor_factor,
+                    bool active_only, const std::vector<int>* covered_floors = nullptr);
+  int grid_detect(std::vector<KpOut>& kps, hipStream_t s, std::string& err);  // one frame (the single-frame workspace)
   void compute_prepare(std::vector<KpOut>& kps, int frame, std::vector<int>& order, std::vector<DescKp>& dk) const;
   // software pipeline of the batch entry point: the device pass of super-frame s + 1 runs while the host replays the
   // adjuster over super-frame s -- a pass's outputs (counts + keypoints, device and pinned host side) exist twice
   int super_pass_enqueue(int nf, int set, int slot, hipStream_t s, std::string& err);
   int super_replay(int nf, int set, int slot, std::vector<std::vector<KpOut>>& kps_per_frame, hipStream_t s, std::string& err,
-                   Deferred* deferred = nullptr);
+                   Deferred& deferred);
   void use_slot(int slot);
   static constexpr int kSets = 3;  // image sets / pass slots of the super-frame pipeline (kSets - 1 passes ahead of the replay)
   uint8_t* d_passout_slot[kSets] = {}; uint8_t* h_passout_slot[kSets] = {};
@@ -75,21 +70,14 @@ struct OrbWorkspace {
   // copy threads ran)
   static constexpr int kStages = kSets + 3;
   uint8_t* himg_stage[kStages] = {};
-  // optional: runs fn(0) .. fn(n - 1) on several threads and returns when all are done (the batch entry point's worker
-  // pool); the replay then runs the per-cell adjuster chains and the per-frame merges through it -- pure host code
-  std::function<void(int, const std::function<void(int)>&)> parallel_for;
   PassView current_pass() const { PassView v; v.totals = h_totals; v.base = h_base; v.raw = pass_raw; return v; }
-  void select_cell(const PassView& pv, int c, int t, std::vector<KpOut>& out) const;   // select_pass for one cell at threshold t
-  // A super-frame whose one pass covers every frame is replayed from COUNTS: the adjuster only needs how many keypoints a
-  // cell would return at a threshold (replay_counts); the selections themselves -- select_cell at each cell's final
-  // threshold, keepStrongest, the aggregate -- are left to whoever prepares the frame's description (select_frame, any thread).
-  int replay_counts(int nf, const std::vector<int>& floors, const PassView& pv, std::vector<int>& thr_final);
-  void select_frame(const PassView& pv, int frame, const int* thr_final, std::vector<KpOut>& kps) const;
-  int count_cell(const PassView& pv, int c, int t, bool* capped) const;
-  int replay_chains(int nf, const std::vector<int>& floors, std::vector<std::vector<KpOut>>& kps_per_frame);
+  // the detector as orb_replay.h sees it (pointers into cells / cell_mask_nonzero: valid until the next prepare())
+  GridDetector detector() const {
+    return GridDetector{grid * grid, cell_min, cell_max, max_total, adjuster_iters, cells.data(), cell_mask_nonzero.data()};
+  }
   long replay_fallbacks = 0;  // super-frames whose replay needed another device pass (diagnostics)
   double super_floor_factor = 0.49;  // floor of a super-frame pass = threshold x this (two x0.7 steps)
-  long super_passes = 0;             // device passes run by super_detect (diagnostics)
+  long device_passes = 0;            // detection passes run or enqueued (diagnostics)
   // enqueue_more (optional) is called after the descriptor work has been enqueued and before the one synchronisation,
   // so that the caller's own launches on the stream ride on the same round trip
   int compute(std::vector<KpOut>& kps, std::vector<uint8_t>& desc, hipStream_t s, std::string& err,
@@ -106,7 +94,7 @@ struct OrbWorkspace {
 
   // detector state (the reference's detector_ object, openni_listener.h:195)
   int grid = 3, adjuster_iters = 5, cell_min = 0, cell_max = 0, max_total = 0;
-  bool lookahead = true;  // grid_detect: one device pass per two adjuster iterations (RGBDFE_DETECT_LOOKAHEAD=0: off)
+  bool lookahead = true;  // one frame: one device pass per two adjuster iterations (RGBDFE_DETECT_LOOKAHEAD=0: off)
   double thresh[64];
   std::vector<char> cell_mask_nonzero;
   // geometry
@@ -160,7 +148,5 @@ struct OrbWorkspace {
     // 5 adjuster + cell merge, 6 removeDepthless + retainBest, 7 compute host prep + enqueue, 8 compute wait, 9 copy-out
   } timing;
 };
-
-double orb_now_us();
 
 }  // namespace rgbdfe

@@ -11,7 +11,6 @@
 
 #include "orb_host.h"
 
-#include <chrono>
 #include <functional>
 #include <mutex>
 #include <cstdio>
@@ -21,21 +20,10 @@ namespace rgbdfe {
 
 namespace {
 
-constexpr int kLevels = 8;           // ORB nlevels
+constexpr int kLevels = kOrbLevels;
 constexpr int kDetectEdge = 15;      // ORB::create(10000, 1.2, 8, 15, ...)   feature_adjuster.cpp:94
 constexpr int kComputeEdge = 31;     // ORB::create() default edgeThreshold    features.cpp:118
-constexpr int kDetectFeatures = 10000;
-
-inline int cv_round_f(float v) { return (int)lrintf(v); }
-
-void level_geometry(int cols, int rows, int nlevels, float* scale, int* lw, int* lh) {
-  const double scaleFactor = (double)1.2f;
-  for (int l = 0; l < nlevels; ++l) {
-    scale[l] = (float)std::pow(scaleFactor, (double)l);
-    lw[l] = cv_round_f((float)cols / scale[l]);
-    lh[l] = cv_round_f((float)rows / scale[l]);
-  }
-}
+static_assert(RGBDFE_OK == 0, "orb_replay.h detect_frames: 0 = the pass succeeded");
 
 #define ORB_HIP(expr)                                   \
   do {                                                  \
@@ -43,55 +31,7 @@ void level_geometry(int cols, int rows, int nlevels, float* scale, int* lw, int*
     if (_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return RGBDFE_ERR_HIP; } \
   } while (0)
 
-struct KP {  // cv::KeyPoint fields in use
-  float x, y, size, angle, response;
-  int octave;
-  float score;  // FAST score (first retainBest)
-};
-
-// KeyPointsFilter::retainBest: keep everything >= the n-th largest response; survivors keep their order
-template <typename F>
-void retain_best(std::vector<KP>& v, int n_points, F key) {
-  if (n_points < 0 || (int)v.size() <= n_points) return;
-  if (n_points == 0) { v.clear(); return; }
-  static thread_local std::vector<float> r;  // scratch: 144 selections per detection pass
-  r.resize(v.size());
-  for (size_t i = 0; i < v.size(); ++i) r[i] = key(v[i]);
-  std::nth_element(r.begin(), r.begin() + (n_points - 1), r.end(), [](float a, float b) { return a > b; });
-  const float ambiguous = r[n_points - 1];
-  size_t m = 0;
-  for (size_t i = 0; i < v.size(); ++i)
-    if (key(v[i]) >= ambiguous) v[m++] = v[i];
-  v.resize(m);
-}
-
-// exactly N strongest by key (descending), ties by original order; survivors keep their order
-template <typename F>
-void keep_strongest(std::vector<KP>& v, int N, F key) {
-  if ((int)v.size() <= N) return;
-  if (N <= 0) { v.clear(); return; }
-  // the N-th element of the order (key descending, position ascending) is the cut: a selection, not a sort
-  static thread_local std::vector<std::pair<float, int>> r;
-  r.resize(v.size());
-  for (size_t i = 0; i < v.size(); ++i) r[i] = std::make_pair(key(v[i]), (int)i);
-  auto before = [](const std::pair<float, int>& a, const std::pair<float, int>& b) {
-    return a.first > b.first || (a.first == b.first && a.second < b.second);
-  };
-  std::nth_element(r.begin(), r.begin() + (N - 1), r.end(), before);
-  const std::pair<float, int> cut = r[(size_t)N - 1];
-  size_t m = 0;
-  for (size_t i = 0; i < v.size(); ++i) {
-    const std::pair<float, int> me = std::make_pair(key(v[i]), (int)i);
-    if (!before(cut, me)) v[m++] = v[i];  // me is at or before the cut
-  }
-  v.resize(m);
-}
-
 }  // namespace
-
-double orb_now_us() {
-  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 OrbWorkspace::~OrbWorkspace() { release(); }
 
@@ -632,159 +572,55 @@ int OrbWorkspace::gpu_pass(const std::vector<int>& active, const std::vector<int
   return RGBDFE_OK;
 }
 
-// The host half: out[c] receives the cell's keypoints (level coordinates scaled to the cell image, cell-local) after
-// orb.cpp computeKeyPoints' per-level selection: retainBest(2*featuresNum) by FAST score, Harris responses,
-// retainBest(featuresNum).  thr[c] may be HIGHER than the threshold the latest gpu_pass ran the cell with: cv::FAST at
-// threshold t keeps the pixels whose best arc has min |difference| m > t that are strict 3x3 maxima of the score
-// m - 1 (non-corners count as 0).  A corner kept at t therefore has score >= t and beats every neighbour whose own score
-// is < t whether that neighbour counts as a corner (floor f <= its score) or as 0; and a pixel that loses against a
-// neighbour at the floor loses against the same neighbour at t when its own score is >= t (the neighbour's is larger
-// still).  So { corners at t } = { corners at f with score >= t }, in the same raster order; Harris response and angle
-// do not depend on the threshold.
-static void per_level_caps(int* per_level) {  // nfeaturesPerLevel (orb.cpp computeKeyPoints)
-  const float factor = (float)(1.0 / (double)1.2f);
-  float nd = kDetectFeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)kLevels));
-  int sum = 0;
-  for (int l = 0; l < kLevels - 1; ++l) { per_level[l] = cv_round_f(nd); sum += per_level[l]; nd *= factor; }
-  per_level[kLevels - 1] = std::max(kDetectFeatures - sum, 0);
+// cv::ORB::detect on the one-cell workspace: one pass at the threshold, computeKeyPoints' selections on the host
+int OrbWorkspace::detect_pass(int thr, std::vector<KpOut>& out, hipStream_t s, std::string& err) {
+  const int rc = gpu_pass({1}, {thr}, s, err);
+  if (rc == RGBDFE_OK) select_cell(cells[0], current_pass(), 0, thr, out);
+  return rc;
 }
 
-// How many keypoints select_cell(c, t) would return, without building them: per level the corners with score >= t -- exact as
-// long as no level reaches its retainBest cap (n <= nfeaturesPerLevel: neither retainBest(2n) nor retainBest(n) cuts, ties
-// included); *capped is set otherwise and the caller runs the selection itself.
-int OrbWorkspace::count_cell(const PassView& pv, int c, int thr_c, bool* capped) const {
-  int per_level[kLevels];
-  per_level_caps(per_level);
-  const int t = std::min(std::max(thr_c, 0), 255);
-  int found = 0;
-  for (int l = 0; l < kLevels; ++l) {
-    const int img = c * kLevels + l;
-    const RawKp* r = pv.raw + pv.base[img];
-    int n = 0;
-    for (int k = 0; k < pv.totals[img]; ++k) n += (int)r[k].score >= t ? 1 : 0;
-    if (n > per_level[l]) { *capped = true; return 0; }
-    found += n;
+// VideoGridAdaptedFeatureDetector::detect for the frames [0, nf) of the current image set in order (orb_replay.h
+// detect_frames), with the device passes it asks for.  A pass runs every (frame, cell) it covers at a FLOOR below the cell's
+// threshold -- the corners at threshold t are the corners at any floor f <= t whose score is >= t (select_cell) -- so that
+// it also holds what the adjuster is expected to ask for next:
+//   grid_detect, one frame: the still-active cells at the threshold their NEXT adjuster iteration would use (x0.7;
+//     `lookahead` off: at their threshold).  The second iteration of a cell that finds too few keypoints -- the common case
+//     on frames the thresholds have not settled on -- needs no second round trip.
+//   super_replay, a super-frame: every cell of the frames from f on, at super_floor_factor (two x0.7 steps).  A cell whose
+//     threshold drops below its floor (rare) triggers another pass, with floors from the thresholds of that moment.
+// covered_floors: a pass over all nf frames at these floors has been read back already.
+int OrbWorkspace::detect_frames(int nf, std::vector<std::vector<KpOut>>& kps_per_frame, hipStream_t s, std::string& err,
+                                double floor_factor, bool active_only, const std::vector<int>* covered_floors) {
+  const int pc = grid * grid;
+  PassCover cover;
+  cover.covered.assign((size_t)n_cells, 0);
+  cover.floors.assign((size_t)n_cells, 0);
+  if (covered_floors) {
+    for (int c = 0; c < nf * pc; ++c) { cover.covered[c] = 1; cover.floors[c] = (*covered_floors)[(size_t)c]; }
+    cover.pv = current_pass();
   }
-  return found;
-}
-
-void OrbWorkspace::select_cell(const PassView& pv, int c, int thr_c, std::vector<KpOut>& out) const {
-  // nfeaturesPerLevel (orb.cpp computeKeyPoints)
-  int per_level[kLevels];
-  {
-    const float factor = (float)(1.0 / (double)1.2f);
-    float nd = kDetectFeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)kLevels));
-    int sum = 0;
-    for (int l = 0; l < kLevels - 1; ++l) { per_level[l] = cv_round_f(nd); sum += per_level[l]; nd *= factor; }
-    per_level[kLevels - 1] = std::max(kDetectFeatures - sum, 0);
-  }
-  const int* totals = pv.totals;
-  const int* base = pv.base;
-  const RawKp* raw = pv.raw;
-  out.clear();
-  const int t = std::min(std::max(thr_c, 0), 255);  // the kernel's clamp
-  float sc[kLevels]; int lw[kLevels], lh[kLevels];
-  level_geometry(cells[c].w, cells[c].h, kLevels, sc, lw, lh);
-  for (int l = 0; l < kLevels; ++l) {
-    const int img = c * kLevels + l;
-    static thread_local std::vector<KP> v;  // scratch: 72 (cell, level) images per pass
-    v.clear();
-    v.reserve((size_t)totals[img]);
-    for (int k = 0; k < totals[img]; ++k) {
-      const RawKp& r = raw[(size_t)base[img] + k];
-      if ((int)r.score < t) continue;
-      v.push_back(KP{(float)r.x, (float)r.y, 31 * sc[l], r.angle, r.harris, l, (float)r.score});
+  auto pass = [&](int f, const std::vector<char>& active, PassCover& cv) -> int {
+    std::vector<int> in_pass((size_t)n_cells, 0);
+    for (int c = 0; c < n_cells; ++c) {
+      in_pass[c] = c / pc >= f && c / pc < nf && (!active_only || active[(size_t)(c % pc)]);
+      cv.covered[c] = (char)in_pass[c];
+      double next = thresh[c % pc] * floor_factor;  // tooFew (:131-136), floor_factor = 0.7: one step ahead
+      if (next < 2) next = 2;
+      cv.floors[c] = std::min((int)thresh[c % pc], (int)next);
     }
-    retain_best(v, 2 * per_level[l], [](const KP& k) { return k.score; });
-    retain_best(v, per_level[l], [](const KP& k) { return k.response; });
-    for (const KP& k : v) out.push_back(KpOut{k.x * sc[l], k.y * sc[l], k.size, k.angle, k.response, l});
-  }
+    device_passes++;
+    const int rc = gpu_pass(in_pass, cv.floors, s, err);
+    cv.pv = current_pass();
+    return rc;
+  };
+  return rgbdfe::detect_frames(detector(), nf, thresh, cover, pass, kps_per_frame, timing.on ? &timing.us[4] : nullptr);
 }
 
-void OrbWorkspace::select_pass(const std::vector<int>& active, const std::vector<int>& thr,
-                               std::vector<std::vector<KpOut>>& out) {
-  const double tp0 = timing.on ? orb_now_us() : 0;
-  const PassView pv = current_pass();
-  for (int c = 0; c < n_cells; ++c)
-    if (active[c]) select_cell(pv, c, thr[c], out[c]);
-  if (timing.on) timing.us[4] += orb_now_us() - tp0;
-}
-
-// One detection pass over the active cells with their current thresholds (cv::ORB::detect on one image).
-int OrbWorkspace::detect_pass(const std::vector<int>& active, const std::vector<int>& thr,
-                              std::vector<std::vector<KpOut>>& out, hipStream_t s, std::string& err) {
-  const int rc = gpu_pass(active, thr, s, err);
-  if (rc != RGBDFE_OK) return rc;
-  select_pass(active, thr, out);
-  return RGBDFE_OK;
-}
-
-// VideoGridAdaptedFeatureDetector::detect over the whole frame (feature_adjuster.cpp:286-317)
 int OrbWorkspace::grid_detect(std::vector<KpOut>& kps, hipStream_t s, std::string& err) {
-  std::vector<std::vector<KpOut>> cellkp((size_t)n_cells);
-  std::vector<int> active((size_t)n_cells, 1), iter_left((size_t)n_cells, adjuster_iters), thr((size_t)n_cells);
-  std::vector<char> checked((size_t)n_cells, 0);
-  // host copy of the mask is needed only for hasNonZero(): done lazily by the caller through mask_nonzero
-  // A device pass runs every active cell at the threshold its NEXT adjuster iteration would use (x0.7, below) and
-  // select_pass filters by score: the second iteration of a cell that finds too few keypoints -- the common case on
-  // frames the thresholds have not settled on -- needs no second round trip.  The corners are those of separate passes.
-  std::vector<int> floor_thr((size_t)n_cells, 0);
-  std::vector<char> covered((size_t)n_cells, 0);
-  bool any = true;
-  while (any) {
-    bool need_gpu = false;
-    for (int c = 0; c < n_cells; ++c) {
-      thr[c] = (int)thresh[c];  // static_cast<int>(thresh_)
-      if (active[c] && (!covered[c] || thr[c] < floor_thr[c])) need_gpu = true;
-    }
-    if (need_gpu) {
-      for (int c = 0; c < n_cells; ++c) {
-        covered[c] = (char)active[c];
-        double next = thresh[c] * 0.7;  // tooFew (:131-136)
-        if (next < 2) next = 2;
-        floor_thr[c] = lookahead ? std::min(thr[c], (int)next) : thr[c];
-      }
-      const int rc = gpu_pass(active, floor_thr, s, err);
-      if (rc != RGBDFE_OK) return rc;
-    }
-    select_pass(active, thr, cellkp);
-    any = false;
-    for (int c = 0; c < n_cells; ++c) {
-      if (!active[c]) continue;
-      const int found = (int)cellkp[c].size();
-      bool again = false;
-      // VideoDynamicAdaptedFeatureDetector::detect (feature_adjuster.cpp:185-224)
-      if (found < cell_min) {
-        thresh[c] *= 0.7;                       // tooFew (:131-136)
-        if (thresh[c] < 2) thresh[c] = 2;
-        bool brk = false;
-        if (found == 0 && !checked[c]) {
-          checked[c] = 1;
-          if (!cell_mask_nonzero[c]) brk = true;  // hasNonZero(mask) (:205-209)
-        }
-        if (!brk) {
-          iter_left[c]--;
-          again = iter_left[c] > 0 && (thresh[c] > 2 && thresh[c] < 10000);  // good() (:147-150)
-        }
-      } else if (found > cell_max) {
-        thresh[c] *= 1.3;                       // tooMany (:138-143)
-        if (thresh[c] > 10000) thresh[c] = 10000;
-      }
-      active[c] = again ? 1 : 0;
-      any |= again;
-    }
-  }
-  const int maxPerCell = max_total / (n_cells);  // :292
-  kps.clear();
-  for (int c = 0; c < n_cells; ++c) {
-    std::vector<KP> v;
-    v.reserve(cellkp[c].size());
-    for (const KpOut& k : cellkp[c]) v.push_back(KP{k.x, k.y, k.size, k.angle, k.response, k.octave, 0.f});
-    keep_strongest(v, maxPerCell, [](const KP& k) { return std::fabs(k.response); });  // :247-255
-    for (const KP& k : v)  // aggregateKeypointsPerGridCell (:259-282)
-      kps.push_back(KpOut{k.x + cells[c].x0, k.y + cells[c].y0, k.size, k.angle, k.response, k.octave});
-  }
-  return RGBDFE_OK;
+  std::vector<std::vector<KpOut>> per_frame;
+  const int rc = detect_frames(1, per_frame, s, err, lookahead ? 0.7 : 1.0, true);
+  if (rc == RGBDFE_OK) kps.swap(per_frame[0]);
+  return rc;
 }
 
 // The device half of a super-frame's detection pass, enqueued only (no wait): the frames [0, nf) of image set `set` at floor
@@ -825,14 +661,16 @@ int OrbWorkspace::super_pass_enqueue(int nf, int set, int slot, hipStream_t s, s
   if (!host_write)
     ORB_HIP(hipMemcpyAsync(hpo, dpo, passout_hdr + sizeof(RawKp) * (size_t)bound, hipMemcpyDeviceToHost, s));
   ORB_HIP(hipEventRecord(ev_pass[slot], s));
-  super_passes++;
+  device_passes++;
   return RGBDFE_OK;
 }
 
-// The host half: waits for the slot's pass, then replays the adjuster frame by frame exactly as super_detect does (see
-// there); re-passes (a threshold fell below its floor) run synchronously behind whatever the stream already holds.
+// The host half: waits for the slot's pass, then replays the adjuster over its frames -- from counts (orb_replay.h
+// replay_counts: the common case, `deferred` then tells whoever describes a frame how to select its keypoints), or, when a
+// threshold fell below its floor, through the sequential loop, which owns the re-passes; they run synchronously behind
+// whatever the stream already holds.  Same thresholds and keypoints either way, those of nf calls of grid_detect.
 int OrbWorkspace::super_replay(int nf, int set, int slot, std::vector<std::vector<KpOut>>& kps_per_frame, hipStream_t s,
-                               std::string& err, Deferred* deferred) {
+                               std::string& err, Deferred& deferred) {
   ORB_HIP(hipEventSynchronize(ev_pass[slot]));
   use_slot(slot);
   use_set(set);
@@ -851,252 +689,14 @@ int OrbWorkspace::super_replay(int nf, int set, int slot, std::vector<std::vecto
     ORB_HIP(hipStreamSynchronize(s));
     pass_raw = big.data();
   }
-  return super_detect(nf, kps_per_frame, s, err, &slot_floor[slot], deferred);
-}
-
-// VideoGridAdaptedFeatureDetector::detect for the frames [0, nf) of a super-frame, IN ORDER: frame f + 1 starts from the
-// per-cell thresholds frame f leaves behind (feature_adjuster.cpp:185-224), exactly as nf calls of grid_detect would.
-// What makes one device pass serve all of them: the corners at threshold t are the corners at any floor f <= t whose
-// score is >= t (select_pass), so the pass runs every (frame, cell) at a floor below the threshold it is expected to
-// end up with, and the adjuster is replayed on the host over the scored corners, frame by frame.  A cell whose threshold
-// drops below its floor (rare: two x0.7 steps inside one super-frame) triggers another pass over the frames from there
-// on, with floors taken from the thresholds of that moment -- results do not depend on the floors.
-// The replay of super_detect when one pass at `floors` covers every frame -- the common case -- as independent work items:
-// the adjuster of a grid cell only ever looks at its own cell (feature_adjuster.cpp:185-224 runs inside one cell's
-// detector object), so the grid^2 chains "cell c9 over frames 0 .. nf - 1" do not interact, and neither do the nf per-frame
-// merges (keepStrongest per cell + aggregate, :247-282) that follow.  Both run through parallel_for.  Returns 0 when a chain
-// met a threshold below its floor: nothing has been committed then, and super_detect's sequential loop (which owns the
-// re-pass logic) starts from the same state.  Same selections in the same order as that loop: identical keypoints.
-int OrbWorkspace::replay_chains(int nf, const std::vector<int>& floors, std::vector<std::vector<KpOut>>& kps_per_frame) {
-  const int pc = grid * grid;
-  std::vector<std::vector<KpOut>> cellkp((size_t)nf * pc);
-  std::vector<double> th_end((size_t)pc);
-  std::vector<char> failed((size_t)pc, 0);
-  const PassView pv = current_pass();
-  parallel_for(pc, [&](int c9) {
-    double th = thresh[c9];
-    for (int f = 0; f < nf && !failed[c9]; ++f) {
-      const int c = f * pc + c9;
-      int iter_left = adjuster_iters;
-      bool checked = false, active = true;
-      while (active) {
-        const int t = (int)th;  // static_cast<int>(thresh_)
-        if (t < floors[(size_t)c]) { failed[c9] = 1; break; }
-        select_cell(pv, c, t, cellkp[(size_t)c]);
-        const int found = (int)cellkp[(size_t)c].size();
-        bool again = false;
-        if (found < cell_min) {
-          th *= 0.7;                                 // tooFew (:131-136)
-          if (th < 2) th = 2;
-          bool brk = false;
-          if (found == 0 && !checked) {
-            checked = true;
-            if (!cell_mask_nonzero[(size_t)c]) brk = true;  // hasNonZero(mask) (:205-209)
-          }
-          if (!brk) {
-            iter_left--;
-            again = iter_left > 0 && (th > 2 && th < 10000);  // good() (:147-150)
-          }
-        } else if (found > cell_max) {
-          th *= 1.3;                                 // tooMany (:138-143)
-          if (th > 10000) th = 10000;
-        }
-        active = again;
-      }
-    }
-    th_end[(size_t)c9] = th;
-  });
-  for (int c9 = 0; c9 < pc; ++c9)
-    if (failed[c9]) return 0;
-  for (int c9 = 0; c9 < pc; ++c9) thresh[c9] = th_end[(size_t)c9];
+  const double tp0 = timing.on ? orb_now_us() : 0;
+  deferred.pv = current_pass();
+  deferred.valid = replay_counts(detector(), nf, slot_floor[slot].data(), deferred.pv, thresh, deferred.thr_final) != 0;
+  if (timing.on) timing.us[4] += orb_now_us() - tp0;
   kps_per_frame.assign((size_t)nf, std::vector<KpOut>());
-  const int maxPerCell = max_total / pc;  // :292
-  parallel_for(nf, [&](int f) {
-    std::vector<KpOut>& kps = kps_per_frame[(size_t)f];
-    std::vector<KP> v;
-    for (int c9 = 0; c9 < pc; ++c9) {
-      const int c = f * pc + c9;
-      v.clear();
-      v.reserve(cellkp[(size_t)c].size());
-      for (const KpOut& k : cellkp[(size_t)c]) v.push_back(KP{k.x, k.y, k.size, k.angle, k.response, k.octave, 0.f});
-      keep_strongest(v, maxPerCell, [](const KP& k) { return std::fabs(k.response); });  // :247-255
-      for (const KP& k : v)  // aggregateKeypointsPerGridCell (:259-282)
-        kps.push_back(KpOut{k.x + cells[c].x0, k.y + cells[c].y0, k.size, k.angle, k.response, k.octave});
-    }
-  });
-  return 1;
-}
-
-// The adjuster over the frames of a covered super-frame from counts alone (see orb_host.h): per grid cell the chain
-// "threshold -> keypoints found -> too few: x0.7 and again / too many: x1.3 for the next frame" (feature_adjuster.cpp:185-224)
-// needs `found` only, and found = the corners of the cell's 8 levels whose score is >= the threshold (count_cell; a level at
-// its retainBest cap falls back to the real selection).  thr_final[c] = the threshold of the LAST detection of (frame, cell)
-// c, the one whose keypoints the reference keeps.  Returns 0 -- nothing committed -- when a threshold falls below its floor.
-int OrbWorkspace::replay_counts(int nf, const std::vector<int>& floors, const PassView& pv, std::vector<int>& thr_final) {
-  const int pc = grid * grid;
-  thr_final.assign((size_t)n_cells, 0);
-  std::vector<double> th_end((size_t)pc);
-  std::vector<KpOut> scratch;
-  for (int c9 = 0; c9 < pc; ++c9) {
-    double th = thresh[c9];
-    for (int f = 0; f < nf; ++f) {
-      const int c = f * pc + c9;
-      int iter_left = adjuster_iters;
-      bool checked = false, active = true;
-      while (active) {
-        const int t = (int)th;  // static_cast<int>(thresh_)
-        if (t < floors[(size_t)c]) return 0;
-        thr_final[(size_t)c] = t;
-        bool capped = false;
-        int found = count_cell(pv, c, t, &capped);
-        if (capped) { select_cell(pv, c, t, scratch); found = (int)scratch.size(); }
-        bool again = false;
-        if (found < cell_min) {
-          th *= 0.7;                                 // tooFew (:131-136)
-          if (th < 2) th = 2;
-          bool brk = false;
-          if (found == 0 && !checked) {
-            checked = true;
-            if (!cell_mask_nonzero[(size_t)c]) brk = true;  // hasNonZero(mask) (:205-209)
-          }
-          if (!brk) {
-            iter_left--;
-            again = iter_left > 0 && (th > 2 && th < 10000);  // good() (:147-150)
-          }
-        } else if (found > cell_max) {
-          th *= 1.3;                                 // tooMany (:138-143)
-          if (th > 10000) th = 10000;
-        }
-        active = again;
-      }
-    }
-    th_end[(size_t)c9] = th;
-  }
-  for (int c9 = 0; c9 < pc; ++c9) thresh[c9] = th_end[(size_t)c9];
-  return 1;
-}
-
-// VideoGridAdaptedFeatureDetector::detect's output for one frame of a super-frame, given each cell's final threshold:
-// the cell's keypoints at that threshold (select_cell), keepStrongest(maxPerCell) (:247-255), cell offsets added and the cells
-// appended in order (aggregateKeypointsPerGridCell, :259-282).  Reads the pass view only: runs on any thread.
-void OrbWorkspace::select_frame(const PassView& pv, int frame, const int* thr_final, std::vector<KpOut>& kps) const {
-  const int pc = grid * grid;
-  const int maxPerCell = max_total / pc;  // :292
-  kps.clear();
-  std::vector<KpOut> cell;
-  std::vector<KP> v;
-  for (int c9 = 0; c9 < pc; ++c9) {
-    const int c = frame * pc + c9;
-    select_cell(pv, c, thr_final[c], cell);
-    v.clear();
-    v.reserve(cell.size());
-    for (const KpOut& k : cell) v.push_back(KP{k.x, k.y, k.size, k.angle, k.response, k.octave, 0.f});
-    keep_strongest(v, maxPerCell, [](const KP& k) { return std::fabs(k.response); });
-    for (const KP& k : v) kps.push_back(KpOut{k.x + cells[c].x0, k.y + cells[c].y0, k.size, k.angle, k.response, k.octave});
-  }
-}
-
-int OrbWorkspace::super_detect(int nf, std::vector<std::vector<KpOut>>& kps_per_frame, hipStream_t s, std::string& err,
-                               const std::vector<int>* covered_floors, Deferred* deferred) {
-  const int pc = grid * grid;
-  if (deferred) deferred->valid = false;
-  if (covered_floors && deferred) {
-    const double tp0 = timing.on ? orb_now_us() : 0;
-    deferred->pv = current_pass();
-    const int done = replay_counts(nf, *covered_floors, deferred->pv, deferred->thr_final);
-    if (timing.on) timing.us[4] += orb_now_us() - tp0;
-    if (done) {
-      deferred->valid = true;
-      kps_per_frame.assign((size_t)nf, std::vector<KpOut>());
-      return RGBDFE_OK;
-    }
-    replay_fallbacks++;
-  } else if (covered_floors && parallel_for) {
-    const double tp0 = timing.on ? orb_now_us() : 0;
-    const int done = replay_chains(nf, *covered_floors, kps_per_frame);
-    if (timing.on) timing.us[4] += orb_now_us() - tp0;
-    if (done) return RGBDFE_OK;
-    replay_fallbacks++;
-  }
-  std::vector<std::vector<KpOut>> cellkp((size_t)n_cells);
-  std::vector<int> act((size_t)n_cells, 0), thr((size_t)n_cells, 0), floor_thr((size_t)n_cells, 0);
-  std::vector<char> covered((size_t)n_cells, 0);
-  if (covered_floors)  // a pass over all nf frames at these floors has already been read back (super_replay)
-    for (int c = 0; c < n_cells && c / pc < nf; ++c) { covered[c] = 1; floor_thr[c] = (*covered_floors)[(size_t)c]; }
-  kps_per_frame.assign((size_t)nf, std::vector<KpOut>());
-  auto run_pass = [&](int f_from) -> int {
-    std::vector<int> pa((size_t)n_cells, 0);
-    for (int c = 0; c < n_cells; ++c) {
-      const int f = c / pc;
-      covered[c] = 0;
-      if (f < f_from || f >= nf) continue;
-      pa[c] = 1;
-      covered[c] = 1;
-      double next = thresh[c % pc] * super_floor_factor;
-      if (next < 2) next = 2;
-      floor_thr[c] = std::min((int)thresh[c % pc], (int)next);
-    }
-    super_passes++;
-    return gpu_pass(pa, floor_thr, s, err);
-  };
-  for (int f = 0; f < nf; ++f) {
-    std::vector<int> iter_left((size_t)pc, adjuster_iters);
-    std::vector<char> checked((size_t)pc, 0), active((size_t)pc, 1);
-    bool any = true;
-    while (any) {
-      bool need_gpu = false;
-      std::fill(act.begin(), act.end(), 0);
-      for (int c9 = 0; c9 < pc; ++c9) {
-        const int c = f * pc + c9;
-        thr[c] = (int)thresh[c9];  // static_cast<int>(thresh_)
-        act[c] = active[c9];
-        if (active[c9] && (!covered[c] || thr[c] < floor_thr[c])) need_gpu = true;
-      }
-      if (need_gpu) {
-        const int rc = run_pass(f);
-        if (rc != RGBDFE_OK) return rc;
-      }
-      select_pass(act, thr, cellkp);
-      any = false;
-      for (int c9 = 0; c9 < pc; ++c9) {
-        if (!active[c9]) continue;
-        const int c = f * pc + c9;
-        const int found = (int)cellkp[c].size();
-        bool again = false;
-        // VideoDynamicAdaptedFeatureDetector::detect (feature_adjuster.cpp:185-224)
-        if (found < cell_min) {
-          thresh[c9] *= 0.7;                       // tooFew (:131-136)
-          if (thresh[c9] < 2) thresh[c9] = 2;
-          bool brk = false;
-          if (found == 0 && !checked[c9]) {
-            checked[c9] = 1;
-            if (!cell_mask_nonzero[c]) brk = true;  // hasNonZero(mask) (:205-209)
-          }
-          if (!brk) {
-            iter_left[c9]--;
-            again = iter_left[c9] > 0 && (thresh[c9] > 2 && thresh[c9] < 10000);  // good() (:147-150)
-          }
-        } else if (found > cell_max) {
-          thresh[c9] *= 1.3;                       // tooMany (:138-143)
-          if (thresh[c9] > 10000) thresh[c9] = 10000;
-        }
-        active[c9] = again ? 1 : 0;
-        any |= again;
-      }
-    }
-    const int maxPerCell = max_total / pc;  // :292
-    std::vector<KpOut>& kps = kps_per_frame[(size_t)f];
-    for (int c9 = 0; c9 < pc; ++c9) {
-      const int c = f * pc + c9;
-      std::vector<KP> v;
-      v.reserve(cellkp[c].size());
-      for (const KpOut& k : cellkp[c]) v.push_back(KP{k.x, k.y, k.size, k.angle, k.response, k.octave, 0.f});
-      keep_strongest(v, maxPerCell, [](const KP& k) { return std::fabs(k.response); });  // :247-255
-      for (const KP& k : v)  // aggregateKeypointsPerGridCell (:259-282)
-        kps.push_back(KpOut{k.x + cells[c].x0, k.y + cells[c].y0, k.size, k.angle, k.response, k.octave});
-    }
-  }
-  return RGBDFE_OK;
+  if (deferred.valid) return RGBDFE_OK;
+  replay_fallbacks++;
+  return detect_frames(nf, kps_per_frame, s, err, super_floor_factor, false, &slot_floor[slot]);
 }
 
 // The CPU half of cv::ORB::compute for one frame of a super-frame (see compute_enqueue): border filter, regroup by level,

@@ -107,15 +107,6 @@ class TaskPool {  // a few persistent worker threads for pure-CPU jobs
     done_.wait(l, [&] { return pending_ == 0; });
   }
   int size() const { return (int)th_.size(); }
-  // fn(0) .. fn(n - 1), the caller working too; returns when all are done (and everything else in the queue)
-  void parallel_for(int n, const std::function<void(int)>& fn) {
-    std::atomic<int> next{0};
-    auto body = [&next, &fn, n] { for (;;) { const int i = next.fetch_add(1); if (i >= n) break; fn(i); } };
-    const int helpers = std::min(n - 1, size());
-    for (int h = 0; h < helpers; ++h) submit(body);
-    body();
-    wait_all();
-  }
  private:
   void run() {
     for (;;) {
@@ -351,6 +342,12 @@ struct rgbdfe_ctx {
 };
 
 namespace rgbdfe_host {
+// the copy threads behind the batch pipelines' staging helpers (StagingRing): RGBDFE_STAGE_THREADS of them, 4 by default
+inline TaskPool& stage_pool(rgbdfe_ctx* ctx) {
+  static const int n = getenv("RGBDFE_STAGE_THREADS") ? std::max(1, atoi(getenv("RGBDFE_STAGE_THREADS"))) : 4;
+  if (!ctx->stage_pool) ctx->stage_pool.reset(new TaskPool(n));
+  return *ctx->stage_pool;
+}
 // PairWork::pad bit 0 for a SIFT pair: dot products < 2^19 (Cauchy-Schwarz over the two nodes' squared norms) and at
 // most 32 column tiles of 32 on either side -- see sift_row_top2_kernel
 inline uint32_t sift_fast_keys(const rgbdfe_ctx* ctx, const NodeEntry& q, const NodeEntry& t) {

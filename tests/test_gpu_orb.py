@@ -256,6 +256,57 @@ def test_detect_describe_batch_equals_frame_by_frame(frames):
             assert np.array_equal(d1, d2) and np.array_equal(x1, x2)
 
 
+def test_detect_describe_batch_min_depth_equals_single_calls_and_oracle():
+    """use_feature_min_depth sends a batch through the frame pipeline (frame k + 1 detected while frame k is described), whose
+    removeDepthless then runs on the neighbourhood depths (the `zmin` compaction) before the max_keypoints cut: the batch, six
+    single calls and the oracle (orb_node_features + projectTo3D, both in min-depth mode) agree bit for bit, thresholds
+    included.  The depth has holes, so that on every frame removeDepthless drops keypoints and the cut still has work."""
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    n, mk = 6, 150
+    fr = synth.make_image_sequence(n_frames=n, seed=5, width=320, height=240)
+    K = (fr["fx"], fr["fy"], fr["cx"], fr["cy"])
+    rng = np.random.default_rng(5)
+    grays = [fr["gray"][f] for f in range(n)]
+    masks = [np.full(g.shape, 255, np.uint8) for g in grays]
+    depths = []
+    for f in range(n):
+        d = fr["depth"][f].copy()
+        d[rng.random(d.shape) < 0.2] = np.nan
+        d[60:140, 100:220] = np.nan
+        depths.append(d)
+    outs = []
+    for mode in ("single", "batch"):
+        fe = FrontEnd(device_id=0, max_nodes=2, max_keypoints=256, max_pairs_per_batch=8)
+        fe.detector_configure(max_keypoints=mk, grid_resolution=3)
+        fe.set_feature_min_depth(True)
+        if mode == "single":
+            res = [fe.detect_describe(g, m, d, *K) for g, m, d in zip(grays, masks, depths)]
+        else:
+            res = fe.detect_describe_batch(grays, masks, depths, *K)
+        outs.append((res, fe.detector_thresholds().copy()))
+        fe.close()
+    pyorb.set_use_feature_min_depth(True)
+    try:
+        st = pyorb.grid_state(mk, 3)
+        for f in range(n):
+            g, m, d = grays[f], masks[f], depths[f]
+            agg = pyorb.grid_detect(type(st).from_buffer_copy(st), g, m)   # the detector's aggregate, on a copy of its state
+            left = po.remove_depthless_min_depth(np.stack([agg["x"], agg["y"]], 1), agg["size"], d)
+            print("frame %d: aggregate %d, after the min-depth removeDepthless %d" % (f, len(agg), len(left)))
+            assert mk < len(left) < len(agg)       # the zmin compaction and the cut both run
+            rk, rdesc = pyorb.node_features(st, g, m, d, mk)
+            okept, oxyz = po.project_to_3d_min_depth(np.stack([rk["x"], rk["y"]], 1), rk["size"], d, *K, 1.0, mk)
+            assert len(okept) == len(rk) <= mk
+            for res, _ in outs:
+                kp, desc, xyz = res[f]
+                assert_kps_equal(kp, rk)
+                assert np.array_equal(desc, rdesc) and np.array_equal(xyz, oxyz)
+        for _, thr in outs:
+            assert np.array_equal(thr, np.array(st.thresh[:9]))
+    finally:
+        pyorb.set_use_feature_min_depth(False)
+
+
 @pytest.mark.parametrize("grid,n_frames,shape,depth", [(3, 37, (480, 640), "3"), (3, 30, (480, 640), "2"), (2, 23, (240, 320), "3"),
                                                        (4, 11, (240, 320), "3"), (1, 16, (120, 160), "3")])
 def test_detect_describe_batch_long_runs_and_grids(grid, n_frames, shape, depth):

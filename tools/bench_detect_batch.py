@@ -1,7 +1,7 @@
 """rgbdfe_detect_describe_batch alone: ms per frame for a run of frames (a recorded bag file), per repetition.
     python tools/bench_detect_batch.py [width height n_kp frames reps]
-Environment switches of the library are read once per process (RGBDFE_SUPER_DEPTH, RGBDFE_SUPER_PARALLEL_REPLAY,
-RGBDFE_DETECT_SUPER, RGBDFE_DETECT_TIMING): run one process per setting."""
+Environment switches of the library are read once per process (RGBDFE_SUPER_DEPTH, RGBDFE_DETECT_SUPER,
+RGBDFE_DETECT_TIMING): run one process per setting."""
 import json
 import os
 import sys
