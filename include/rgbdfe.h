@@ -792,6 +792,96 @@ int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, doub
                                      rgbdfe_pose_graph_report* report);
 int rgbdfe_pose_graph_transforms(const rgbdfe_pose_graph* g, int32_t n, const int32_t* node_ids, float* out);
 
+/* ---- ICP fallback (Node::matchNodePair node.cpp:1349-1378, filterCloud and icpAlignment icp.cpp:20-89) ----------
+ * What the reference does when RANSAC finds no transformation between two adjacent frames: both dense clouds are
+ * subsampled and aligned by icp_method "icp", PCL's point-to-point IterativeClosestPoint.  icp_nl and GICP are not
+ * served.  PCL is not part of the reference tree: the contract is this library's restatement (restated, not pinned;
+ * DESIGN.md 4.22), tests/icp_oracle.py states it literally and the device gives its bytes.  The nearest neighbour is an
+ * exact brute-force search (no kd-tree).  Clouds are rows of 4 floats (x, y, z, rgb bits).  Every float and double
+ * operation is rounded once (-ffp-contract=off); sums of three products are (a0 b0 + a1 b1) + a2 b2.
+ *
+ *   Subsampling = filterCloud, literally.  V = the indices of the rows whose z is not NaN, ascending.
+ *     step = (float)|V| / (float)desired_size, and step < 1 becomes 1.  The samples are the rows V[(unsigned)i] for
+ *     `float i = 0; i < (float)|V|; i += step`.  The float recurrence is part of the contract: |V| = 3072 and
+ *     desired_size = 100 give 101 samples, (2999, 7) gives 8.  desired_size <= 0: RGBDFE_ERR_INVALID_ARG.  A cloud of more
+ *     than 2^24 rows: RGBDFE_ERR_CAPACITY (beyond it the recurrence need not advance).
+ *     Named deviation: within the alignment a sampled row with a non-finite x or y takes part in nothing, neither as source
+ *     nor as target (createXYZRGBPointCloud never makes such a row).  rgbdfe_filter_cloud returns the rows as they are.
+ *   Alignment = icpAlignment.  Source S and target T are the two sampled clouds, the guess G a column-major Matrix4f of
+ *     which the upper three rows are used.  Working copy P = G S: ((R0 x + R1 y) + R2 z) + t per row, as rgbdfe_assemble_map
+ *     transforms.  F = G, mse_0 = DBL_MAX.  Iteration k = 1, 2, ...:
+ *     1. Correspondences.  For every source row i the running minimum starts at +inf without an index and takes target row
+ *        j, in ascending j, when d2 = (dx dx + dy dy) + dz dz (float, dx = P.x - T.x) is < the minimum: equal distances
+ *        answer with the lowest index, a row whose every d2 is +inf or NaN has no neighbour (j = -1).  The pair is kept iff
+ *        j >= 0 and !((double)d2 > maxdist * maxdist) (the product in double).  c = the number kept.  c < 3: the job stops,
+ *        state RGBDFE_ICP_NO_CORRESPONDENCES, converged = 0 (mse is then the sum of d2 / c, 0 for c = 0).
+ *     2. Seventeen sums in double over the source rows in ascending i, a row without a kept pair contributing zero: c, d2,
+ *        P (3), T_j (3), T_j P' (9; the products of the two floats in double).  Each goes through the tree of the pose-graph
+ *        block: leaves of 64 consecutive values (zero padded) halved 32, 16 .. 1; leaf k is added into accumulator k % 64 in
+ *        ascending k; the 64 accumulators are halved the same way.  No floating-point atomics.
+ *     3. Increment.  H = (sum T P' - (sum T)(sum P)' / c) / c in double, each entry rounded once to float; m_P = sum P / c
+ *        and m_T = sum T / c likewise.  U, V = the JacobiSVD<Matrix3f> restatement of the RANSAC stage on H;
+ *        R = U diag(1, 1, s) V' with s = -1 iff det(U) det(V) < 0 (Eigen's umeyama rule for rank >= 2; its det(Sigma) test
+ *        for lower rank is not mirrored: named deviation); t = m_T - R m_P.  P <- R P + t per row as above;
+ *        F <- [R t] F: its rotation R R_F, its translation (R t_F) + t, its last row (0, 0, 0, 1).
+ *     4. Stop rules, in this order: k >= max_iterations -> RGBDFE_ICP_ITERATIONS;
+ *        0.5 ((R00 + R11) + R22 - 1) >= 1 - transformation_epsilon and (tx tx + ty ty) + tz tz <= transformation_epsilon,
+ *        both in double -> RGBDFE_ICP_TRANSFORM; with mse_k = sum d2 / c: |mse_k - mse_(k-1)| < 1e-12 -> RGBDFE_ICP_ABS_MSE;
+ *        |mse_k - mse_(k-1)| / mse_(k-1) < euclidean_fitness_epsilon -> RGBDFE_ICP_REL_MSE; otherwise the next iteration.
+ *        All four count as converged.
+ *     The result is F if converged, else G's sixteen floats as given (icp.cpp:81-87).
+ *   A reproduced quirk: with the reference's setEuclideanFitnessEpsilon(1) the relative test passes at k = 2 for almost any
+ *     input, so the reference's fallback is a two-step ICP.  rgbdfe_icp_default_params reproduces it; a caller who passes
+ *     1e-6 gets the full loop.
+ *
+ * rgbdfe_icp_default_params: the values icpAlignment sets and gicp_max_cloud_size: 0.05, 50, 1e-8, 1.0, 10000.
+ *   max_iterations outside 1 .. 1000, a NaN parameter or a negative distance: RGBDFE_ERR_INVALID_ARG.
+ * rgbdfe_icp_align_nodes: n_jobs alignments over resident node clouds (rgbdfe_upload_node_cloud, the sensor batch path) as
+ *   one batch, jobs of different sizes mixed; an id may repeat.  guesses: n_jobs x 16 floats, NULL = identity.
+ *   transforms_out: n_jobs x 16 floats, column-major.  reports_out may be NULL.  An id without a cloud:
+ *   RGBDFE_ERR_UNKNOWN_NODE before any device work.  n_jobs == 0: RGBDFE_OK.  More than 65535 jobs: RGBDFE_ERR_CAPACITY.
+ *   In the reference's use the source is the OLDER node's cloud and the target the newer one's (node.cpp:1362-1364).
+ * rgbdfe_icp_align_clouds: the same for two host clouds.  nn_index_out / nn_d2_out (each may be NULL): j(i) and d2 of the
+ *   last iteration for every sampled source row, dropped pairs included; debug_capacity rows, fewer than the sampled source
+ *   count is RGBDFE_ERR_CAPACITY.
+ * rgbdfe_filter_cloud: filterCloud alone: the sampled rows' indices and the rows (each may be NULL); capacity < *n_out:
+ *   RGBDFE_ERR_CAPACITY with *n_out = the needed size.
+ * report: launches and readbacks are those of the whole call (the same in every job's report).  The loop: two launches
+ *   per iteration for the whole batch, enqueued in chunks of 2, 4, 8, 16, 16 ... iterations with one read of the jobs'
+ *   records per chunk; an iteration enqueued after a job has stopped returns at once for that job.
+ * Device memory: a call keeps, in buffers that grow to the largest call and stay with the context, 8 bytes per 256 rows of
+ *   every distinct cloud it names (the rows too for host clouds) and about 50 bytes per sample and job.
+ * Multi-device handles use their first device. */
+#define RGBDFE_ICP_RUNNING 0   /* never reported */
+#define RGBDFE_ICP_NO_CORRESPONDENCES 1
+#define RGBDFE_ICP_ITERATIONS 2
+#define RGBDFE_ICP_TRANSFORM 3
+#define RGBDFE_ICP_ABS_MSE 4
+#define RGBDFE_ICP_REL_MSE 5
+typedef struct rgbdfe_icp_params {
+  double max_correspondence_distance;
+  double transformation_epsilon;
+  double euclidean_fitness_epsilon;
+  int32_t max_iterations;
+  int32_t desired_size;
+} rgbdfe_icp_params;
+typedef struct rgbdfe_icp_report {
+  int32_t converged, state, iterations;
+  int32_t correspondences;      /* c of the last iteration */
+  double mse;                   /* of the last iteration */
+  int32_t n_source, n_target;   /* the sample counts */
+  int64_t launches, readbacks;
+} rgbdfe_icp_report;
+void rgbdfe_icp_default_params(rgbdfe_icp_params* p);
+int rgbdfe_icp_align_nodes(rgbdfe_ctx* ctx, int32_t n_jobs, const int32_t* source_ids, const int32_t* target_ids,
+                           const float* guesses, const rgbdfe_icp_params* params, float* transforms_out,
+                           rgbdfe_icp_report* reports_out);
+int rgbdfe_icp_align_clouds(rgbdfe_ctx* ctx, const float* source, int64_t n_source, const float* target, int64_t n_target,
+                            const float* guess, const rgbdfe_icp_params* params, float* transform_out,
+                            rgbdfe_icp_report* report_out, int32_t* nn_index_out, float* nn_d2_out, int64_t debug_capacity);
+int rgbdfe_filter_cloud(rgbdfe_ctx* ctx, const float* cloud, int64_t n, int32_t desired_size, int32_t* indices_out,
+                        float* rows_out, int64_t capacity, int64_t* n_out);
+
 /* GPU prefilter in front of the pair path (second half): what loop_closing.cpp's
  * GraphManager::getNeighbours (:190-277, behind DO_LOOP_CLOSING, never wired into nodeComparisons) sketched -- every
  * descriptor of the new node votes `k_neighbours - rank` (:241) for the nodes holding its k nearest descriptors, a
@@ -1100,7 +1190,8 @@ int rgbdfe_sensor_detect_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames,
 /* When enabled, every launch of the dominant kernels is bracketed by HIP events on the
  * stream it runs on; totals are read back with rgbdfe_get_kernel_time. */
 enum { RGBDFE_KERNEL_HAMMING = 0, RGBDFE_KERNEL_RANSAC = 1, RGBDFE_KERNEL_SIFT_DOT = 2,
-       RGBDFE_KERNEL_SIFT_FINISH = 3, RGBDFE_KERNEL_EMM = 4, RGBDFE_KERNEL_COUNT = 5 };
+       RGBDFE_KERNEL_SIFT_FINISH = 3, RGBDFE_KERNEL_EMM = 4, RGBDFE_KERNEL_ICP_NN = 5 /* `pairs` counts job-iterations */,
+       RGBDFE_KERNEL_COUNT = 6 };
 int rgbdfe_set_profiling(rgbdfe_ctx* ctx, int enable);
 int rgbdfe_get_kernel_time(rgbdfe_ctx* ctx, int which, double* total_ms, int64_t* launches,
                            int64_t* pairs);

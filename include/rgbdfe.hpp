@@ -46,6 +46,7 @@ struct MatchingResult {  // src/matching_result.h:24-46
   float rmse = 0.0f;
   std::array<float, 16> ransac_trafo{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
   std::array<float, 16> final_trafo{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+  std::array<float, 16> icp_trafo{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};   // set by GraphManager::icpFallback
   unsigned int inlier_points = 0, outlier_points = 0, occluded_points = 0, all_points = 0;  // environment measurement model
 };
 
@@ -413,6 +414,44 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
                                  (int32_t)out.size(), out.data(), score.data(), &n_out) != RGBDFE_OK)
       return {};
     return std::vector<int>(out.begin(), out.begin() + n_out);
+  }
+  // Node::matchNodePair's ICP branch (node.cpp:1356-1377) for the results of nodeComparisons(new_node, nodes_to_comp): every
+  // result WITHOUT an edge whose node is adjacent (new id - its id <= 1) is aligned by rgbdfe_icp_align_nodes in one batch,
+  // source = the older node's resident cloud, target = the new node's, guess = identity.  When converged: icp_trafo,
+  // final_trafo = icp_trafo (the literal assignment, whatever direction the RANSAC transforms have), edge.id1 / id2 and
+  // edge.transform are set (:1370-1373) and nothing else.  Returns the number of results that got an edge, -1 on an error.
+  int icpFallback(const Node* new_node, const std::vector<const Node*>& nodes_to_comp, std::vector<MatchingResult>& results,
+                  const rgbdfe_icp_params* params = nullptr, std::vector<rgbdfe_icp_report>* reports = nullptr) const {
+    rgbdfe_icp_params prm;
+    if (params) prm = *params; else rgbdfe_icp_default_params(&prm);
+    std::vector<size_t> served;
+    std::vector<int32_t> source, target;
+    for (size_t i = 0; i < results.size() && i < nodes_to_comp.size(); ++i)
+      if (results[i].edge.id1 < 0 && new_node->id_ - nodes_to_comp[i]->id_ <= 1) {
+        served.push_back(i);
+        source.push_back(nodes_to_comp[i]->id_);
+        target.push_back(new_node->id_);
+      }
+    if (served.empty()) return 0;
+    std::vector<float> T(16 * served.size());
+    std::vector<rgbdfe_icp_report> rep(served.size());
+    if (rgbdfe_icp_align_nodes(fe_.get(), (int32_t)served.size(), source.data(), target.data(), nullptr, &prm, T.data(),
+                               rep.data()) != RGBDFE_OK)
+      return -1;
+    int edges = 0;
+    for (size_t k = 0; k < served.size(); ++k) {
+      if (!rep[k].converged) continue;
+      MatchingResult& mr = results[served[k]];
+      for (int i = 0; i < 16; ++i) {
+        mr.icp_trafo[i] = mr.final_trafo[i] = T[16 * k + i];
+        mr.edge.transform[i] = (double)T[16 * k + i];
+      }
+      mr.edge.id1 = source[k];
+      mr.edge.id2 = target[k];
+      ++edges;
+    }
+    if (reports) *reports = rep;
+    return edges;
   }
   // 1:1 replacement of QtConcurrent::blockingMapped(nodes_to_comp, bind(&Node::matchNodePair, new_node, _1))
   std::vector<MatchingResult> nodeComparisons(const Node* new_node, const std::vector<const Node*>& nodes_to_comp) const {

@@ -21,6 +21,7 @@ KERNEL_RANSAC = 1
 KERNEL_SIFT_DOT = 2
 KERNEL_SIFT_FINISH = 3
 KERNEL_EMM = 4
+KERNEL_ICP_NN = 5   # the ICP fallback's nearest-neighbour kernel (pairs = job-iterations)
 
 
 class RgbdfeParams(C.Structure):
@@ -99,6 +100,18 @@ class PoseGraphReport(C.Structure):   # rgbdfe_pose_graph_report
     _fields_ = [("iterations", C.c_int32), ("recorded", C.c_int32), ("chi2", C.c_double), ("launches", C.c_int64),
                 ("readbacks", C.c_int64), ("upload_seconds", C.c_double), ("total_seconds", C.c_double),
                 ("it", PoseGraphIteration * POSE_GRAPH_REPORT_ITERATIONS)]
+
+
+class IcpParams(C.Structure):   # rgbdfe_icp_params
+    _fields_ = [("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double), ("max_iterations", C.c_int32), ("desired_size", C.c_int32)]
+
+
+# rgbdfe_icp_report
+ICP_REPORT_DTYPE = np.dtype([("converged", "<i4"), ("state", "<i4"), ("iterations", "<i4"), ("correspondences", "<i4"),
+                             ("mse", "<f8"), ("n_source", "<i4"), ("n_target", "<i4"), ("launches", "<i8"),
+                             ("readbacks", "<i8")])
+ICP_NO_CORRESPONDENCES, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE = 1, 2, 3, 4, 5
 
 
 # rgbdfe_octomap_leaf
@@ -499,6 +512,14 @@ def load():
     L.rgbdfe_potential_edge_targets.restype = C.c_int
     L.rgbdfe_potential_edge_targets.argtypes = [vp, i32, i32, i32, i32, i32, i32, RAND_FN, vp, C.c_uint32, vp, i32,
                                                 C.POINTER(i32)]
+    L.rgbdfe_icp_default_params.restype = None
+    L.rgbdfe_icp_default_params.argtypes = [C.POINTER(IcpParams)]
+    L.rgbdfe_icp_align_nodes.restype = C.c_int
+    L.rgbdfe_icp_align_nodes.argtypes = [vp, i32, vp, vp, vp, C.POINTER(IcpParams), vp, vp]
+    L.rgbdfe_icp_align_clouds.restype = C.c_int
+    L.rgbdfe_icp_align_clouds.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(IcpParams), vp, vp, vp, vp, C.c_int64]
+    L.rgbdfe_filter_cloud.restype = C.c_int
+    L.rgbdfe_filter_cloud.argtypes = [vp, vp, C.c_int64, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -543,4 +564,5 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_sift_detect_orb_describe", "rgbdfe_sift_detect_orb_describe_batch_nodes",
     "rgbdfe_sizeof_sensor_frame", "rgbdfe_ingest_frame", "rgbdfe_sensor_detect_describe",
     "rgbdfe_sensor_detect_describe_batch_nodes",
+    "rgbdfe_icp_default_params", "rgbdfe_icp_align_nodes", "rgbdfe_icp_align_clouds", "rgbdfe_filter_cloud",
 ]

@@ -971,6 +971,31 @@ int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, doub
   return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_optimize_graph(c, g, break_criterion, report));
 }
 
+// the ICP fallback runs on one device (the first of a group)
+void rgbdfe_icp_default_params(rgbdfe_icp_params* p) { impl::rgbdfe_icp_default_params(p); }
+
+int rgbdfe_icp_align_nodes(rgbdfe_ctx* ctx, int32_t n_jobs, const int32_t* source_ids, const int32_t* target_ids,
+                           const float* guesses, const rgbdfe_icp_params* params, float* transforms_out,
+                           rgbdfe_icp_report* reports_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_icp_align_nodes(c, n_jobs, source_ids, target_ids, guesses, params, transforms_out,
+                                                        reports_out));
+}
+
+int rgbdfe_icp_align_clouds(rgbdfe_ctx* ctx, const float* source, int64_t n_source, const float* target, int64_t n_target,
+                            const float* guess, const rgbdfe_icp_params* params, float* transform_out,
+                            rgbdfe_icp_report* report_out, int32_t* nn_index_out, float* nn_d2_out, int64_t debug_capacity) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_icp_align_clouds(c, source, n_source, target, n_target, guess, params, transform_out,
+                                                         report_out, nn_index_out, nn_d2_out, debug_capacity));
+}
+
+int rgbdfe_filter_cloud(rgbdfe_ctx* ctx, const float* cloud, int64_t n, int32_t desired_size, int32_t* indices_out,
+                        float* rows_out, int64_t capacity, int64_t* n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_filter_cloud(c, cloud, n, desired_size, indices_out, rows_out, capacity, n_out));
+}
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

@@ -274,6 +274,8 @@ struct rgbdfe_ctx {
   // scratch for single-pair helpers / project_to_3d
   void* d_scratch = nullptr;
   size_t scratch_bytes = 0;
+  void* d_icp = nullptr;     // api_icp.hip: the samples, working copies and records of a call (d_scratch holds its tile counts and offsets)
+  size_t icp_bytes = 0;
   OrbWorkspace orb;
   OrbWorkspace orb_super;  // rgbdfe_detect_describe_batch: up to 7 frames per launch chain (its own image sets)
   std::unique_ptr<TaskPool> detect_pool, stage_pool;  // its worker threads (created by the first batch call, kept)
@@ -579,6 +581,11 @@ int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2);
 int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* errors, double* weights, int32_t edge_capacity, int32_t* n_edges, int32_t* free_ids, double* h_diag, double* b, int32_t vertex_capacity, int32_t* n_free, int32_t* off_rows, int32_t* off_cols, double* h_off, int32_t block_capacity, int32_t* n_blocks, double* chi2);
 int rgbdfe_pose_graph_optimize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, int32_t iterations, rgbdfe_pose_graph_report* report);
 int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double break_criterion, rgbdfe_pose_graph_report* report);
+// api_icp.hip
+void rgbdfe_icp_default_params(rgbdfe_icp_params* p);
+int rgbdfe_icp_align_nodes(rgbdfe_ctx* ctx, int32_t n_jobs, const int32_t* source_ids, const int32_t* target_ids, const float* guesses, const rgbdfe_icp_params* params, float* transforms_out, rgbdfe_icp_report* reports_out);
+int rgbdfe_icp_align_clouds(rgbdfe_ctx* ctx, const float* source, int64_t n_source, const float* target, int64_t n_target, const float* guess, const rgbdfe_icp_params* params, float* transform_out, rgbdfe_icp_report* report_out, int32_t* nn_index_out, float* nn_d2_out, int64_t debug_capacity);
+int rgbdfe_filter_cloud(rgbdfe_ctx* ctx, const float* cloud, int64_t n, int32_t desired_size, int32_t* indices_out, float* rows_out, int64_t capacity, int64_t* n_out);
 // api_octomap.hip (the map keeps the context it lives on; `owner` is the handle it was created through)
 void rgbdfe_octomap_default_params(rgbdfe_octomap_params* p);
 rgbdfe_ctx* octomap_owner(rgbdfe_octomap* map);

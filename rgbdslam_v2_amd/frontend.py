@@ -1231,6 +1231,92 @@ class FrontEnd:
                 int(c[i, 0]), int(c[i, 1]), int(c[i, 2] + c[i, 0] + c[i, 1]), observability_threshold, C.byref(q)))
         return c, met
 
+    # -- the ICP fallback --------------------------------------------------------------------
+    def icp_params(self, **kw):
+        """rgbdfe_icp_default_params (icpAlignment's settings and gicp_max_cloud_size), with keyword overrides."""
+        p = _lib.IcpParams()
+        self._L.rgbdfe_icp_default_params(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise TypeError("no ICP parameter %r" % k)
+            setattr(p, k, v)
+        return p
+
+    def filter_cloud(self, cloud, desired_size):
+        """filterCloud (icp.cpp:20-45): returns (indices, rows) of the sampled rows of cloud, [n, 4] float32."""
+        pts = np.ascontiguousarray(cloud, np.float32).reshape(-1, 4)
+        n_out = C.c_int64(0)
+        cap = len(pts)
+        idx, rows = np.empty(cap, np.int32), np.empty((cap, 4), np.float32)
+        self._check(self._L.rgbdfe_filter_cloud(self._ctx, pts.ctypes.data if len(pts) else None, len(pts), int(desired_size),
+                                                idx.ctypes.data, rows.ctypes.data, cap, C.byref(n_out)))
+        return idx[:n_out.value].copy(), rows[:n_out.value].copy()
+
+    def icp_align_clouds(self, source, target, guess=None, params=None, debug=False):
+        """icpAlignment (icp.cpp:47-89) of two host clouds, [n, 4] float32, after filterCloud on both.  guess: a 4 x 4
+        numpy matrix (row-major; None = identity).  Returns (T, report) -- T a 4 x 4 float32 numpy matrix, report a
+        record of ICP_REPORT_DTYPE -- and with debug also (nn_index, nn_d2) of the last iteration's sampled source rows."""
+        src = np.ascontiguousarray(source, np.float32).reshape(-1, 4)
+        tgt = np.ascontiguousarray(target, np.float32).reshape(-1, 4)
+        prm = params if params is not None else self.icp_params()
+        G = None if guess is None else np.ascontiguousarray(np.asarray(guess, np.float32).reshape(4, 4).T)
+        T = np.empty(16, np.float32)
+        rep = np.zeros(1, _lib.ICP_REPORT_DTYPE)
+        cap = len(src) if debug else 0
+        nn_j, nn_d2 = np.full(cap, -1, np.int32), np.zeros(cap, np.float32)
+        self._check(self._L.rgbdfe_icp_align_clouds(
+            self._ctx, src.ctypes.data if len(src) else None, len(src), tgt.ctypes.data if len(tgt) else None, len(tgt),
+            G.ctypes.data if G is not None else None, C.byref(prm), T.ctypes.data, rep.ctypes.data,
+            nn_j.ctypes.data if debug else None, nn_d2.ctypes.data if debug else None, cap))
+        T = T.reshape(4, 4).T.copy()
+        if debug:
+            ns = int(rep[0]["n_source"])
+            return T, rep[0], nn_j[:ns], nn_d2[:ns]
+        return T, rep[0]
+
+    def icp_align_nodes(self, source_ids, target_ids, guesses=None, params=None):
+        """rgbdfe_icp_align_nodes: one batch of alignments over resident node clouds.  guesses: n x 4 x 4 numpy matrices
+        (None = identity).  Returns (T, reports): n x 4 x 4 float32 numpy matrices and ICP_REPORT_DTYPE records."""
+        src = np.ascontiguousarray(source_ids, np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(target_ids, np.int32).reshape(-1)
+        if len(src) != len(tgt):
+            raise ValueError("one target per source")
+        n = len(src)
+        prm = params if params is not None else self.icp_params()
+        G = None
+        if guesses is not None:
+            G = np.ascontiguousarray(np.asarray(guesses, np.float32).reshape(n, 4, 4).transpose(0, 2, 1))
+        T = np.empty((n, 16), np.float32)
+        rep = np.zeros(n, _lib.ICP_REPORT_DTYPE)
+        self._check(self._L.rgbdfe_icp_align_nodes(self._ctx, n, src.ctypes.data, tgt.ctypes.data,
+                                                   G.ctypes.data if G is not None else None, C.byref(prm), T.ctypes.data,
+                                                   rep.ctypes.data))
+        return T.reshape(n, 4, 4).transpose(0, 2, 1).copy(), rep
+
+    def icp_fallback(self, results, new_id, candidate_ids, params=None):
+        """Node::matchNodePair's ICP branch (node.cpp:1356-1377) for the records of one new node against candidate_ids:
+        every record WITHOUT an edge (id1 < 0) whose new_id - candidate_id <= 1 is served.  The source is the OLDER node's
+        cloud, the target the new node's, the guess the identity (:1362-1364).  When the alignment converged -- the
+        reference then sets found_transformation = true regardless of any quality measure -- the record's trafo
+        (final_trafo) becomes icp_trafo and id1 / id2 the older / the new id (:1370-1373); nothing else changes, the
+        information scale included.  The assignment final_trafo = icp_trafo is reproduced literally: icp_trafo maps the
+        older cloud onto the newer one, whatever direction the RANSAC transform of the other records has.
+        Returns (records, served, icp_trafos, reports): a copy of results, the positions served, their n x 4 x 4
+        transforms and ICP_REPORT_DTYPE records."""
+        out = np.array(results, copy=True)
+        cand = np.asarray(candidate_ids, np.int64).reshape(-1)
+        if len(cand) != len(out):
+            raise ValueError("one candidate id per record")
+        served = np.array([i for i in range(len(out)) if int(out[i]["id1"]) < 0 and int(new_id) - int(cand[i]) <= 1], np.int64)
+        if len(served) == 0:
+            return out, served, np.zeros((0, 4, 4), np.float32), np.zeros(0, _lib.ICP_REPORT_DTYPE)
+        T, rep = self.icp_align_nodes(cand[served].astype(np.int32), np.full(len(served), int(new_id), np.int32), None, params)
+        for k, i in enumerate(served):
+            if rep[k]["converged"]:
+                out[i]["trafo"] = T[k].T.reshape(16)   # column-major storage
+                out[i]["id1"], out[i]["id2"] = int(cand[i]), int(new_id)
+        return out, served, T, rep
+
     def set_latency_mode(self, max_pairs=(1 << 31) - 1, chunk_iterations=0):
         """Batches of at most max_pairs pairs spread each pair's RANSAC iterations over several waves (record /
         replay, identical results; the default for every batch size); max_pairs = 0 forces one wave per pair,
