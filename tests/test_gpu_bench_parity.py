@@ -122,3 +122,53 @@ def test_pack_inliers_equals_its_host_twin(n_kp, per_frame):
         assert int(d_tot.item()) == 0 and np.all(e["id1"] == -1) and np.all(e["n_inl"] == 0)
     finally:
         fe.close()
+
+
+@pytest.mark.parametrize("n,first_with_inliers", [(1024, 0), (1025, 0), (2500, 0), (2500, 1024)])
+def test_pack_inliers_over_more_records_than_one_trip(n, first_with_inliers):
+    """inlier_scan_kernel covers 1024 records a trip and carries the list position: fabricated records (random masks and
+    match lists, no matching) at one full trip, one record more and three trips, and once with no inlier in the first 1024
+    records, so that the second trip starts from position 0."""
+    import torch
+    from rgbdslam_v2_amd._lib import INLIER_HEADER_DTYPE, RESULT_DTYPE, RGBDFE_MASK_WORDS, RGBDFE_MAX_MATCHES, inlier_stream_of
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    rng = np.random.default_rng(n + first_with_inliers)
+    rec = np.zeros(n, RESULT_DTYPE)
+    mask = rng.integers(0, 2**64, (n, RGBDFE_MASK_WORDS), dtype=np.uint64)
+    mask[rng.random(n) < 0.2] = 0  # records without an inlier among the others
+    mask[:first_with_inliers] = 0
+    mask[n - 1, 0] |= np.uint64(1)  # the last record has one
+    counts = np.unpackbits(mask.view(np.uint8), axis=1).sum(1)
+    rec["inlier_mask"] = mask
+    rec["n_inl"] = counts
+    rec["n_all"] = RGBDFE_MAX_MATCHES
+    rec["id1"] = np.where(counts > 0, rng.integers(0, 1000, n), -1)
+    rec["id2"] = np.where(counts > 0, rng.integers(0, 1000, n), -1)
+    rec["rmse"] = rng.random(n, dtype=np.float32)
+    rec["trafo"] = rng.random((n, 16), dtype=np.float32)
+    rec["info_scale"] = rng.random(n)
+    rec["valid_iterations"] = rng.integers(0, 100, n)
+    rec["real_iterations"] = rng.integers(0, 100, n)
+    rec["all_q"] = rng.integers(0, 65536, (n, RGBDFE_MAX_MATCHES), dtype=np.uint16)
+    rec["all_t"] = rng.integers(0, 65536, (n, RGBDFE_MAX_MATCHES), dtype=np.uint16)
+    rec["all_hd"] = rng.integers(0, 256, (n, RGBDFE_MAX_MATCHES), dtype=np.uint8)
+    n_hdr = n + 5
+    hdr, lst = inlier_stream_of(rec, n_hdr)
+    if n > 1024:  # lists behind record 1024 whose positions need the carried total
+        assert counts[1024:].sum() > 0 and hdr["first_inlier"][n - 1] == len(lst) - counts[n - 1]
+        assert (hdr["first_inlier"][1024] == 0) == (first_with_inliers == 1024)
+    want = np.concatenate([hdr.view(np.uint8).reshape(-1), lst.view(np.uint8).reshape(-1)])
+    fe = FrontEnd(device_id=0, max_nodes=2, max_keypoints=64, max_pairs_per_batch=16)
+    try:
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(-1).copy()).to("cuda")
+        d_stream = torch.full((len(want) + 4096,), 0xAB, dtype=torch.uint8, device="cuda")
+        d_tot = torch.zeros(1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()  # the copies run on torch's stream, the packing on the context's
+        fe.pack_inliers(d_rec.data_ptr(), n, n_hdr, d_stream.data_ptr(), d_tot.data_ptr())
+        fe.synchronize()
+        assert int(d_tot.item()) == len(lst) == int(counts.sum())
+        got = d_stream.cpu().numpy()
+        assert np.array_equal(got[:len(want)], want)
+        assert np.all(got[len(want):] == 0xAB)  # nothing written behind the stream
+    finally:
+        fe.close()

@@ -222,3 +222,71 @@ def test_profiling_times_the_nearest_neighbour_launches_and_changes_nothing(fe):
     assert same(timed, plain, np.float32) and rep1.tobytes() == rep0.tobytes()
     enqueued = record_reads(int(rep0["iterations"]), case["params"]["max_iterations"])[1]
     assert launches == enqueued == jobs and ms > 0
+
+
+# ---- the later trips of icp_scan_kernel (csrc/icp.hip): 256 tiles of 256 rows a trip, then icp_gather_kernel's search over them
+SCAN_TILE, SCAN_TRIP = 256, 256 * 256  # kIcpScanTile; the rows of one trip
+
+
+def empty_tiles(cloud):
+    """No depth in the rows of tiles 0 .. 3 and 100 .. 102: runs of equal entries in tile_first."""
+    cloud[:4 * SCAN_TILE, 2] = np.nan
+    cloud[100 * SCAN_TILE:103 * SCAN_TILE, 2] = np.nan
+    return cloud
+
+
+@pytest.fixture(scope="module")
+def quarter_vga():
+    """320 x 240 = 76 800 rows = 300 tiles: a second trip of 44 tiles."""
+    return empty_tiles(io.room_corner(320, 240, holes=5000, seed=9))
+
+
+def check_filter(fe, cloud, desired):
+    idx, rows = fe.filter_cloud(cloud, desired)
+    ref_idx, ref_rows = io.filter_cloud(cloud, desired)
+    assert len(idx) == len(ref_idx) and np.array_equal(idx, ref_idx) and same(rows, ref_rows, np.float32)
+    return ref_idx
+
+
+@pytest.mark.parametrize("desired", [7, 5000, 76800])
+def test_filter_cloud_over_more_tiles_than_one_trip(fe, quarter_vga, desired):
+    valid = ~np.isnan(quarter_vga[:, 2])
+    assert len(quarter_vga) == 300 * SCAN_TILE and valid[SCAN_TRIP:].sum() > 10000 and not valid[:4 * SCAN_TILE].any()
+    ref_idx = check_filter(fe, quarter_vga, desired)
+    assert ref_idx.max() >= SCAN_TRIP and ref_idx.min() >= 4 * SCAN_TILE  # samples whose tile lies in the second trip
+    assert desired < 76800 or len(ref_idx) == valid.sum()
+
+
+@pytest.mark.parametrize("n,n_trips", [(65536, 1), (65537, 2), (640 * 480, 5)])
+def test_filter_cloud_at_one_full_trip_one_row_more_and_five_trips(fe, n, n_trips):
+    cols, rows = (640, 480) if n > 320 * 240 else (320, 240)
+    cloud = empty_tiles(io.room_corner(cols, rows, holes=n // 16, seed=n % 1000))[:n].copy()
+    cloud[n - 1, 2] = np.float32(2.0)  # the last row is valid: at 65 537 rows it is tile 256, the second trip, alone
+    assert -(-(-(-n // SCAN_TILE)) // SCAN_TILE) == n_trips
+    check_filter(fe, cloud, 1000)
+    ref_idx = check_filter(fe, cloud, n)  # every valid row comes back, the last one too
+    assert ref_idx[-1] == n - 1 and len(ref_idx) == (~np.isnan(cloud[:, 2])).sum()
+
+
+def test_a_resident_pair_of_more_tiles_than_one_trip(fe):
+    """Two 320 x 240 resident clouds (300 tiles each, the first five without depth) aligned by icp_align_nodes: the
+    samples come from both trips of the scan."""
+    prm = dict(max_correspondence_distance=0.25, max_iterations=12, desired_size=1000, **io.FULL_LOOP)
+    clouds = {}
+    try:
+        for nid, mv in ((50, None), (51, 2.0)):
+            depth, (fx, fy, cx, cy) = io.corner_depth(320, 240, None if mv is None else io._pose(mv), holes=3000, seed=nid)
+            depth[:4, :] = np.nan  # 1280 rows: tiles 0 .. 4
+            clouds[nid] = fe.upload_node_cloud(nid, depth, fx, fy, cx, cy, cloud_skip=1, return_cloud=True).reshape(-1, 4).copy()
+            idx, _ = io.filter_cloud(clouds[nid], prm["desired_size"])
+            assert len(clouds[nid]) == 300 * SCAN_TILE and np.isnan(clouds[nid][:5 * SCAN_TILE, 2]).all()
+            assert (idx >= SCAN_TRIP).sum() > 100 and (idx < SCAN_TRIP).sum() > 100
+        T, rep = fe.icp_align_nodes([50, 51], [51, 50], None, fe.icp_params(**prm))
+        for k, (s, t) in enumerate(((50, 51), (51, 50))):
+            ref = io.align_clouds(clouds[s], clouds[t], None, **prm)
+            assert ref["c"] > 100 and ref["iterations"] >= 2
+            check_report(rep[k], ref)
+            assert same(T[k], ref["T"], np.float32)
+    finally:
+        for nid in clouds:
+            fe.release_node_cloud(nid)

@@ -262,3 +262,49 @@ def test_two_identical_calls_give_identical_bytes(fe, scene):
         a = fe.assemble_map(ids, Ts, 2.5, raster, return_offsets=True)
         b = fe.assemble_map(ids, Ts, 2.5, raster, return_offsets=True)
         assert a[0].tobytes() == b[0].tobytes() and np.array_equal(a[1], b[1])
+
+
+# ---- the later trips of map_scan_kernel (csrc/map_assembly.hip): 1024 tile counts a trip, then 1024 nodes' first rows a stride
+MAP_TILE = 1024  # kMapTile; a tile never crosses a node
+
+
+@pytest.fixture(scope="module")
+def small_clouds(fe):
+    """Nodes 40, 41, 42 of 1, 63 and 1025 points: one full tile is never reached, so the tiles' counts differ."""
+    rng = np.random.default_rng(57)
+    clouds = [upload(fe, 40, np.full((1, 1), 1.5, np.float32), seed=40)]
+    for k, (rows, cols) in ((41, (7, 9)), (42, (25, 41))):
+        d = rng.uniform(0.3, 5.0, (rows, cols)).astype(np.float32)
+        d[rng.random((rows, cols)) < 0.1] = np.nan
+        clouds.append(upload(fe, k, d, seed=k))
+    assert [c.size // 4 for c in clouds] == [1, 63, 1025]
+    yield clouds
+    for k in (40, 41, 42):
+        fe.release_node_cloud(k)
+
+
+@pytest.mark.parametrize("which,n_tiles", [("1100 nodes", 1466), ("exactly 1024 tiles", 1024)])
+def test_more_tiles_and_more_nodes_than_one_trip_of_the_scan(fe, small_clouds, which, n_tiles):
+    """Compact mode over a list that repeats three resident clouds: more than 1024 tiles and more than 1023 nodes (the
+    node_first loop takes 1024 entries a stride, the sentinel included), and once exactly 1024 tiles.  maximum_depth 2.5
+    clips a part of every larger cloud."""
+    rng = np.random.default_rng(58)
+    if which == "1100 nodes":
+        pick = np.arange(1100) % 3
+    else:
+        pick = np.concatenate([np.full(300, 2), np.full(212, 1), np.full(212, 0)])  # 600 + 424 tiles
+    pick = rng.permutation(pick)
+    clouds = [small_clouds[k] for k in pick]
+    Ts = random_transforms(rng, len(pick))
+    per_node = np.array([-(-(c.size // 4) // MAP_TILE) for c in clouds])
+    first_tile = np.cumsum(per_node) - per_node
+    assert per_node.sum() == n_tiles
+    want, want_off = mo.assemble(clouds, Ts, 2.5)
+    kept = np.diff(want_off)
+    if which == "1100 nodes":  # kept points behind tile 1024 and nodes behind entry 1024: both loops go round again
+        assert len(pick) + 1 > 1024 and kept[first_tile >= 1024].sum() > 1000 and kept[1024:].sum() > 0
+        assert len({int(k) for k in kept[first_tile >= 1024]}) >= 3  # nodes, and so tiles, of different counts
+    assert 0 < len(want) < mo.assemble(clouds, Ts, np.inf)[1][-1]  # the clip takes points away
+    got, off = fe.assemble_map(40 + pick, Ts, 2.5, False, return_offsets=True)
+    assert np.array_equal(off, want_off) and len(got) == off[-1]
+    assert mo.mismatch(got, want) is None, mo.mismatch(got, want)

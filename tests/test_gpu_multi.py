@@ -133,6 +133,47 @@ def test_allgather_of_accepted_edges_only(ids):
     grp.close()
 
 
+def test_allgather_of_edges_over_more_records_than_one_trip():
+    """edge_scan_kernel covers 1024 records a trip and carries the count of accepted edges: the 66 pairs of the test above
+    17 times over, 1122 records in one shard, with edges on both sides of record 1024."""
+    import torch
+    from rgbdslam_v2_amd.frontend import FrontEnd
+    a = synth.make_sequence(n_frames=6, n_kp=400, n_world=1500, seed=31)
+    b = synth.make_sequence(n_frames=6, n_kp=400, n_world=1500, seed=32)
+    desc = list(a["desc"]) + list(b["desc"])
+    xyz = list(a["xyz1"]) + list(b["xyz1"])
+    F = 12
+    pq = np.tile(np.array([q for q in range(F) for t in range(q)], np.int32), 17)
+    pt = np.tile(np.array([t for q in range(F) for t in range(q)], np.int32), 17)
+    n = len(pq)
+    assert n == 1122
+
+    def make(device_ids):
+        fe = FrontEnd(device_id=0, max_nodes=16, max_keypoints=512, max_pairs_per_batch=2048, device_ids=device_ids)
+        for f in range(F):
+            fe.upload_node(f, desc[f], xyz[f])
+        return fe
+
+    one = make(None)
+    ref = one.match_pair_list(pq, pt)
+    one.close()
+    is_edge = ref["id1"] >= 0
+    want = np.flatnonzero(is_edge)
+    assert is_edge[:1024].sum() >= 10 * 15 and is_edge[1024:].sum() >= 10  # positions behind record 1024 need the carried count
+    grp = make([0])
+    rec = RESULT_DTYPE.itemsize
+    buf = torch.zeros(n * rec, dtype=torch.uint8, device="cuda:0")
+    idx = torch.full((n,), -7, dtype=torch.int32, device="cuda:0")
+    torch.cuda.synchronize()
+    counts, stride = grp.match_pair_list_allgather_edges(pq, pt, [buf.data_ptr()], [idx.data_ptr()])
+    assert counts.tolist() == [len(want)] and stride == len(want)
+    got = np.frombuffer(buf.cpu().numpy().tobytes(), dtype=RESULT_DTYPE)[:len(want)]
+    assert got.tobytes() == ref[want].tobytes()
+    back = idx.cpu().numpy()
+    assert np.array_equal(back[:len(want)], want) and np.all(back[len(want):] == -7)
+    grp.close()
+
+
 def test_group_refuses_device_pointer_entry_points(data):
     import torch
     seq, pq, pt = data

@@ -231,3 +231,33 @@ def test_refused_parameters(fe):
     for cap in (0, -1, 2**31):
         with pytest.raises(RgbdfeError):
             fe.octomap(cap)
+
+
+def colour_passes(cap):
+    """Host twin of insert_clouds (csrc/api_octomap.hip): the colour rows are sorted by slot, `cap` standing for "no leaf",
+    in the 8-bit passes that cover 0 .. cap."""
+    return -(-int(cap).bit_length() // 8)
+
+
+def test_the_pass_counts_of_the_capacities_above():
+    """2 * leaves + 64 slots give one, two and three passes of the colour sort, never four."""
+    for name, passes in (("n 1 res 0.4 range 2.8", 1), ("n 1025 res 0.1 range 2.8", 2), ("n 3072 res 0.05 range 2.8", 3)):
+        cap = 2 * len(want(case_named(name))) + 64
+        print("%s: %d slots, %d passes" % (name, cap, colour_passes(cap)))
+        assert colour_passes(cap) == passes
+
+
+@pytest.mark.parametrize("cap,passes", [(255, 1), (256, 2), (70000, 3), (2**24, 4)])
+def test_every_number_of_colour_sort_passes(fe, cap, passes):
+    """Coloured families into tables of one, two, three and four passes: leaves and colours are the oracle's, the capacity
+    does not show.  5000 samples of one cell and 400 of two are the rows the sort has to bring together."""
+    assert colour_passes(cap) == passes
+    names = ["5000 in one cell", "two cells alternating", "n 1025 res 0.4 range 2.8"]
+    if cap >= 70000:
+        names[2] = "n 3072 res 0.05 range 2.8"
+    for name in names:
+        case, ref = case_named(name), want(case_named(name))
+        assert len(ref) <= cap
+        with build(fe, case, cap) as m:
+            assert m.capacity == cap and len(m) == len(ref)
+            same(m.leaves(), ref)

@@ -37,6 +37,37 @@ def fe():
     f.close()
 
 
+def home_slot(key, cap):
+    """Host twin of home_slot (csrc/octomap.hip): the first slot a key is tried at in a table of `cap` slots."""
+    k = np.asarray(key, np.uint64)
+    h = k[:, 0] | (k[:, 1] << np.uint64(16)) | (k[:, 2] << np.uint64(32))
+    with np.errstate(over="ignore"):
+        h ^= h >> np.uint64(33)
+        h *= np.uint64(0xff51afd7ed558ccd)
+        h ^= h >> np.uint64(33)
+        h *= np.uint64(0xc4ceb9fe1a85ec53)
+        h ^= h >> np.uint64(33)
+    return (((h >> np.uint64(32)) * np.uint64(cap)) >> np.uint64(32)).astype(np.int64)
+
+
+def occupied_slots(home, cap):
+    """The slots that hold a leaf in a table of `cap` slots: with linear probing the set does not depend on the order in
+    which the leaves went in."""
+    taken = set()
+    for h in home:
+        s = int(h)
+        while s in taken:
+            s = s + 1 if s + 1 < cap else 0
+        taken.add(s)
+    return np.array(sorted(taken))
+
+
+# two keys found by search: the first has slot 2^20, the one slot of tile 1024, in a table of 2^20 + 1 slots; the second a
+# slot behind 2^21, in the third trip, in a table of 2^21 + 1025
+LATE_SLOT_LEAVES = to.leaf_records([((48479, 63624, 53141), np.float32(0.75), (200, 100, 50)),
+                                    ((50595, 28226, 26079), np.float32(-1.25), (3, 2, 1))])
+
+
 def rowmajor(T):
     return np.asarray(T, np.float32).reshape(4, 4).T
 
@@ -162,6 +193,19 @@ def test_the_table_does_not_show(fe):
         with fe.octomap(cap, **case[1]) as m:
             m.set_leaves(leaves)
             same(m.tree(), rec, "capacity %d" % cap)
+    # tables of more than 1024 slot tiles: tree_scan_kernel's later trips over the gather stage's counts
+    leaves = np.concatenate([dict(PLANTED)["random 1025"], LATE_SLOT_LEAVES])
+    lit = to.LiteralTree(leaves)
+    rec = lit.records()
+    for cap, n_trips in ((2**20, 1), (2**20 + 1, 2), (2**21 + 1025, 3)):
+        taken = occupied_slots(home_slot(leaves["key"], cap), cap)
+        assert -(-(-(-cap // 1024)) // 1024) == n_trips
+        for trip in range(1, n_trips):  # leaves in the slots of every later trip: their rows need the carried base
+            assert np.any((taken >= trip * 2**20) & (taken < (trip + 1) * 2**20))
+        with fe.octomap(cap) as m:
+            m.set_leaves(leaves)
+            same(m.tree(), rec, "capacity %d" % cap)
+            same(m.nodes_at_depth(16), lit.at_depth(16), "depth 16, capacity %d" % cap)
 
 
 def test_a_tree_call_between_inserts_changes_nothing(fe):

@@ -151,7 +151,7 @@ def test_optimize_graph_is_the_oracles_bytes(fe, name, criterion):
 
 def test_more_leaves_than_accumulators(fe):
     """4161 edges = 66 leaves of the reduction tree: the second level takes more than one leaf per accumulator.  (The same
-    path over vertices needs more than 4096 free vertices: the benchmark's size, not a test's.)"""
+    path over vertices needs more than 4096 free vertices: test_more_vertex_leaves_than_accumulators.)"""
     rng = np.random.default_rng(21)
     pairs = [(int(a), int(b)) for a, b in (rng.choice(5, 2, replace=False) for _ in range(4161))]
     g = po.make_graph(5, pairs, 21)
@@ -162,6 +162,29 @@ def test_more_leaves_than_accumulators(fe):
     assert bits(got["chi2"]) == bits(lin["chi2"]) and bits(pg.chi2(fe)) == bits(lin["chi2"])
     want = po.new_report()
     po.optimize(g, 2, want)
+    check_report(pg.optimize(fe, 2), want)
+    check_estimates(pg, g)
+    pg.close()
+
+
+def test_more_vertex_leaves_than_accumulators(fe):
+    """4097 free vertices = 65 leaves: pg_tree_finish over part_b (pg_pcg_start, pg_pcg_alpha, pg_pcg_beta, pg_trial_finish)
+    takes a second leaf into accumulator 0.  Two fixed hubs, every other vertex on one of them, 40 edges between
+    neighbours: the PCG solves stay short, and the first one is still read back in a second chunk."""
+    star = [(v % 2, v) for v in range(2, 4099)]
+    cross = [(v, v + 1) for v in range(2, 202, 5)]
+    g = po.make_graph(4099, star + cross, 3, fixed=(0, 1))
+    assert len(g.ei) == 4137 and g.n - int(np.sum(g.fixed)) == 4097 and -(-4097 // po.TILE) == 65 > po.TILE
+    lin = po.linearize(g)
+    pg = library_graph(g)
+    got = pg.linearize(fe)
+    assert same(got["e"], lin["e"]) and same(got["Hd"], lin["Hd"]) and same(got["B"], lin["B"]) and same(got["b"], lin["b"])
+    assert bits(got["chi2"]) == bits(lin["chi2"]) and bits(pg.chi2(fe)) == bits(lin["chi2"])
+    want = po.new_report()
+    po.optimize(g, 2, want)
+    counts = [int(c) for r in want["its"] for c in r["pcg"][:r["trials"]]]
+    print("PCG iterations per solve:", counts)
+    assert len(want["its"]) == 2 and max(counts) <= 20 and max(counts) > po.PCG_FIRST_CHUNK
     check_report(pg.optimize(fe, 2), want)
     check_estimates(pg, g)
     pg.close()

@@ -284,3 +284,79 @@ def test_two_identical_calls_give_identical_bytes(fe):
     a = fe.voxel_filter(pts, 0.1, return_flags=True)
     b = fe.voxel_filter(pts, 0.1, return_flags=True)
     assert a[1] == b[1] and a[0].tobytes() == b[0].tobytes() and len(a[0]) > 0
+
+
+# ---- the later trips of block_scan_1024 (csrc/voxel_filter.hip): one workgroup covers 1024 tiles a trip and carries `base`
+TILE, SORT_TILE, TRIP = 1024, 4096, 1024  # kVoxTile, kVoxSortTile, the tiles of one trip
+
+
+def tiles(n, tile=TILE):
+    return -(-n // tile)
+
+
+def trips(n_tiles):
+    return -(-n_tiles // TRIP)
+
+
+def cells_starting_behind(info, at):
+    """The occupied cells whose first sorted pair stands at position `at` or behind it."""
+    start = np.cumsum(info["count"]) - info["count"]
+    return int((start >= at).sum())
+
+
+@pytest.mark.parametrize("n,side,leaf,point_trips,head_trips,passes", [
+    (1048576, 3.0, 0.05, 1, 1, 3), (1048577, 3.0, 0.05, 2, 1, 3), (2097153, 3.0, 0.05, 3, 2, 3), (1048577, 6.0, 0.02, 2, 1, 4),
+    (2097153, 6.0, 0.02, 3, 2, 4)])
+def test_more_point_and_cell_tiles_than_one_trip_of_the_scan(fe, n, side, leaf, point_trips, head_trips, passes):
+    """vox_finish_kernel scans ceil(n / 1024) tile counts, vox_head_scan_kernel ceil(n_valid / 1024): 1024 tiles are one full
+    trip of block_scan_1024, 1025 a second trip of one tile, 2049 a third.  The last row is made valid, so that the one
+    point of tile 1024 (2048) takes its rank from the carried base."""
+    pts = vo.cloud(n, seed=n % 1000 + int(side), side=side)
+    pts[n - 1, :3] = np.float32(0.125) * np.float32(side)
+    assert trips(tiles(n)) == point_trips
+    valid = np.isfinite(pts[:, :3]).all(axis=1)
+    for trip in range(1, point_trips):  # every later trip has valid points: ranks that need the carried base
+        assert valid[trip * TRIP * TILE:(trip + 1) * TRIP * TILE].any()
+    info = check(fe, pts, leaf)
+    assert info["passes"] == passes
+    assert trips(tiles(info["n_valid"])) == head_trips
+    if head_trips > 1:  # cells that start in the second trip of the head scan
+        assert info["n_valid"] > TRIP * TILE and cells_starting_behind(info, TRIP * TILE) > 1000
+    print("n %d leaf %g: %d tiles of points, %d valid points in %d tiles, %d cells" % (n, leaf, tiles(n), info["n_valid"],
+                                                                                     tiles(info["n_valid"]), len(info["count"])))
+
+
+def test_a_second_trip_from_base_zero_and_one_that_adds_nothing(fe):
+    """1 049 601 points = 1026 tiles.  First no valid point in the first 1024 tiles: the second trip starts from base 0.
+    Then valid points in the first 1024 tiles only: the second trip adds nothing to a base of 1 048 576."""
+    n, first = 1049601, TRIP * TILE
+    assert tiles(n) == 1026
+    late = vo.cloud(n, seed=71)
+    late[:first, 2] = np.nan
+    info = check(fe, late, 0.05)
+    assert 0 < info["n_valid"] <= n - first and np.isfinite(late[first:, :3]).all(axis=1).sum() == info["n_valid"]
+    early = vo.cloud(n, seed=72, nan_share=0, infs=False)
+    early[first:, 2] = np.nan
+    info = check(fe, early, 0.05)
+    assert info["n_valid"] == first and tiles(info["n_valid"]) == TRIP  # the head scan: exactly one full trip
+
+
+def test_more_sort_tiles_than_one_trip_of_the_digit_scan(fe):
+    """4 198 401 valid points = 1026 sort tiles of 4096 pairs: vox_digit_scan_kernel makes a second trip over every digit's
+    row in each of the three passes, and the point and head scans make five.  Through both entry points."""
+    import torch
+    n = 4198401
+    pts = vo.cloud(n, seed=73, side=6.0, nan_share=0, infs=False)
+    want, want_flags, info = vo.voxel_filter(pts, 0.05)
+    assert info["n_valid"] > 4194304 and tiles(info["n_valid"], SORT_TILE) == 1026 and trips(1026) == 2
+    assert info["passes"] == 3 and want_flags == 0 and cells_starting_behind(info, 4 * TRIP * TILE) > 0
+    d_in = torch.from_numpy(pts).to("cuda:0")
+    d_out = torch.full((len(want) + 3, 4), -7.0, dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()  # the copies run on torch's stream, the filter on the context's
+    n_out, flags = fe.voxel_filter_device(d_in, 0.05, d_out, return_flags=True)
+    back = d_out.cpu().numpy()
+    assert (n_out, flags) == (len(want), 0) and np.all(back[n_out:] == -7.0)
+    assert back[:n_out].tobytes() == want.tobytes(), mo.mismatch(back[:n_out], want)
+    del d_in, d_out
+    got, flags = fe.voxel_filter(pts, 0.05, return_flags=True)
+    assert flags == 0 and got.shape == want.shape and got.tobytes() == want.tobytes(), mo.mismatch(got, want)
