@@ -396,10 +396,18 @@ int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_it
  * without splitting the train rows, 256 otherwise (every live-SLAM batch); environment variable RGBDFE_HAMMING_WIDE = 0 / 1
  * (read by rgbdfe_create) fixes it, and rgbdfe_set_hamming_mode(ctx, 3) asks for 256-query blocks by name.
  * rgbdfe_hamming_wide_last: 1 = the latest Hamming launch of the context ran 512-query blocks, 0 = it did not, -1 = there
- * was none yet. */
+ * was none yet.
+ * Mode 3's 512-query blocks exist on both shapes of the fp4 MFMA: 32x32x64 tiles (mode 4's kernel) and 16x16x128 tiles
+ * (same blocks, same slab, same keys).  rgbdfe_set_hamming_shape(ctx, 0 | 16 | 32): 0 = the library's choice, 16 / 32 =
+ * that tile wherever mode 3 runs 512-query blocks; environment variable RGBDFE_HAMMING_SHAPE (read by rgbdfe_create) sets
+ * the same.  256-query blocks, modes 1, 2 and mode 4 by name are 32x32x64 whatever the shape.
+ * rgbdfe_hamming_shape_last: 16 / 32 = the MFMA tile of the latest Hamming launch of the context, 0 = it ran the popcount
+ * kernel, -1 = there was none yet. */
 #define RGBDFE_HAMMING_MODE_DEFAULT 3
 int rgbdfe_set_hamming_mode(rgbdfe_ctx* ctx, int32_t mode);
 int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx);
+int rgbdfe_set_hamming_shape(rgbdfe_ctx* ctx, int32_t shape);
+int rgbdfe_hamming_shape_last(rgbdfe_ctx* ctx);
 
 /* ---- frame-level data either side of the pair path ----------------
  * rgbdfe_depth_to_mono8: depthToCV8UC1 (misc.cpp:414-430), the detection mask the listener derives from

@@ -418,6 +418,10 @@ def load():
     L.rgbdfe_set_hamming_mode.argtypes = [ctx, i32]
     L.rgbdfe_hamming_wide_last.restype = C.c_int
     L.rgbdfe_hamming_wide_last.argtypes = [ctx]
+    L.rgbdfe_set_hamming_shape.restype = C.c_int
+    L.rgbdfe_set_hamming_shape.argtypes = [ctx, i32]
+    L.rgbdfe_hamming_shape_last.restype = C.c_int
+    L.rgbdfe_hamming_shape_last.argtypes = [ctx]
     L.rgbdfe_match_pair_list_allgather_compact.restype = C.c_int
     L.rgbdfe_match_pair_list_allgather_compact.argtypes = [ctx, vp, vp, i32, vp, C.POINTER(i32)]
     L.rgbdfe_pack_compact.restype = C.c_int
@@ -552,7 +556,7 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_pose_graph_add_edge_se3", "rgbdfe_pose_graph_chi2", "rgbdfe_pose_graph_linearize",
     "rgbdfe_pose_graph_optimize", "rgbdfe_pose_graph_optimize_graph", "rgbdfe_pose_graph_transforms",
     "rgbdfe_create_multi", "rgbdfe_device_count", "rgbdfe_device_context", "rgbdfe_match_pair_list_allgather",
-    "rgbdfe_gather_transport", "rgbdfe_gather_exchanges", "rgbdfe_set_hamming_mode", "rgbdfe_hamming_wide_last", "rgbdfe_project_to_3d_cloud", "rgbdfe_detect_describe_cloud",
+    "rgbdfe_gather_transport", "rgbdfe_gather_exchanges", "rgbdfe_set_hamming_mode", "rgbdfe_hamming_wide_last", "rgbdfe_set_hamming_shape", "rgbdfe_hamming_shape_last", "rgbdfe_project_to_3d_cloud", "rgbdfe_detect_describe_cloud",
     "rgbdfe_detect_describe_batch", "rgbdfe_detect_describe_batch_nodes", "rgbdfe_match_pair_list_allgather_edges",
     "rgbdfe_set_feature_min_depth", "rgbdfe_project_to_3d_min_depth",
     "rgbdfe_place_recognition", "rgbdfe_place_recognition_batch", "rgbdfe_upload_float_node",

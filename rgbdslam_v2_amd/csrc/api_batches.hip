@@ -167,16 +167,21 @@ bool hamming_on_mfma(const rgbdfe_ctx* ctx) { return ctx->hamming_mode != 0 && (
 
 HammingGeometry hamming_geometry(const rgbdfe_ctx* ctx, uint32_t n, uint32_t max_nq, uint32_t max_nt) {
   const uint32_t cap = (uint32_t)ctx->cfg.max_pairs_per_batch;
-  if (!hamming_on_mfma(ctx)) return hamming_nn_geometry(n, max_nq, max_nt, cap);
+  if (!hamming_on_mfma(ctx)) {
+    HammingGeometry g = hamming_nn_geometry(n, max_nq, max_nt, cap);
+    g.shape = 0;
+    return g;
+  }
   // the pipelined kernel's block width: mode 4 = 512 queries, mode 3 = the context's choice (rgbdfe_host.h: hamming_wide)
   const int pipe_wide = ctx->hamming_mode == 4 ? 1 : ctx->hamming_mode == 3 ? ctx->hamming_wide : 0;
-  return hamming_mfma_geometry(n, max_nq, max_nt, cap, pipe_wide);
+  // the MFMA tile of 512-query blocks: mode 4 is the 32x32x64 kernel by name, mode 3 takes the context's choice (hamming_shape)
+  return hamming_mfma_geometry(n, max_nq, max_nt, cap, pipe_wide, ctx->hamming_mode == 3 ? ctx->hamming_shape : 32);
 }
 
 uint32_t launch_hamming(rgbdfe_ctx* ctx, const PairWork* d_work, uint32_t* d_keys, uint32_t n, HammingGeometry geom,
                         hipStream_t stream) {
   const uint32_t mk = (uint32_t)ctx->cfg.max_keypoints;
-  if (n > 0 && geom.qblocks > 0) ctx->hamming_wide_last = (int)geom.wide;
+  if (n > 0 && geom.qblocks > 0) { ctx->hamming_wide_last = (int)geom.wide; ctx->hamming_shape_last = (int)geom.shape; }
   if (hamming_on_mfma(ctx))
     return launch_hamming_mfma(ctx->d_desc4, d_work, d_keys, mk, n, geom, ctx->hamming_mode, stream);
   return launch_hamming_nn(ctx->d_desc, d_work, d_keys, mk, n, geom, stream);
@@ -272,14 +277,14 @@ int enqueue_pairs(rgbdfe_ctx* ctx, const int32_t* qids, const int32_t* tids, int
     // node sizes enter the launches only through the Hamming stage's geometry (query blocks and train splits per pair)
     const HammingGeometry geom = sift ? HammingGeometry{0, 1, 0}
                                       : hamming_geometry(ctx, (uint32_t)(piece < n ? piece : n), max_nq, max_nt);
-    if (!sift && geom.qblocks > 0) ctx->hamming_wide_last = (int)geom.wide;   // (a replayed graph launches nothing by hand)
+    if (!sift && geom.qblocks > 0) { ctx->hamming_wide_last = (int)geom.wide; ctx->hamming_shape_last = (int)geom.shape; }   // (a replayed graph launches nothing by hand)
     rgbdfe_ctx::GraphEntry* ge = nullptr;
     bool capturing = false;
     if (graphable) {
       rgbdfe_ctx::GraphKey key;
       memset(&key, 0, sizeof(key));
       key.n = n; key.qblocks = geom.qblocks; key.tsplit = geom.tsplit; key.slot = (int32_t)(ticket % rgbdfe_ctx::kRing);
-      key.latency = latency ? 1 : 0; key.chunk = chunk; key.hamming_mode = ctx->hamming_mode | (int32_t)(geom.wide << 8); key.n_phases = pp.n_phases;
+      key.latency = latency ? 1 : 0; key.chunk = chunk; key.hamming_mode = ctx->hamming_mode | (int32_t)(geom.wide << 8) | (int32_t)(geom.shape << 16); key.n_phases = pp.n_phases;
       for (int i = 0; i < 4; ++i) key.ends[i] = i < pp.n_phases ? pp.ends[i] : 0;
       memcpy(&key.rc, &ctx->rc, sizeof(RansacConst));
       key.d_out = d_out; key.d_recs = lane.d_recs; key.d_ec = lane.d_ec; key.d_walk = lane.d_walk; key.d_keys = lane.d_keys;

@@ -37,6 +37,7 @@ int rgbdfe_create(const rgbdfe_config* cfg, rgbdfe_ctx** out) {
   if (const char* sf = getenv("RGBDFE_SIFT_FAST_KEYS")) ctx->sift_fast = atoi(sf) != 0;
   if (const char* hm = getenv("RGBDFE_HAMMING_MODE")) ctx->hamming_mode = atoi(hm) < 0 || atoi(hm) > 4 ? RGBDFE_HAMMING_MODE_DEFAULT : atoi(hm);
   if (const char* hw = getenv("RGBDFE_HAMMING_WIDE")) ctx->hamming_wide = atoi(hw) != 0 ? 1 : 0;   // (mode 3's block width)
+  if (const char* hs = getenv("RGBDFE_HAMMING_SHAPE")) ctx->hamming_shape = atoi(hs) == 16 || atoi(hs) == 32 ? atoi(hs) : 0;   // (the MFMA tile of mode 3's 512-query blocks)
   if (const char* gr = getenv("RGBDFE_GRAPHS")) ctx->use_graphs = atoi(gr) != 0;   // (rgbdfe_set_graph_capture overrides)
   auto bail = [&](int code) { ::rgbdfe_destroy(ctx); return code; };   // (the C entry point: it owns the teardown order)
   if (hipSetDevice(cfg->device_id) != hipSuccess) return bail(RGBDFE_ERR_NO_DEVICE);

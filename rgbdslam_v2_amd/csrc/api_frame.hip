@@ -647,6 +647,19 @@ int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx) {
   return ctx->hamming_wide_last;
 }
 
+int rgbdfe_set_hamming_shape(rgbdfe_ctx* ctx, int32_t shape) {
+  if (!ctx || (shape != 0 && shape != 16 && shape != 32)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "hamming shape must be 0, 16 or 32");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  ctx->hamming_shape = shape;
+  return RGBDFE_OK;
+}
+
+int rgbdfe_hamming_shape_last(rgbdfe_ctx* ctx) {
+  if (!ctx) return -1;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return ctx->hamming_shape_last;
+}
+
 int rgbdfe_set_profiling(rgbdfe_ctx* ctx, int enable) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(ctx->mu);

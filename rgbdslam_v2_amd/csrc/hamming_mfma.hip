@@ -22,7 +22,8 @@
 // MODE 1 adds the row term inside the MFMA (C operand); MODE 2 starts from C = 0 and adds it with v_add_f32 (kept as
 // the conservative variant: it does not rely on the matrix core adding a 2^-14-granular C to the integer sum exactly);
 // MODE 3 (hamming_mfma_pipe_kernel below, the default since round 4) is mode 1's arithmetic as a software pipeline inside
-// every wave: reductions and LDS reads between the MFMAs, train tiles by global_load_lds through three LDS buffers.
+// every wave: reductions and LDS reads between the MFMAs, train tiles by global_load_lds through three LDS buffers;
+// hamming_mfma_x16_kernel (further below, what mode 3 runs for large batches) is its 512-query block on 16x16x128 tiles.
 // Keys are identical to the popcount kernel's, bit for bit (tests/test_gpu_hamming.py runs every mode against the
 // golden vectors of the reference function).  Usable while max_keypoints <= 32768 (15 index bits next to 9 distance
 // bits in a 24-bit significand); the host falls back to the popcount kernel above that.
@@ -752,6 +753,281 @@ void hamming_mfma_pipe_kernel(const uint4* __restrict__ slab,
   }
 }
 #undef HP_MFMA
+
+// ------------------------------------------------------------------------------------------------
+// The 512-query block on 16x16x128 tiles (v_mfma_f32_16x16x128_f8f6f4): the same blocks, stages, slots and keys as the
+// QT = 4 form above, out of the small shape of the instruction.
+//   * No other slab format: a dot product does not care which k a bit sits at as long as both operands agree.  The small
+//     MFMA takes, from lane g*16 + r, 32 nibbles of row r for k-group g; k-step S (of two) and k-group g together are
+//     descriptor dword 4S + g, so the lane reads the 16-byte piece (2S + (g >> 1))*64 + (g & 1)*32 + 16u + r of the 32-row
+//     tile image for the 16-row sub-tile u -- the query side from global memory, the train side from LDS.  The four lane
+//     groups of a ds_read_b128 each touch sixteen different 16-byte slots of the 256-byte bank row: no conflicts.
+//   * A wave holds 128 queries as EIGHT 16-query operand tiles (64 registers, as the four 32-query tiles above).  A unit is
+//     one 16-row sub-tile x one query tile: a chain of TWO MFMAs into a 4-register accumulator, reduced by two v_min3_u32
+//     straight into the running minimum (one register per query tile).  Nothing is added behind the MFMA: the C operand
+//     carries 256 + (absolute row) / 2^14, one 4-register C per sub-tile, moved on from train tile to train tile in place by
+//     the block-uniform distance between them (8 v_add_f32 per 32 MFMAs; multiples of 2^-14 below 2^10: exact).
+//   * The stream is a rotation over four accumulators: step n issues the first MFMA of unit n, the second MFMA of unit
+//     n - 1 and the reduction of unit n - 3, so no MFMA waits for the one in front of it and a reduction reads a result that
+//     is three MFMAs old.  A 16-cycle MFMA leaves room for about two single-issue instructions: a step carries two or three
+//     VALU instructions and at most one ds_read_b128, pinned by sched_group_barrier as above.
+//   * Two A operand sets (16 registers each) alternate tile by tile, the next tile's four reads ride in steps 1..4; the
+//     registers are there because the accumulators take 16, not 32.  The ragged tile is excluded in LDS as in the QT = 4 form.
+//   * The stage is ONE loop body with one way out (the buffers rotate as addresses, see below): written as three copies like
+//     the forms above, the copies' accumulators and operand sets met at the joins in different registers and were spilled.
+//   148 VGPRs, no scratch (tests/test_hamming_x16_build.py); measured against the QT = 4 form in DESIGN 4.1c.
+// ------------------------------------------------------------------------------------------------
+typedef float v4f __attribute__((ext_vector_type(4)));
+#define HX_MFMA(ACC, A, B, C) ACC = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(op8(A), op8(B), C, 4, 4, 0, 0, 0, 0);
+
+template <bool SPLIT>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RGBDFE_HAMMING_PIPE_WAVES, RGBDFE_HAMMING_PIPE_WAVES)))
+void hamming_mfma_x16_kernel(const uint4* __restrict__ slab, const PairWork* __restrict__ work, uint32_t* __restrict__ keys,
+                             uint32_t max_kp, uint32_t tiles_per_slot, uint32_t n_pairs, uint32_t qblocks, uint32_t tsplit) {
+  __shared__ uint4 lds0[kPipeStage][256], lds1[kPipeStage][256], lds2[kPipeStage][256];   // the three stage buffers
+  constexpr uint32_t kQPB = 512u;
+  const uint32_t L = blockIdx.x;
+  const uint32_t xcd = L & 7u;
+  const uint32_t j = L >> 3;
+  const uint32_t subs = qblocks * tsplit;
+  const uint32_t pair = (j / subs) * 8u + xcd;
+  if (pair >= n_pairs) return;
+  const uint32_t sub = j % subs;
+  const uint32_t qblock = sub / tsplit;
+  const uint32_t split = sub % tsplit;
+
+  const PairWork w = work[pair];
+  const uint32_t nq = w.nq;
+  if (qblock * kQPB >= nq) return;
+  const HammingSlots slots = HammingSlots::make(w.nt, SPLIT ? tsplit : 1u, SPLIT ? split : 0u, kPipeStage);
+  const uint32_t nt_search = slots.nt_search, n_stages = slots.n_stages;
+  const bool has_ragged = slots.has_ragged;
+  // A slot without a tile of its own repeats one of the block's tiles (a minimum does not mind seeing a row twice): the
+  // block's first full tile, or -- in a block that has the ragged tile alone -- the ragged tile.  So every slot has a real
+  // base and the C operands below stay exact sums of small multiples of 2^-14.
+  const uint32_t dup_tile = slots.n_full > 0u ? slots.tile0 : slots.n_ttiles - 1u;
+  auto slot_tile = [&](uint32_t s) -> uint32_t {   // block-uniform
+    const uint32_t t = slots.tile(s);
+    return t == kHammingPhantomTile ? dup_tile : t;
+  };
+
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t grp = lane >> 4;   // k-group of the operands, row group of the accumulator
+  // this lane's 16-byte piece of (k-step 0, sub-tile 0) in a tile image; k-step S adds 128 pieces, sub-tile u adds 16
+  const uint32_t lpiece = (grp >> 1) * 64u + (grp & 1u) * 32u + (lane & 15u);
+
+  v4i bq[8][2];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    uint32_t qt = qblock * (kQPB / 32u) + wave * 4u + (uint32_t)(q >> 1);
+    qt = min(qt, tiles_per_slot - 1u);
+    const uint4* __restrict__ qs = slab + ((size_t)w.q_slot * tiles_per_slot + qt) * 256u;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const uint4 v = qs[s * 128 + (q & 1) * 16 + lpiece];
+      bq[q][s][0] = (int)v.x; bq[q][s][1] = (int)v.y; bq[q][s][2] = (int)v.z; bq[q][s][3] = (int)v.w;
+    }
+  }
+
+  // (the sign flip after all sixteen loads, each operand in the registers it arrived in)
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bq[q][s] ^= (int)0x88888888u;
+      asm volatile("" : "+v"(bq[q][s]));
+    }
+
+  // accumulator register i of this lane belongs to train row 16u + 4*grp + i of the tile
+  v4f c[2];   // the C operands of the two sub-tiles: 256 + (absolute row) / 2^14, moved from tile to tile by the stream
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[u][i] = kBias + (float)(16 * u + 4 * (int)grp + i) * kRowUnit;
+  uint32_t best[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) best[q] = __float_as_uint(kNone);
+
+  const uint32_t last_tile = tiles_per_slot - 1u;
+  const char* __restrict__ ts = reinterpret_cast<const char*>(slab + (size_t)w.t_slot * tiles_per_slot * 256u);
+  const uint64_t ts_u = reinterpret_cast<uint64_t>(ts);
+  const uint32_t ts_lo = __builtin_amdgcn_readfirstlane((uint32_t)ts_u);
+  const uint32_t ts_hi = __builtin_amdgcn_readfirstlane((uint32_t)(ts_u >> 32));
+  const uint32_t vo16 = threadIdx.x * 16u;
+  // The three stage buffers take turns as CUR / NXT / the one being filled; the stream below is ONE loop body, so they are
+  // LDS byte addresses in scalar registers that rotate once per stage (the reads are the stream's own ds_read_b128 and the
+  // fills are LDS-DMA: neither needs the compiler to tell the buffers apart).
+  typedef __attribute__((address_space(3))) char lds_char;
+  const uint32_t o0 = (uint32_t)(size_t)(lds_char*)&lds0[0][0];
+  const uint32_t o1 = (uint32_t)(size_t)(lds_char*)&lds1[0][0];
+  const uint32_t o2 = (uint32_t)(size_t)(lds_char*)&lds2[0][0];
+  auto load_stage = [&](uint32_t st, uint32_t buf) {
+#pragma unroll
+    for (int i = 0; i < kPipeStage; ++i) {
+      const uint32_t tl = min(slot_tile(st * kPipeStage + (uint32_t)i), last_tile);
+      const char* tb = reinterpret_cast<const char*>((((uint64_t)ts_hi << 32) | ts_lo) + (uint64_t)tl * 4096u);
+      uint32_t vo = vo16;
+      asm volatile("" : "+v"(vo));
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tb + vo),
+                                       (__attribute__((address_space(3))) void*)(lds_char*)(size_t)(buf + (uint32_t)i * 4096u + wave * 1024u),
+                                       16, 0, 0);
+    }
+  };
+
+  if (n_stages > 0) {
+    load_stage(0, o0);
+    if (n_stages > 1) load_stage(1, o1);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    __syncthreads();
+    // as in the QT = 4 form: the rows of the ragged tile that do not take part become copies of its row 0 (slot `slot` of `buf`)
+    auto patch_ragged = [&](uint32_t buf, uint32_t slot) {
+      const uint32_t t = threadIdx.x;
+      __attribute__((address_space(3))) v4i* tile = (__attribute__((address_space(3))) v4i*)(lds_char*)(size_t)(buf + slot * 4096u);
+      if ((t & 31u) >= (nt_search & 31u)) tile[t] = tile[t & ~31u];
+    };
+    if (has_ragged && slots.n_full == 0u) {   // one stage, the ragged tile in all four slots
+#pragma unroll
+      for (int i = 0; i < kPipeStage; ++i) patch_ragged(o0, (uint32_t)i);
+      __syncthreads();
+    } else if (has_ragged && n_stages == 1u) {   // (a later last stage is patched in the loop, once it is published)
+      patch_ragged(o0, kPipeStage - 1u);
+    }
+
+    v4i aA[2][2], aB[2][2];   // [sub-tile][k-step] of the even / odd slots of a stage
+    // LDS reads are this stream's own ds_read_b128, as in the QT = 4 form and for its reason: the operand lands in the
+    // registers it replaces (input and output of the statement), so the two sets stay the same 32 registers round the loop.
+    // The stream counts its own waits: a tile's four reads are issued in its steps 1..4 and the next tile starts with
+    // lgkmcnt(0), eleven steps later.
+    const uint32_t lp16 = lpiece * 16u;
+    uint32_t cur = o0, nxt = o1, fill = o2;   // block-uniform
+    uint32_t rdc, rdn;                        // this lane's piece of (slot 0, k-step 0, sub-tile 0) in CUR / NXT
+#define HX_RD(DST, RD, SLOT, U, S)                                                                                    \
+      asm volatile("ds_read_b128 %0, %1 offset:%2" : "+v"(DST[U][S]) : "v"(RD), "n"((SLOT) * 4096 + (S) * 2048 + (U) * 256) : "memory");
+#define HX_WAIT() __builtin_amdgcn_s_waitcnt(0xC07F); HP_FENCE()   /* lgkmcnt(0) alone */
+#define HX_NORD
+    // the way from the tile of slot SLOT - 1 to the tile of slot SLOT of this stage, in key units (block-uniform, exact)
+#define HX_DELTA(SLOT) __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(                                \
+      (float)((int)slot_tile(st * kPipeStage + (SLOT)) - (int)slot_tile(st * kPipeStage + (SLOT) - 1u)) * kRowUnitPerTile)))
+    // the C operand of sub-tile U moves on by D, one register per step, in place
+#define HX_C(U, I, D) c[U][I] += (D); asm volatile("" : "+v"(c[U][I]));
+#define HX_EPI(ACC, BEST) {                                                                                             \
+      const uint32_t m_ = min(min(__float_as_uint(ACC[0]), __float_as_uint(ACC[1])), __float_as_uint(ACC[2]));          \
+      BEST = min(min(m_, __float_as_uint(ACC[3])), BEST);                                                               \
+      asm volatile("" : "+v"(BEST)); }
+    // step N of a tile (N = 8u + q): first MFMA of this unit, second MFMA of the previous unit (operand set P, sub-tile PU,
+    // query tile PQ), reduction of the unit three back (query tile RQ); EXTRA = one ds_read_b128 and / or one v_add_f32
+#define HX_STEP(N, X, P, PU, PQ, RQ, EXTRA, SCHED)                                       \
+      HX_MFMA(acc[(N) & 3], X[(N) >> 3][0], bq[(N) & 7][0], c[(N) >> 3])                 \
+      EXTRA                                                                              \
+      HX_MFMA(acc[((N) + 3) & 3], P[PU][1], bq[PQ][1], acc[((N) + 3) & 3])               \
+      HX_EPI(acc[((N) + 1) & 3], best[RQ])                                               \
+      SCHED                                                                              \
+      HP_FENCE()
+#define HX_SCHED_V  HP_SGB(0x008, 1) HP_SGB(0x002, 1) HP_SGB(0x008, 1) HP_SGB(0x002, 1)
+#define HX_SCHED_VV HP_SGB(0x008, 1) HP_SGB(0x002, 2) HP_SGB(0x008, 1) HP_SGB(0x002, 1)
+#define HX_SCHED_DV HP_SGB(0x008, 1) HP_SGB(0x100, 1) HP_SGB(0x002, 1) HP_SGB(0x008, 1) HP_SGB(0x002, 1)
+#define HX_SCHED_DVV HP_SGB(0x008, 1) HP_SGB(0x100, 1) HP_SGB(0x002, 2) HP_SGB(0x008, 1) HP_SGB(0x002, 1)
+    // one train tile out of operand set X; Y is refilled with slot RSLOT behind RD; B = the way from the previous tile to
+    // this one (sub-tile 1 follows in steps 0..3), BN = from this one to the next (sub-tile 0 goes ahead in steps 8..11)
+#define HX_TILE(X, Y, RD, RSLOT, B, BN)                                                                   \
+      HX_WAIT()                                                                                           \
+      HX_STEP(0, X, Y, 1, 7, 5, HX_C(1, 0, B), HX_SCHED_VV)                                               \
+      HX_STEP(1, X, X, 0, 0, 6, HX_RD(Y, RD, RSLOT, 0, 0) HX_C(1, 1, B), HX_SCHED_DVV)                    \
+      HX_STEP(2, X, X, 0, 1, 7, HX_RD(Y, RD, RSLOT, 0, 1) HX_C(1, 2, B), HX_SCHED_DVV)                    \
+      HX_STEP(3, X, X, 0, 2, 0, HX_RD(Y, RD, RSLOT, 1, 0) HX_C(1, 3, B), HX_SCHED_DVV)                    \
+      HX_STEP(4, X, X, 0, 3, 1, HX_RD(Y, RD, RSLOT, 1, 1), HX_SCHED_DV)                                   \
+      HX_STEP(5, X, X, 0, 4, 2, HX_NORD, HX_SCHED_V)                                                      \
+      HX_STEP(6, X, X, 0, 5, 3, HX_NORD, HX_SCHED_V)                                                      \
+      HX_STEP(7, X, X, 0, 6, 4, HX_NORD, HX_SCHED_V)                                                      \
+      HX_STEP(8, X, X, 0, 7, 5, HX_C(0, 0, BN), HX_SCHED_VV)                                              \
+      HX_STEP(9, X, X, 1, 0, 6, HX_C(0, 1, BN), HX_SCHED_VV)                                              \
+      HX_STEP(10, X, X, 1, 1, 7, HX_C(0, 2, BN), HX_SCHED_VV)                                             \
+      HX_STEP(11, X, X, 1, 2, 0, HX_C(0, 3, BN), HX_SCHED_VV)                                             \
+      HX_STEP(12, X, X, 1, 3, 1, HX_NORD, HX_SCHED_V)                                                     \
+      HX_STEP(13, X, X, 1, 4, 2, HX_NORD, HX_SCHED_V)                                                     \
+      HX_STEP(14, X, X, 1, 5, 3, HX_NORD, HX_SCHED_V)                                                     \
+      HX_STEP(15, X, X, 1, 6, 4, HX_NORD, HX_SCHED_V)
+    // A stage out of buffer CUR in two halves.  The barrier between them publishes the NEXT stage (this wave's LDS-DMA of it
+    // was issued a whole stage ago) and frees the buffer of the PREVIOUS one for the stage after the next, as in the forms above.
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) { aA[u][s] = v4i{0, 0, 0, 0}; aB[u][s] = v4i{0, 0, 0, 0}; }
+    rdc = cur + lp16;
+    HX_RD(aA, rdc, 0, 0, 0) HX_RD(aA, rdc, 0, 0, 1) HX_RD(aA, rdc, 0, 1, 0) HX_RD(aA, rdc, 0, 1, 1)
+    // the first three steps finish and reduce units that do not exist: their accumulators are kNone and stay it
+    v4f acc[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) acc[a] = v4f{kNone, kNone, kNone, kNone};
+    {
+      const float b0 = (float)slot_tile(0) * kRowUnitPerTile;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { c[0][i] += b0; c[1][i] += b0; }
+    }
+    for (uint32_t st = 0;;) {
+      {
+        const float b0 = st > 0u ? HX_DELTA(0) : 0.f, b1 = HX_DELTA(1), b2 = HX_DELTA(2);
+        rdc = cur + lp16;
+        HP_FENCE()
+        HX_TILE(aA, aB, rdc, 1, b0, b1)
+        HX_TILE(aB, aA, rdc, 2, b1, b2)
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's share of the next stage has landed
+        __syncthreads();
+        if (has_ragged && st + 2u == n_stages) patch_ragged(nxt, kPipeStage - 1u);   // the next stage is the last one
+      }
+      {
+        if (st + 2u < n_stages) load_stage(st + 2u, fill);
+        const float b2 = HX_DELTA(2), b3 = HX_DELTA(3), b4 = HX_DELTA(4);   // (slot 4 = the next stage's slot 0)
+        rdn = nxt + lp16;
+        HP_FENCE()
+        HX_TILE(aA, aB, rdc, 3, b2, b3)
+        HX_TILE(aB, aA, rdn, 0, b3, b4)
+      }
+      if (++st == n_stages) break;
+      const uint32_t t_ = cur; cur = nxt; nxt = fill; fill = t_;
+    }
+    // the last unit's second MFMA and the last three reductions (behind the last tile's reads, which nobody uses: their
+    // registers are free for others only once they have landed)
+    HX_WAIT()
+    HX_MFMA(acc[3], aB[1][1], bq[7][1], acc[3])
+    HX_EPI(acc[1], best[5])
+    HX_EPI(acc[2], best[6])
+    HX_EPI(acc[3], best[7])
+#undef HX_TILE
+#undef HX_SCHED_V
+#undef HX_SCHED_VV
+#undef HX_SCHED_DV
+#undef HX_SCHED_DVV
+#undef HX_STEP
+#undef HX_EPI
+#undef HX_C
+#undef HX_DELTA
+#undef HX_NORD
+#undef HX_WAIT
+#undef HX_RD
+  }
+
+  // a query's minimum is spread over the four row groups of its column: lanes q, q + 16, q + 32, q + 48
+  uint32_t* kout = keys + ((size_t)pair * tsplit + split) * max_kp;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    uint32_t bb = best[q];
+    bb = min(bb, (uint32_t)__shfl_xor((int)bb, 16));
+    bb = min(bb, (uint32_t)__shfl_xor((int)bb, 32));
+    const float b = __uint_as_float(bb);
+    const uint32_t qi = qblock * kQPB + (wave * 4u + (uint32_t)(q >> 1)) * 32u + (uint32_t)(q & 1) * 16u + (lane & 15u);
+    if (grp == 0 && qi < nq) {
+      uint32_t key = kNoMatchKey;
+      if (b < 1024.0f) {  // real keys: 2*hd + row / 2^14 < 516; phantoms are >= 2^22
+        const uint32_t k = (uint32_t)(b * 16384.0f);
+        key = ((k >> 15) << 16) | (k & 32767u);
+      }
+      kout[qi] = key;
+    }
+  }
+}
+#undef HX_MFMA
 #undef HP_SGB
 #undef HP_FENCE
 
@@ -799,14 +1075,25 @@ void launch_hamming_expand(const uint32_t* node_rows, uint32_t* slab, uint32_t s
 constexpr uint32_t kHammingBlockSlots = 256u * 3u;
 constexpr uint32_t kWideMinBlocksPerSlot = 10u;
 
-// pipe_wide: -1 = choose (the pipelined kernel only), 0 = 256-query blocks, 1 = 512-query blocks
+// The MFMA tile the automatic choice gives 512-query blocks: what was measured faster at both batch sizes.
+// (A variant build that fixes RGBDFE_HAMMING_PIPE_QT is there to time the 32x32x64 kernels: it keeps their tile.)
+#ifndef RGBDFE_HAMMING_WIDE_SHAPE
+#if RGBDFE_HAMMING_PIPE_QT == 0
+#define RGBDFE_HAMMING_WIDE_SHAPE 16
+#else
+#define RGBDFE_HAMMING_WIDE_SHAPE 32
+#endif
+#endif
+
+// pipe_wide: -1 = choose (the pipelined kernel only), 0 = 256-query blocks, 1 = 512-query blocks;
+// wide_shape: 0 = choose, 16 / 32 = the MFMA tile of 512-query blocks
 HammingGeometry hamming_mfma_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_t max_nt, uint32_t key_planes_capacity,
-                                      int pipe_wide) {
-  HammingGeometry g{0, 1, 0};
+                                      int pipe_wide, int wide_shape) {
+  HammingGeometry g{0, 1, 0, 32};
   if (n_pairs == 0 || max_nq == 0) return g;
   const uint32_t ttiles = (max_nt + 31u) / 32u;
   auto shape = [&](uint32_t queries_per_block) {
-    HammingGeometry h{(max_nq + queries_per_block - 1u) / queries_per_block, 1, 0};
+    HammingGeometry h{(max_nq + queries_per_block - 1u) / queries_per_block, 1, 0, 32};
     // small batches (live SLAM: ~20 pairs per frame) split the train tiles over several blocks, one key plane each
     const uint32_t blocks1 = n_pairs * h.qblocks;
     if (blocks1 < 1024 && ttiles > kStage) {
@@ -835,6 +1122,7 @@ HammingGeometry hamming_mfma_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_
   if (pipe_wide > 0) {
     g = shape(2u * kQueriesPerBlock);
     g.wide = 1;
+    g.shape = wide_shape == 16 || wide_shape == 32 ? (uint32_t)wide_shape : (uint32_t)RGBDFE_HAMMING_WIDE_SHAPE;
   }
   return g;
 }
@@ -853,8 +1141,13 @@ uint32_t launch_hamming_mfma(const uint32_t* slab, const PairWork* work, uint32_
 #define RGBDFE_LAUNCH_HP(QT, S)                                                                                        \
   hipLaunchKernelGGL((hamming_mfma_pipe_kernel<QT, S>), dim3(grid), dim3(kThreads), 0, stream, s4, work, keys, max_kp, \
                      tiles_per_slot, n_pairs, qblocks, tsplit)
+#define RGBDFE_LAUNCH_HX(S)                                                                                        \
+  hipLaunchKernelGGL((hamming_mfma_x16_kernel<S>), dim3(grid), dim3(kThreads), 0, stream, s4, work, keys, max_kp, \
+                     tiles_per_slot, n_pairs, qblocks, tsplit)
   if (mode == 3 || mode == 4) {   // the geometry says which form (mode 4's is always wide, an explicit mode 3's never)
-    if (geom.wide) {
+    if (geom.wide && geom.shape == 16) {
+      if (tsplit > 1) RGBDFE_LAUNCH_HX(true); else RGBDFE_LAUNCH_HX(false);
+    } else if (geom.wide) {
       if (tsplit > 1) RGBDFE_LAUNCH_HP(4, true); else RGBDFE_LAUNCH_HP(4, false);
     } else {
       if (tsplit > 1) RGBDFE_LAUNCH_HP(2, true); else RGBDFE_LAUNCH_HP(2, false);
@@ -864,6 +1157,7 @@ uint32_t launch_hamming_mfma(const uint32_t* slab, const PairWork* work, uint32_
   } else {
     if (tsplit > 1) RGBDFE_LAUNCH_HM(1, true); else RGBDFE_LAUNCH_HM(1, false);
   }
+#undef RGBDFE_LAUNCH_HX
 #undef RGBDFE_LAUNCH_HP
 #undef RGBDFE_LAUNCH_HM
   return tsplit;

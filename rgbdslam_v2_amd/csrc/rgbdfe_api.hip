@@ -1044,6 +1044,16 @@ int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx) {
   return impl::rgbdfe_hamming_wide_last(RGBDFE_IS_GROUP(ctx) ? ctx->group->children[0] : ctx);   // (a value, not a status)
 }
 
+int rgbdfe_set_hamming_shape(rgbdfe_ctx* ctx, int32_t shape) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_ALL(ctx, impl::rgbdfe_set_hamming_shape(c, shape));
+}
+
+int rgbdfe_hamming_shape_last(rgbdfe_ctx* ctx) {
+  if (!ctx) return -1;
+  return impl::rgbdfe_hamming_shape_last(RGBDFE_IS_GROUP(ctx) ? ctx->group->children[0] : ctx);   // (a value, not a status)
+}
+
 int rgbdfe_set_profiling(rgbdfe_ctx* ctx, int enable) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;
   return RGBDFE_ALL(ctx, impl::rgbdfe_set_profiling(c, enable));

@@ -171,6 +171,9 @@ struct rgbdfe_ctx {
   int hamming_wide = -1;       // mode 3: -1 = 256- or 512-query blocks per batch (hamming_mfma_geometry), 0 / 1 = always that one
                                // (RGBDFE_HAMMING_WIDE at rgbdfe_create; rgbdfe_set_hamming_mode(3) sets 0, mode 4 is always wide)
   int hamming_wide_last = -1;  // the latest Hamming launch: 1 = 512-query blocks, 0 = any other kernel, -1 = none yet
+  int hamming_shape = 0;       // MFMA tile of mode 3's 512-query blocks: 0 = the library's choice, 16 = 16x16x128, 32 = 32x32x64
+                               // (RGBDFE_HAMMING_SHAPE at rgbdfe_create, rgbdfe_set_hamming_shape; mode 4 is always 32)
+  int hamming_shape_last = -1; // the latest Hamming launch: 16 / 32 = its MFMA tile, 0 = the popcount kernel, -1 = none yet
   // Batches run on kLanes internal HIP streams ("lanes"), each with its own keys / results
   // staging, so that batch k+1's Hamming kernel fills the SIMDs that batch k's RANSAC tail
   // leaves idle.  The pair lists go through a ring of pinned buffers so the host can prepare
@@ -609,6 +612,8 @@ int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);
 int rgbdfe_set_hamming_mode(rgbdfe_ctx* ctx, int32_t mode);
 int rgbdfe_hamming_wide_last(rgbdfe_ctx* ctx);
+int rgbdfe_set_hamming_shape(rgbdfe_ctx* ctx, int32_t shape);
+int rgbdfe_hamming_shape_last(rgbdfe_ctx* ctx);
 int rgbdfe_set_profiling(rgbdfe_ctx* ctx, int enable);
 int rgbdfe_get_kernel_time(rgbdfe_ctx* ctx, int which, double* total_ms, int64_t* launches, int64_t* pairs);
 int rgbdfe_reset_kernel_time(rgbdfe_ctx* ctx);

@@ -38,8 +38,10 @@ struct RansacConst {
 // takes the min over planes.  key_planes_capacity = planes the keys buffer can hold in total.
 // HammingGeometry = everything of a Hamming launch that depends on the batch's node sizes: query blocks per pair and
 // train-row splits (key planes) per pair.  Batches with equal (n_pairs, geometry) are the same launch -- what the
-// hipGraph cache of api_batches.hip keys on.  wide = 1: the pipelined MFMA kernel's 512-query blocks (hamming_mfma.hip).
-struct HammingGeometry { uint32_t qblocks, tsplit, wide; };
+// hipGraph cache of api_batches.hip keys on.  wide = 1: the pipelined MFMA kernel's 512-query blocks (hamming_mfma.hip);
+// shape = the MFMA tile of the launch: 16 = 16x16x128 (hamming_mfma_x16_kernel, 512-query blocks only), 32 = 32x32x64,
+// 0 = no MFMA (the popcount kernel).
+struct HammingGeometry { uint32_t qblocks, tsplit, wide, shape; };
 HammingGeometry hamming_nn_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_t max_nt, uint32_t key_planes_capacity);
 uint32_t launch_hamming_nn(const uint32_t* desc_pool, const PairWork* work, uint32_t* keys,
                            uint32_t max_kp, uint32_t n_pairs, HammingGeometry geom, hipStream_t stream);
@@ -50,9 +52,10 @@ uint32_t hamming_mfma_tiles_per_slot(uint32_t max_kp);
 size_t hamming_mfma_slab_bytes(uint32_t max_nodes, uint32_t max_kp);
 void launch_hamming_expand(const uint32_t* node_rows, uint32_t* slab, uint32_t slot, uint32_t max_kp, uint32_t n,
                            hipStream_t stream);
-// pipe_wide (the pipelined kernel, modes 3 / 4): -1 = the library chooses between 256- and 512-query blocks, 0 / 1 = forced
+// pipe_wide (the pipelined kernel, modes 3 / 4): -1 = the library chooses between 256- and 512-query blocks, 0 / 1 = forced;
+// wide_shape: the MFMA tile of 512-query blocks, 0 = the library chooses, 16 / 32 = forced (256-query blocks are always 32)
 HammingGeometry hamming_mfma_geometry(uint32_t n_pairs, uint32_t max_nq, uint32_t max_nt, uint32_t key_planes_capacity,
-                                      int pipe_wide);
+                                      int pipe_wide, int wide_shape);
 uint32_t launch_hamming_mfma(const uint32_t* slab, const PairWork* work, uint32_t* keys, uint32_t max_kp,
                              uint32_t n_pairs, HammingGeometry geom, int mode, hipStream_t stream);
 // place_recognition.hip: every query descriptor votes k - rank for the k candidate nodes holding its nearest matches

@@ -123,6 +123,16 @@ class FrontEnd:
         """1 = the latest Hamming launch ran the pipelined kernel's 512-query blocks, 0 = it did not, -1 = none yet."""
         return int(self._L.rgbdfe_hamming_wide_last(self._ctx))
 
+    def set_hamming_shape(self, shape: int):
+        """The MFMA tile of mode 3's 512-query blocks: 16 = 16x16x128, 32 = 32x32x64, 0 = the library's choice
+        (include/rgbdfe.h; every other kernel is 32x32x64 whatever this says)."""
+        self._check(self._L.rgbdfe_set_hamming_shape(self._ctx, shape))
+
+    @property
+    def hamming_shape_last(self) -> int:
+        """16 / 32 = the MFMA tile of the latest Hamming launch, 0 = it ran the popcount kernel, -1 = none yet."""
+        return int(self._L.rgbdfe_hamming_shape_last(self._ctx))
+
     @property
     def hamming_mode(self) -> int:
         """The Hamming kernel in use (the library falls back to 0 above 32768 keypoints per node)."""
