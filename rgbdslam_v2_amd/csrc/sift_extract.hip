@@ -56,7 +56,8 @@ __device__ __forceinline__ PolarGradient polar_gradient(const float* __restrict_
 // direction bins, none is moved whole): hardware square root (1 ulp) and an arctangent of |error| < 3e-7 rad -- one
 // reciprocal, the octant folded to |t| <= tan(pi / 8) by (mn - mx) / (mn + mx), a four-term odd polynomial (the classic
 // single-precision minimax set for that interval) -- in a quarter of libm's instructions.  3e-7 rad is 4e-7 of a
-// direction bin; tests/test_gpu_sift_extract.py allows descriptors 1e-3.
+// direction bin; tests/test_gpu_sift_extract.py allows descriptors 1e-3 against the reference, tests/test_gpu_sift_features.py
+// 3.12e-5 against a float64 restatement at the kernel's own feature.
 #ifndef RGBDFE_SIFT_DESC_LIBM
 #define RGBDFE_SIFT_DESC_LIBM 0   // 1: libm's sqrtf / atan2f / expf in the descriptor kernel (A/B: tools/sift_extract_ab.sh)
 #endif
@@ -119,8 +120,9 @@ __device__ __forceinline__ float lane_value(float v, int src) { return __shfl(v,
 // same bit pattern on every run and for every dealing of pixels to lanes, by construction.  And the LDS adds integers at the
 // rate it writes, whereas ds_add_f32 was measured at ~35 cycles per wave instruction whatever the collisions (descriptor kernel
 // 52 us per VGA frame with float adds, 18 with integer ones: profiles/r06_logs/sift_descriptor_forms.txt).  k is chosen per
-// feature from a bound of the largest possible sum (gradient length <= 0.7072 for planes in [0, 1], weights <= 1): the
-// counters cannot wrap, the grid is 2^-31 of that bound (~1e-7 absolute for a typical feature, where votes are 1e-3 .. 1).
+// feature from a bound of the largest possible sum (gradient length <= 0.7072 for planes in [0, 1], weights <= 1; the
+// smaller of a cell's area and the window's pixel count, see the kernel): the counters cannot wrap, the grid is 2^-31 of that
+// bound (~1e-7 absolute for a typical feature, where votes are 1e-3 .. 1).
 // (The ORIENTATION stage keeps float sums: its peak tests are strict comparisons of neighbouring bins, and on mirror-symmetric
 // patterns exact sums produce exact ties -- no peak at all -- where the reference's float rounding leaves one bin ahead:
 // tests/test_gpu_sift_extract.py, the 0 / 255 block pattern, lost 0.7 % of its orientations to that.)
@@ -250,13 +252,16 @@ __global__ __launch_bounds__(64) void sift_descriptor_kernel(const LevelJobs* __
   const float m_c = cs / cell, m_s = sn / cell;     // M = [m_c m_s; -m_s m_c]
   // the support |a|, |b| < 2.5 is a rotated square; its bounding box in the image
   const Window wd = window_around(f.x, f.y, 2.5f * cell * (fabsf(cs) + fabsf(sn)), stride, jobs.h[seg]);
-  // a bin's sum: at most 0.7072 x the lattice sum of a cell's tent weights, which is about cell^2 and below (cell + 1)^2
-  const float to_fixed = fixed_point_scale((cell + 2.0f) * (cell + 2.0f));
+  // a bin's sum: at most 0.7072 x the lattice sum of a cell's tent weights, which is about cell^2 and below (cell + 1)^2 --
+  // and at most 0.7072 x the window's pixels (a pixel's shares add up to its vote), the smaller bound where the plane cuts
+  // the window: a keypoint above the last scale band has cells far larger than the coarsest plane, and a grid sized by the
+  // cell alone left its votes (~1e-3 each) 13 bits -- 1e-3 off the reference (tests/test_gpu_sift_features.py, "extremes")
+  const int pixels = wd.cols * wd.rows;
+  const float to_fixed = fixed_point_scale(fminf((cell + 2.0f) * (cell + 2.0f), (float)max(pixels, 1)));
 #pragma unroll
   for (int i = 0; i < kDescBins * kCopies / 64; ++i) hist[i * 64 + lane] = 0u;
   __syncthreads();
   unsigned* mine = hist + (lane & (kCopies - 1));
-  const int pixels = wd.cols * wd.rows;
   const float per_col = 1.0f / (float)max(wd.cols, 1);
   for (int t = lane; t < pixels; t += 64) {
     const int r = (int)(((float)t + 0.5f) * per_col), c = t - r * wd.cols;   // see the orientation kernel
