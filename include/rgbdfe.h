@@ -716,7 +716,8 @@ int rgbdfe_potential_edge_targets(const rgbdfe_pose_graph* g, int32_t sequential
  * literally and the device gives its bytes.  Everything is double; the only operations are + - * / sqrt and comparisons.
  *
  *   Vertices: the nodes of the graph object in ascending node id, each an SE(3) estimate (identity until set) and a
- *     `fixed` flag (pose_relative_to = first / previous / largest_loop: the caller sets flags, fixationOfVertices :911-937).
+ *     `fixed` flag (rgbdfe_pose_graph_set_fixed, or a pose_relative_to strategy kept by the graph: the block
+ *     "fixation strategies, pruning and the evaluation rounds" below; fixationOfVertices :911-937).
  *     Free vertices are numbered in that order.  No fixed vertex at all is legal.
  *   Edges: those added with rgbdfe_pose_graph_add_edge_se3, in insertion order: measurement Z and a 6x6 information
  *     matrix O (row-major; any symmetric matrix).  Edges of rgbdfe_pose_graph_add_edge carry no measurement: ignored.
@@ -799,6 +800,101 @@ int rgbdfe_pose_graph_optimize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, int32_t it
 int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double break_criterion,
                                      rgbdfe_pose_graph_report* report);
 int rgbdfe_pose_graph_transforms(const rgbdfe_pose_graph* g, int32_t n, const int32_t* node_ids, float* out);
+
+/* ---- fixation strategies, pruning and the evaluation rounds (OpenNIListener::evaluation, openni_listener.cpp:431-518) ----
+ * What the reference runs at the end of every benchmark sequence, on the graph object of the block above and under its
+ * contract (restated, not pinned; tests/pose_graph_eval_oracle.py states it literally, the device gives
+ * its bytes).  A graph that calls none of these behaves as before.
+ *
+ * Strategies (pose_relative_to).  rgbdfe_pose_graph_set_strategy keeps one of RGBDFE_POSE_RELATIVE_TO_* in the graph.
+ *   NONE (the default): the flags of rgbdfe_pose_graph_set_fixed are used as they stand, nothing below applies.  Otherwise:
+ *   rgbdfe_pose_graph_add_node sets earliest_loop_closure_node to the new node's id (graph_manager.cpp:444).
+ *   rgbdfe_pose_graph_add_edge_se3: INAFFECTED clears the flags of both vertices (:889-892); LARGEST_LOOP sets
+ *     earliest = min(earliest, id1, id2) (:893-896).
+ *   rgbdfe_pose_graph_optimize_graph starts with fixationOfVertices (:911-937): FIRST: all flags cleared, the node of
+ *     lowest id fixed (the reference indexes graph_[0], its first node); PREVIOUS: with more than two nodes, all flags
+ *     cleared and the node of second-highest id fixed (graph_[size - 2]), otherwise the flags stay; LARGEST_LOOP:
+ *     fixed = (id < earliest) for every node; INAFFECTED: nothing.  It ends (:1031-1036) with every flag set under
+ *     INAFFECTED and every flag cleared under the others, on every return path.
+ *   The reference's quirk is kept: the Dijkstra vertex set of its `inaffected` branch (:969-977) is overridden by
+ *     initializeOptimization(cam_cam_edges_) at :991, so every active measured edge takes part under every strategy and an
+ *     edge between two fixed vertices counts in chi2.
+ *   rgbdfe_pose_graph_optimize, _linearize and _chi2 apply no strategy.
+ *
+ * rgbdfe_pose_graph_edge_errors: per measured edge in insertion order, at the current estimates: chi2 = e'Oe before Huber
+ *   (g2o's Edge::chi2()), err_sq = e.e summed left to right (printEdgeErrors :1321-1334), the active flag.  Any array may be
+ *   NULL.  A pruned edge reports 0, 0, 0.  capacity below the count: RGBDFE_ERR_CAPACITY with *n_edges set.
+ * rgbdfe_pose_graph_prune_edges: pruneEdgesWithErrorAbove (:1106-1246) as it behaves, on the device, a lane per edge.
+ *   Every ACTIVE edge with chi2 > (double)thresh (a NaN chi2 compares false: kept) is counted, its measurement becomes the
+ *   identity, and:  |id1 - id2| != 1 and both vertices have degree > 1: the edge becomes inactive (RGBDFE_PRUNE_REMOVED; its
+ *   information stays);  |id1 - id2| != 1 otherwise: information = 1e-100 I (RGBDFE_PRUNE_DISCOUNTED);  |id1 - id2| == 1:
+ *   information = I, the zero-motion assumption (RGBDFE_PRUNE_ZERO_MOTION).  Every other edge: RGBDFE_PRUNE_KEPT.
+ *   Degree = the measured edges ever added that touch the node, inactive ones included (the reference erases an edge from
+ *   cam_cam_edges_ only, never from the optimiser: v->edges().size() never shrinks).  Hence: verdicts do not depend on the
+ *   order of the edges within a call; and both edges of a degree-2 vertex can be removed in one call, which disconnects
+ *   the vertex in spite of the reference's comment.  verdicts (may be NULL): a byte per edge; *n_pruned: the count.
+ *   capacity below the edge count: RGBDFE_ERR_CAPACITY with *n_pruned = the edge count, nothing changed.
+ *   An inactive edge keeps its slot and contributes nothing from then on: rho 0 in its place of the chi2 tree (whose shape
+ *   still depends on the number of edges ever added alone), no entry in the lists of H and b, no part in later prune
+ *   calls; rgbdfe_pose_graph_linearize reports error 0 and weight 0 for it.  An optimisation with no active edge does
+ *   0 iterations.
+ * rgbdfe_pose_graph_get_edge: an edge by insertion index: ids, measurement (16 doubles, column-major), information (36,
+ *   row-major), active; any output may be NULL.  index out of range: RGBDFE_ERR_INVALID_ARG.
+ * rgbdfe_pose_graph_get_fixed: a node's flag.
+ * rgbdfe_pose_graph_sanity_check: sanityCheck (:1347-1360), host code: thresh *= thresh in FLOAT; an active edge whose
+ *   measurement has (tx tx + ty ty) + tz tz > (double)thresh takes information 0.000001 I.  Returns the number of edges
+ *   changed (a negative status on a NULL graph or a NaN threshold).
+ * rgbdfe_pose_graph_evaluate: evaluation()'s five rounds.  Round 0: optimize_graph(optimizer_iterations) under the current
+ *   strategy; the strategy then becomes FIRST and stays; round 1: optimize_graph(optimizer_iterations); rounds 2, 3, 4:
+ *   prune_edges(5.0f / 1.0f / 0.25f) > 0 ? optimize_graph(optimizer_iterations) : optimize_graph(1.0).  The rounds are
+ *   issued as those single calls (each uploads its own plan), so the bytes are theirs.  out (may be NULL): per round chi2,
+ *   iterations, edges pruned, launches, read-backs, upload seconds (prune and optimisation together), seconds in all.
+ *   estimates (may be NULL): after every round the estimates of all nodes in ascending id, 16 column-major doubles each:
+ *   5 * n * 16 values, what saveTrajectory(.. iteration_k) logs.  capacity_nodes below n: RGBDFE_ERR_CAPACITY, nothing done.
+ * rgbdfe_pose_graph_write_trajectory: the estimate file of saveTrajectory (graph_mgr_io.cpp:615-677, logTransform
+ *   misc.cpp:90-93), host code.  Per listed node world2base = ((init_base_pose * base2points) * X) * base2points^-1 in
+ *   double (16 column-major doubles each, NULL = identity; one base2points for all nodes; products by the sum rule above;
+ *   the rigid inverse is R', -R't), written as "%.6f %.6f %.6f %.6f %.6f %.6f %.6f %.6f\n" = stamp, tx ty tz, then x y z w
+ *   of the matrix -> quaternion conversion above (QTextStream's fixed notation has precision 6).  That conversion returns
+ *   w >= 0 where tf's getRotation does not flip: the same rotation, which ATE tools do not see.  With frame_id != NULL
+ *   the first line is "# TF Coordinate Frame ID: <frame_id>(data: <child_frame_id>)".  The ground-truth file is the
+ *   caller's.  An unknown node: RGBDFE_ERR_UNKNOWN_NODE, a path that cannot be opened: RGBDFE_ERR_INVALID_ARG (as
+ *   rgbdfe_octomap_write), nothing written.
+ * An unknown strategy, a NULL graph: RGBDFE_ERR_INVALID_ARG; in every error case the graph is unchanged. */
+#define RGBDFE_POSE_RELATIVE_TO_NONE 0
+#define RGBDFE_POSE_RELATIVE_TO_FIRST 1
+#define RGBDFE_POSE_RELATIVE_TO_PREVIOUS 2
+#define RGBDFE_POSE_RELATIVE_TO_LARGEST_LOOP 3
+#define RGBDFE_POSE_RELATIVE_TO_INAFFECTED 4
+#define RGBDFE_PRUNE_KEPT 0
+#define RGBDFE_PRUNE_REMOVED 1
+#define RGBDFE_PRUNE_DISCOUNTED 2
+#define RGBDFE_PRUNE_ZERO_MOTION 3
+#define RGBDFE_POSE_GRAPH_EVALUATION_ROUNDS 5
+typedef struct rgbdfe_pose_graph_round {
+  double chi2;
+  int32_t iterations;   /* Levenberg-Marquardt iterations of the round's optimize_graph */
+  int32_t pruned;       /* edges counted by the round's prune call (rounds 2 .. 4) */
+  int64_t launches, readbacks;
+  double upload_seconds, seconds;
+} rgbdfe_pose_graph_round;
+typedef struct rgbdfe_pose_graph_evaluation {
+  rgbdfe_pose_graph_round round[RGBDFE_POSE_GRAPH_EVALUATION_ROUNDS];
+} rgbdfe_pose_graph_evaluation;
+int rgbdfe_pose_graph_set_strategy(rgbdfe_pose_graph* g, int32_t strategy);
+int rgbdfe_pose_graph_get_fixed(const rgbdfe_pose_graph* g, int32_t node_id, int32_t* fixed);
+int rgbdfe_pose_graph_get_edge(const rgbdfe_pose_graph* g, int32_t index, int32_t* node_id1, int32_t* node_id2, double* transform,
+                               double* information, int32_t* active);
+int rgbdfe_pose_graph_sanity_check(rgbdfe_pose_graph* g, float thresh);
+int rgbdfe_pose_graph_edge_errors(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2, double* err_sq, int32_t* active,
+                                  int32_t capacity, int32_t* n_edges);
+int rgbdfe_pose_graph_prune_edges(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, float thresh, uint8_t* verdicts, int32_t capacity,
+                                  int32_t* n_pruned);
+int rgbdfe_pose_graph_evaluate(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double optimizer_iterations,
+                               rgbdfe_pose_graph_evaluation* out, double* estimates, int32_t capacity_nodes);
+int rgbdfe_pose_graph_write_trajectory(const rgbdfe_pose_graph* g, const char* path, int32_t n, const int32_t* node_ids,
+                                       const double* timestamps, const double* base2points, const double* init_base_pose,
+                                       const char* frame_id, const char* child_frame_id);
 
 /* ---- ICP fallback (Node::matchNodePair node.cpp:1349-1378, filterCloud and icpAlignment icp.cpp:20-89) ----------
  * What the reference does when RANSAC finds no transformation between two adjacent frames: both dense clouds are

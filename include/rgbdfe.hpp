@@ -367,7 +367,9 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
     return rgbdfe_pose_graph_add_edge_se3(topology_.get(), edge.id1, edge.id2, edge.transform.data(), info,
                                           set_estimate ? 1 : 0) == RGBDFE_OK;
   }
-  // pose_relative_to (fixationOfVertices, :911-937): the caller fixes the vertices of its choice
+  // pose_relative_to (fixationOfVertices, :911-937): the caller fixes the vertices of its choice, or the graph keeps a strategy
+  // (RGBDFE_POSE_RELATIVE_TO_FIRST / _PREVIOUS / _LARGEST_LOOP / _INAFFECTED; _NONE: the flags of setFixed as they stand)
+  bool setPoseRelativeTo(int strategy) { return rgbdfe_pose_graph_set_strategy(topology_.get(), strategy) == RGBDFE_OK; }
   bool setFixed(int node_id, bool fixed = true) {
     return rgbdfe_pose_graph_set_fixed(topology_.get(), node_id, fixed ? 1 : 0) == RGBDFE_OK;
   }
@@ -378,6 +380,35 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
     rgbdfe_pose_graph_report* rep = report ? report : &local;
     if (rgbdfe_pose_graph_optimize_graph(fe_.get(), topology_.get(), break_criterion, rep) != RGBDFE_OK) return -1.0;
     return rep->chi2;
+  }
+  // unsigned int GraphManager::pruneEdgesWithErrorAbove(float thresh) (:1106-1246) on the device; -1 on failure.
+  // verdicts (optional): RGBDFE_PRUNE_* per measured edge in insertion order
+  int pruneEdgesWithErrorAbove(float thresh, std::vector<uint8_t>* verdicts = nullptr) {
+    int32_t n = 0;
+    rgbdfe_pose_graph_edge_errors(fe_.get(), topology_.get(), nullptr, nullptr, nullptr, 0, &n);  // the edge count
+    std::vector<uint8_t> local((size_t)n);
+    int32_t pruned = 0;
+    if (rgbdfe_pose_graph_prune_edges(fe_.get(), topology_.get(), thresh, local.data(), n, &pruned) != RGBDFE_OK) return -1;
+    if (verdicts) verdicts->swap(local);
+    return pruned;
+  }
+  // void GraphManager::sanityCheck(float thresh) (:1347-1360); returns the number of edges changed
+  int sanityCheck(float thresh) { return rgbdfe_pose_graph_sanity_check(topology_.get(), thresh); }
+  // the five optimisation rounds of OpenNIListener::evaluation (openni_listener.cpp:431-518); estimates (optional): after
+  // every round all nodes in ascending id, 16 column-major doubles each
+  bool evaluation(double optimizer_iterations, rgbdfe_pose_graph_evaluation* out = nullptr, std::vector<double>* estimates = nullptr,
+                  int n_nodes = 0) {
+    if (estimates) estimates->assign((size_t)RGBDFE_POSE_GRAPH_EVALUATION_ROUNDS * 16 * (size_t)n_nodes, 0.0);
+    return rgbdfe_pose_graph_evaluate(fe_.get(), topology_.get(), optimizer_iterations, out, estimates ? estimates->data() : nullptr,
+                                      n_nodes) == RGBDFE_OK;
+  }
+  // GraphManager::saveTrajectory's estimate file (graph_mgr_io.cpp:615-677), TUM format
+  bool saveTrajectory(const std::string& path, const std::vector<int32_t>& node_ids, const std::vector<double>& stamps,
+                      const double* base2points = nullptr, const double* init_base_pose = nullptr, const char* frame_id = nullptr,
+                      const char* child_frame_id = nullptr) const {
+    if (node_ids.size() != stamps.size()) return false;
+    return rgbdfe_pose_graph_write_trajectory(topology_.get(), path.c_str(), (int32_t)node_ids.size(), node_ids.data(), stamps.data(),
+                                              base2points, init_base_pose, frame_id, child_frame_id) == RGBDFE_OK;
   }
   // the estimates of node_ids as n x 16 floats (column-major Matrix4f): the world2cam of assembleMap / the OctoMap calls
   std::vector<float> transforms(const std::vector<int32_t>& node_ids) const {

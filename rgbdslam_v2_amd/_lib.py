@@ -96,6 +96,20 @@ class PoseGraphIteration(C.Structure):   # rgbdfe_pose_graph_iteration
                 ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("lam", C.c_double)]
 
 
+POSE_GRAPH_EVALUATION_ROUNDS = 5
+POSE_RELATIVE_TO = dict(none=0, first=1, previous=2, largest_loop=3, inaffected=4)   # RGBDFE_POSE_RELATIVE_TO_*
+PRUNE_VERDICTS = ("kept", "removed", "discounted", "zero_motion")                    # RGBDFE_PRUNE_*
+
+
+class PoseGraphRound(C.Structure):   # rgbdfe_pose_graph_round
+    _fields_ = [("chi2", C.c_double), ("iterations", C.c_int32), ("pruned", C.c_int32), ("launches", C.c_int64),
+                ("readbacks", C.c_int64), ("upload_seconds", C.c_double), ("seconds", C.c_double)]
+
+
+class PoseGraphEvaluation(C.Structure):   # rgbdfe_pose_graph_evaluation
+    _fields_ = [("round", PoseGraphRound * POSE_GRAPH_EVALUATION_ROUNDS)]
+
+
 class PoseGraphReport(C.Structure):   # rgbdfe_pose_graph_report
     _fields_ = [("iterations", C.c_int32), ("recorded", C.c_int32), ("chi2", C.c_double), ("launches", C.c_int64),
                 ("readbacks", C.c_int64), ("upload_seconds", C.c_double), ("total_seconds", C.c_double),
@@ -513,6 +527,22 @@ def load():
     L.rgbdfe_pose_graph_optimize_graph.argtypes = [vp, vp, C.c_double, C.POINTER(PoseGraphReport)]
     L.rgbdfe_pose_graph_transforms.restype = C.c_int
     L.rgbdfe_pose_graph_transforms.argtypes = [vp, i32, vp, vp]
+    L.rgbdfe_pose_graph_set_strategy.restype = C.c_int
+    L.rgbdfe_pose_graph_set_strategy.argtypes = [vp, i32]
+    L.rgbdfe_pose_graph_get_fixed.restype = C.c_int
+    L.rgbdfe_pose_graph_get_fixed.argtypes = [vp, i32, C.POINTER(i32)]
+    L.rgbdfe_pose_graph_get_edge.restype = C.c_int
+    L.rgbdfe_pose_graph_get_edge.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, C.POINTER(i32)]
+    L.rgbdfe_pose_graph_sanity_check.restype = C.c_int
+    L.rgbdfe_pose_graph_sanity_check.argtypes = [vp, C.c_float]
+    L.rgbdfe_pose_graph_edge_errors.restype = C.c_int
+    L.rgbdfe_pose_graph_edge_errors.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
+    L.rgbdfe_pose_graph_prune_edges.restype = C.c_int
+    L.rgbdfe_pose_graph_prune_edges.argtypes = [vp, vp, C.c_float, vp, i32, C.POINTER(i32)]
+    L.rgbdfe_pose_graph_evaluate.restype = C.c_int
+    L.rgbdfe_pose_graph_evaluate.argtypes = [vp, vp, C.c_double, C.POINTER(PoseGraphEvaluation), vp, i32]
+    L.rgbdfe_pose_graph_write_trajectory.restype = C.c_int
+    L.rgbdfe_pose_graph_write_trajectory.argtypes = [vp, C.c_char_p, i32, vp, vp, vp, vp, C.c_char_p, C.c_char_p]
     L.rgbdfe_potential_edge_targets.restype = C.c_int
     L.rgbdfe_potential_edge_targets.argtypes = [vp, i32, i32, i32, i32, i32, i32, RAND_FN, vp, C.c_uint32, vp, i32,
                                                 C.POINTER(i32)]
@@ -555,6 +585,9 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_pose_graph_set_estimate", "rgbdfe_pose_graph_get_estimate", "rgbdfe_pose_graph_set_fixed",
     "rgbdfe_pose_graph_add_edge_se3", "rgbdfe_pose_graph_chi2", "rgbdfe_pose_graph_linearize",
     "rgbdfe_pose_graph_optimize", "rgbdfe_pose_graph_optimize_graph", "rgbdfe_pose_graph_transforms",
+    "rgbdfe_pose_graph_set_strategy", "rgbdfe_pose_graph_get_fixed", "rgbdfe_pose_graph_get_edge",
+    "rgbdfe_pose_graph_sanity_check", "rgbdfe_pose_graph_edge_errors", "rgbdfe_pose_graph_prune_edges",
+    "rgbdfe_pose_graph_evaluate", "rgbdfe_pose_graph_write_trajectory",
     "rgbdfe_create_multi", "rgbdfe_device_count", "rgbdfe_device_context", "rgbdfe_match_pair_list_allgather",
     "rgbdfe_gather_transport", "rgbdfe_gather_exchanges", "rgbdfe_set_hamming_mode", "rgbdfe_hamming_wide_last", "rgbdfe_set_hamming_shape", "rgbdfe_hamming_shape_last", "rgbdfe_project_to_3d_cloud", "rgbdfe_detect_describe_cloud",
     "rgbdfe_detect_describe_batch", "rgbdfe_detect_describe_batch_nodes", "rgbdfe_match_pair_list_allgather_edges",

@@ -18,6 +18,7 @@ class PoseGraph:
         self._g = self._L.rgbdfe_pose_graph_create()
         if not self._g:
             raise _lib.RgbdfeError("rgbdfe_pose_graph_create failed")
+        self._ids = set()
 
     def close(self):
         if self._g:
@@ -35,6 +36,7 @@ class PoseGraph:
         """A Node entering graph_ (GraphManager::addNode, graph_manager.cpp:681; firstNode :326)."""
         self._check(self._L.rgbdfe_pose_graph_add_node(self._g, int(node_id), int(node_id if vertex_id is None else vertex_id),
                                                        int(bool(matchable)), int(bool(keyframe))))
+        self._ids.add(int(node_id))
 
     def add_edge(self, id1, id2):
         """An edge entering the optimizer (GraphManager::addEdgeToG2O, graph_manager.cpp:811)."""
@@ -108,6 +110,87 @@ class PoseGraph:
         rep = _lib.PoseGraphReport()
         self._check(self._L.rgbdfe_pose_graph_optimize_graph(self._ctx(front_end), self._g, float(break_criterion), C.byref(rep)))
         return self._report(rep)
+
+    # ---- fixation strategies, pruning and the evaluation rounds (include/rgbdfe.h) ----
+    def set_strategy(self, strategy):
+        """pose_relative_to: "none" (the default: set_fixed's flags as they stand), "first", "previous", "largest_loop",
+        "inaffected", or the RGBDFE_POSE_RELATIVE_TO_* number."""
+        s = _lib.POSE_RELATIVE_TO[strategy] if isinstance(strategy, str) else int(strategy)
+        self._check(self._L.rgbdfe_pose_graph_set_strategy(self._g, s))
+
+    def get_fixed(self, node_id):
+        out = C.c_int32(0)
+        self._check(self._L.rgbdfe_pose_graph_get_fixed(self._g, int(node_id), C.byref(out)))
+        return bool(out.value)
+
+    def edge(self, index):
+        """A measured edge by insertion index: dict(id1, id2, transform[4,4], information[6,6], active)."""
+        i1, i2, act = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        t, info = np.zeros((4, 4)), np.zeros((6, 6))
+        self._check(self._L.rgbdfe_pose_graph_get_edge(self._g, int(index), C.byref(i1), C.byref(i2), t.ctypes.data,
+                                                       info.ctypes.data, C.byref(act)))
+        return dict(id1=i1.value, id2=i2.value, transform=t.T.copy(), information=info, active=bool(act.value))
+
+    def sanity_check(self, thresh):
+        """GraphManager::sanityCheck: the number of edges whose information became 0.000001 I."""
+        n = self._L.rgbdfe_pose_graph_sanity_check(self._g, float(thresh))
+        if n < 0:
+            self._check(n)
+        return n
+
+    def edge_errors(self, front_end):
+        """Per measured edge: dict(chi2[E] (before Huber), err_sq[E], active[E])."""
+        ne = C.c_int32(0)
+        rc = self._L.rgbdfe_pose_graph_edge_errors(self._ctx(front_end), self._g, None, None, None, 0, C.byref(ne))
+        if rc not in (0, -5):  # RGBDFE_ERR_CAPACITY: the count is set
+            self._check(rc)
+        chi2, sq, act = np.zeros(ne.value), np.zeros(ne.value), np.zeros(ne.value, np.int32)
+        self._check(self._L.rgbdfe_pose_graph_edge_errors(self._ctx(front_end), self._g, chi2.ctypes.data, sq.ctypes.data,
+                                                          act.ctypes.data, ne.value, C.byref(ne)))
+        return dict(chi2=chi2, err_sq=sq, active=act.astype(bool))
+
+    def prune_edges(self, front_end, thresh, n_edges=None):
+        """GraphManager::pruneEdgesWithErrorAbove: (edges pruned, a verdict per edge: RGBDFE_PRUNE_* as uint8)."""
+        if n_edges is None:
+            ne = C.c_int32(0)
+            rc = self._L.rgbdfe_pose_graph_edge_errors(self._ctx(front_end), self._g, None, None, None, 0, C.byref(ne))
+            if rc not in (0, -5):
+                self._check(rc)
+            n_edges = ne.value
+        verdicts = np.zeros(max(int(n_edges), 1), np.uint8)
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_pose_graph_prune_edges(self._ctx(front_end), self._g, float(thresh), verdicts.ctypes.data,
+                                                          int(n_edges), C.byref(n)))
+        return n.value, verdicts[:int(n_edges)].copy()
+
+    def evaluate(self, front_end, optimizer_iterations=0.01):
+        """OpenNIListener::evaluation's five rounds: (rounds: a list of dicts, estimates[5, n, 4, 4] in ascending node id)."""
+        ev = _lib.PoseGraphEvaluation()
+        n_nodes = self.node_count()
+        est = np.zeros((_lib.POSE_GRAPH_EVALUATION_ROUNDS, n_nodes, 16))
+        self._check(self._L.rgbdfe_pose_graph_evaluate(self._ctx(front_end), self._g, float(optimizer_iterations), C.byref(ev),
+                                                       est.ctypes.data, n_nodes))
+        rounds = [dict(chi2=float(r.chi2), iterations=int(r.iterations), pruned=int(r.pruned), launches=int(r.launches),
+                       readbacks=int(r.readbacks), upload_seconds=float(r.upload_seconds), seconds=float(r.seconds))
+                  for r in ev.round]
+        return rounds, est.reshape(-1, n_nodes, 4, 4).transpose(0, 1, 3, 2).copy()
+
+    def node_count(self):
+        return len(self._ids)
+
+    def write_trajectory(self, path, node_ids, timestamps, base2points=None, init_base_pose=None, frame_id=None,
+                         child_frame_id=None):
+        """GraphManager::saveTrajectory's estimate file (TUM format: stamp tx ty tz qx qy qz qw)."""
+        ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        ts = np.ascontiguousarray(timestamps, np.float64).reshape(-1)
+        if len(ids) != len(ts):
+            raise ValueError("one time stamp per node")
+        mat = lambda m: None if m is None else np.ascontiguousarray(np.asarray(m, np.float64).reshape(4, 4).T)
+        b2p, init = mat(base2points), mat(init_base_pose)
+        enc = lambda v: None if v is None else str(v).encode()
+        self._check(self._L.rgbdfe_pose_graph_write_trajectory(
+            self._g, str(path).encode(), len(ids), ids.ctypes.data, ts.ctypes.data, None if b2p is None else b2p.ctypes.data,
+            None if init is None else init.ctypes.data, enc(frame_id), enc(child_frame_id)))
 
     def transforms(self, node_ids):
         """The estimates as n x 4 x 4 float32 (row, column) matrices: the `transforms` of FrontEnd.assemble_map and

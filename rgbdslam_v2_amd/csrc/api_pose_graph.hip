@@ -2,6 +2,9 @@
 // over the kernels of pose_graph.hip.  Per call the host builds the plan (free-vertex map, incidence and block lists, all in
 // insertion order), uploads it with the estimates and the edges in one copy, drives Levenberg-Marquardt (the scalars of a
 // trial come back in one small record per chunk of PCG iterations) and reads the estimates back once at the end.
+// Then the reference's last stage on the same graph (include/rgbdfe.h, "fixation strategies, pruning and the evaluation rounds"):
+// the pose_relative_to flags around optimize_graph, per-edge figures, pruneEdgesWithErrorAbove (one launch and one read-back
+// per call; the host owns the topology and mirrors the verdicts into its edges) and the rounds of OpenNIListener::evaluation.
 // (one of the host-side translation units of librgbdfe.so; shared declarations: rgbdfe_host.h)
 #include "rgbdfe_host.h"
 #include "pose_graph.h"
@@ -47,6 +50,12 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
   std::vector<int32_t> node_of;              // vertex -> node id
   std::vector<int32_t> free_of, vert_of, blk_rc;
   PgScalars hs{};
+  const std::vector<uint8_t>* topo = nullptr;  // a prune call's topology bits: uploaded with room for its results
+  uint8_t* d_topo = nullptr;
+  double* d_edge_in = nullptr;
+  int32_t* d_active = nullptr;
+  int32_t* d_prune_out = nullptr;              // the count, then a verdict byte per edge
+  int32_t n_active = 0;                        // measured edges that still take part
   int64_t launches = 0, readbacks = 0;
   double upload_seconds = 0;
 
@@ -71,7 +80,7 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
       est_h.insert(est_h.end(), kv.second.est, kv.second.est + 12);
     }
     const size_t nv = node_of.size(), nf = vert_of.size(), ne = g->edges.size();
-    std::vector<int32_t> edge_ij(2 * ne);
+    std::vector<int32_t> edge_ij(2 * ne), edge_active(ne);
     std::vector<double> edge_in((size_t)kPgEdgeIn * ne);
     std::vector<std::vector<int32_t>> vert_list(nf), blk_list, vb_list(nf);
     std::map<std::pair<int32_t, int32_t>, int32_t> block_at;
@@ -82,6 +91,9 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
       edge_ij[2 * e + 1] = vj;
       std::copy(m.z, m.z + 12, edge_in.begin() + kPgEdgeIn * e);
       std::copy(m.info, m.info + 36, edge_in.begin() + kPgEdgeIn * e + kPgPose);
+      edge_active[e] = m.active ? 1 : 0;
+      if (!m.active) continue;  // a pruned edge is in no list
+      ++n_active;
       const int32_t fi = free_of[vi], fj = free_of[vj];
       if (fi >= 0) vert_list[fi].push_back((int32_t)(2 * e));
       if (fj >= 0) vert_list[fj].push_back((int32_t)(2 * e + 1));
@@ -127,7 +139,9 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
                  o_bi = put(blk_items.data(), 4 * blk_items.size()), o_vbp = put(vb_ptr.data(), 4 * vb_ptr.size()),
                  o_vbi = put(vb_items.data(), 4 * vb_items.size()), o_rc = put(blk_rc.data(), 4 * blk_rc.size());
     PgScalars zero{};
-    const size_t o_s = put(&zero, sizeof(zero));
+    const size_t o_s = put(&zero, sizeof(zero)), o_act = put(edge_active.data(), 4 * ne);
+    const std::vector<uint8_t> prune_zero(topo ? 4 + ne : 0, 0);
+    const size_t o_topo = put(topo ? topo->data() : nullptr, topo ? ne : 0), o_po = put(prune_zero.data(), prune_zero.size());
     size_t total = stage.size();
     auto room = [&](size_t bytes) { const size_t at = total; total += up(bytes); return at; };
     const size_t leaves = std::max((ne + kPgTile - 1) / kPgTile, (nf + kPgTile - 1) / kPgTile) + 1;
@@ -166,6 +180,8 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
     P.free_of = (const int32_t*)(base + o_free); P.vert_of = (const int32_t*)(base + o_vert);
     P.edge_ij = (const int32_t*)(base + o_ij); P.edge_in = (const double*)(base + o_in);
     P.edge_out = (double*)(base + o_out);
+    d_edge_in = (double*)(base + o_in); d_active = (int32_t*)(base + o_act); P.edge_active = d_active;
+    d_topo = (uint8_t*)(base + o_topo); d_prune_out = (int32_t*)(base + o_po);
     P.vert_ptr = (const int32_t*)(base + o_vp); P.vert_items = (const int32_t*)(base + o_vi);
     P.blk_ptr = (const int32_t*)(base + o_bp); P.blk_items = (const int32_t*)(base + o_bi);
     P.vb_ptr = (const int32_t*)(base + o_vbp); P.vb_items = (const int32_t*)(base + o_vbi);
@@ -212,7 +228,7 @@ void append(rgbdfe_pose_graph_report* rep, const rgbdfe_pose_graph_iteration& it
 int optimize_run(PgRun& run, int32_t iterations, rgbdfe_pose_graph_report* rep, int32_t* done) {
   const PgProblem& P = run.P;
   *done = 0;
-  if (P.n_edge == 0 || P.n_free == 0) return run.chi2_now(&rep->chi2);
+  if (run.n_active == 0 || P.n_free == 0) return run.chi2_now(&rep->chi2);
   const int32_t max_iter = 6 * P.n_free;
   double lambda = 0.0, ni = 2.0;
   for (int32_t it = 0; it < iterations; ++it) {
@@ -285,6 +301,35 @@ void close_report(const PgRun& run, rgbdfe_pose_graph_report* rep, std::chrono::
   rep->total_seconds = seconds_since(t0);
 }
 
+// fixationOfVertices (graph_manager.cpp:911-937), at the start of optimizeGraphImpl
+void apply_fixation(rgbdfe_pose_graph* g) {
+  auto clear_all = [&]() { for (auto& kv : g->nodes) kv.second.fixed = false; };
+  switch (g->strategy) {
+    case RGBDFE_POSE_RELATIVE_TO_FIRST:  // the reference indexes graph[0]; here: the node of lowest id
+      clear_all();
+      if (!g->nodes.empty()) g->nodes.begin()->second.fixed = true;
+      break;
+    case RGBDFE_POSE_RELATIVE_TO_PREVIOUS:  // graph[size - 2]: the node of second-highest id
+      if (g->nodes.size() > 2) {
+        clear_all();
+        std::next(g->nodes.rbegin())->second.fixed = true;
+      }
+      break;
+    case RGBDFE_POSE_RELATIVE_TO_LARGEST_LOOP:
+      for (auto& kv : g->nodes) kv.second.fixed = kv.first < g->earliest_loop_closure_node;
+      break;
+    default:
+      break;  // NONE, INAFFECTED: the flags as they stand
+  }
+}
+
+// after the optimisation (:1031-1036)
+void release_fixation(rgbdfe_pose_graph* g) {
+  if (g->strategy == RGBDFE_POSE_RELATIVE_TO_NONE) return;
+  const bool fixed = g->strategy == RGBDFE_POSE_RELATIVE_TO_INAFFECTED;
+  for (auto& kv : g->nodes) kv.second.fixed = fixed;
+}
+
 }  // namespace
 
 int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2) {
@@ -331,6 +376,10 @@ int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* e
     for (int32_t e = 0; e < P.n_edge; ++e) {
       if (errors) std::copy(out.begin() + (size_t)kPgEdgeOut * e, out.begin() + (size_t)kPgEdgeOut * e + 6, errors + 6 * (size_t)e);
       if (weights) weights[e] = out[(size_t)kPgEdgeOut * e + kPgW];
+      if (!g->edges[(size_t)e].active) {  // a pruned edge wrote no record: error 0, weight 0
+        if (errors) std::fill(errors + 6 * (size_t)e, errors + 6 * (size_t)e + 6, 0.0);
+        if (weights) weights[e] = 0.0;
+      }
     }
   } else {
     if (h_diag) std::fill(h_diag, h_diag + 36 * (size_t)P.n_free, 0.0);
@@ -373,6 +422,11 @@ int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, doub
   rgbdfe_pose_graph_report local;
   rgbdfe_pose_graph_report* rep = report ? report : &local;
   memset(rep, 0, sizeof(*rep));
+  apply_fixation(g);
+  struct Release {  // the flags after the optimisation, on every way out
+    rgbdfe_pose_graph* g;
+    ~Release() { release_fixation(g); }
+  } release{g};
   if (g->edges.empty()) return RGBDFE_OK;
   std::lock_guard<std::mutex> lock(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
@@ -400,6 +454,154 @@ int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, doub
   rc = run.finish();
   close_report(run, rep, t0);
   return rc;
+}
+
+int rgbdfe_pose_graph_edge_errors(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2, double* err_sq, int32_t* active,
+                                  int32_t capacity, int32_t* n_edges) {
+  if (!ctx || !g || !n_edges || capacity < 0) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  const size_t ne = g->edges.size();
+  *n_edges = (int32_t)ne;
+  if (ne > (size_t)capacity) return fail(ctx, RGBDFE_ERR_CAPACITY, "pose graph: the output arrays are too small (the count is set)");
+  if (ne == 0) return RGBDFE_OK;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  PgRun run;
+  const int rc = begin(ctx, g, &run);
+  if (rc != RGBDFE_OK) return rc;
+  run.launches += launch_pg_edges(run.P, run.est[0], false, run.st);
+  HIP_TRY(ctx, hipGetLastError());
+  std::vector<double> head(7 * ne);  // e[6], chi2 of every record
+  HIP_TRY(ctx, hipMemcpy2DAsync(head.data(), 7 * sizeof(double), run.P.edge_out, kPgEdgeOut * sizeof(double), 7 * sizeof(double), ne,
+                                hipMemcpyDeviceToHost, run.st));
+  HIP_TRY(ctx, hipStreamSynchronize(run.st));
+  for (size_t e = 0; e < ne; ++e) {
+    const bool on = g->edges[e].active;
+    const double* h = head.data() + 7 * e;
+    double sq = h[0] * h[0];
+    for (int k = 1; k < 6; ++k) sq = sq + h[k] * h[k];
+    if (chi2) chi2[e] = on ? h[kPgChi2] : 0.0;
+    if (err_sq) err_sq[e] = on ? sq : 0.0;
+    if (active) active[e] = on ? 1 : 0;
+  }
+  return RGBDFE_OK;
+}
+
+namespace {
+
+// one prune call; stats (may be NULL) takes its launches, read-backs and upload time
+int prune_run(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, float thresh, uint8_t* verdicts, int32_t* n_pruned, PgRun* stats) {
+  const size_t ne = g->edges.size();
+  *n_pruned = 0;
+  if (ne == 0) return RGBDFE_OK;
+  // the topology is the host's: the degree counts every measured edge ever added, pruned ones included (the reference erases
+  // an edge from cam_cam_edges_ only, never from the optimiser: v->edges().size() does not shrink)
+  std::map<int32_t, int32_t> degree;
+  for (const auto& m : g->edges) { ++degree[m.id1]; ++degree[m.id2]; }
+  std::vector<uint8_t> topo(ne);
+  for (size_t e = 0; e < ne; ++e) {
+    const auto& m = g->edges[e];
+    const int64_t d = (int64_t)m.id1 - (int64_t)m.id2;
+    topo[e] = (uint8_t)(((d == 1 || d == -1) ? kPgTopoSequential : 0) |
+                        ((degree[m.id1] > 1 && degree[m.id2] > 1) ? kPgTopoBothJoined : 0));
+  }
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  PgRun run;
+  run.topo = &topo;
+  const int rc = begin(ctx, g, &run);
+  if (rc != RGBDFE_OK) return rc;
+  run.launches += launch_pg_prune(run.P, run.est[0], (double)thresh, run.d_topo, run.d_edge_in, run.d_active,
+                                  (uint8_t*)(run.d_prune_out + 1), run.d_prune_out, run.st);
+  HIP_TRY(ctx, hipGetLastError());
+  std::vector<uint8_t> back(4 + ne);  // the one read-back: the count and the verdict bytes
+  HIP_TRY(ctx, hipMemcpyAsync(back.data(), run.d_prune_out, back.size(), hipMemcpyDeviceToHost, run.st));
+  HIP_TRY(ctx, hipStreamSynchronize(run.st));
+  ++run.readbacks;
+  memcpy(n_pruned, back.data(), 4);
+  for (size_t e = 0; e < ne; ++e) {  // the host's copy of the edges follows the device's
+    const uint8_t v = back[4 + e];
+    verdicts[e] = v;
+    if (v == kPgPruneKept) continue;
+    auto& m = g->edges[e];
+    for (int k = 0; k < kPgPose; ++k) m.z[k] = (k < 9 && k % 4 == 0) ? 1.0 : 0.0;
+    if (v == kPgPruneRemoved) {
+      m.active = false;
+    } else {
+      const double diag = v == kPgPruneDiscounted ? 1e-100 : 1.0;
+      for (int k = 0; k < 36; ++k) m.info[k] = (k % 7 == 0) ? diag : 0.0;
+    }
+  }
+  if (stats) {
+    stats->launches = run.launches;
+    stats->readbacks = run.readbacks;
+    stats->upload_seconds = run.upload_seconds;
+  }
+  return RGBDFE_OK;
+}
+
+}  // namespace
+
+int rgbdfe_pose_graph_prune_edges(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, float thresh, uint8_t* verdicts, int32_t capacity,
+                                  int32_t* n_pruned) {
+  if (!ctx || !g || !n_pruned || capacity < 0 || thresh != thresh) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  if (g->edges.size() > (size_t)capacity) {
+    *n_pruned = (int32_t)g->edges.size();
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "pose graph: the verdict array is too small (the edge count is set)");
+  }
+  std::vector<uint8_t> local(verdicts ? 0 : g->edges.size());
+  return prune_run(ctx, g, thresh, verdicts ? verdicts : local.data(), n_pruned, nullptr);
+}
+
+int rgbdfe_pose_graph_evaluate(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double optimizer_iterations,
+                               rgbdfe_pose_graph_evaluation* out, double* estimates, int32_t capacity_nodes) {
+  if (!ctx || !g || !std::isfinite(optimizer_iterations) || optimizer_iterations > 1e9 || capacity_nodes < 0)
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  const size_t nn = g->nodes.size();
+  if (estimates && nn > (size_t)capacity_nodes)
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "pose graph: the estimates array is too small");
+  rgbdfe_pose_graph_evaluation local;
+  rgbdfe_pose_graph_evaluation* ev = out ? out : &local;
+  memset(ev, 0, sizeof(*ev));
+  static const float kThresh[RGBDFE_POSE_GRAPH_EVALUATION_ROUNDS] = {0.f, 0.f, 5.0f, 1.0f, 0.25f};
+  std::vector<uint8_t> verdicts(g->edges.size());
+  for (int r = 0; r < RGBDFE_POSE_GRAPH_EVALUATION_ROUNDS; ++r) {  // the calls of OpenNIListener::evaluation, one after another
+    const auto t0 = std::chrono::steady_clock::now();
+    rgbdfe_pose_graph_round& rd = ev->round[r];
+    double criterion = optimizer_iterations;
+    if (r == 1) g->strategy = RGBDFE_POSE_RELATIVE_TO_FIRST;  // and it stays
+    if (r >= 2) {
+      PgRun stats;
+      const int rc = prune_run(ctx, g, kThresh[r], verdicts.data(), &rd.pruned, &stats);
+      if (rc != RGBDFE_OK) return rc;
+      rd.launches = stats.launches;
+      rd.readbacks = stats.readbacks;
+      rd.upload_seconds = stats.upload_seconds;
+      if (rd.pruned == 0) criterion = 1.0;
+    }
+    rgbdfe_pose_graph_report rep;
+    const int rc = impl::rgbdfe_pose_graph_optimize_graph(ctx, g, criterion, &rep);
+    if (rc != RGBDFE_OK) return rc;
+    rd.chi2 = rep.chi2;
+    rd.iterations = rep.iterations;
+    rd.launches += rep.launches;
+    rd.readbacks += rep.readbacks;
+    rd.upload_seconds += rep.upload_seconds;
+    rd.seconds = seconds_since(t0);
+    if (estimates) {
+      double* dst = estimates + 16 * nn * (size_t)r;
+      for (const auto& kv : g->nodes) {
+        const double* est = kv.second.est;
+        for (int a = 0; a < 3; ++a) {
+          for (int c = 0; c < 3; ++c) dst[4 * c + a] = est[3 * a + c];
+          dst[12 + a] = est[9 + a];
+          dst[4 * a + 3] = 0.0;
+        }
+        dst[15] = 1.0;
+        dst += 16;
+      }
+    }
+  }
+  return RGBDFE_OK;
 }
 
 }  // namespace impl

@@ -10,7 +10,10 @@
 //   keyframe_ids_ (QList<int>)                                     PoseGraph::keyframes
 //   g2o::HyperDijkstra::shortestPaths(v, UniformCostFunction, geodesic_depth)   bounded_neighbourhood()
 //   rand()                                                         the caller's generator (NULL: a counter-based one)
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <deque>
 #include <limits>
 #include <map>
@@ -85,6 +88,7 @@ int rgbdfe_pose_graph_add_node(rgbdfe_pose_graph* g, int32_t node_id, int32_t ve
   rgbdfe_pose_graph::NodeInfo& nd = g->nodes[node_id];  // a node added again keeps its estimate and its fixed flag
   nd.vertex_id = vertex_id;
   nd.matchable = matchable != 0;
+  if (g->strategy != RGBDFE_POSE_RELATIVE_TO_NONE) g->earliest_loop_closure_node = node_id;  // graph_manager.cpp:444
   g->camera_vertices.insert(vertex_id);
   g->adjacency[vertex_id];
   if (keyframe) g->keyframes.push_back(node_id);
@@ -275,6 +279,12 @@ int rgbdfe_pose_graph_add_edge_se3(rgbdfe_pose_graph* g, int32_t node_id1, int32
   g->edges.push_back(m);
   g->adjacency[a->second.vertex_id].insert(b->second.vertex_id);
   g->adjacency[b->second.vertex_id].insert(a->second.vertex_id);
+  if (g->strategy == RGBDFE_POSE_RELATIVE_TO_INAFFECTED) {  // :889-892
+    a->second.fixed = false;
+    b->second.fixed = false;
+  } else if (g->strategy == RGBDFE_POSE_RELATIVE_TO_LARGEST_LOOP) {  // :893-896
+    g->earliest_loop_closure_node = std::min(g->earliest_loop_closure_node, std::min(node_id1, node_id2));
+  }
   if (set_estimate) {  // X2 = X1 * Z (addEdgeToG2O, graph_manager.cpp:858,864)
     const double* x = a->second.est;
     double* y = b->second.est;
@@ -305,6 +315,134 @@ int rgbdfe_pose_graph_transforms(const rgbdfe_pose_graph* g, int32_t n, const in
     m[15] = 1.0f;
   }
   return RGBDFE_OK;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+// ---- fixation strategies, pruning helpers and the trajectory file (include/rgbdfe.h; the device work: api_pose_graph.hip) ---
+int rgbdfe_pose_graph_set_strategy(rgbdfe_pose_graph* g, int32_t strategy) {
+  if (!g || strategy < RGBDFE_POSE_RELATIVE_TO_NONE || strategy > RGBDFE_POSE_RELATIVE_TO_INAFFECTED) return RGBDFE_ERR_INVALID_ARG;
+  g->strategy = strategy;
+  return RGBDFE_OK;
+}
+
+int rgbdfe_pose_graph_get_fixed(const rgbdfe_pose_graph* g, int32_t node_id, int32_t* fixed) try {
+  if (!g || !fixed) return RGBDFE_ERR_INVALID_ARG;
+  const auto a = g->nodes.find(node_id);
+  if (a == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;
+  *fixed = a->second.fixed ? 1 : 0;
+  return RGBDFE_OK;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_get_edge(const rgbdfe_pose_graph* g, int32_t index, int32_t* node_id1, int32_t* node_id2, double* transform,
+                               double* information, int32_t* active) {
+  if (!g || index < 0 || (size_t)index >= g->edges.size()) return RGBDFE_ERR_INVALID_ARG;
+  const rgbdfe_pose_graph::MeasuredEdge& m = g->edges[(size_t)index];
+  if (node_id1) *node_id1 = m.id1;
+  if (node_id2) *node_id2 = m.id2;
+  if (transform) {
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) transform[4 * c + r] = m.z[3 * r + c];
+      transform[12 + r] = m.z[9 + r];
+      transform[4 * r + 3] = 0.0;
+    }
+    transform[15] = 1.0;
+  }
+  if (information)
+    for (int k = 0; k < 36; ++k) information[k] = m.info[k];
+  if (active) *active = m.active ? 1 : 0;
+  return RGBDFE_OK;
+}
+
+int rgbdfe_pose_graph_sanity_check(rgbdfe_pose_graph* g, float thresh) {
+  if (!g || thresh != thresh) return RGBDFE_ERR_INVALID_ARG;
+  thresh *= thresh;  // in float, as the reference's (graph_manager.cpp:1348)
+  int changed = 0;
+  for (rgbdfe_pose_graph::MeasuredEdge& m : g->edges) {
+    if (!m.active) continue;
+    const double sq = (m.z[9] * m.z[9] + m.z[10] * m.z[10]) + m.z[11] * m.z[11];
+    if (sq > (double)thresh) {
+      for (int k = 0; k < 36; ++k) m.info[k] = (k % 7 == 0) ? 0.000001 : 0.0;
+      ++changed;
+    }
+  }
+  return changed;
+}
+
+namespace {
+// poses as est: rotation row-major [0..8], translation [9..11]
+void pose_mul(const double* a, const double* b, double* out) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) out[3 * r + c] = dot3(a[3 * r], a[3 * r + 1], a[3 * r + 2], b[c], b[3 + c], b[6 + c]);
+    out[9 + r] = dot3(a[3 * r], a[3 * r + 1], a[3 * r + 2], b[9], b[10], b[11]) + a[9 + r];
+  }
+}
+// (x, y, z, w): the contract's matrix -> quaternion conversion (csrc/pose_graph.hip quat_from_rot)
+void quat_from_rot(const double* R, double* q) {
+  const double tr = (R[0] + R[4]) + R[8];
+  double x, y, z, w;
+  if (tr > 0.0) {
+    double s = std::sqrt(tr + 1.0);
+    w = 0.5 * s;
+    s = 0.5 / s;
+    x = (R[7] - R[5]) * s;
+    y = (R[2] - R[6]) * s;
+    z = (R[3] - R[1]) * s;
+  } else {
+    int i = 0;
+    if (R[4] > R[0]) i = 1;
+    if (R[8] > R[4 * i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double s = std::sqrt(((R[4 * i] - R[4 * j]) - R[4 * k]) + 1.0);
+    double v[3];
+    v[i] = 0.5 * s;
+    s = 0.5 / s;
+    w = (R[3 * k + j] - R[3 * j + k]) * s;
+    v[j] = (R[3 * j + i] + R[3 * i + j]) * s;
+    v[k] = (R[3 * k + i] + R[3 * i + k]) * s;
+    x = v[0]; y = v[1]; z = v[2];
+  }
+  const double n = std::sqrt(((x * x + y * y) + z * z) + w * w);
+  x = x / n; y = y / n; z = z / n; w = w / n;
+  if (w < 0.0) { x = -x; y = -y; z = -z; w = -w; }
+  q[0] = x; q[1] = y; q[2] = z; q[3] = w;
+}
+}  // namespace
+
+int rgbdfe_pose_graph_write_trajectory(const rgbdfe_pose_graph* g, const char* path, int32_t n, const int32_t* node_ids,
+                                       const double* timestamps, const double* base2points, const double* init_base_pose,
+                                       const char* frame_id, const char* child_frame_id) try {
+  if (!g || !path || n < 0 || (n > 0 && (!node_ids || !timestamps))) return RGBDFE_ERR_INVALID_ARG;
+  if ((base2points && !all_finite(base2points, 16)) || (init_base_pose && !all_finite(init_base_pose, 16)))
+    return RGBDFE_ERR_INVALID_ARG;
+  for (int32_t i = 0; i < n; ++i)
+    if (g->nodes.find(node_ids[i]) == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;  // before anything is written
+  const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  double b2p[12], init[12], inv[12], left[12];
+  std::copy(ident, ident + 12, b2p);
+  std::copy(ident, ident + 12, init);
+  if (base2points) pose_from_matrix(base2points, b2p);
+  if (init_base_pose) pose_from_matrix(init_base_pose, init);
+  for (int r = 0; r < 3; ++r) {  // the rigid inverse: R', -R't
+    for (int c = 0; c < 3; ++c) inv[3 * r + c] = b2p[3 * c + r];
+    inv[9 + r] = -dot3(b2p[r], b2p[3 + r], b2p[6 + r], b2p[9], b2p[10], b2p[11]);
+  }
+  pose_mul(init, b2p, left);
+  FILE* f = fopen(path, "w");
+  if (!f) return RGBDFE_ERR_INVALID_ARG;
+  bool ok = true;
+  if (frame_id) ok = fprintf(f, "# TF Coordinate Frame ID: %s(data: %s)\n", frame_id, child_frame_id ? child_frame_id : "") >= 0;
+  for (int32_t i = 0; i < n && ok; ++i) {
+    double lx[12], w2b[12], q[4];
+    pose_mul(left, g->nodes.find(node_ids[i])->second.est, lx);
+    pose_mul(lx, inv, w2b);
+    quat_from_rot(w2b, q);
+    ok = fprintf(f, "%.6f %.6f %.6f %.6f %.6f %.6f %.6f %.6f\n", timestamps[i], w2b[9], w2b[10], w2b[11], q[0], q[1], q[2], q[3]) >= 0;
+  }
+  ok = (fclose(f) == 0) && ok;
+  return ok ? RGBDFE_OK : RGBDFE_ERR_INTERNAL;
 } catch (...) {
   return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
 }

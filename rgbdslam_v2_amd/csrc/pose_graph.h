@@ -36,6 +36,7 @@ struct PgProblem {
   const int32_t* edge_ij;      // [2 n_edge]: vertex indices
   const double* edge_in;       // [n_edge][kPgEdgeIn]
   double* edge_out;            // [n_edge][kPgEdgeOut]
+  const int32_t* edge_active;  // [n_edge]: 0 = a pruned edge: rho 0 in its slot, no record, in no list; nullptr: all active
   // lists, all in insertion order: per free vertex its incident edges (edge * 2 + side), per block its edges
   // (edge * 2 + transposed), per free vertex its blocks (block * 2 + the vertex is the block's column)
   const int32_t *vert_ptr, *vert_items, *blk_ptr, *blk_items, *vb_ptr, *vb_items;
@@ -60,5 +61,13 @@ int launch_pg_pcg_begin(const PgProblem& P, double lambda, int32_t max_iter, hip
 int launch_pg_pcg_iterations(const PgProblem& P, double lambda, int32_t first, int32_t count, int32_t max_iter, hipStream_t st);
 // when PCG has stopped as iteration `next` sees it: est_out = est_in (+) x, its chi2 into s->trial_chi2, s->scale, s->applied = 1
 int launch_pg_trial(const PgProblem& P, double lambda, int32_t next, const double* est_in, double* est_out, hipStream_t st);
+
+// pruneEdgesWithErrorAbove (graph_manager.cpp:1106-1246), a lane per edge, in place in the uploaded edge arrays.  topo[e]:
+// bit 0 = |id1 - id2| == 1, bit 1 = both vertices have more than one measured edge (the host owns the topology).
+// An active edge with chi2 > thresh at est: *count += 1, Z = identity, and verdict / information / gate as kPgPrune*.
+constexpr uint8_t kPgPruneKept = 0, kPgPruneRemoved = 1, kPgPruneDiscounted = 2, kPgPruneZeroMotion = 3;
+constexpr uint8_t kPgTopoSequential = 1, kPgTopoBothJoined = 2;
+int launch_pg_prune(const PgProblem& P, const double* est, double thresh, const uint8_t* topo, double* edge_in,
+                    int32_t* edge_active, uint8_t* verdict, int32_t* count, hipStream_t st);
 
 }  // namespace rgbdfe

@@ -10,6 +10,7 @@
 //   pcg      begin (factor H_ff + lambda I = L L', x = 0, r = b, z, p), then per iteration four launches: q = A p with the
 //            leaves of p'q; alpha; x, r, z with the leaves of r'z; beta and p.  The scalars live in PgScalars; an iteration
 //            enqueued after the stop returns at once, so the host enqueues chunks and reads one record per chunk.
+//   prune    a lane per edge: pruneEdgesWithErrorAbove (:1106-1246) on the uploaded edge arrays, in place
 //   trial    gated on the stop: the update applied to a second set of estimates, their chi2, dx'(lambda dx + b)
 //
 // Double throughout; + - * / sqrt and comparisons only (-ffp-contract=off).  Every sum has one order: the terms of a small
@@ -82,40 +83,48 @@ __device__ __forceinline__ void quat_from_rot(const double* R, double* q) {
   q[0] = x; q[1] = y; q[2] = z; q[3] = w;
 }
 
-// a 64-thread workgroup may use the whole register file of a wave: the 6 x 6 products stay in registers
+// e = toVectorMQT(Z^-1 Xi^-1 Xj) into err, and chi2 = e'Oe; Ra, ta, RD, q and Oe stay for the jacobians
+__device__ __forceinline__ double pg_edge_error(const double* Xi, const double* Xj, const double* Z, const double* Om, double* Ra,
+                                                double* ta, double* RD, double* q, double* err, double* Oe) {
+  double d[3];
+  for (int k = 0; k < 3; ++k) d[k] = Xj[9 + k] - Xi[9 + k];
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) Ra[3 * a + b] = dot3(Xi[a], Xi[3 + a], Xi[6 + a], Xj[b], Xj[3 + b], Xj[6 + b]);
+    ta[a] = dot3(Xi[a], Xi[3 + a], Xi[6 + a], d[0], d[1], d[2]);
+  }
+  for (int k = 0; k < 3; ++k) d[k] = ta[k] - Z[9 + k];
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) RD[3 * a + b] = dot3(Z[a], Z[3 + a], Z[6 + a], Ra[b], Ra[3 + b], Ra[6 + b]);
+    err[a] = dot3(Z[a], Z[3 + a], Z[6 + a], d[0], d[1], d[2]);
+  }
+  quat_from_rot(RD, q);
+  err[3] = q[0]; err[4] = q[1]; err[5] = q[2];
+  for (int a = 0; a < 6; ++a) {
+    double acc = Om[6 * a] * err[0];
+    for (int k = 1; k < 6; ++k) acc = acc + Om[6 * a + k] * err[k];
+    Oe[a] = acc;
+  }
+  double chi2 = err[0] * Oe[0];
+  for (int k = 1; k < 6; ++k) chi2 = chi2 + err[k] * Oe[k];
+  return chi2;
+}
+
+// a 64-thread workgroup may use the whole register file of a wave: the 6 x 6 products stay in registers.  A pruned edge
+// (edge_active 0) keeps rho 0 in its place in the tree and writes no record.
 template <bool kJac>
 __global__ void __launch_bounds__(kPgTile) pg_edges_kernel(PgProblem P, const double* est, const int32_t* gate) {
   __shared__ double lds[kPgTile];
   if (gate && !*gate) return;
   const int e = (int)(blockIdx.x * kPgTile + threadIdx.x);
   double rho = 0.0;
-  if (e < P.n_edge) {
+  if (e < P.n_edge && (!P.edge_active || P.edge_active[e])) {
     const double* Xi = est + (size_t)kPgPose * P.edge_ij[2 * e];
     const double* Xj = est + (size_t)kPgPose * P.edge_ij[2 * e + 1];
     const double* Z = P.edge_in + (size_t)kPgEdgeIn * e;
     const double* Om = Z + kPgPose;
     double* out = P.edge_out + (size_t)kPgEdgeOut * e;
-    double Ra[9], ta[3], RD[9], err[6], d[3], q[4];
-    for (int k = 0; k < 3; ++k) d[k] = Xj[9 + k] - Xi[9 + k];
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) Ra[3 * a + b] = dot3(Xi[a], Xi[3 + a], Xi[6 + a], Xj[b], Xj[3 + b], Xj[6 + b]);
-      ta[a] = dot3(Xi[a], Xi[3 + a], Xi[6 + a], d[0], d[1], d[2]);
-    }
-    for (int k = 0; k < 3; ++k) d[k] = ta[k] - Z[9 + k];
-    for (int a = 0; a < 3; ++a) {
-      for (int b = 0; b < 3; ++b) RD[3 * a + b] = dot3(Z[a], Z[3 + a], Z[6 + a], Ra[b], Ra[3 + b], Ra[6 + b]);
-      err[a] = dot3(Z[a], Z[3 + a], Z[6 + a], d[0], d[1], d[2]);
-    }
-    quat_from_rot(RD, q);
-    err[3] = q[0]; err[4] = q[1]; err[5] = q[2];
-    double Oe[6];
-    for (int a = 0; a < 6; ++a) {
-      double acc = Om[6 * a] * err[0];
-      for (int k = 1; k < 6; ++k) acc = acc + Om[6 * a + k] * err[k];
-      Oe[a] = acc;
-    }
-    double chi2 = err[0] * Oe[0];
-    for (int k = 1; k < 6; ++k) chi2 = chi2 + err[k] * Oe[k];
+    double Ra[9], ta[3], RD[9], err[6], q[4], Oe[6];
+    const double chi2 = pg_edge_error(Xi, Xj, Z, Om, Ra, ta, RD, q, err, Oe);
     double w = 1.0;
     rho = chi2;
     if (!(chi2 <= 1.0)) {  // Huber, delta = 1
@@ -447,6 +456,46 @@ __global__ void pg_trial_finish_kernel(PgProblem P, const int32_t* gate) {
   }
 }
 
+// pruneEdgesWithErrorAbove, a lane per edge (one wave a workgroup): the error code of pg_edges_kernel, then the verdict from
+// the host's topology bits.  The patched measurement and information, the gate and the verdict go in place; the count is an
+// integer (one atomic per wave: any order gives the same number).  NaN compares false: the edge is kept.
+__global__ void __launch_bounds__(kPgTile) pg_prune_kernel(PgProblem P, const double* est, double thresh, const uint8_t* topo,
+                                                           double* edge_in, int32_t* edge_active, uint8_t* verdict, int32_t* count) {
+  const int e = (int)(blockIdx.x * kPgTile + threadIdx.x);
+  bool pruned = false;
+  if (e < P.n_edge) {
+    uint8_t v = kPgPruneKept;
+    if (edge_active[e]) {
+      const double* Xi = est + (size_t)kPgPose * P.edge_ij[2 * e];
+      const double* Xj = est + (size_t)kPgPose * P.edge_ij[2 * e + 1];
+      double* Z = edge_in + (size_t)kPgEdgeIn * e;
+      double* Om = Z + kPgPose;
+      double Ra[9], ta[3], RD[9], err[6], q[4], Oe[6];
+      const double chi2 = pg_edge_error(Xi, Xj, Z, Om, Ra, ta, RD, q, err, Oe);
+      if (chi2 > thresh) {
+        pruned = true;
+        for (int k = 0; k < kPgPose; ++k) Z[k] = (k < 9 && k % 4 == 0) ? 1.0 : 0.0;
+        const uint8_t tp = topo[e];
+        double diag = 1.0;
+        if (tp & kPgTopoSequential) {
+          v = kPgPruneZeroMotion;
+        } else if (tp & kPgTopoBothJoined) {
+          v = kPgPruneRemoved;
+          edge_active[e] = 0;
+        } else {
+          v = kPgPruneDiscounted;
+          diag = 1e-100;
+        }
+        if (v != kPgPruneRemoved)
+          for (int k = 0; k < 36; ++k) Om[k] = (k % 7 == 0) ? diag : 0.0;
+      }
+    }
+    verdict[e] = v;
+  }
+  const int n = __popcll(__ballot(pruned ? 1 : 0));
+  if (threadIdx.x == 0 && n > 0) atomicAdd(count, n);
+}
+
 inline unsigned grid_for(long long n) { return (unsigned)(n > 0 ? (n + kPgTile - 1) / kPgTile : 1); }
 
 }  // namespace
@@ -457,6 +506,13 @@ int launch_pg_edges(const PgProblem& P, const double* est, bool jacobians, hipSt
     hipLaunchKernelGGL((pg_edges_kernel<true>), dim3(grid_for(P.n_edge)), dim3(kPgTile), 0, st, P, est, gate);
   else
     hipLaunchKernelGGL((pg_edges_kernel<false>), dim3(grid_for(P.n_edge)), dim3(kPgTile), 0, st, P, est, gate);
+  return 1;
+}
+
+int launch_pg_prune(const PgProblem& P, const double* est, double thresh, const uint8_t* topo, double* edge_in,
+                    int32_t* edge_active, uint8_t* verdict, int32_t* count, hipStream_t st) {
+  hipLaunchKernelGGL(pg_prune_kernel, dim3(grid_for(P.n_edge)), dim3(kPgTile), 0, st, P, est, thresh, topo, edge_in, edge_active,
+                     verdict, count);
   return 1;
 }
 

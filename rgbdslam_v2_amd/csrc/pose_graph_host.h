@@ -19,12 +19,15 @@ struct rgbdfe_pose_graph {
     int32_t id1, id2;
     double z[12];
     double info[36];
+    bool active = true;      // false once pruned with verdict REMOVED: the slot stays, the edge contributes nothing
   };
   std::map<int32_t, NodeInfo> nodes;                 // node id -> node (graph_)
   std::set<int32_t> camera_vertices;                 // vertex ids
   std::map<int32_t, std::set<int32_t>> adjacency;    // vertex id -> vertex ids joined by an edge
   std::deque<int32_t> keyframes;
   std::vector<MeasuredEdge> edges;                   // in insertion order; edges without a measurement are not here
+  int32_t strategy = 0;                              // RGBDFE_POSE_RELATIVE_TO_*
+  int32_t earliest_loop_closure_node = 0;            // graph_manager.cpp:444, :893-896 (kept while a strategy is set)
   void* device = nullptr;                            // the optimiser's buffers (api_pose_graph.hip)
   void (*device_free)(void*) = nullptr;
 };

@@ -971,6 +971,24 @@ int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, doub
   return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_optimize_graph(c, g, break_criterion, report));
 }
 
+int rgbdfe_pose_graph_edge_errors(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2, double* err_sq, int32_t* active,
+                                  int32_t capacity, int32_t* n_edges) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_edge_errors(c, g, chi2, err_sq, active, capacity, n_edges));
+}
+
+int rgbdfe_pose_graph_prune_edges(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, float thresh, uint8_t* verdicts, int32_t capacity,
+                                  int32_t* n_pruned) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_prune_edges(c, g, thresh, verdicts, capacity, n_pruned));
+}
+
+int rgbdfe_pose_graph_evaluate(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double optimizer_iterations,
+                               rgbdfe_pose_graph_evaluation* out, double* estimates, int32_t capacity_nodes) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_pose_graph_evaluate(c, g, optimizer_iterations, out, estimates, capacity_nodes));
+}
+
 // the ICP fallback runs on one device (the first of a group)
 void rgbdfe_icp_default_params(rgbdfe_icp_params* p) { impl::rgbdfe_icp_default_params(p); }
 

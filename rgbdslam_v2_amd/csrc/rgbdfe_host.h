@@ -584,6 +584,9 @@ int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2);
 int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* errors, double* weights, int32_t edge_capacity, int32_t* n_edges, int32_t* free_ids, double* h_diag, double* b, int32_t vertex_capacity, int32_t* n_free, int32_t* off_rows, int32_t* off_cols, double* h_off, int32_t block_capacity, int32_t* n_blocks, double* chi2);
 int rgbdfe_pose_graph_optimize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, int32_t iterations, rgbdfe_pose_graph_report* report);
 int rgbdfe_pose_graph_optimize_graph(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double break_criterion, rgbdfe_pose_graph_report* report);
+int rgbdfe_pose_graph_edge_errors(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2, double* err_sq, int32_t* active, int32_t capacity, int32_t* n_edges);
+int rgbdfe_pose_graph_prune_edges(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, float thresh, uint8_t* verdicts, int32_t capacity, int32_t* n_pruned);
+int rgbdfe_pose_graph_evaluate(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double optimizer_iterations, rgbdfe_pose_graph_evaluation* out, double* estimates, int32_t capacity_nodes);
 // api_icp.hip
 void rgbdfe_icp_default_params(rgbdfe_icp_params* p);
 int rgbdfe_icp_align_nodes(rgbdfe_ctx* ctx, int32_t n_jobs, const int32_t* source_ids, const int32_t* target_ids, const float* guesses, const rgbdfe_icp_params* params, float* transforms_out, rgbdfe_icp_report* reports_out);

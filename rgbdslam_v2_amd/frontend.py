@@ -1389,7 +1389,8 @@ class Node:
 
 class GraphManager:
     """The fan-out of GraphManager::nodeComparisons (src/graph_manager.cpp:531-583) and, over a candidates.PoseGraph,
-    addEdgeToG2O (:811-909) and optimizeGraph (:938-1066)."""
+    addEdgeToG2O (:811-909), optimizeGraph (:938-1066), pruneEdgesWithErrorAbove (:1106-1246), sanityCheck (:1347-1360),
+    the rounds of OpenNIListener::evaluation and saveTrajectory's estimate file."""
 
     def __init__(self, frontend: FrontEnd, pose_graph=None):
         self.frontend = frontend
@@ -1408,6 +1409,28 @@ class GraphManager:
     def optimize_graph(self, break_criterion: float = 0.01):
         """optimizeGraph with optimizer_iterations = break_criterion; the report (its "chi2" is what the reference returns)."""
         return self._graph().optimize_graph(self.frontend, break_criterion)
+
+    def set_pose_relative_to(self, strategy: str):
+        """pose_relative_to: "first", "previous", "largest_loop", "inaffected" ("none": the flags of set_fixed as they are)."""
+        self._graph().set_strategy(strategy)
+
+    def pruneEdgesWithErrorAbove(self, thresh: float):
+        """pruneEdgesWithErrorAbove (:1106-1246) on the device; returns the number of edges pruned."""
+        return self._graph().prune_edges(self.frontend, thresh)[0]
+
+    def sanityCheck(self, thresh: float):
+        """sanityCheck (:1347-1360); returns the number of edges whose information became 0.000001 I."""
+        return self._graph().sanity_check(thresh)
+
+    def evaluation(self, optimizer_iterations: float = 0.01):
+        """The five optimisation rounds of OpenNIListener::evaluation (openni_listener.cpp:431-518):
+        (a dict per round, the estimates after every round as [5, n, 4, 4])."""
+        return self._graph().evaluate(self.frontend, optimizer_iterations)
+
+    def saveTrajectory(self, path, node_ids, timestamps, base2points=None, init_base_pose=None, frame_id=None,
+                       child_frame_id=None):
+        """saveTrajectory's estimate file (graph_mgr_io.cpp:615-677) in TUM format, for tools/evaluate_ate.py."""
+        self._graph().write_trajectory(path, node_ids, timestamps, base2points, init_base_pose, frame_id, child_frame_id)
 
     def nodeComparisons(self, new_node: Node, nodes_to_comp: Sequence[Node]) -> List[MatchingResult]:
         recs = self.frontend.match_node_pairs(new_node.id_, [n.id_ for n in nodes_to_comp])
