@@ -986,6 +986,74 @@ int rgbdfe_icp_align_clouds(rgbdfe_ctx* ctx, const float* source, int64_t n_sour
 int rgbdfe_filter_cloud(rgbdfe_ctx* ctx, const float* cloud, int64_t n, int32_t desired_size, int32_t* indices_out,
                         float* rows_out, int64_t capacity, int64_t* n_out);
 
+/* ---- display geometry: resident node clouds as GL points, triangles and triangle strips -------------------
+ * rgbdfe_display_geometry is GLViewer::addPointCloud's choice (glviewer.cpp:693-711) among pointCloud2GLPoints
+ *   (:955-987), pointCloud2GLTriangleList (:989-1042) and pointCloud2GLStrip (:776-906) for every listed node, with
+ *   setGLColor in its plain form (:91-93; not HEMACLOUDS, not RGB_IS_4TH_DIM), on the device.  The contract is that
+ *   code, statement by statement; its quirks are reproduced (DESIGN.md 4.24 lists them).
+ *   node_ids / transforms as rgbdfe_assemble_map takes them (ids may repeat, cloud sizes may be mixed); transforms may be
+ *   NULL: the vertices stay in the node frame.
+ *   A vertex is a row of 4 floats: x, y, z of a glVertex3f call and the rgb word, bit for bit, of the point the
+ *   preceding setGLColor call was given (bytes 0, 1, 2 = b, g, r: a GL_BGRA colour as it stands).  A node's vertex
+ *   stream is the sequence of glVertex3f calls of the reference function for its cloud.
+ *   Validity (validXYZ, :44-47): a point is invalid iff max_depth < z or any of z, y, x is not finite, with max_depth =
+ *   (float)maximum_depth.  The test is on z, not on the range; the finite x, y "at 1 m" beside a NaN z is invalid.
+ *   Distances (squaredEuclideanDistance, :768-773): (dx*dx + dy*dy) + dz*dz in float, one rounding per operation.  Every
+ *   test is `d / depth <= t` or `d / depth > t` with an IEEE float division, t = (float)squared_meshing_threshold, depth
+ *   the squared distance of the named point from the origin.  A point in the origin gives depth 0: the inf and NaN
+ *   ratios decide as the comparison operators decide them.
+ *   Form of node k (node_types[k]; may be NULL): RGBDFE_DISPLAY_POINTS when its cloud has rows <= 1 (the state
+ *   rgbdfe_reduce_node_cloud leaves) or squared_meshing_threshold < 0, else display_type.
+ *   POINTS: x outer over [0, cols), y inner over [0, rows); every valid point, in that order.
+ *   TRIANGLES: x outer over [0, cols - 1), y inner over [0, rows - 1); per cell with pi = (x, y), pj = (x + 1, y), pk =
+ *   (x, y + 1), pl = (x + 1, y + 1) the triangles (pi, pl, pj) and then (pi, pk, pl) under the conditions of :1016-1036.
+ *   visualization_skip_step is not read.
+ *   TRIANGLE_STRIP: the state machine of :798-898 with step = visualization_skip_step: rows y = 0, step, ... < rows -
+ *   step; columns x = 0; x < cols - step; x += step, with the extra x++ of :829 (afterwards x need not be a multiple of
+ *   step).  Both start forms (upper point first; lower first, `flip`), the doubled test of :810-811; `*(ul - step)` is
+ *   the point step columns to the left in the same row.  The second vertex of a running step has the lower (flip: the
+ *   upper) point's x, y, z and the rgb word of the step's first vertex (:886).  A strip ends at every glEnd, the one at
+ *   the end of a row included; strips of one or two vertices are strips.
+ *   With transforms every vertex is ((R0 x + R1 y) + R2 z) + t per row of its point, the arithmetic of
+ *   rgbdfe_assemble_map in the same order: a vertex equals the assembled map's row of that point bit for bit.  All
+ *   validity and threshold tests use the untransformed point (the viewer applies cloud_matrices in GL).
+ *   Output.  vertices: vertex_capacity rows; the nodes' streams in the order of node_ids.  *n_vertices = the rows;
+ *   node_offsets (may be NULL; n_nodes + 1 entries) = the first vertex of every node, then *n_vertices.  strips:
+ *   strip_capacity records of two int64 (first vertex as an index into the whole stream, vertex count), one per
+ *   glBegin(GL_TRIANGLE_STRIP), in stream order.  *n_strips = the records; node_strip_offsets (may be NULL; n_nodes + 1
+ *   entries) = the first record of every node, then *n_strips.  POINTS and TRIANGLES nodes own no records.
+ *   Errors.  display_type not one of the three, visualization_skip_step < 1: RGBDFE_ERR_INVALID_ARG, nothing is
+ *   written.  An id without a cloud: RGBDFE_ERR_UNKNOWN_NODE, before any device work.  vertex_capacity < *n_vertices or
+ *   strip_capacity < *n_strips: RGBDFE_ERR_CAPACITY with both needed sizes, the offsets and node_types set (the
+ *   buffers' contents are then untouched).  n_nodes == 0: RGBDFE_OK, both sizes 0.
+ *   Sizes that always suffice for a cloud of rows x cols points: POINTS rows * cols vertices; TRIANGLES 6 * (rows - 1) *
+ *   (cols - 1) vertices (two triangles per cell); TRIANGLE_STRIP with Y = ceil((rows - step) / step) visited rows and X
+ *   = ceil((cols - step) / step) visited columns at most (none unless rows > step and cols > step): 2 * X * Y vertices
+ *   (a column sends at most two; an all-valid flat row reaches 2 * X) and ceil(X / 2) * Y records (the column whose test
+ *   ends a strip starts none).
+ * rgbdfe_display_geometry_device: the same with d_vertices / d_strips device pointers of the context's device (the
+ *   first device of a multi-device handle); no vertex crosses to the host.  The kernels run on `stream` (NULL: the
+ *   context's own); the call returns when they have finished.  Sizes, offsets and node_types are host pointers.
+ * rgbdfe_display_default_params: POINTS, 1, 0.0009, +inf (parameter_server.cpp:151, :139, :148, :38). */
+#define RGBDFE_DISPLAY_POINTS 0
+#define RGBDFE_DISPLAY_TRIANGLES 1
+#define RGBDFE_DISPLAY_TRIANGLE_STRIP 2
+typedef struct rgbdfe_display_params {
+  int32_t display_type;             /* cloud_display_type (default "POINTS") */
+  int32_t visualization_skip_step;  /* default 1; read by the strip form only, as in the reference */
+  double squared_meshing_threshold; /* default 0.0009; < 0: every node is drawn as points (glviewer.cpp:697) */
+  double maximum_depth;             /* default +inf */
+} rgbdfe_display_params;
+void rgbdfe_display_default_params(rgbdfe_display_params* p);
+int rgbdfe_display_geometry(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                            const rgbdfe_display_params* params, float* vertices, int64_t vertex_capacity,
+                            int64_t* n_vertices, int64_t* node_offsets, int64_t* strips, int64_t strip_capacity,
+                            int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types);
+int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                                   const rgbdfe_display_params* params, void* d_vertices, int64_t vertex_capacity,
+                                   int64_t* n_vertices, int64_t* node_offsets, void* d_strips, int64_t strip_capacity,
+                                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, void* stream);
+
 /* GPU prefilter in front of the pair path (second half): what loop_closing.cpp's
  * GraphManager::getNeighbours (:190-277, behind DO_LOOP_CLOSING, never wired into nodeComparisons) sketched -- every
  * descriptor of the new node votes `k_neighbours - rank` (:241) for the nodes holding its k nearest descriptors, a

@@ -548,6 +548,44 @@ inline bool assembleAllClouds(const FrontEnd& fe, const std::vector<int32_t>& no
   return true;
 }
 
+// GLViewer::addPointCloud (src/glviewer.cpp:693-735) for every listed node, on the device: what pointCloud2GLPoints,
+// pointCloud2GLTriangleList or pointCloud2GLStrip would have sent to the node's display list (rgbdfe_display_geometry).
+// display_type is the parameter "cloud_display_type" ("POINTS", "TRIANGLES", anything else but "ELLIPSOIDS" / "NONE":
+// TRIANGLE_STRIP); world2cam as assembleAllClouds takes it, or empty for vertices in the node frame (the viewer's own way: it
+// applies cloud_matrices in GL).  vertices = rows of (x, y, z, rgb bits: a GL_BGRA colour); strips = (first vertex, vertex
+// count) per glBegin(GL_TRIANGLE_STRIP).
+struct DisplayGeometry {
+  std::vector<float> vertices;
+  std::vector<int64_t> strips, node_offsets, node_strip_offsets;
+  std::vector<int32_t> node_types;  // RGBDFE_DISPLAY_* per node: a cloud of one row is drawn as points
+};
+inline int32_t displayTypeFromParameter(const std::string& cloud_display_type) {
+  if (cloud_display_type == "TRIANGLES") return RGBDFE_DISPLAY_TRIANGLES;
+  if (cloud_display_type == "POINTS") return RGBDFE_DISPLAY_POINTS;
+  return RGBDFE_DISPLAY_TRIANGLE_STRIP;  // glviewer.cpp:708: "TRIANGLE_STRIP is default"
+}
+inline bool displayGeometry(const FrontEnd& fe, const std::vector<int32_t>& node_ids, const std::vector<float>& world2cam,
+                            const rgbdfe_display_params& params, DisplayGeometry* out) {
+  if (!world2cam.empty() && world2cam.size() != node_ids.size() * 16) return false;
+  const int32_t n = (int32_t)node_ids.size();
+  const float* T = world2cam.empty() ? nullptr : world2cam.data();
+  out->node_offsets.assign(node_ids.size() + 1, 0);
+  out->node_strip_offsets.assign(node_ids.size() + 1, 0);
+  out->node_types.assign(node_ids.size(), 0);
+  int64_t nv = 0, ns = 0;
+  // the sizes first (RGBDFE_ERR_CAPACITY reports both; an empty stream is RGBDFE_OK), then the vertices and records
+  int rc = rgbdfe_display_geometry(fe.get(), n, node_ids.data(), T, &params, nullptr, 0, &nv, out->node_offsets.data(), nullptr, 0,
+                                   &ns, out->node_strip_offsets.data(), out->node_types.data());
+  if (rc != RGBDFE_OK && rc != RGBDFE_ERR_CAPACITY) return false;
+  out->vertices.resize((size_t)nv * 4);
+  out->strips.resize((size_t)ns * 2);
+  if (rc == RGBDFE_ERR_CAPACITY &&
+      rgbdfe_display_geometry(fe.get(), n, node_ids.data(), T, &params, out->vertices.data(), nv, &nv, out->node_offsets.data(),
+                              out->strips.data(), ns, &ns, out->node_strip_offsets.data(), out->node_types.data()) != RGBDFE_OK)
+    return false;
+  return true;
+}
+
 // pcl::VoxelGrid with a cubic leaf of voxelfilter_size over a device buffer of n_in rows (x, y, z, rgb bits) into another of
 // `capacity` rows on the context's device (rgbdfe_voxel_filter_device): the consumer of rgbdfe_assemble_map_device's output.
 // Returns the rows written, or -1 (needed: the rows that would have been; flags: RGBDFE_VOXEL_LEAF_TOO_SMALL).

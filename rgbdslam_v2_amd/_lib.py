@@ -121,6 +121,14 @@ class IcpParams(C.Structure):   # rgbdfe_icp_params
                 ("euclidean_fitness_epsilon", C.c_double), ("max_iterations", C.c_int32), ("desired_size", C.c_int32)]
 
 
+class RgbdfeDisplayParams(C.Structure):   # rgbdfe_display_params
+    _fields_ = [("display_type", C.c_int32), ("visualization_skip_step", C.c_int32),
+                ("squared_meshing_threshold", C.c_double), ("maximum_depth", C.c_double)]
+
+
+DISPLAY_POINTS, DISPLAY_TRIANGLES, DISPLAY_TRIANGLE_STRIP = 0, 1, 2
+
+
 # rgbdfe_icp_report
 ICP_REPORT_DTYPE = np.dtype([("converged", "<i4"), ("state", "<i4"), ("iterations", "<i4"), ("correspondences", "<i4"),
                              ("mse", "<f8"), ("n_source", "<i4"), ("n_target", "<i4"), ("launches", "<i8"),
@@ -354,6 +362,13 @@ def load():
     L.rgbdfe_assemble_map.argtypes = [ctx, i32, vp, vp, C.c_double, i32, vp, C.c_int64, C.POINTER(C.c_int64), vp]
     L.rgbdfe_assemble_map_device.restype = C.c_int
     L.rgbdfe_assemble_map_device.argtypes = [ctx, i32, vp, vp, C.c_double, i32, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]
+    L.rgbdfe_display_default_params.restype = None
+    L.rgbdfe_display_default_params.argtypes = [C.POINTER(RgbdfeDisplayParams)]
+    L.rgbdfe_display_geometry.restype = C.c_int
+    L.rgbdfe_display_geometry.argtypes = [ctx, i32, vp, vp, C.POINTER(RgbdfeDisplayParams), vp, C.c_int64, C.POINTER(C.c_int64),
+                                          vp, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]
+    L.rgbdfe_display_geometry_device.restype = C.c_int
+    L.rgbdfe_display_geometry_device.argtypes = L.rgbdfe_display_geometry.argtypes + [vp]
     L.rgbdfe_download_node_cloud.restype = C.c_int
     L.rgbdfe_download_node_cloud.argtypes = [ctx, i32, vp, C.c_int64, C.POINTER(i32), C.POINTER(i32)]
     L.rgbdfe_voxel_filter.restype = C.c_int
@@ -573,6 +588,7 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_upload_node_cloud", "rgbdfe_release_node_cloud", "rgbdfe_observation_likelihood",
     "rgbdfe_assemble_map", "rgbdfe_assemble_map_device", "rgbdfe_download_node_cloud",
     "rgbdfe_voxel_filter", "rgbdfe_voxel_filter_device", "rgbdfe_reduce_node_cloud",
+    "rgbdfe_display_default_params", "rgbdfe_display_geometry", "rgbdfe_display_geometry_device",
     "rgbdfe_octomap_default_params", "rgbdfe_octomap_create", "rgbdfe_octomap_destroy", "rgbdfe_octomap_reset",
     "rgbdfe_octomap_reserve", "rgbdfe_octomap_insert_nodes", "rgbdfe_octomap_insert_cloud", "rgbdfe_octomap_size",
     "rgbdfe_octomap_leaves", "rgbdfe_octomap_stats",

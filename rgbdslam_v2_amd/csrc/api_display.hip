@@ -1,0 +1,188 @@
+// api_display.hip -- display geometry: the resident node clouds as GL points, triangles and triangle strips (kernels:
+// display_geometry.hip)
+// (one of the host-side translation units of librgbdfe.so; shared declarations: rgbdfe_host.h)
+#include "rgbdfe_host.h"
+
+#include "display_geometry.h"
+
+namespace impl {
+
+namespace {
+
+struct DeviceBuffer {  // the host entry point's staging: as large as one call's output, not kept
+  void* p = nullptr;
+  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+};
+
+// GLViewer::addPointCloud (glviewer.cpp:693-711) for every listed node.  Exactly one of the host / device pairs receives
+// the output.
+int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                   const rgbdfe_display_params* params, float* h_vertices, void* d_vertices, int64_t vertex_capacity,
+                   int64_t* n_vertices, int64_t* node_offsets, int64_t* h_strips, void* d_strips, int64_t strip_capacity,
+                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, bool to_device, void* stream) {
+  if (!ctx || n_nodes < 0 || !params || !n_vertices || !n_strips || vertex_capacity < 0 || strip_capacity < 0 ||
+      (n_nodes > 0 && !node_ids) || (vertex_capacity > 0 && !(to_device ? d_vertices != nullptr : h_vertices != nullptr)) ||
+      (strip_capacity > 0 && !(to_device ? d_strips != nullptr : h_strips != nullptr)))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad display geometry arguments");
+  if (params->display_type != RGBDFE_DISPLAY_POINTS && params->display_type != RGBDFE_DISPLAY_TRIANGLES &&
+      params->display_type != RGBDFE_DISPLAY_TRIANGLE_STRIP)
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "display geometry: unknown display_type");
+  if (params->visualization_skip_step < 1)
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "display geometry: visualization_skip_step must be at least 1");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  // the node table and the tile -> node map: one blob, one copy
+  const size_t n = (size_t)n_nodes;
+  std::vector<DispNode> table(n + 1);
+  const bool as_points = params->squared_meshing_threshold < 0;  // :697
+  const int64_t step = params->visualization_skip_step;
+  int64_t tiles = 0, rows = 0;
+  bool have_items = false, have_rows = false;
+  for (size_t k = 0; k < n; ++k) {
+    auto it = ctx->clouds.find(node_ids[k]);
+    if (it == ctx->clouds.end() || !it->second.d)
+      return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "display geometry: no cloud for a listed node");
+    const CloudEntry& ce = it->second;
+    const int64_t w = ce.cw, h = ce.ch;
+    if (w * h > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: a cloud of more than 2^31 points");
+    DispNode& m = table[k];
+    memset(&m, 0, sizeof(m));
+    m.cloud = ce.d;
+    m.w = (int32_t)w;
+    m.h = (int32_t)h;
+    m.type = (h <= 1 || as_points) ? RGBDFE_DISPLAY_POINTS : params->display_type;  // !isOrganized(): height == 1
+    m.step = (int32_t)step;
+    int64_t items = 0, tile = kDispItemTile;
+    if (m.type == RGBDFE_DISPLAY_POINTS) {
+      items = w * h;
+      m.items_h = (uint32_t)h;
+    } else if (m.type == RGBDFE_DISPLAY_TRIANGLES) {
+      items = w >= 2 ? (w - 1) * (h - 1) : 0;
+      m.items_h = (uint32_t)(h - 1);
+    } else {  // the rows y = 0, step, ... < h - step; none of them visits a column unless 0 < w - step
+      items = (h > step && w > step) ? (h - 1) / step : 0;
+      tile = kDispRowTile;
+      m.first_row = (uint32_t)rows;
+      rows += items;
+    }
+    m.n_items = (uint32_t)items;
+    m.first_tile = (uint32_t)tiles;
+    if (items > 0) (m.type == RGBDFE_DISPLAY_TRIANGLE_STRIP ? have_rows : have_items) = true;
+    if (transforms) {
+      const float* T = transforms + k * 16;  // column-major Matrix4f
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) m.R[r * 3 + c] = T[c * 4 + r];
+        m.t[r] = T[12 + r];
+      }
+    }
+    tiles += (items + tile - 1) / tile;
+    if (tiles > (int64_t)INT32_MAX || rows > (int64_t)INT32_MAX)
+      return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: more than 2^31 tiles in one call");
+  }
+  *n_vertices = 0;
+  *n_strips = 0;
+  if (node_types)
+    for (size_t k = 0; k < n; ++k) node_types[k] = table[k].type;
+  if (n_nodes == 0) {
+    if (node_offsets) node_offsets[0] = 0;
+    if (node_strip_offsets) node_strip_offsets[0] = 0;
+    return RGBDFE_OK;
+  }
+  DispNode& end = table[n];
+  memset(&end, 0, sizeof(end));
+  end.first_tile = (uint32_t)tiles;
+  end.first_row = (uint32_t)rows;
+  const size_t n_tiles = (size_t)tiles;
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_table = up(sizeof(DispNode) * (n + 1)), b_map = up(4 * n_tiles);
+  std::vector<uint8_t> blob(b_table + b_map);
+  memcpy(blob.data(), table.data(), sizeof(DispNode) * (n + 1));
+  uint32_t* tile_node = reinterpret_cast<uint32_t*>(blob.data() + b_table);
+  for (size_t k = 0; k < n; ++k)
+    for (uint32_t t = table[k].first_tile; t < table[k + 1].first_tile; ++t) tile_node[t] = (uint32_t)k;
+
+  DispParams prm;
+  prm.mesh_thresh = (float)params->squared_meshing_threshold;  // `const float mesh_thresh` (:784, :997)
+  prm.max_depth = (float)params->maximum_depth;                // `const float max_depth` (:785, :972, :1007)
+  prm.transform = transforms ? 1u : 0u;
+
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  const size_t b_count = up(8 * n_tiles), b_rows = up(8 * (size_t)rows), b_first = up(16 * (n_tiles + 1)),
+               b_nodes = up(16 * (n + 1));
+  int rc = ensure_scratch(ctx, b_table + b_map + b_count + b_rows + b_first + b_nodes);
+  if (rc != RGBDFE_OK) return rc;
+  char* base = (char*)ctx->d_scratch;
+  const DispNode* d_table = (const DispNode*)base;
+  const uint32_t* d_tile_node = (const uint32_t*)(base + b_table);
+  uint2* d_count = (uint2*)(base + b_table + b_map);
+  uint2* d_rows = (uint2*)(base + b_table + b_map + b_count);
+  int64_t* d_first = (int64_t*)(base + b_table + b_map + b_count + b_rows);
+  int64_t* d_node_first = (int64_t*)(base + b_table + b_map + b_count + b_rows + b_first);
+  HIP_TRY(ctx, hipMemcpyAsync(base, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+
+  launch_display_count_scan(d_table, d_tile_node, (uint32_t)n, (uint32_t)n_tiles, prm, have_items, have_rows, d_count, d_rows,
+                            d_first, d_node_first, st);
+  HIP_TRY(ctx, hipGetLastError());
+  std::vector<int64_t> first(2 * (n + 1));  // the one read of the sizes: the nodes' firsts and the totals
+  HIP_TRY(ctx, hipMemcpyAsync(first.data(), d_node_first, 16 * (n + 1), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  const int64_t total_v = first[2 * n], total_s = first[2 * n + 1];
+  *n_vertices = total_v;
+  *n_strips = total_s;
+  for (size_t k = 0; k <= n; ++k) {
+    if (node_offsets) node_offsets[k] = first[2 * k];
+    if (node_strip_offsets) node_strip_offsets[k] = first[2 * k + 1];
+  }
+  if (vertex_capacity < total_v || strip_capacity < total_s)
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: a buffer is too small (*n_vertices rows and *n_strips records are needed)");
+  if (total_v == 0) return RGBDFE_OK;  // no vertex, so no strip either
+  DeviceBuffer stage_v, stage_s;
+  float4* d_v = (float4*)d_vertices;
+  int64_t* d_s = (int64_t*)d_strips;
+  if (!to_device) {
+    if (hipMalloc(&stage_v.p, (size_t)total_v * sizeof(float4)) != hipSuccess ||
+        (total_s > 0 && hipMalloc(&stage_s.p, (size_t)total_s * 16) != hipSuccess)) {
+      (void)hipGetLastError();
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "display geometry: staging allocation failed");
+    }
+    d_v = (float4*)stage_v.p;
+    d_s = (int64_t*)stage_s.p;
+  }
+  launch_display_write(d_table, d_tile_node, (uint32_t)n_tiles, prm, have_items, have_rows, d_rows, d_first, d_v, d_s, st);
+  HIP_TRY(ctx, hipGetLastError());
+  if (!to_device) {
+    HIP_TRY(ctx, hipMemcpyAsync(h_vertices, d_v, (size_t)total_v * sizeof(float4), hipMemcpyDeviceToHost, st));
+    if (total_s > 0) HIP_TRY(ctx, hipMemcpyAsync(h_strips, d_s, (size_t)total_s * 16, hipMemcpyDeviceToHost, st));
+  }
+  // the table in the context's scratch is this call's: it returns when the stream has passed it
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return RGBDFE_OK;
+}
+
+}  // namespace
+
+void rgbdfe_display_default_params(rgbdfe_display_params* p) {
+  if (!p) return;
+  p->display_type = RGBDFE_DISPLAY_POINTS;        // parameter_server.cpp:151
+  p->visualization_skip_step = 1;                 // :139
+  p->squared_meshing_threshold = 0.0009;          // :148
+  p->maximum_depth = std::numeric_limits<double>::infinity();  // :38
+}
+
+int rgbdfe_display_geometry(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                            const rgbdfe_display_params* params, float* vertices, int64_t vertex_capacity, int64_t* n_vertices,
+                            int64_t* node_offsets, int64_t* strips, int64_t strip_capacity, int64_t* n_strips,
+                            int64_t* node_strip_offsets, int32_t* node_types) {
+  return display_common(ctx, n_nodes, node_ids, transforms, params, vertices, nullptr, vertex_capacity, n_vertices, node_offsets,
+                        strips, nullptr, strip_capacity, n_strips, node_strip_offsets, node_types, false, nullptr);
+}
+
+int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                                   const rgbdfe_display_params* params, void* d_vertices, int64_t vertex_capacity,
+                                   int64_t* n_vertices, int64_t* node_offsets, void* d_strips, int64_t strip_capacity,
+                                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, void* stream) {
+  return display_common(ctx, n_nodes, node_ids, transforms, params, nullptr, d_vertices, vertex_capacity, n_vertices, node_offsets,
+                        nullptr, d_strips, strip_capacity, n_strips, node_strip_offsets, node_types, true, stream);
+}
+
+}  // namespace impl

@@ -1014,6 +1014,29 @@ int rgbdfe_filter_cloud(rgbdfe_ctx* ctx, const float* cloud, int64_t n, int32_t 
   return RGBDFE_FIRST(ctx, impl::rgbdfe_filter_cloud(c, cloud, n, desired_size, indices_out, rows_out, capacity, n_out));
 }
 
+void rgbdfe_display_default_params(rgbdfe_display_params* p) { impl::rgbdfe_display_default_params(p); }
+
+// the clouds are replicated on every device of a group: served from the first one, like map assembly
+int rgbdfe_display_geometry(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                            const rgbdfe_display_params* params, float* vertices, int64_t vertex_capacity, int64_t* n_vertices,
+                            int64_t* node_offsets, int64_t* strips, int64_t strip_capacity, int64_t* n_strips,
+                            int64_t* node_strip_offsets, int32_t* node_types) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_display_geometry(c, n_nodes, node_ids, transforms, params, vertices, vertex_capacity,
+                                                         n_vertices, node_offsets, strips, strip_capacity, n_strips,
+                                                         node_strip_offsets, node_types));
+}
+
+int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                                   const rgbdfe_display_params* params, void* d_vertices, int64_t vertex_capacity,
+                                   int64_t* n_vertices, int64_t* node_offsets, void* d_strips, int64_t strip_capacity,
+                                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, void* stream) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_display_geometry_device(c, n_nodes, node_ids, transforms, params, d_vertices,
+                                                                vertex_capacity, n_vertices, node_offsets, d_strips,
+                                                                strip_capacity, n_strips, node_strip_offsets, node_types, stream));
+}
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

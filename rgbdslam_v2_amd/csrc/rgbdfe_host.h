@@ -579,6 +579,10 @@ int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_ou
 int rgbdfe_voxel_filter(rgbdfe_ctx* ctx, const float* points, int64_t n_in, double voxelfilter_size, float* out, int64_t capacity, int64_t* n_out, int32_t* flags);
 int rgbdfe_voxel_filter_device(rgbdfe_ctx* ctx, const void* d_points, int64_t n_in, double voxelfilter_size, void* d_out, int64_t capacity, int64_t* n_out, int32_t* flags, void* stream);
 int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilter_size, int64_t* n_out, int32_t* flags);
+// api_display.hip
+void rgbdfe_display_default_params(rgbdfe_display_params* p);
+int rgbdfe_display_geometry(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, const rgbdfe_display_params* params, float* vertices, int64_t vertex_capacity, int64_t* n_vertices, int64_t* node_offsets, int64_t* strips, int64_t strip_capacity, int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types);
+int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, const rgbdfe_display_params* params, void* d_vertices, int64_t vertex_capacity, int64_t* n_vertices, int64_t* node_offsets, void* d_strips, int64_t strip_capacity, int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, void* stream);
 // api_pose_graph.hip
 int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2);
 int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* errors, double* weights, int32_t edge_capacity, int32_t* n_edges, int32_t* free_ids, double* h_diag, double* b, int32_t vertex_capacity, int32_t* n_free, int32_t* off_rows, int32_t* off_cols, double* h_off, int32_t block_capacity, int32_t* n_blocks, double* chi2);

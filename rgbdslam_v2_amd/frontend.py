@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import DEFAULT_HAMMING_MODE, RESULT_DTYPE, RgbdfeConfig, RgbdfeError, RgbdfeParams
+from ._lib import DISPLAY_POINTS, DISPLAY_TRIANGLES, DISPLAY_TRIANGLE_STRIP  # noqa: F401
 
 
 @dataclass
@@ -1164,6 +1165,67 @@ class FrontEnd:
             self._ctx, n, node_ids.ctypes.data, T.ctypes.data, float(maximum_depth), int(bool(preserve_raster)),
             out.data_ptr() if out.shape[0] else None, int(out.shape[0]), C.byref(n_out), offsets.ctypes.data, stream))
         return (n_out.value, offsets) if return_offsets else n_out.value
+
+    def _display_args(self, node_ids, transforms, display_type, visualization_skip_step, squared_meshing_threshold,
+                      maximum_depth):
+        node_ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        T = None
+        if transforms is not None:
+            node_ids, T = self._map_args(node_ids, transforms)
+        prm = _lib.RgbdfeDisplayParams(int(display_type), int(visualization_skip_step), float(squared_meshing_threshold),
+                                       float(maximum_depth))
+        return node_ids, T, prm
+
+    def display_geometry(self, node_ids, transforms=None, display_type=DISPLAY_POINTS, visualization_skip_step=1,
+                         squared_meshing_threshold=0.0009, maximum_depth=float("inf")):
+        """GLViewer::addPointCloud (glviewer.cpp:693-711) over the resident clouds of node_ids, in that order: the
+        glVertex3f calls of pointCloud2GLPoints / pointCloud2GLTriangleList / pointCloud2GLStrip as rows (x, y, z, rgb
+        bits).  transforms: n x 4 x 4 as assemble_map takes them, or None for the node frame.  The sizes are counted first
+        and the buffers sized to them.  Returns a dict: vertices [n, 4] float32, node_offsets [n_nodes + 1] int64, strips
+        [m, 2] int64 (first vertex in the whole stream, vertex count; one per glBegin(GL_TRIANGLE_STRIP)),
+        node_strip_offsets [n_nodes + 1] int64, node_types [n_nodes] int32 (the form each node was drawn in)."""
+        node_ids, T, prm = self._display_args(node_ids, transforms, display_type, visualization_skip_step,
+                                              squared_meshing_threshold, maximum_depth)
+        n = len(node_ids)
+        nv, ns = C.c_int64(0), C.c_int64(0)
+        off, soff, types = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(n, np.int32)
+
+        def call(v, s):
+            return self._L.rgbdfe_display_geometry(
+                self._ctx, n, node_ids.ctypes.data, T.ctypes.data if T is not None else None, C.byref(prm),
+                v.ctypes.data if v is not None and len(v) else None, len(v) if v is not None else 0, C.byref(nv),
+                off.ctypes.data, s.ctypes.data if s is not None and len(s) else None, len(s) if s is not None else 0,
+                C.byref(ns), soff.ctypes.data, types.ctypes.data)
+        st = call(None, None)  # the sizes: RGBDFE_ERR_CAPACITY with both set, or OK for an empty stream
+        if st != -5:
+            self._check(st)
+        v, s = np.empty((nv.value, 4), np.float32), np.empty((ns.value, 2), np.int64)
+        if st == -5:
+            self._check(call(v, s))
+        return dict(vertices=v, node_offsets=off, strips=s, node_strip_offsets=soff, node_types=types)
+
+    def display_geometry_device(self, node_ids, vertices, strips, transforms=None, display_type=DISPLAY_POINTS,
+                                visualization_skip_step=1, squared_meshing_threshold=0.0009, maximum_depth=float("inf"),
+                                stream=None):
+        """display_geometry into `vertices`, a contiguous float32 torch tensor [capacity, 4], and `strips`, a contiguous
+        int64 torch tensor [capacity, 2], on this context's device; no vertex crosses to the host.  Returns a dict:
+        n_vertices, n_strips, node_offsets, node_strip_offsets, node_types.  A buffer that is too small raises
+        RgbdfeError (RGBDFE_ERR_CAPACITY)."""
+        node_ids, T, prm = self._display_args(node_ids, transforms, display_type, visualization_skip_step,
+                                              squared_meshing_threshold, maximum_depth)
+        for t, cols, size, name in ((vertices, 4, 4, "vertices"), (strips, 2, 8, "strips")):
+            if not (t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == cols and t.element_size() == size):
+                raise ValueError("%s must be a contiguous [capacity, %d] tensor of %d-byte elements on the device" %
+                                 (name, cols, size))
+        n = len(node_ids)
+        nv, ns = C.c_int64(0), C.c_int64(0)
+        off, soff, types = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64), np.zeros(n, np.int32)
+        self._check(self._L.rgbdfe_display_geometry_device(
+            self._ctx, n, node_ids.ctypes.data, T.ctypes.data if T is not None else None, C.byref(prm),
+            vertices.data_ptr() if vertices.shape[0] else None, int(vertices.shape[0]), C.byref(nv), off.ctypes.data,
+            strips.data_ptr() if strips.shape[0] else None, int(strips.shape[0]), C.byref(ns), soff.ctypes.data,
+            types.ctypes.data, stream))
+        return dict(n_vertices=nv.value, n_strips=ns.value, node_offsets=off, node_strip_offsets=soff, node_types=types)
 
     def voxel_filter(self, points, voxelfilter_size, return_flags=False):
         """pcl::VoxelGrid with a cubic leaf of voxelfilter_size (Node::reducePointCloud, node.cpp:1448-1460) over points,
