@@ -146,7 +146,7 @@ void rgbdfe_destroy(rgbdfe_ctx* ctx) {
   if (ctx->d_desc4) (void)hipFree(ctx->d_desc4);
   if (ctx->d_kp2d) (void)hipFree(ctx->d_kp2d);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-  if (ctx->d_icp) (void)hipFree(ctx->d_icp);
+  if (ctx->icp.p) (void)hipFree(ctx->icp.p);
   for (hipEvent_t e : ctx->orb_upload_done) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->orb_describe_done) if (e) (void)hipEventDestroy(e);
   if (ctx->orb_upload_stream) (void)hipStreamDestroy(ctx->orb_upload_stream);

@@ -577,13 +577,14 @@ struct DetectFrame {
     const bool min_depth = ctx->feature_min_depth;
     if (min_depth && !kps.empty()) {
       const int n0 = (int)kps.size();
-      const size_t b_depth = ((size_t)rows * cols * 4 + 255) & ~(size_t)255;
-      const size_t b_kp = ((size_t)n0 * 12 + 255) & ~(size_t)255;
-      rc = ensure_scratch(ctx, b_depth + b_kp + (size_t)n0 * 4 + 256);
+      DeviceLayout lay;
+      const Block b_depth = lay.room((size_t)rows * cols * 4), b_kp = lay.room((size_t)n0 * 12), b_z = lay.room((size_t)n0 * 4);
+      lay.room(256);
+      rc = ensure_scratch(ctx, lay.total());
       if (rc != RGBDFE_OK) return rc;
-      float* d_depth = sensor ? ctx->sensor.d_depth[depth_set] : (float*)ctx->d_scratch;
-      float* d_kps3 = (float*)((char*)ctx->d_scratch + b_depth);
-      float* d_z = (float*)((char*)ctx->d_scratch + b_depth + b_kp);
+      float* d_depth = sensor ? ctx->sensor.d_depth[depth_set] : at<float>(ctx->d_scratch, b_depth);
+      float* d_kps3 = at<float>(ctx->d_scratch, b_kp);
+      float* d_z = at<float>(ctx->d_scratch, b_z);
       std::vector<float> h3((size_t)n0 * 3);
       for (int i = 0; i < n0; ++i) { h3[3 * i] = kps[i].x; h3[3 * i + 1] = kps[i].y; h3[3 * i + 2] = kps[i].size; }
       zmin.resize((size_t)n0);

@@ -9,11 +9,6 @@ namespace impl {
 
 namespace {
 
-struct DeviceBuffer {  // the host entry point's staging: as large as one call's output, not kept
-  void* p = nullptr;
-  ~DeviceBuffer() { if (p) (void)hipFree(p); }
-};
-
 // GLViewer::addPointCloud (glviewer.cpp:693-711) for every listed node.  Exactly one of the host / device pairs receives
 // the output.
 int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
@@ -38,10 +33,9 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
   int64_t tiles = 0, rows = 0;
   bool have_items = false, have_rows = false;
   for (size_t k = 0; k < n; ++k) {
-    auto it = ctx->clouds.find(node_ids[k]);
-    if (it == ctx->clouds.end() || !it->second.d)
-      return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "display geometry: no cloud for a listed node");
-    const CloudEntry& ce = it->second;
+    const CloudEntry* found = resident_cloud(ctx, node_ids[k]);
+    if (!found) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "display geometry: no cloud for a listed node");
+    const CloudEntry& ce = *found;
     const int64_t w = ce.cw, h = ce.ch;
     if (w * h > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: a cloud of more than 2^31 points");
     DispNode& m = table[k];
@@ -67,13 +61,7 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
     m.n_items = (uint32_t)items;
     m.first_tile = (uint32_t)tiles;
     if (items > 0) (m.type == RGBDFE_DISPLAY_TRIANGLE_STRIP ? have_rows : have_items) = true;
-    if (transforms) {
-      const float* T = transforms + k * 16;  // column-major Matrix4f
-      for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) m.R[r * 3 + c] = T[c * 4 + r];
-        m.t[r] = T[12 + r];
-      }
-    }
+    if (transforms) rigid_of_matrix4f(transforms + k * 16, m.R, m.t);
     tiles += (items + tile - 1) / tile;
     if (tiles > (int64_t)INT32_MAX || rows > (int64_t)INT32_MAX)
       return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: more than 2^31 tiles in one call");
@@ -92,13 +80,8 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
   end.first_tile = (uint32_t)tiles;
   end.first_row = (uint32_t)rows;
   const size_t n_tiles = (size_t)tiles;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_table = up(sizeof(DispNode) * (n + 1)), b_map = up(4 * n_tiles);
-  std::vector<uint8_t> blob(b_table + b_map);
-  memcpy(blob.data(), table.data(), sizeof(DispNode) * (n + 1));
-  uint32_t* tile_node = reinterpret_cast<uint32_t*>(blob.data() + b_table);
-  for (size_t k = 0; k < n; ++k)
-    for (uint32_t t = table[k].first_tile; t < table[k + 1].first_tile; ++t) tile_node[t] = (uint32_t)k;
+  DeviceLayout lay;
+  const NodeTableBlocks b_nodes_in = put_node_table(lay, table);
 
   DispParams prm;
   prm.mesh_thresh = (float)params->squared_meshing_threshold;  // `const float mesh_thresh` (:784, :997)
@@ -107,18 +90,18 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
 
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  const size_t b_count = up(8 * n_tiles), b_rows = up(8 * (size_t)rows), b_first = up(16 * (n_tiles + 1)),
-               b_nodes = up(16 * (n + 1));
-  int rc = ensure_scratch(ctx, b_table + b_map + b_count + b_rows + b_first + b_nodes);
+  const Block b_count = lay.room(8 * n_tiles), b_rows = lay.room(8 * (size_t)rows), b_first = lay.room(16 * (n_tiles + 1)),
+              b_nodes = lay.room(16 * (n + 1));
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* base = (char*)ctx->d_scratch;
-  const DispNode* d_table = (const DispNode*)base;
-  const uint32_t* d_tile_node = (const uint32_t*)(base + b_table);
-  uint2* d_count = (uint2*)(base + b_table + b_map);
-  uint2* d_rows = (uint2*)(base + b_table + b_map + b_count);
-  int64_t* d_first = (int64_t*)(base + b_table + b_map + b_count + b_rows);
-  int64_t* d_node_first = (int64_t*)(base + b_table + b_map + b_count + b_rows + b_first);
-  HIP_TRY(ctx, hipMemcpyAsync(base, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  void* base = ctx->d_scratch;
+  const DispNode* d_table = at<DispNode>(base, b_nodes_in.table);
+  const uint32_t* d_tile_node = at<uint32_t>(base, b_nodes_in.tile_node);
+  uint2* d_count = at<uint2>(base, b_count);
+  uint2* d_rows = at<uint2>(base, b_rows);
+  int64_t* d_first = at<int64_t>(base, b_first);
+  int64_t* d_node_first = at<int64_t>(base, b_nodes);
+  HIP_TRY(ctx, hipMemcpyAsync(base, lay.staged(), lay.staged_bytes(), hipMemcpyHostToDevice, st));
 
   launch_display_count_scan(d_table, d_tile_node, (uint32_t)n, (uint32_t)n_tiles, prm, have_items, have_rows, d_count, d_rows,
                             d_first, d_node_first, st);
@@ -136,24 +119,16 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
   if (vertex_capacity < total_v || strip_capacity < total_s)
     return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: a buffer is too small (*n_vertices rows and *n_strips records are needed)");
   if (total_v == 0) return RGBDFE_OK;  // no vertex, so no strip either
-  DeviceBuffer stage_v, stage_s;
-  float4* d_v = (float4*)d_vertices;
-  int64_t* d_s = (int64_t*)d_strips;
-  if (!to_device) {
-    if (hipMalloc(&stage_v.p, (size_t)total_v * sizeof(float4)) != hipSuccess ||
-        (total_s > 0 && hipMalloc(&stage_s.p, (size_t)total_s * 16) != hipSuccess)) {
-      (void)hipGetLastError();
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "display geometry: staging allocation failed");
-    }
-    d_v = (float4*)stage_v.p;
-    d_s = (int64_t*)stage_s.p;
-  }
-  launch_display_write(d_table, d_tile_node, (uint32_t)n_tiles, prm, have_items, have_rows, d_rows, d_first, d_v, d_s, st);
+  OutputSink sink_v(to_device ? d_vertices : nullptr), sink_s(to_device ? d_strips : nullptr);
+  const char* no_staging = "display geometry: staging allocation failed";
+  rc = sink_v.ready(ctx, (size_t)total_v * sizeof(float4), no_staging);
+  if (rc == RGBDFE_OK && total_s > 0) rc = sink_s.ready(ctx, (size_t)total_s * 16, no_staging);
+  if (rc != RGBDFE_OK) return rc;
+  launch_display_write(d_table, d_tile_node, (uint32_t)n_tiles, prm, have_items, have_rows, d_rows, d_first, (float4*)sink_v.d,
+                       (int64_t*)sink_s.d, st);
   HIP_TRY(ctx, hipGetLastError());
-  if (!to_device) {
-    HIP_TRY(ctx, hipMemcpyAsync(h_vertices, d_v, (size_t)total_v * sizeof(float4), hipMemcpyDeviceToHost, st));
-    if (total_s > 0) HIP_TRY(ctx, hipMemcpyAsync(h_strips, d_s, (size_t)total_s * 16, hipMemcpyDeviceToHost, st));
-  }
+  HIP_TRY(ctx, sink_v.finish(h_vertices, st));
+  if (total_s > 0) HIP_TRY(ctx, sink_s.finish(h_strips, st));
   // the table in the context's scratch is this call's: it returns when the stream has passed it
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return RGBDFE_OK;

@@ -112,11 +112,13 @@ int rgbdfe_place_recognition_batch(rgbdfe_ctx* ctx, const int32_t* query_ids, in
   seg[(size_t)n_queries] = (uint32_t)total;
   std::vector<uint32_t> votes((size_t)total, 0u);
   if (max_nq > 0 && max_nt > 0) {
-    const size_t b_votes = ((size_t)total * 4 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, b_votes + ((size_t)n_queries + 1) * 4 + 256);
+    DeviceLayout lay;
+    const Block b_votes = lay.room((size_t)total * 4), b_seg = lay.room(((size_t)n_queries + 1) * 4);
+    lay.room(256);
+    int rc = ensure_scratch(ctx, lay.total());
     if (rc != RGBDFE_OK) return rc;
-    uint32_t* d_votes = (uint32_t*)ctx->d_scratch;
-    uint32_t* d_seg = (uint32_t*)((char*)ctx->d_scratch + b_votes);
+    uint32_t* d_votes = at<uint32_t>(ctx->d_scratch, b_votes);
+    uint32_t* d_seg = at<uint32_t>(ctx->d_scratch, b_seg);
     HIP_TRY(ctx, hipMemcpyAsync(slot.d_work, slot.h_work, sizeof(PairWork) * (size_t)total, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_seg, seg.data(), ((size_t)n_queries + 1) * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(d_votes, 0, (size_t)total * 4, st));
@@ -175,6 +177,21 @@ int rgbdfe_hamming_nn_host(rgbdfe_ctx* ctx, const uint8_t* qdesc, int32_t nq, co
   return rc;
 }
 
+// what a projection launch left in the scratch: the count first, then (if any) the kept indices and their points
+static int kept_to_host(rgbdfe_ctx* ctx, const int32_t* d_n, const int32_t* d_idx, const float4* d_xyz, int32_t* kept_idx,
+                        float* xyz1, int32_t* n_out) {
+  int32_t n = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (n > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(kept_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(xyz1, d_xyz, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *n_out = n;
+  return RGBDFE_OK;
+}
+
 int rgbdfe_project_to_3d(rgbdfe_ctx* ctx, const float* kp_xy, int32_t n_kp, const float* depth,
                          int32_t rows, int32_t cols, double fx, double fy, double cx, double cy,
                          double depth_scaling, int32_t max_keypoints, int32_t* kept_idx,
@@ -186,34 +203,24 @@ int rgbdfe_project_to_3d(rgbdfe_ctx* ctx, const float* kp_xy, int32_t n_kp, cons
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   *n_out = 0;
   if (n_kp == 0 || max_keypoints == 0) return RGBDFE_OK;
-  const size_t b_kp = ((size_t)n_kp * 8 + 255) & ~(size_t)255;
-  const size_t b_depth = ((size_t)rows * cols * 4 + 255) & ~(size_t)255;
-  const size_t b_idx = ((size_t)n_kp * 4 + 255) & ~(size_t)255;
-  const size_t b_xyz = ((size_t)n_kp * 16 + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, b_kp + b_depth + b_idx + b_xyz + 256);
+  DeviceLayout lay;
+  const Block b_kp = lay.room((size_t)n_kp * 8), b_depth = lay.room((size_t)rows * cols * 4), b_idx = lay.room((size_t)n_kp * 4),
+              b_xyz = lay.room((size_t)n_kp * 16), b_n = lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* base = (char*)ctx->d_scratch;
-  float* d_kp = (float*)base;
-  float* d_depth = (float*)(base + b_kp);
-  int32_t* d_idx = (int32_t*)(base + b_kp + b_depth);
-  float4* d_xyz = (float4*)(base + b_kp + b_depth + b_idx);
-  int32_t* d_n = (int32_t*)(base + b_kp + b_depth + b_idx + b_xyz);
+  void* base = ctx->d_scratch;
+  float* d_kp = at<float>(base, b_kp);
+  float* d_depth = at<float>(base, b_depth);
+  int32_t* d_idx = at<int32_t>(base, b_idx);
+  float4* d_xyz = at<float4>(base, b_xyz);
+  int32_t* d_n = at<int32_t>(base, b_n);
   HIP_TRY(ctx, hipMemcpyAsync(d_kp, kp_xy, (size_t)n_kp * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_depth, depth, (size_t)rows * cols * 4, hipMemcpyHostToDevice, ctx->stream));
   // node.cpp:913-916: fxinv = float(1./fx) etc.
   launch_project_to_3d(d_kp, n_kp, d_depth, rows, cols, (float)(1. / fx), (float)(1. / fy), (float)cx,
                        (float)cy, depth_scaling, max_keypoints, d_idx, d_xyz, d_n, ctx->stream);
   HIP_TRY(ctx, hipGetLastError());
-  int32_t n = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (n > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(kept_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(xyz1, d_xyz, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  *n_out = n;
-  return RGBDFE_OK;
+  return kept_to_host(ctx, d_n, d_idx, d_xyz, kept_idx, xyz1, n_out);
 }
 
 int rgbdfe_set_feature_min_depth(rgbdfe_ctx* ctx, int32_t on) {
@@ -236,20 +243,20 @@ int rgbdfe_project_to_3d_min_depth(rgbdfe_ctx* ctx, const float* kp_xy, const fl
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   *n_out = 0;
   if (n_kp == 0 || max_keypoints == 0) return RGBDFE_OK;
-  const size_t b_kp = ((size_t)n_kp * 12 + 255) & ~(size_t)255;   // (x, y, size) for the neighbourhood kernel
-  const size_t b_xyz_in = ((size_t)n_kp * 12 + 255) & ~(size_t)255;  // x, y pairs followed by the n depths
-  const size_t b_depth = ((size_t)rows * cols * 4 + 255) & ~(size_t)255;
-  const size_t b_idx = ((size_t)n_kp * 4 + 255) & ~(size_t)255;
-  const size_t b_xyz = ((size_t)n_kp * 16 + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, b_kp + b_xyz_in + b_depth + b_idx + b_xyz + 256);
+  DeviceLayout lay;
+  const Block b_kp = lay.room((size_t)n_kp * 12);      // (x, y, size) for the neighbourhood kernel
+  const Block b_xyz_in = lay.room((size_t)n_kp * 12);  // x, y pairs followed by the n depths
+  const Block b_depth = lay.room((size_t)rows * cols * 4), b_idx = lay.room((size_t)n_kp * 4), b_xyz = lay.room((size_t)n_kp * 16),
+              b_n = lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* base = (char*)ctx->d_scratch;
-  float* d_kp3 = (float*)base;
-  float* d_in = (float*)(base + b_kp);
-  float* d_depth = (float*)(base + b_kp + b_xyz_in);
-  int32_t* d_idx = (int32_t*)(base + b_kp + b_xyz_in + b_depth);
-  float4* d_xyz = (float4*)(base + b_kp + b_xyz_in + b_depth + b_idx);
-  int32_t* d_n = (int32_t*)(base + b_kp + b_xyz_in + b_depth + b_idx + b_xyz);
+  void* base = ctx->d_scratch;
+  float* d_kp3 = at<float>(base, b_kp);
+  float* d_in = at<float>(base, b_xyz_in);
+  float* d_depth = at<float>(base, b_depth);
+  int32_t* d_idx = at<int32_t>(base, b_idx);
+  float4* d_xyz = at<float4>(base, b_xyz);
+  int32_t* d_n = at<int32_t>(base, b_n);
   std::vector<float> h3((size_t)n_kp * 3);
   for (int32_t i = 0; i < n_kp; ++i) { h3[3 * i] = kp_xy[2 * i]; h3[3 * i + 1] = kp_xy[2 * i + 1]; h3[3 * i + 2] = kp_size[i]; }
   HIP_TRY(ctx, hipMemcpyAsync(d_kp3, h3.data(), h3.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -260,16 +267,7 @@ int rgbdfe_project_to_3d_min_depth(rgbdfe_ctx* ctx, const float* kp_xy, const fl
   launch_project_to_3d(d_in, n_kp, nullptr, rows, cols, (float)(1. / fx), (float)(1. / fy), (float)cx, (float)cy,
                        depth_scaling, max_keypoints, d_idx, d_xyz, d_n, ctx->stream, false, d_in + (size_t)2 * n_kp);
   HIP_TRY(ctx, hipGetLastError());
-  int32_t n = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (n > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(kept_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(xyz1, d_xyz, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  *n_out = n;
-  return RGBDFE_OK;
+  return kept_to_host(ctx, d_n, d_idx, d_xyz, kept_idx, xyz1, n_out);
 }
 
 // Node::projectTo3D, point-cloud overload (node.cpp:855-898).  The organised cloud stays on the host: the point under
@@ -280,17 +278,17 @@ static int project_cloud_common(rgbdfe_ctx* ctx, const float* kp_xy, int32_t n_k
                                 int32_t* n_out) {
   *n_out = 0;
   if (n_kp == 0 || max_keypoints == 0) return RGBDFE_OK;
-  const size_t b_kp = ((size_t)n_kp * 8 + 255) & ~(size_t)255;
-  const size_t b_pts = ((size_t)n_kp * 16 + 255) & ~(size_t)255;
-  const size_t b_idx = ((size_t)n_kp * 4 + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, b_kp + 2 * b_pts + b_idx + 256);
+  DeviceLayout lay;
+  const Block b_kp = lay.room((size_t)n_kp * 8), b_pts = lay.room((size_t)n_kp * 16), b_idx = lay.room((size_t)n_kp * 4),
+              b_xyz = lay.room((size_t)n_kp * 16), b_n = lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* base = (char*)ctx->d_scratch;
-  float* d_kp = (float*)base;
-  float4* d_pts = (float4*)(base + b_kp);
-  int32_t* d_idx = (int32_t*)(base + b_kp + b_pts);
-  float4* d_xyz = (float4*)(base + b_kp + b_pts + b_idx);
-  int32_t* d_n = (int32_t*)(base + b_kp + 2 * b_pts + b_idx);
+  void* base = ctx->d_scratch;
+  float* d_kp = at<float>(base, b_kp);
+  float4* d_pts = at<float4>(base, b_pts);
+  int32_t* d_idx = at<int32_t>(base, b_idx);
+  float4* d_xyz = at<float4>(base, b_xyz);
+  int32_t* d_n = at<int32_t>(base, b_n);
   std::vector<float> pts((size_t)n_kp * 4, 0.f);
   for (int32_t i = 0; i < n_kp; ++i) {
     const float x = kp_xy[2 * i], y = kp_xy[2 * i + 1];
@@ -301,16 +299,7 @@ static int project_cloud_common(rgbdfe_ctx* ctx, const float* kp_xy, int32_t n_k
   HIP_TRY(ctx, hipMemcpyAsync(d_pts, pts.data(), (size_t)n_kp * 16, hipMemcpyHostToDevice, ctx->stream));
   launch_project_cloud(d_kp, n_kp, d_pts, true, rows, cols, maximum_depth, max_keypoints, d_idx, d_xyz, d_n, ctx->stream);
   HIP_TRY(ctx, hipGetLastError());
-  int32_t n = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&n, d_n, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (n > 0) {
-    HIP_TRY(ctx, hipMemcpyAsync(kept_idx, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(xyz1, d_xyz, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  *n_out = n;
-  return RGBDFE_OK;
+  return kept_to_host(ctx, d_n, d_idx, d_xyz, kept_idx, xyz1, n_out);
 }
 
 int rgbdfe_project_to_3d_cloud(rgbdfe_ctx* ctx, const float* kp_xy, int32_t n_kp, const float* cloud, int32_t rows,
@@ -396,24 +385,25 @@ int rgbdfe_sift_node_features(rgbdfe_ctx* ctx, const float* kp_xy, const float* 
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   *n_out = 0;
   if (n_kp == 0 || max_keypoints == 0) return RGBDFE_OK;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const int cap = n_kp < max_keypoints ? n_kp : max_keypoints;
-  const size_t b_kp = up((size_t)n_kp * 8), b_depth = up((size_t)rows * cols * 4), b_idx = up((size_t)n_kp * 4);
-  const size_t b_xyz = up((size_t)n_kp * 16), b_in = up((size_t)n_kp * 512), b_out = up((size_t)cap * 512);
-  const size_t b_kp3 = kp_size ? up((size_t)n_kp * 12) : 0, b_z = kp_size ? up((size_t)n_kp * 4) : 0;
-  int rc = ensure_scratch(ctx, b_kp + b_depth + b_idx + b_xyz + b_in + 2 * b_out + b_kp3 + b_z + 256);
+  DeviceLayout lay;
+  const Block b_kp3 = lay.room(kp_size ? (size_t)n_kp * 12 : 0), b_z = lay.room(kp_size ? (size_t)n_kp * 4 : 0);
+  const Block b_kp = lay.room((size_t)n_kp * 8), b_depth = lay.room((size_t)rows * cols * 4), b_idx = lay.room((size_t)n_kp * 4);
+  const Block b_xyz = lay.room((size_t)n_kp * 16), b_in = lay.room((size_t)n_kp * 512), b_raw = lay.room((size_t)cap * 512),
+              b_feat = lay.room((size_t)cap * 512), b_n = lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* p = (char*)ctx->d_scratch;
-  float* d_kp3 = (float*)p;         p += b_kp3;
-  float* d_z = (float*)p;           p += b_z;
-  float* d_kp = (float*)p;          p += b_kp;
-  float* d_depth = (float*)p;       p += b_depth;
-  int32_t* d_idx = (int32_t*)p;     p += b_idx;
-  float4* d_xyz = (float4*)p;       p += b_xyz;
-  float* d_in = (float*)p;          p += b_in;
-  float* d_raw = (float*)p;         p += b_out;
-  float* d_feat = (float*)p;        p += b_out;
-  int32_t* d_n = (int32_t*)p;
+  void* base = ctx->d_scratch;
+  float* d_kp3 = at<float>(base, b_kp3);
+  float* d_z = at<float>(base, b_z);
+  float* d_kp = at<float>(base, b_kp);
+  float* d_depth = at<float>(base, b_depth);
+  int32_t* d_idx = at<int32_t>(base, b_idx);
+  float4* d_xyz = at<float4>(base, b_xyz);
+  float* d_in = at<float>(base, b_in);
+  float* d_raw = at<float>(base, b_raw);
+  float* d_feat = at<float>(base, b_feat);
+  int32_t* d_n = at<int32_t>(base, b_n);
   HIP_TRY(ctx, hipMemcpyAsync(d_kp, kp_xy, (size_t)n_kp * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_depth, depth, (size_t)rows * cols * 4, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_in, desc_in, (size_t)n_kp * 512, hipMemcpyHostToDevice, ctx->stream));
@@ -451,14 +441,14 @@ int rgbdfe_depth_to_mono8(rgbdfe_ctx* ctx, const void* depth, int32_t depth_is_u
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   const size_t n = (size_t)rows * (size_t)cols;
-  const size_t b_in = ((n * (depth_is_u16 ? 2 : 4)) + 255) & ~(size_t)255;
-  const size_t b_m8 = (n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, b_in + b_m8 + n * 4 + 256);
+  DeviceLayout lay;
+  const Block b_in = lay.room(n * (depth_is_u16 ? 2 : 4)), b_m8 = lay.room(n), b_f = lay.room(n * 4);
+  lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* p = (char*)ctx->d_scratch;
-  void* d_in = p;
-  uint8_t* d_m8 = (uint8_t*)(p + b_in);
-  float* d_f = (float*)(p + b_in + b_m8);
+  void* d_in = at<void>(ctx->d_scratch, b_in);
+  uint8_t* d_m8 = at<uint8_t>(ctx->d_scratch, b_m8);
+  float* d_f = at<float>(ctx->d_scratch, b_f);
   HIP_TRY(ctx, hipMemcpyAsync(d_in, depth, n * (depth_is_u16 ? 2 : 4), hipMemcpyHostToDevice, ctx->stream));
   if (depth_is_u16) launch_depth_u16((const uint16_t*)d_in, n, d_m8, d_f, ctx->stream);
   else launch_depth_to_mono8_f32((const float*)d_in, n, d_m8, ctx->stream);
@@ -481,12 +471,13 @@ int rgbdfe_upload_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* dept
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   const int ch = rows / cloud_skip, cw = cols / cloud_skip;
   const size_t n = (size_t)rows * (size_t)cols;
-  const size_t b_depth = (n * 4 + 255) & ~(size_t)255;
-  const size_t b_rgb = rgb ? ((n * (size_t)rgb_channels + 255) & ~(size_t)255) : 0;
-  int rc = ensure_scratch(ctx, b_depth + b_rgb + 256);
+  DeviceLayout lay;
+  const Block b_depth = lay.room(n * 4), b_rgb = lay.room(rgb ? n * (size_t)rgb_channels : 0);
+  lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  float* d_depth = (float*)ctx->d_scratch;
-  uint8_t* d_rgb = rgb ? (uint8_t*)ctx->d_scratch + b_depth : nullptr;
+  float* d_depth = at<float>(ctx->d_scratch, b_depth);
+  uint8_t* d_rgb = rgb ? at<uint8_t>(ctx->d_scratch, b_rgb) : nullptr;
   CloudEntry& ce = ctx->clouds[node_id];
   if (ce.d && (ce.ch != ch || ce.cw != cw)) {
     if (const int rc_ = wait_for_pair_lanes(ctx)) return rc_;
@@ -579,11 +570,13 @@ int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new
     for (int32_t i = 0; i < n; ++i) { out[i].inliers = out[i].all = 1; out[i].outliers = out[i].occluded = 0; }
     return RGBDFE_OK;
   }
-  const size_t b_jobs = (sizeof(EmmJob) * (size_t)n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, b_jobs + (size_t)n * 16 + 256);
+  DeviceLayout lay;
+  const Block b_jobs = lay.room(sizeof(EmmJob) * (size_t)n), b_counts = lay.room((size_t)n * 16);
+  lay.room(256);
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  EmmJob* d_jobs = (EmmJob*)ctx->d_scratch;
-  uint32_t* d_counts = (uint32_t*)((char*)ctx->d_scratch + b_jobs);
+  EmmJob* d_jobs = at<EmmJob>(ctx->d_scratch, b_jobs);
+  uint32_t* d_counts = at<uint32_t>(ctx->d_scratch, b_counts);
   HIP_TRY(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(EmmJob) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   // cdf(x, mu, sigma) = 0.5 * (1 + erf((x - mu) / (sigma * SQRT_2))), sigma = sqrt(old_sigma + new_sigma),
   // both = cloud_creation_skip_step * depth_covariance() (misc.cpp:809-812, 914-922; a18: frozen value)

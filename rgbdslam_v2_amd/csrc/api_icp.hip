@@ -25,20 +25,7 @@ struct JobRef {
   float G[16];
 };
 
-size_t up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int ensure_icp(rgbdfe_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->icp_bytes) return RGBDFE_OK;
-  if (ctx->d_icp) (void)hipFree(ctx->d_icp);
-  ctx->d_icp = nullptr;
-  ctx->icp_bytes = 0;
-  if (hipMalloc(&ctx->d_icp, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "icp: device allocation failed");
-  }
-  ctx->icp_bytes = bytes;
-  return RGBDFE_OK;
-}
+int ensure_icp(rgbdfe_ctx* ctx, size_t bytes) { return ctx->icp.ensure(ctx, bytes, "icp: device allocation failed"); }
 
 // the events of a profiled chunk: back in the context's pool when the chunk ends, however it ends
 struct ChunkEvents {
@@ -101,28 +88,29 @@ struct IcpCall {
       if (!clouds[c].d) host_rows += clouds[c].n;
       max_tiles = std::max(max_tiles, t);
     }
-    const size_t o_table = 0, o_count = o_table + up(sizeof(IcpCloud) * nc), o_first = o_count + up(4 * tiles),
-                 o_nvalid = o_first + up(4 * tiles), o_host = o_nvalid + up(4 * nc), total = o_host + up(16 * host_rows);
-    int rc = ensure_scratch(ctx, total);
+    DeviceLayout lay;
+    const Block o_table = lay.room(sizeof(IcpCloud) * nc), o_count = lay.room(4 * tiles), o_first = lay.room(4 * tiles),
+                o_nvalid = lay.room(4 * nc), o_host = lay.room(16 * host_rows);
+    int rc = ensure_scratch(ctx, lay.total());
     if (rc != RGBDFE_OK) return rc;
-    char* base = (char*)ctx->d_scratch;
+    void* base = ctx->d_scratch;
     size_t at_host = 0, h = 0;
     for (size_t c = 0; c < nc; ++c) {
       if (clouds[c].d) {
         table[c].d = clouds[c].d;
       } else {
-        float4* d = (float4*)(base + o_host) + at_host;
+        float4* d = at<float4>(base, o_host) + at_host;
         table[c].d = d;
         if (clouds[c].n) HIP_TRY(ctx, hipMemcpyAsync(d, host_clouds[h], 16 * (size_t)clouds[c].n, hipMemcpyHostToDevice, st));
         at_host += clouds[c].n;
         ++h;
       }
     }
-    d_table = (IcpCloud*)(base + o_table);
+    d_table = at<IcpCloud>(base, o_table);
     HIP_TRY(ctx, hipMemcpyAsync(d_table, table.data(), sizeof(IcpCloud) * nc, hipMemcpyHostToDevice, st));
-    uint32_t* d_nvalid = (uint32_t*)(base + o_nvalid);
-    d_tile_first = (uint32_t*)(base + o_first);
-    launches += launch_icp_compact(d_table, (uint32_t)nc, max_tiles, (uint32_t*)(base + o_count), d_tile_first, d_nvalid, st);
+    uint32_t* d_nvalid = at<uint32_t>(base, o_nvalid);
+    d_tile_first = at<uint32_t>(base, o_first);
+    launches += launch_icp_compact(d_table, (uint32_t)nc, max_tiles, at<uint32_t>(base, o_count), d_tile_first, d_nvalid, st);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<uint32_t> n_valid(nc);
     HIP_TRY(ctx, hipMemcpyAsync(n_valid.data(), d_nvalid, 4 * nc, hipMemcpyDeviceToHost, st));
@@ -144,20 +132,21 @@ struct IcpCall {
     *n_out = (int64_t)ns;
     if ((int64_t)ns > capacity) return fail(ctx, RGBDFE_ERR_CAPACITY, "filter_cloud: the outputs are too small (*n_out rows are needed)");
     if (ns == 0) return RGBDFE_OK;
-    const size_t o_pos = 0, o_rows = o_pos + up(4 * ns), o_idx = o_rows + up(16 * ns), total = o_idx + up(4 * ns);
-    rc = ensure_icp(ctx, total);
+    DeviceLayout lay;
+    const Block o_pos = lay.room(4 * ns), o_rows = lay.room(16 * ns), o_idx = lay.room(4 * ns);
+    rc = ensure_icp(ctx, lay.total());
     if (rc != RGBDFE_OK) return rc;
-    char* base = (char*)ctx->d_icp;
-    table[0].pos = (const uint32_t*)(base + o_pos);
-    table[0].samples = (float4*)(base + o_rows);
-    table[0].sample_index = (uint32_t*)(base + o_idx);
+    void* base = ctx->icp.p;
+    table[0].pos = at<uint32_t>(base, o_pos);
+    table[0].samples = at<float4>(base, o_rows);
+    table[0].sample_index = at<uint32_t>(base, o_idx);
     table[0].poison = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_pos, pos[0].data(), 4 * ns, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(at<uint32_t>(base, o_pos), pos[0].data(), 4 * ns, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_table, table.data(), sizeof(IcpCloud), hipMemcpyHostToDevice, st));
     launches += launch_icp_gather(d_table, 1, (uint32_t)ns, d_tile_first, st);
     HIP_TRY(ctx, hipGetLastError());
-    if (rows_out) HIP_TRY(ctx, hipMemcpyAsync(rows_out, base + o_rows, 16 * ns, hipMemcpyDeviceToHost, st));
-    if (indices_out) HIP_TRY(ctx, hipMemcpyAsync(indices_out, base + o_idx, 4 * ns, hipMemcpyDeviceToHost, st));
+    if (rows_out) HIP_TRY(ctx, hipMemcpyAsync(rows_out, table[0].samples, 16 * ns, hipMemcpyDeviceToHost, st));
+    if (indices_out) HIP_TRY(ctx, hipMemcpyAsync(indices_out, table[0].sample_index, 4 * ns, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     ++readbacks;
     return RGBDFE_OK;
@@ -171,15 +160,9 @@ struct IcpCall {
     if ((nn_index_out || nn_d2_out) && (int64_t)pos[(size_t)jobs[0].source].size() > debug_capacity)
       return fail(ctx, RGBDFE_ERR_CAPACITY, "icp: debug_capacity is below the sampled source count");
     // phase 2: the uploaded part first (positions, jobs, records: one copy), then the working arrays
-    std::vector<char> stage;
-    auto put = [&](const void* src, size_t bytes) {
-      const size_t at = stage.size();
-      stage.resize(at + up(bytes), 0);
-      if (bytes) memcpy(stage.data() + at, src, bytes);
-      return at;
-    };
-    std::vector<size_t> o_pos(nc), o_samples(nc);
-    for (size_t c = 0; c < nc; ++c) o_pos[c] = put(pos[c].data(), 4 * pos[c].size());
+    DeviceLayout lay;
+    std::vector<Block> o_pos(nc), o_samples(nc);
+    for (size_t c = 0; c < nc; ++c) o_pos[c] = lay.put(pos[c].data(), 4 * pos[c].size());
     std::vector<IcpJob> job_h(nj);
     std::vector<IcpRecord> rec_h(2 * nj);
     memset(rec_h.data(), 0, sizeof(IcpRecord) * rec_h.size());
@@ -187,11 +170,7 @@ struct IcpCall {
     for (size_t j = 0; j < nj; ++j) {
       IcpJob& jb = job_h[j];
       memset(&jb, 0, sizeof(jb));
-      const float* G = jobs[j].G;
-      for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) jb.GR[r * 3 + c] = G[c * 4 + r];
-        jb.Gt[r] = G[12 + r];
-      }
+      rigid_of_matrix4f(jobs[j].G, jb.GR, jb.Gt);
       jb.ns = (int32_t)pos[(size_t)jobs[j].source].size();
       jb.nt = (int32_t)pos[(size_t)jobs[j].target].size();
       max_ns = std::max(max_ns, (uint32_t)jb.ns);
@@ -203,41 +182,40 @@ struct IcpCall {
       }
       for (int a = 0; a < 3; ++a) r0.Ft[a] = jb.Gt[a];
     }
-    const size_t o_jobs = put(job_h.data(), sizeof(IcpJob) * nj), o_rec = put(rec_h.data(), sizeof(IcpRecord) * 2 * nj);
-    size_t total = stage.size();
-    auto room = [&](size_t bytes) { const size_t at = total; total += up(bytes); return at; };
+    const Block o_jobs = lay.put(job_h.data(), sizeof(IcpJob) * nj), o_rec = lay.put(rec_h.data(), sizeof(IcpRecord) * 2 * nj);
     for (size_t c = 0; c < nc; ++c) {
-      o_samples[c] = room(16 * pos[c].size());
+      o_samples[c] = lay.room(16 * pos[c].size());
       max_samples = std::max(max_samples, (uint32_t)pos[c].size());
     }
-    std::vector<size_t> o_P(nj), o_nnj(nj), o_nnd(nj), o_part(nj);
+    std::vector<Block> o_P(nj), o_nnj(nj), o_nnd(nj), o_part(nj);
     for (size_t j = 0; j < nj; ++j) {
       const size_t ns = (size_t)job_h[j].ns, leaves = (ns + kIcpLeaf - 1) / kIcpLeaf;
-      o_P[j] = room(16 * ns);
-      o_nnj[j] = room(4 * ns);
-      o_nnd[j] = room(4 * ns);
-      o_part[j] = room(8 * (size_t)kIcpSums * leaves);
+      o_P[j] = lay.room(16 * ns);
+      o_nnj[j] = lay.room(4 * ns);
+      o_nnd[j] = lay.room(4 * ns);
+      o_part[j] = lay.room(8 * (size_t)kIcpSums * leaves);
     }
-    rc = ensure_icp(ctx, total);
+    rc = ensure_icp(ctx, lay.total());
     if (rc != RGBDFE_OK) return rc;
-    char* base = (char*)ctx->d_icp;
+    void* base = ctx->icp.p;
     for (size_t c = 0; c < nc; ++c) {
-      table[c].pos = (const uint32_t*)(base + o_pos[c]);
-      table[c].samples = (float4*)(base + o_samples[c]);
+      table[c].pos = at<uint32_t>(base, o_pos[c]);
+      table[c].samples = at<float4>(base, o_samples[c]);
       table[c].sample_index = nullptr;
       table[c].poison = 1;
     }
-    IcpJob* jp = reinterpret_cast<IcpJob*>(stage.data() + o_jobs);
+    IcpRecord* d_rec = at<IcpRecord>(base, o_rec);
+    IcpJob* jp = lay.staged<IcpJob>(o_jobs);
     for (size_t j = 0; j < nj; ++j) {
       jp[j].S = table[(size_t)jobs[j].source].samples;
       jp[j].T = table[(size_t)jobs[j].target].samples;
-      jp[j].P = (float4*)(base + o_P[j]);
-      jp[j].nn_j = (int32_t*)(base + o_nnj[j]);
-      jp[j].nn_d2 = (float*)(base + o_nnd[j]);
-      jp[j].part = (double*)(base + o_part[j]);
-      jp[j].rec = (IcpRecord*)(base + o_rec) + 2 * j;
+      jp[j].P = at<float4>(base, o_P[j]);
+      jp[j].nn_j = at<int32_t>(base, o_nnj[j]);
+      jp[j].nn_d2 = at<float>(base, o_nnd[j]);
+      jp[j].part = at<double>(base, o_part[j]);
+      jp[j].rec = d_rec + 2 * j;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(base, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(base, lay.staged(), lay.staged_bytes(), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_table, table.data(), sizeof(IcpCloud) * nc, hipMemcpyHostToDevice, st));
     launches += launch_icp_gather(d_table, (uint32_t)nc, max_samples, d_tile_first, st);
     HIP_TRY(ctx, hipGetLastError());
@@ -247,7 +225,7 @@ struct IcpCall {
     stop.transformation_epsilon = prm.transformation_epsilon;
     stop.euclidean_fitness_epsilon = prm.euclidean_fitness_epsilon;
     stop.max_iterations = prm.max_iterations;
-    const IcpJob* d_jobs = (const IcpJob*)(base + o_jobs);
+    const IcpJob* d_jobs = at<IcpJob>(base, o_jobs);
     int32_t next = 1, chunk = kIcpFirstChunk;
     for (;;) {
       const int32_t count = std::min(chunk, prm.max_iterations - next + 1);
@@ -267,7 +245,7 @@ struct IcpCall {
       }
       next += count;
       HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipMemcpyAsync(rec_h.data(), base + o_rec, sizeof(IcpRecord) * 2 * nj, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipMemcpyAsync(rec_h.data(), d_rec, sizeof(IcpRecord) * 2 * nj, hipMemcpyDeviceToHost, st));
       HIP_TRY(ctx, hipStreamSynchronize(st));  // (the first one also covers the staging vector's copy)
       ++readbacks;
       for (size_t e = 0; e + 1 < ev.size(); e += 2) {
@@ -286,8 +264,8 @@ struct IcpCall {
     }
     if (nn_index_out || nn_d2_out) {
       const size_t ns = (size_t)job_h[0].ns;
-      if (ns && nn_index_out) HIP_TRY(ctx, hipMemcpyAsync(nn_index_out, base + o_nnj[0], 4 * ns, hipMemcpyDeviceToHost, st));
-      if (ns && nn_d2_out) HIP_TRY(ctx, hipMemcpyAsync(nn_d2_out, base + o_nnd[0], 4 * ns, hipMemcpyDeviceToHost, st));
+      if (ns && nn_index_out) HIP_TRY(ctx, hipMemcpyAsync(nn_index_out, at<int32_t>(base, o_nnj[0]), 4 * ns, hipMemcpyDeviceToHost, st));
+      if (ns && nn_d2_out) HIP_TRY(ctx, hipMemcpyAsync(nn_d2_out, at<float>(base, o_nnd[0]), 4 * ns, hipMemcpyDeviceToHost, st));
       HIP_TRY(ctx, hipStreamSynchronize(st));
       ++readbacks;
     }
@@ -354,13 +332,13 @@ int rgbdfe_icp_align_nodes(rgbdfe_ctx* ctx, int32_t n_jobs, const int32_t* sourc
   auto cloud_index = [&](int32_t id, int* out) -> int {
     auto at = cloud_of.find(id);
     if (at != cloud_of.end()) { *out = at->second; return RGBDFE_OK; }
-    auto it = ctx->clouds.find(id);
-    if (it == ctx->clouds.end() || !it->second.d) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "icp: no cloud for a listed node");
-    const int64_t n = (int64_t)it->second.ch * (int64_t)it->second.cw;
+    const CloudEntry* ce = resident_cloud(ctx, id);
+    if (!ce) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "icp: no cloud for a listed node");
+    const int64_t n = (int64_t)ce->ch * (int64_t)ce->cw;
     if (n > kIcpMaxRows) return fail(ctx, RGBDFE_ERR_CAPACITY, "icp: a cloud of more than 2^24 rows");
     *out = (int)call.clouds.size();
     cloud_of[id] = *out;
-    call.clouds.push_back(CloudRef{it->second.d, (uint32_t)n});
+    call.clouds.push_back(CloudRef{ce->d, (uint32_t)n});
     return RGBDFE_OK;
   };
   call.jobs.resize((size_t)n_jobs);

@@ -7,11 +7,6 @@ namespace impl {
 
 namespace {
 
-struct DeviceBuffer {  // the host entry point's staging for the assembled points: as large as one call's output, not kept
-  void* p = nullptr;
-  ~DeviceBuffer() { if (p) (void)hipFree(p); }
-};
-
 // GraphManager::saveAllCloudsToFile's loop (graph_mgr_io.cpp:529-552).  Exactly one of h_out / d_out receives the points.
 int assemble_map_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth,
                         int32_t preserve_raster, float* h_out, void* d_out, bool to_device, int64_t capacity, int64_t* n_out,
@@ -30,19 +25,14 @@ int assemble_map_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
   std::vector<MapNode> table(n + 1);
   int64_t points = 0, tiles = 0;
   for (size_t k = 0; k < n; ++k) {
-    auto it = ctx->clouds.find(node_ids[k]);
-    if (it == ctx->clouds.end() || !it->second.d) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "map assembly: no cloud for a listed node");
-    const CloudEntry& ce = it->second;
+    const CloudEntry* ce = resident_cloud(ctx, node_ids[k]);
+    if (!ce) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "map assembly: no cloud for a listed node");
     MapNode& m = table[k];
-    m.cloud = ce.d;
+    m.cloud = ce->d;
     m.first_point = points;
-    m.n_points = (uint32_t)((size_t)ce.ch * (size_t)ce.cw);
+    m.n_points = (uint32_t)((size_t)ce->ch * (size_t)ce->cw);
     m.first_tile = (uint32_t)tiles;
-    const float* T = transforms + k * 16;  // column-major Matrix4f
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) m.R[r * 3 + c] = T[c * 4 + r];
-      m.t[r] = T[12 + r];
-    }
+    rigid_of_matrix4f(transforms + k * 16, m.R, m.t);
     points += (int64_t)m.n_points;
     tiles += (int64_t)((m.n_points + kMapTile - 1) / kMapTile);
     if (tiles > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "map assembly: more than 2^31 tiles in one call");
@@ -52,13 +42,8 @@ int assemble_map_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
   end.first_point = points;
   end.first_tile = (uint32_t)tiles;
   const size_t n_tiles = (size_t)tiles;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_table = up(sizeof(MapNode) * (n + 1)), b_map = up(4 * n_tiles);
-  std::vector<uint8_t> blob(b_table + b_map);
-  memcpy(blob.data(), table.data(), sizeof(MapNode) * (n + 1));
-  uint32_t* tile_node = reinterpret_cast<uint32_t*>(blob.data() + b_table);
-  for (size_t k = 0; k < n; ++k)
-    for (uint32_t t = table[k].first_tile; t < table[k + 1].first_tile; ++t) tile_node[t] = (uint32_t)k;
+  DeviceLayout lay;
+  const NodeTableBlocks b_nodes_in = put_node_table(lay, table);
 
   const bool compact = preserve_raster == 0;
   const float md = (float)maximum_depth;  // `float max_Depth` (misc.cpp:185)
@@ -73,16 +58,16 @@ int assemble_map_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
 
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  const size_t b_count = up(4 * n_tiles), b_first = up(8 * (n_tiles + 1)), b_nodes = up(8 * (n + 1));
-  int rc = ensure_scratch(ctx, b_table + b_map + b_count + b_first + b_nodes);
+  const Block b_count = lay.room(4 * n_tiles), b_first = lay.room(8 * (n_tiles + 1)), b_nodes = lay.room(8 * (n + 1));
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* base = (char*)ctx->d_scratch;
-  const MapNode* d_table = (const MapNode*)base;
-  const uint32_t* d_tile_node = (const uint32_t*)(base + b_table);
-  uint32_t* d_count = (uint32_t*)(base + b_table + b_map);
-  int64_t* d_first = (int64_t*)(base + b_table + b_map + b_count);
-  int64_t* d_node_first = (int64_t*)(base + b_table + b_map + b_count + b_first);
-  HIP_TRY(ctx, hipMemcpyAsync(base, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  void* base = ctx->d_scratch;
+  const MapNode* d_table = at<MapNode>(base, b_nodes_in.table);
+  const uint32_t* d_tile_node = at<uint32_t>(base, b_nodes_in.tile_node);
+  uint32_t* d_count = at<uint32_t>(base, b_count);
+  int64_t* d_first = at<int64_t>(base, b_first);
+  int64_t* d_node_first = at<int64_t>(base, b_nodes);
+  HIP_TRY(ctx, hipMemcpyAsync(base, lay.staged(), lay.staged_bytes(), hipMemcpyHostToDevice, st));
 
   int64_t total = points;
   if (compact) {
@@ -97,24 +82,18 @@ int assemble_map_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_id
     if (capacity < total) return fail(ctx, RGBDFE_ERR_CAPACITY, "map assembly: `out` is too small (*n_out rows are needed)");
   }
   if (total == 0) {
-    HIP_TRY(ctx, hipStreamSynchronize(st));  // (the table's copy reads `blob`)
+    HIP_TRY(ctx, hipStreamSynchronize(st));  // (the table's copy reads the layout's staging)
     return RGBDFE_OK;
   }
-  DeviceBuffer stage;
-  float4* d_points = (float4*)d_out;
-  if (!to_device) {
-    if (hipMalloc(&stage.p, (size_t)total * sizeof(float4)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "map assembly: staging allocation failed");
-    }
-    d_points = (float4*)stage.p;
-  }
+  OutputSink sink(to_device ? d_out : nullptr);
+  rc = sink.ready(ctx, (size_t)total * sizeof(float4), "map assembly: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  float4* d_points = (float4*)sink.d;
   if (compact) launch_map_write(d_table, d_tile_node, (uint32_t)n_tiles, d_first, clip, md2, d_points, st);
   else launch_map_raster(d_table, d_tile_node, (uint32_t)n_tiles, clip, md2, d_points, st);
   HIP_TRY(ctx, hipGetLastError());
-  if (!to_device)
-    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_points, (size_t)total * sizeof(float4), hipMemcpyDeviceToHost, st));
-  // the table in the context's scratch and `blob` are this call's: it returns when the stream has passed them
+  HIP_TRY(ctx, sink.finish(h_out, st));
+  // the table in the context's scratch and the layout's staging are this call's: it returns when the stream has passed them
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return RGBDFE_OK;
 }
@@ -139,9 +118,9 @@ int rgbdfe_download_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, float* cloud_ou
   if (!ctx || capacity_points < 0 || (capacity_points > 0 && !cloud_out))
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   std::lock_guard<std::mutex> g(ctx->mu);
-  auto it = ctx->clouds.find(node_id);
-  if (it == ctx->clouds.end() || !it->second.d) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "no cloud for this node");
-  const CloudEntry& ce = it->second;
+  const CloudEntry* found = resident_cloud(ctx, node_id);
+  if (!found) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "no cloud for this node");
+  const CloudEntry& ce = *found;
   if (rows) *rows = ce.ch;
   if (cols) *cols = ce.cw;
   const size_t n = (size_t)ce.ch * (size_t)ce.cw;

@@ -18,8 +18,7 @@ struct rgbdfe_octomap {
   int64_t n_leaves = 0;
   int64_t launches = 0;         // kernel launches of the last insert call (tools/bench_octomap.py)
   // the tree calls' workspace (octomap_tree.hip): one allocation, grown when a call needs more, freed with the map
-  void* tree_ws = nullptr;
-  size_t tree_ws_bytes = 0;
+  GrowBuffer tree_ws;
   int64_t tree_launches = 0;    // kernel launches of the last tree / depth / write call (tools/bench_octomap_tree.py)
 };
 
@@ -27,32 +26,33 @@ namespace impl {
 
 namespace {
 
-struct DeviceBuffer {  // staging that lives for one call
-  void* p = nullptr;
-  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+// a table of `cap` slots in its one allocation: the keys, values and colours (cleared to 0xff bytes), then the marks (to 0)
+struct TableLayout {
+  DeviceLayout lay;
+  Block key, value, colour, mark;
+  explicit TableLayout(uint32_t cap)
+      : key(lay.room(8 * (size_t)cap)), value(lay.room(4 * (size_t)cap)), colour(lay.room(4 * (size_t)cap)),
+        mark(lay.room(4 * (size_t)cap)) {}
+  hipError_t clear(void* blob, hipStream_t st) const {
+    const hipError_t e = hipMemsetAsync(blob, 0xff, mark.off, st);
+    return e != hipSuccess ? e : hipMemsetAsync(at<uint32_t>(blob, mark), 0, lay.total() - mark.off, st);
+  }
 };
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // a table of `cap` free slots
 int alloc_table(rgbdfe_ctx* ctx, uint32_t cap, OctoTable* tb, void** blob, hipStream_t st) {
-  const size_t b_key = up256(8 * (size_t)cap), b_f = up256(4 * (size_t)cap);
-  char* p = nullptr;
-  if (hipMalloc((void**)&p, b_key + 3 * b_f) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: table allocation failed");
-  }
-  tb->key = (unsigned long long*)p;
-  tb->value = (float*)(p + b_key);
-  tb->colour = (uint32_t*)(p + b_key + b_f);
-  tb->mark = (uint32_t*)(p + b_key + 2 * b_f);
+  const TableLayout tl(cap);
+  DeviceBuffer buf;
+  const int rc = buf.alloc(ctx, tl.lay.total(), "octomap: table allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  if (tl.clear(buf.p, st) != hipSuccess) return fail(ctx, RGBDFE_ERR_HIP, "octomap: clearing the table failed");
+  tb->key = at<unsigned long long>(buf.p, tl.key);
+  tb->value = at<float>(buf.p, tl.value);
+  tb->colour = at<uint32_t>(buf.p, tl.colour);
+  tb->mark = at<uint32_t>(buf.p, tl.mark);
   tb->cap = cap;
-  *blob = p;
-  if (hipMemsetAsync(p, 0xff, b_key + 2 * b_f, st) != hipSuccess || hipMemsetAsync(tb->mark, 0, b_f, st) != hipSuccess) {
-    (void)hipFree(p);
-    *blob = nullptr;
-    return fail(ctx, RGBDFE_ERR_HIP, "octomap: clearing the table failed");
-  }
+  *blob = buf.p;
+  buf.p = nullptr;  // the table is the caller's now
   return RGBDFE_OK;
 }
 
@@ -88,6 +88,17 @@ int rehouse(rgbdfe_octomap* map, uint32_t cap) {
 
 struct CloudRef { const float4* d; uint32_t n; };
 
+// the sort's buffers of an OctoScratch / a TreeScratch
+template <class Scratch>
+void fill_sort_pointers(void* base, const SortWorkspace& w, Scratch* s) {
+  for (int i = 0; i < 2; ++i) {
+    s->keys[i] = at<uint32_t>(base, w.keys[i]);
+    s->idx[i] = at<uint32_t>(base, w.idx[i]);
+  }
+  s->hist = at<uint32_t>(base, w.hist);
+  s->digits = at<uint32_t>(base, w.digits);
+}
+
 // the clouds one after another; ctx->mu is held and the device is set
 int insert_clouds(rgbdfe_octomap* map, const std::vector<CloudRef>& clouds, const float* transforms, double max_range,
                   int32_t* n_done) {
@@ -95,22 +106,19 @@ int insert_clouds(rgbdfe_octomap* map, const std::vector<CloudRef>& clouds, cons
   hipStream_t st = ctx->stream;
   uint32_t n_max = 0;
   for (const CloudRef& c : clouds) n_max = std::max(n_max, c.n);
-  const size_t n = n_max, n_tiles = (n + kVoxTile - 1) / kVoxTile, n_sort_tiles = (n + kVoxSortTile - 1) / kVoxSortTile;
-  const size_t b_hdr = 256, b_count = up256(4 * n_tiles), b_first = up256(4 * (n_tiles + 1)), b_pairs = up256(4 * n),
-               b_hist = up256(4 * 256 * n_sort_tiles), b_digits = 1024, b_cells = up256(4 * (n + 1));
-  int rc = ensure_scratch(ctx, b_hdr + b_count + b_first + 4 * b_pairs + b_hist + b_digits + b_cells);
+  const size_t n = n_max, n_tiles = (n + kVoxTile - 1) / kVoxTile;
+  DeviceLayout lay;
+  const Block b_hdr = lay.room(256), b_count = lay.room(4 * n_tiles), b_first = lay.room(4 * (n_tiles + 1));
+  const SortWorkspace b_sort = sort_workspace(lay, n);
+  const Block b_cells = lay.room(4 * (n + 1));
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* at = (char*)ctx->d_scratch;
-  auto take = [&at](size_t b) { char* p = at; at += b; return p; };
   OctoScratch s{};
-  s.hdr = (VoxHeader*)take(b_hdr);
-  s.tile_count = (uint32_t*)take(b_count);
-  s.tile_first = (uint32_t*)take(b_first);
-  s.keys[0] = (uint32_t*)take(b_pairs); s.keys[1] = (uint32_t*)take(b_pairs);
-  s.idx[0] = (uint32_t*)take(b_pairs); s.idx[1] = (uint32_t*)take(b_pairs);
-  s.hist = (uint32_t*)take(b_hist);
-  s.digits = (uint32_t*)take(b_digits);
-  s.cell_start = (uint32_t*)take(b_cells);
+  s.hdr = at<VoxHeader>(ctx->d_scratch, b_hdr);
+  s.tile_count = at<uint32_t>(ctx->d_scratch, b_count);
+  s.tile_first = at<uint32_t>(ctx->d_scratch, b_first);
+  s.cell_start = at<uint32_t>(ctx->d_scratch, b_cells);
+  fill_sort_pointers(ctx->d_scratch, b_sort, &s);
 
   // the colour rows are sorted by slot, `cap` standing for "no leaf": the passes that cover 0 .. cap
   int bits = 1;
@@ -137,11 +145,7 @@ int insert_clouds(rgbdfe_octomap* map, const std::vector<CloudRef>& clouds, cons
       map->epoch = 0;
     }
     oc.epoch = ++map->epoch;
-    const float* T = transforms + k * 16;  // column-major Matrix4f
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) oc.R[r * 3 + c] = T[c * 4 + r];
-      oc.t[r] = T[12 + r];
-    }
+    rigid_of_matrix4f(transforms + k * 16, oc.R, oc.t);
     launch_octo_cloud(map->tb, map->d_ctl, clouds[k].d, clouds[k].n, oc, passes, s, st);
     map->launches += clouds[k].n == 0 ? 1 : 7 + 3 * passes;
   }
@@ -217,7 +221,7 @@ void rgbdfe_octomap_destroy(rgbdfe_octomap* map) {
     (void)hipStreamSynchronize(map->ctx->stream);
     if (map->blob) (void)hipFree(map->blob);
     if (map->d_ctl) (void)hipFree(map->d_ctl);
-    if (map->tree_ws) (void)hipFree(map->tree_ws);
+    if (map->tree_ws.p) (void)hipFree(map->tree_ws.p);
   }
   delete map;
 }
@@ -225,9 +229,7 @@ void rgbdfe_octomap_destroy(rgbdfe_octomap* map) {
 // no leaves, the same table; ctx->mu is held and the device is set
 static int clear_map(rgbdfe_octomap* map) {
   rgbdfe_ctx* ctx = map->ctx;
-  const size_t b_key = up256(8 * (size_t)map->tb.cap), b_f = up256(4 * (size_t)map->tb.cap);
-  HIP_TRY(ctx, hipMemsetAsync(map->blob, 0xff, b_key + 2 * b_f, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(map->tb.mark, 0, b_f, ctx->stream));
+  HIP_TRY(ctx, TableLayout(map->tb.cap).clear(map->blob, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   map->epoch = 0;
   map->n_leaves = 0;
@@ -261,10 +263,10 @@ int rgbdfe_octomap_insert_nodes(rgbdfe_octomap* map, int32_t n_nodes, const int3
   if (n_nodes == 0) return RGBDFE_OK;
   std::vector<CloudRef> clouds((size_t)n_nodes);
   for (size_t k = 0; k < clouds.size(); ++k) {
-    auto it = ctx->clouds.find(node_ids[k]);
-    if (it == ctx->clouds.end() || !it->second.d) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "octomap: no cloud for a listed node");
-    clouds[k].d = it->second.d;
-    clouds[k].n = (uint32_t)((size_t)it->second.ch * (size_t)it->second.cw);
+    const CloudEntry* ce = resident_cloud(ctx, node_ids[k]);
+    if (!ce) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "octomap: no cloud for a listed node");
+    clouds[k].d = ce->d;
+    clouds[k].n = (uint32_t)((size_t)ce->ch * (size_t)ce->cw);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   return insert_clouds(map, clouds, transforms, max_range, n_done);
@@ -279,10 +281,8 @@ int rgbdfe_octomap_insert_cloud(rgbdfe_octomap* map, const float* points, int64_
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   DeviceBuffer stage;
   if (n > 0) {
-    if (hipMalloc(&stage.p, (size_t)n * sizeof(float4)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
-    }
+    const int rc = stage.alloc(ctx, (size_t)n * sizeof(float4), "octomap: staging allocation failed");
+    if (rc != RGBDFE_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(stage.p, points, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
   }
   std::vector<CloudRef> clouds(1);
@@ -352,40 +352,33 @@ int tree_workspace(rgbdfe_octomap* map, TreeScratch* t) {
   const size_t n = (size_t)map->n_leaves, cap = map->tb.cap;
   if (17 * (uint64_t)n > (uint64_t)UINT32_MAX)
     return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: the tree of this map may have 2^32 nodes or more");
-  const size_t tiles = (std::max(n, cap) + kTreeTile - 1) / kTreeTile, sort_tiles = (n + kVoxSortTile - 1) / kVoxSortTile;
-  const size_t b_hdr = 256, b8 = up256(8 * n), b4 = up256(4 * n), b_hist = up256(4 * 256 * sort_tiles), b_digits = 1024,
-               b_count = up256(4 * tiles), b_first = up256(4 * (tiles + 1));
-  const size_t bytes = b_hdr + 2 * b8 + 13 * b4 + b_hist + b_digits + b_count + b_first;
-  if (bytes > map->tree_ws_bytes) {
-    if (map->tree_ws) (void)hipFree(map->tree_ws);
-    map->tree_ws = nullptr;
-    map->tree_ws_bytes = 0;
-    if (hipMalloc(&map->tree_ws, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      map->tree_ws = nullptr;
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: tree workspace allocation failed");
-    }
-    map->tree_ws_bytes = bytes;
-  }
-  char* at = (char*)map->tree_ws;
-  auto take = [&at](size_t b) { char* p = at; at += b; return p; };
-  t->hdr = (TreeHdr*)take(b_hdr);
-  t->code = (unsigned long long*)take(b8);
-  t->scode = (unsigned long long*)take(b8);
-  t->slot = (uint32_t*)take(b4);
-  t->keys[0] = (uint32_t*)take(b4); t->keys[1] = (uint32_t*)take(b4);
-  t->idx[0] = (uint32_t*)take(b4); t->idx[1] = (uint32_t*)take(b4);
-  t->top = (uint32_t*)take(b4);
-  t->off = (uint32_t*)take(b4);
+  const size_t tiles = (std::max(n, cap) + kTreeTile - 1) / kTreeTile;
+  // (the sort's histogram and digit totals sit behind its pairs, in front of top / off / the levels)
+  DeviceLayout lay;
+  const Block b_hdr = lay.room(256), b_code = lay.room(8 * n), b_scode = lay.room(8 * n), b_slot = lay.room(4 * n);
+  const SortWorkspace b_sort = sort_workspace(lay, n);
+  const Block b_top = lay.room(4 * n), b_off = lay.room(4 * n);
+  Block b_level[2][3];
+  for (auto& level : b_level)
+    for (Block& b : level) b = lay.room(4 * n);
+  const Block b_count = lay.room(4 * tiles), b_first = lay.room(4 * (tiles + 1));
+  const int rc = map->tree_ws.ensure(ctx, lay.total(), "octomap: tree workspace allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  void* base = map->tree_ws.p;
+  t->hdr = at<TreeHdr>(base, b_hdr);
+  t->code = at<unsigned long long>(base, b_code);
+  t->scode = at<unsigned long long>(base, b_scode);
+  t->slot = at<uint32_t>(base, b_slot);
+  fill_sort_pointers(base, b_sort, t);
+  t->top = at<uint32_t>(base, b_top);
+  t->off = at<uint32_t>(base, b_off);
   for (int l = 0; l < 2; ++l) {
-    t->level[l].value = (float*)take(b4);
-    t->level[l].colour = (uint32_t*)take(b4);
-    t->level[l].first = (uint32_t*)take(b4);
+    t->level[l].value = at<float>(base, b_level[l][0]);
+    t->level[l].colour = at<uint32_t>(base, b_level[l][1]);
+    t->level[l].first = at<uint32_t>(base, b_level[l][2]);
   }
-  t->hist = (uint32_t*)take(b_hist);
-  t->digits = (uint32_t*)take(b_digits);
-  t->tile_count = (uint32_t*)take(b_count);
-  t->tile_first = (uint32_t*)take(b_first);
+  t->tile_count = at<uint32_t>(base, b_count);
+  t->tile_first = at<uint32_t>(base, b_first);
   return RGBDFE_OK;
 }
 
@@ -420,19 +413,12 @@ int tree_common(rgbdfe_octomap* map, rgbdfe_octomap_node* h_out, void* d_out, bo
   } else if (capacity < total) {
     return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: `out` is too small (*n_nodes records are needed)");
   }
-  DeviceBuffer stage;
-  void* d_rec = d_out;
-  if (!to_device) {
-    if (hipMalloc(&stage.p, (size_t)total * sizeof(rgbdfe_octomap_node)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
-    }
-    d_rec = stage.p;
-  }
-  launches += launch_tree_levels(n, 0u, t, d_rec, st);
+  OutputSink sink(to_device ? d_out : nullptr);
+  rc = sink.ready(ctx, (size_t)total * sizeof(rgbdfe_octomap_node), "octomap: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  launches += launch_tree_levels(n, 0u, t, sink.d, st);
   HIP_TRY(ctx, hipGetLastError());
-  if (!to_device)
-    HIP_TRY(ctx, hipMemcpyAsync(h_out, d_rec, (size_t)total * sizeof(rgbdfe_octomap_node), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, sink.finish(h_out, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   map->tree_launches = launches;
   return RGBDFE_OK;
@@ -463,19 +449,19 @@ int set_leaves_locked(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, in
     in[i].value = l.log_odds;
     in[i].colour = ((uint32_t)l.rgb[0] << 16) | ((uint32_t)l.rgb[1] << 8) | (uint32_t)l.rgb[2];
   }
+  DeviceLayout lay;
+  const Block b_in = lay.room(in.size() * sizeof(OctoLeafIn)), b_dup = lay.room(256);
   DeviceBuffer stage;
-  const size_t b_in = up256(in.size() * sizeof(OctoLeafIn));
-  if (hipMalloc(&stage.p, b_in + 256) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
-  }
-  uint32_t* d_dup = (uint32_t*)((char*)stage.p + b_in);
+  rc = stage.alloc(ctx, lay.total(), "octomap: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  OctoLeafIn* d_in = at<OctoLeafIn>(stage.p, b_in);
+  uint32_t* d_dup = at<uint32_t>(stage.p, b_dup);
   OctoCtl ctl{};
   uint32_t dup = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(stage.p, in.data(), in.size() * sizeof(OctoLeafIn), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in, in.data(), b_in.bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemsetAsync(d_dup, 0, 4, st));
   HIP_TRY(ctx, hipMemcpyAsync(map->d_ctl, &ctl, sizeof(ctl), hipMemcpyHostToDevice, st));
-  launch_octo_set_leaves((const OctoLeafIn*)stage.p, (uint32_t)n, map->tb, map->d_ctl, d_dup, st);
+  launch_octo_set_leaves(d_in, (uint32_t)n, map->tb, map->d_ctl, d_dup, st);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(&ctl, map->d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(&dup, d_dup, 4, hipMemcpyDeviceToHost, st));
@@ -524,10 +510,8 @@ int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_
   // the nodes of a depth are at most min(leaves, 8^depth): the staging is sized before anything runs
   const uint64_t bound = depth >= 11 ? (uint64_t)n : std::min<uint64_t>(n, (uint64_t)1 << (3 * depth));
   DeviceBuffer stage;
-  if (hipMalloc(&stage.p, (size_t)bound * sizeof(rgbdfe_octomap_leaf)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "octomap: staging allocation failed");
-  }
+  rc = stage.alloc(ctx, (size_t)bound * sizeof(rgbdfe_octomap_leaf), "octomap: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
   HIP_TRY(ctx, hipMemsetAsync(t.hdr, 0, sizeof(TreeHdr), st));
   int launches = launch_tree_leaves(map->tb, n, t, st);
   launches += launch_tree_levels(n, (uint32_t)depth, t, nullptr, st);

@@ -124,31 +124,24 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
     csr(vb_list, &vb_ptr, &vb_items);
 
     // the layout: the uploaded part first (one copy), then the working arrays
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    std::vector<char> stage;
-    auto put = [&](const void* src, size_t bytes) {
-      const size_t at = stage.size();
-      stage.resize(at + up(bytes), 0);
-      if (bytes) memcpy(stage.data() + at, src, bytes);
-      return at;
-    };
-    const size_t o_est = put(est_h.data(), 8 * est_h.size()), o_free = put(free_of.data(), 4 * nv),
+    DeviceLayout lay;
+    auto put = [&lay](const void* src, size_t bytes) { return lay.put(src, bytes); };
+    auto room = [&lay](size_t bytes) { return lay.room(bytes); };
+    const Block o_est = put(est_h.data(), 8 * est_h.size()), o_free = put(free_of.data(), 4 * nv),
                  o_vert = put(vert_of.data(), 4 * nf), o_ij = put(edge_ij.data(), 4 * edge_ij.size()),
                  o_in = put(edge_in.data(), 8 * edge_in.size()), o_vp = put(vert_ptr.data(), 4 * vert_ptr.size()),
                  o_vi = put(vert_items.data(), 4 * vert_items.size()), o_bp = put(blk_ptr.data(), 4 * blk_ptr.size()),
                  o_bi = put(blk_items.data(), 4 * blk_items.size()), o_vbp = put(vb_ptr.data(), 4 * vb_ptr.size()),
                  o_vbi = put(vb_items.data(), 4 * vb_items.size()), o_rc = put(blk_rc.data(), 4 * blk_rc.size());
     PgScalars zero{};
-    const size_t o_s = put(&zero, sizeof(zero)), o_act = put(edge_active.data(), 4 * ne);
-    const std::vector<uint8_t> prune_zero(topo ? 4 + ne : 0, 0);
-    const size_t o_topo = put(topo ? topo->data() : nullptr, topo ? ne : 0), o_po = put(prune_zero.data(), prune_zero.size());
-    size_t total = stage.size();
-    auto room = [&](size_t bytes) { const size_t at = total; total += up(bytes); return at; };
+    const Block o_s = put(&zero, sizeof(zero)), o_act = put(edge_active.data(), 4 * ne);
+    const Block o_topo = put(topo ? topo->data() : nullptr, topo ? ne : 0), o_po = put(nullptr, topo ? 4 + ne : 0);
     const size_t leaves = std::max((ne + kPgTile - 1) / kPgTile, (nf + kPgTile - 1) / kPgTile) + 1;
-    const size_t o_est1 = room(8 * est_h.size()), o_out = room(8 * (size_t)kPgEdgeOut * ne), o_Hd = room(8 * 36 * nf),
+    const Block o_est1 = room(8 * est_h.size()), o_out = room(8 * (size_t)kPgEdgeOut * ne), o_Hd = room(8 * 36 * nf),
                  o_B = room(8 * 36 * nb), o_b = room(8 * 6 * nf), o_L = room(8 * 36 * nf), o_x = room(8 * 6 * nf),
                  o_r = room(8 * 6 * nf), o_z = room(8 * 6 * nf), o_p = room(8 * 6 * nf), o_q = room(8 * 6 * nf),
                  o_pa = room(8 * leaves), o_pb = room(8 * leaves);
+    const size_t total = lay.total();
 
     PgDevice* d = static_cast<PgDevice*>(g->device);
     if (!d) {
@@ -172,26 +165,28 @@ struct PgRun {  // one call's problem on the device; ctx->mu is held while it li
       }
       d->bytes = total;
     }
-    char* base = static_cast<char*>(d->blob);
-    HIP_TRY(ctx, hipMemcpyAsync(base, stage.data(), stage.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_est1, base + o_est, 8 * est_h.size(), hipMemcpyDeviceToDevice, st));
+    void* base = d->blob;
+    auto f64 = [base](Block b) { return at<double>(base, b); };
+    auto i32 = [base](Block b) { return at<int32_t>(base, b); };
+    est[0] = f64(o_est);
+    est[1] = f64(o_est1);
+    HIP_TRY(ctx, hipMemcpyAsync(base, lay.staged(), lay.staged_bytes(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(est[1], est[0], 8 * est_h.size(), hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));  // the staging vector goes out of scope; and the upload's share is timed
     P.n_vert = (int32_t)nv; P.n_free = (int32_t)nf; P.n_edge = (int32_t)ne; P.n_block = (int32_t)nb;
-    P.free_of = (const int32_t*)(base + o_free); P.vert_of = (const int32_t*)(base + o_vert);
-    P.edge_ij = (const int32_t*)(base + o_ij); P.edge_in = (const double*)(base + o_in);
-    P.edge_out = (double*)(base + o_out);
-    d_edge_in = (double*)(base + o_in); d_active = (int32_t*)(base + o_act); P.edge_active = d_active;
-    d_topo = (uint8_t*)(base + o_topo); d_prune_out = (int32_t*)(base + o_po);
-    P.vert_ptr = (const int32_t*)(base + o_vp); P.vert_items = (const int32_t*)(base + o_vi);
-    P.blk_ptr = (const int32_t*)(base + o_bp); P.blk_items = (const int32_t*)(base + o_bi);
-    P.vb_ptr = (const int32_t*)(base + o_vbp); P.vb_items = (const int32_t*)(base + o_vbi);
-    P.blk_rc = (const int32_t*)(base + o_rc);
-    P.Hd = (double*)(base + o_Hd); P.B = (double*)(base + o_B); P.b = (double*)(base + o_b); P.L = (double*)(base + o_L);
-    P.x = (double*)(base + o_x); P.r = (double*)(base + o_r); P.z = (double*)(base + o_z); P.p = (double*)(base + o_p);
-    P.q = (double*)(base + o_q); P.part_a = (double*)(base + o_pa); P.part_b = (double*)(base + o_pb);
-    P.s = (PgScalars*)(base + o_s);
-    est[0] = (double*)(base + o_est);
-    est[1] = (double*)(base + o_est1);
+    P.free_of = i32(o_free); P.vert_of = i32(o_vert);
+    P.edge_ij = i32(o_ij); P.edge_in = f64(o_in);
+    P.edge_out = f64(o_out);
+    d_edge_in = f64(o_in); d_active = i32(o_act); P.edge_active = d_active;
+    d_topo = at<uint8_t>(base, o_topo); d_prune_out = i32(o_po);
+    P.vert_ptr = i32(o_vp); P.vert_items = i32(o_vi);
+    P.blk_ptr = i32(o_bp); P.blk_items = i32(o_bi);
+    P.vb_ptr = i32(o_vbp); P.vb_items = i32(o_vbi);
+    P.blk_rc = i32(o_rc);
+    P.Hd = f64(o_Hd); P.B = f64(o_B); P.b = f64(o_b); P.L = f64(o_L);
+    P.x = f64(o_x); P.r = f64(o_r); P.z = f64(o_z); P.p = f64(o_p);
+    P.q = f64(o_q); P.part_a = f64(o_pa); P.part_b = f64(o_pb);
+    P.s = at<PgScalars>(base, o_s);
     upload_seconds = seconds_since(t0);
     return RGBDFE_OK;
   }

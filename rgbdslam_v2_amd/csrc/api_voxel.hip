@@ -7,11 +7,6 @@ namespace impl {
 
 namespace {
 
-struct DeviceBuffer {  // staging that lives for one call
-  void* p = nullptr;
-  ~DeviceBuffer() { if (p) (void)hipFree(p); }
-};
-
 // what the first half of a run leaves for the second
 struct VoxRun {
   bool too_small = false;  // the leaf is too small for the cloud's extent: the output is the input
@@ -32,23 +27,24 @@ int vox_count_cells(rgbdfe_ctx* ctx, const float4* d_in, int64_t n_in, float inv
   *run = VoxRun();
   if (n_in == 0) return RGBDFE_OK;
   const uint32_t n = (uint32_t)n_in;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t n_tiles = ((size_t)n + kVoxTile - 1) / kVoxTile, n_sort_tiles = ((size_t)n + kVoxSortTile - 1) / kVoxSortTile;
-  const size_t b_hdr = 256, b_box = up(24 * n_tiles), b_count = up(4 * n_tiles), b_first = up(4 * (n_tiles + 1)),
-               b_pairs = up(4 * (size_t)n), b_hist = up(4 * 256 * n_sort_tiles), b_digits = 1024, b_cells = up(4 * ((size_t)n + 1));
-  int rc = ensure_scratch(ctx, b_hdr + b_box + b_count + b_first + 4 * b_pairs + b_hist + b_digits + b_cells);
+  const size_t n_tiles = ((size_t)n + kVoxTile - 1) / kVoxTile;
+  DeviceLayout lay;
+  const Block b_hdr = lay.room(256), b_box = lay.room(24 * n_tiles), b_count = lay.room(4 * n_tiles),
+              b_first = lay.room(4 * (n_tiles + 1));
+  const SortWorkspace b_sort = sort_workspace(lay, n);
+  const Block b_cells = lay.room(4 * ((size_t)n + 1));
+  int rc = ensure_scratch(ctx, lay.total());
   if (rc != RGBDFE_OK) return rc;
-  char* at = (char*)ctx->d_scratch;
-  auto take = [&at](size_t b) { char* p = at; at += b; return p; };
-  VoxHeader* d_hdr = (VoxHeader*)take(b_hdr);
-  float* d_box = (float*)take(b_box);
-  uint32_t* d_count = (uint32_t*)take(b_count);
-  uint32_t* d_first = (uint32_t*)take(b_first);
-  uint32_t* d_keys[2] = {(uint32_t*)take(b_pairs), (uint32_t*)take(b_pairs)};
-  uint32_t* d_idx[2] = {(uint32_t*)take(b_pairs), (uint32_t*)take(b_pairs)};
-  uint32_t* d_hist = (uint32_t*)take(b_hist);
-  uint32_t* d_digits = (uint32_t*)take(b_digits);
-  uint32_t* d_cells = (uint32_t*)take(b_cells);
+  void* base = ctx->d_scratch;
+  VoxHeader* d_hdr = at<VoxHeader>(base, b_hdr);
+  float* d_box = at<float>(base, b_box);
+  uint32_t* d_count = at<uint32_t>(base, b_count);
+  uint32_t* d_first = at<uint32_t>(base, b_first);
+  uint32_t* d_keys[2] = {at<uint32_t>(base, b_sort.keys[0]), at<uint32_t>(base, b_sort.keys[1])};
+  uint32_t* d_idx[2] = {at<uint32_t>(base, b_sort.idx[0]), at<uint32_t>(base, b_sort.idx[1])};
+  uint32_t* d_hist = at<uint32_t>(base, b_sort.hist);
+  uint32_t* d_digits = at<uint32_t>(base, b_sort.digits);
+  uint32_t* d_cells = at<uint32_t>(base, b_cells);
 
   launch_vox_stats(d_in, n, d_box, d_count, d_first, d_hdr, st);
   HIP_TRY(ctx, hipGetLastError());
@@ -135,34 +131,28 @@ int voxel_filter_common(rgbdfe_ctx* ctx, const float* h_in, const void* d_in, in
   if (n_in == 0) return RGBDFE_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  DeviceBuffer in_stage, out_stage;
+  DeviceBuffer in_stage;
   const float4* d_points = (const float4*)d_in;
+  int rc = RGBDFE_OK;
   if (!device) {
-    if (hipMalloc(&in_stage.p, (size_t)n_in * sizeof(float4)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "voxel filter: staging allocation failed");
-    }
+    rc = in_stage.alloc(ctx, (size_t)n_in * sizeof(float4), "voxel filter: staging allocation failed");
+    if (rc != RGBDFE_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(in_stage.p, h_in, (size_t)n_in * sizeof(float4), hipMemcpyHostToDevice, st));
     d_points = (const float4*)in_stage.p;
   }
   VoxRun run;
-  int rc = vox_count_cells(ctx, d_points, n_in, inv, st, &run);
+  rc = vox_count_cells(ctx, d_points, n_in, inv, st, &run);
   if (rc != RGBDFE_OK) return rc;
   *n_out = run.rows;
   if (flags && run.too_small) *flags |= RGBDFE_VOXEL_LEAF_TOO_SMALL;
   if (capacity < run.rows) return fail(ctx, RGBDFE_ERR_CAPACITY, "voxel filter: `out` is too small (*n_out rows are needed)");
   if (run.rows == 0) return RGBDFE_OK;
-  float4* d_rows = (float4*)d_out;
-  if (!device) {
-    if (hipMalloc(&out_stage.p, (size_t)run.rows * sizeof(float4)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, "voxel filter: staging allocation failed");
-    }
-    d_rows = (float4*)out_stage.p;
-  }
-  rc = vox_emit(ctx, d_points, run, d_rows, nullptr, st);
+  OutputSink sink(device ? d_out : nullptr);
+  rc = sink.ready(ctx, (size_t)run.rows * sizeof(float4), "voxel filter: staging allocation failed");
   if (rc != RGBDFE_OK) return rc;
-  if (!device) HIP_TRY(ctx, hipMemcpyAsync(h_out, d_rows, (size_t)run.rows * sizeof(float4), hipMemcpyDeviceToHost, st));
+  rc = vox_emit(ctx, d_points, run, (float4*)sink.d, nullptr, st);
+  if (rc != RGBDFE_OK) return rc;
+  HIP_TRY(ctx, sink.finish(h_out, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));  // the scratch and the staging are this call's
   return RGBDFE_OK;
 }
@@ -188,9 +178,9 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
   std::lock_guard<std::mutex> g(ctx->mu);
   *n_out = 0;
   if (flags) *flags = 0;
-  auto it = ctx->clouds.find(node_id);
-  if (it == ctx->clouds.end() || !it->second.d) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "no cloud for this node");
-  CloudEntry& ce = it->second;
+  CloudEntry* found = resident_cloud(ctx, node_id);
+  if (!found) return fail(ctx, RGBDFE_ERR_UNKNOWN_NODE, "no cloud for this node");
+  CloudEntry& ce = *found;
   HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
   const int64_t n_in = (int64_t)ce.ch * (int64_t)ce.cw;
   VoxRun run;

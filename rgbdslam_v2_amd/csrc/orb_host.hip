@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "orb_host.h"
+#include "device_layout.h"
 
 #include <functional>
 #include <mutex>
@@ -248,7 +249,7 @@ int OrbWorkspace::prepare(int cols, int rows, bool use_grid, std::string& err, i
   ORB_HIP(hipMalloc((void**)&d_row_off, sizeof(int) * (row_off + 16)));
   ORB_HIP(hipMalloc((void**)&d_keep, sizeof(uint64_t) * (keep_words + 16)));
   // a pass's outputs in ONE buffer -- [per-image counts | keypoints] -- so that they come back in one copy
-  passout_hdr = (sizeof(int) * (cell_imgs.size() + 1) + 255) & ~(size_t)255;  // per-image counts + their sum
+  passout_hdr = rgbdfe_host::round256(sizeof(int) * (cell_imgs.size() + 1));  // per-image counts + their sum
   ORB_HIP(hipMalloc((void**)&d_passout, passout_hdr + sizeof(RawKp) * (size_t)kp_cap));
   d_img_total = reinterpret_cast<int*>(d_passout);
   d_kps = reinterpret_cast<RawKp*>(d_passout + passout_hdr);

@@ -23,6 +23,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "device_layout.h"
 #include "fast_host.h"
 #include "orb_host.h"
 #include "sift_extract.h"
@@ -146,6 +147,47 @@ inline hipError_t create_side_stream(hipStream_t* s, int which) {
   if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || lo == hi) { (void)hipGetLastError(); return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
   return hipStreamCreateWithPriority(s, hipStreamNonBlocking, which > 0 ? hi : lo);
 }
+
+struct rgbdfe_ctx;
+namespace rgbdfe_host {
+int fail(rgbdfe_ctx* ctx, int code, const std::string& msg);
+
+// device memory that lives for one call (or, as a member, with its owner)
+struct DeviceBuffer {
+  void* p = nullptr;
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  ~DeviceBuffer() { if (p) (void)hipFree(p); }
+  int alloc(rgbdfe_ctx* ctx, size_t bytes, const char* msg) {
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, msg);
+    }
+    return RGBDFE_OK;
+  }
+};
+
+// a buffer that only grows: ensure() frees and allocates larger when `bytes` exceeds what it holds.  The owner frees p.
+struct GrowBuffer {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int ensure(rgbdfe_ctx* ctx, size_t want, const char* msg) {
+    if (want <= bytes) return RGBDFE_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    if (hipMalloc(&p, want) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return fail(ctx, RGBDFE_ERR_OUT_OF_MEMORY, msg);
+    }
+    bytes = want;
+    return RGBDFE_OK;
+  }
+};
+}  // namespace rgbdfe_host
 
 struct rgbdfe_ctx {
   rgbdfe_config cfg{};
@@ -277,8 +319,7 @@ struct rgbdfe_ctx {
   // scratch for single-pair helpers / project_to_3d
   void* d_scratch = nullptr;
   size_t scratch_bytes = 0;
-  void* d_icp = nullptr;     // api_icp.hip: the samples, working copies and records of a call (d_scratch holds its tile counts and offsets)
-  size_t icp_bytes = 0;
+  GrowBuffer icp;            // api_icp.hip: the samples, working copies and records of a call (d_scratch holds its tile counts and offsets)
   OrbWorkspace orb;
   OrbWorkspace orb_super;  // rgbdfe_detect_describe_batch: up to 7 frames per launch chain (its own image sets)
   std::unique_ptr<TaskPool> detect_pool, stage_pool;  // its worker threads (created by the first batch call, kept)
@@ -432,9 +473,62 @@ inline SiftKey keypoint_to_sift_key(const rgbdfe_keypoint& p) {
 // one allocation carved into 256-byte aligned pieces: carve() hands out offsets, at<T>() turns one into a pointer
 struct Arena {
   size_t size = 0;
-  size_t carve(size_t bytes) { const size_t off = size; size += (bytes + 255) & ~(size_t)255; return off; }
+  size_t carve(size_t bytes) { const size_t off = size; size += round256(bytes); return off; }
 };
 template <class T> T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+
+// ---- device memory of the mapping and geometry entry points (api_frame / api_map / api_display / api_voxel / api_octomap /
+// api_icp / api_pose_graph.hip): the layouts come from device_layout.h, the pieces below need HIP or the context
+static_assert(kSortTilePairs == kVoxSortTile, "sort_workspace() sizes launch_vox_sort's histogram");
+
+// the node's resident cloud, or NULL (the caller fails with RGBDFE_ERR_UNKNOWN_NODE in its own words)
+inline CloudEntry* resident_cloud(rgbdfe_ctx* ctx, int32_t node_id) {
+  auto it = ctx->clouds.find(node_id);
+  return (it == ctx->clouds.end() || !it->second.d) ? nullptr : &it->second;
+}
+
+// a column-major Matrix4f as the row-major rotation and the translation the kernels take
+inline void rigid_of_matrix4f(const float* T, float R[9], float t[3]) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[r * 3 + c] = T[c * 4 + r];
+    t[r] = T[12 + r];
+  }
+}
+
+// The node table of a call and its tile -> node map as the first two uploaded blocks of a layout: `table` holds the n nodes
+// and the sentinel row behind them, whose first_tile is the number of tiles.
+struct NodeTableBlocks { Block table, tile_node; };
+template <class Node>
+NodeTableBlocks put_node_table(DeviceLayout& lay, const std::vector<Node>& table) {
+  NodeTableBlocks b;
+  b.table = lay.put(table.data(), sizeof(Node) * table.size());
+  b.tile_node = lay.put(nullptr, 4 * (size_t)table.back().first_tile);
+  uint32_t* tile_node = lay.staged<uint32_t>(b.tile_node);
+  for (size_t k = 0; k + 1 < table.size(); ++k)   // (the bounds by value: the stores may alias the table as far as the compiler knows)
+    std::fill(tile_node + table[k].first_tile, tile_node + table[k + 1].first_tile, (uint32_t)k);
+  return b;
+}
+
+// where a call's output goes: the caller's device pointer, or (NULL) a staging buffer of the call's own that finish() copies
+// to the host
+struct OutputSink {
+  void* d;   // where the kernels write (staged: valid after ready())
+  explicit OutputSink(void* d_caller) : d(d_caller), staged_(d_caller == nullptr) {}
+  int ready(rgbdfe_ctx* ctx, size_t bytes, const char* msg) {
+    if (!staged_) return RGBDFE_OK;
+    bytes_ = bytes;
+    const int rc = stage_.alloc(ctx, bytes, msg);
+    d = stage_.p;
+    return rc;
+  }
+  hipError_t finish(void* h_out, hipStream_t st) {   // enqueues the copy back; the caller synchronises before the sink goes
+    return staged_ ? hipMemcpyAsync(h_out, d, bytes_, hipMemcpyDeviceToHost, st) : hipSuccess;
+  }
+ private:
+  bool staged_;
+  size_t bytes_ = 0;
+  DeviceBuffer stage_;
+};
 
 // ---- the SIFT chunk pipeline (api_detect.hip): three extractors (ctx->sift, sift2, sift3), three chunk streams, chunks of
 // SiftExtractor::kMaxBatch frames in the order begin(c + 2) / finish_orientations(c + 1) / finish_descriptors(c) /

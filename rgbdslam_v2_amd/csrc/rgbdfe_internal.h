@@ -345,7 +345,7 @@ struct OctoLeafIn {
 };
 void launch_octo_set_leaves(const OctoLeafIn* src, uint32_t n, const OctoTable& to, OctoCtl* ctl, uint32_t* dup, hipStream_t stream);
 // octomap_tree.hip: the octree of a map's leaves (include/rgbdfe.h, "the tree of a leaf set"; the stages: the head of that
-// file).  Workspace of a map of n leaves in a table of cap slots: see api_octomap_tree.hip.
+// file).  Workspace of a map of n leaves in a table of cap slots: see tree_workspace (api_octomap.hip).
 constexpr uint32_t kTreeTile = 1024;  // elements of a workgroup in a count / write pass
 struct TreeHdr {
   uint32_t cnt[17];  // nodes of depth d (cnt[16] = leaves), as far as the passes went
