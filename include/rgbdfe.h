@@ -534,7 +534,7 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
  *   Parameters (rgbdfe_octomap_default_params: parameter_server.cpp:56-64): resolution > 0 and finite with a finite
  *   inverse, prob_hit / prob_miss / clamping_min / clamping_max inside (0, 1), clamping_min <= clamping_max, else
  *   RGBDFE_ERR_INVALID_ARG.  logodds(p) = (float)log(p / (1 - p)) (double, then one conversion); occupancy_threshold
- *   is carried and used by nothing here.
+ *   is used by the read side only (the third block) and is checked there.
  *   A cloud = rows of 4 floats (x, y, z, rgb bits) and a column-major Matrix4f (as rgbdfe_assemble_map takes it);
  *   origin = its translation column (T[12], T[13], T[14]).
  *   Transform: a row whose x, y and z are finite becomes p[a] = ((R[a][0] * x + R[a][1] * y) + R[a][2] * z) + t[a] in
@@ -585,7 +585,8 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
  * rgbdfe_octomap_leaves: the leaves as 16-byte records in ascending key[0] | key[1] << 16 | key[2] << 32; capacity <
  *   the number of leaves: RGBDFE_ERR_CAPACITY with *n_out = the needed size, before anything is written.
  * rgbdfe_octomap_stats: out[0] = capacity_cells, out[1] = leaves, out[2] = kernel launches of the last insert call,
- *   out[3] = kernel launches of the last tree / tree_device / nodes_at_depth / write call; further entries 0. */
+ *   out[3] = kernel launches of the last tree / tree_device / nodes_at_depth / write call, out[4] = kernel launches
+ *   of the last search / cast_rays / view_cloud / view_cloud_device call; further entries 0. */
 typedef struct rgbdfe_octomap rgbdfe_octomap;
 typedef struct rgbdfe_octomap_params {
   double resolution;           /* octomap_resolution, 0.05 */
@@ -593,7 +594,7 @@ typedef struct rgbdfe_octomap_params {
   double prob_miss;            /* octomap_prob_miss, 0.4 */
   double clamping_min;         /* octomap_clamping_min, 0.001 */
   double clamping_max;         /* octomap_clamping_max, 0.999 */
-  double occupancy_threshold;  /* octomap_occupancy_threshold, 0.5: carried, unused */
+  double occupancy_threshold;  /* octomap_occupancy_threshold, 0.5: the read side's default */
 } rgbdfe_octomap_params;
 typedef struct rgbdfe_octomap_leaf {
   uint16_t key[3];
@@ -680,6 +681,99 @@ int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_
 int rgbdfe_octomap_write(rgbdfe_octomap* map, const char* path);
 int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n);
 int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path);
+
+/* ---- occupancy map: the read side -- point lookups, ray casts, the map seen from a pose ------------------------
+ * What a consumer of the map asks it: OcTreeBaseImpl::search, OccupancyOcTreeBase::isNodeOccupied / castRay -- the
+ *   primitives under ColorOctomapServer::occupancyFilter (ColorOctomapServer.cpp:132-185: coordToKey, search,
+ *   keyToCoord; the filter itself stays out of scope for the reasons of the first block).  As above, the contract is this
+ *   library's restatement of the published octomap 1.6-1.9 line (restated, not pinned), one rounding per
+ *   operation.  Keys, centres and the norm are those of the first block; a centre as a float is (float)centre(k).
+ *   Leaf at a key: a leaf exists iff the table holds the key and its value word is a leaf's (a key that an unfinished
+ *   cloud claimed and that never became a leaf is not one).  All leaves are at depth 16, so search(key) is this lookup.
+ *   Occupied: a leaf is occupied iff log_odds >= occupied_log_odds by float comparison.  occupied_log_odds is a float
+ *   of the call; NaN stands for the map's own, logodds(params.occupancy_threshold), which rgbdfe_octomap_occupied_log_odds
+ *   returns.  occupancy_threshold is checked where it is used: that getter, and a call that passes NaN, return
+ *   RGBDFE_ERR_INVALID_ARG unless it lies inside (0, 1); rgbdfe_octomap_create accepts any value.
+ *   Search of a point (three floats, world frame): found = 2 if a coordinate is non-finite or the key invalid (the record
+ *   is zero); otherwise the record carries the key, and found = 1 with the leaf's log-odds and colour, or found = 0
+ *   with both zero.
+ *   Ray cast (castRay) of origin o and direction d, three floats each; the checks in this order:
+ *   1. o non-finite or its key invalid: BAD_ORIGIN (steps 0, key and centre zero).  Otherwise end = o's cell.
+ *   2. The origin's cell: an occupied leaf there: HIT with 0 steps.  No leaf and ignore_unknown == 0: UNKNOWN with 0
+ *      steps.  (A leaf that is not occupied, or no leaf with ignore_unknown != 0: go on.)
+ *   3. n = sqrt((double)((dx * dx + dy * dy) + dz * dz)) with the sum in float, dir = d / (float)n in float, step[a] =
+ *      sign of dir[a].  n not > 0 (NaN too), a non-finite dir[a], or step == (0, 0, 0) (an infinite n divides every
+ *      component to zero): BAD_DIRECTION with 0 steps, end = o's cell.
+ *   4. For step[a] != 0: tMax[a] = ((centre(key[a]) + ((double)step[a] * resolution) * 0.5) - (double)o[a]) /
+ *      (double)dir[a], tDelta[a] = resolution / fabs((double)dir[a]); DBL_MAX both where step[a] == 0.  This is
+ *      computeRayKeys of the first block with one difference: the half-cell offset is taken in double and not rounded
+ *      through float -- castRay's own wording, restated from memory like the rest.
+ *   5. Each iteration takes a = tMax0 < tMax1 ? (tMax0 < tMax2 ? 0 : 2) : (tMax1 < tMax2 ? 1 : 2) (a tie falls to the
+ *      later axis).  key[a] == 0 with step[a] < 0, or key[a] == 65535 with step[a] > 0: OUT_OF_BOUNDS, end = the
+ *      current cell (nothing wraps here, unlike insertion).  Otherwise key[a] += step[a], tMax[a] += tDelta[a], steps
+ *      += 1, end = the new cell.  Then, if max_range > 0: q = (float)centre(end) - o per axis in float, s =
+ *      ((double)(q0 * q0) + (double)(q1 * q1)) + (double)(q2 * q2) with the squares in float; s > max_range *
+ *      max_range (double): OUT_OF_RANGE (equality goes on).  Then the cell: an occupied leaf: HIT; a leaf that is not
+ *      occupied: the walk goes on; no leaf: UNKNOWN unless ignore_unknown != 0.
+ *   6. After 196608 iterations: STEP_LIMIT.  Every iteration moves one key one cell in a fixed direction or ends the
+ *      walk, so no walk gets there; the status exists so that the loop is finite without that argument.
+ *   max_range NaN: RGBDFE_ERR_INVALID_ARG; max_range <= 0: no range limit.
+ *   Hit record (rgbdfe_octomap_ray_hit, 36 bytes, rgbdfe_sizeof_octomap_ray_hit): status, steps (the cells moved), the
+ *   end cell's key and float centre, and -- zero unless the status is HIT -- the leaf's log-odds and colour.
+ *   View cloud: a column-major Matrix4f camera -> world (R and t as the first block reads them; R is taken as given),
+ *   fx, fy, cx, cy (doubles, converted to float once; any value: a pixel whose direction comes out unusable is
+ *   BAD_DIRECTION), rows x cols.  Pixel (row v, column u): o = t; x = ((float)u - (float)cx) / (float)fx, y = ((float)v -
+ *   (float)cy) / (float)fy; d[a] = (R[a][0] * x + R[a][1] * y) + R[a][2] in float; then the ray cast above.  Output row
+ *   v * cols + u, 4 floats as a node cloud's: for a HIT, with q = (float)centre(end) - o per axis in float, p[c] =
+ *   (R[0][c] * q0 + R[1][c] * q1) + R[2][c] * q2 (the camera frame again) and the word r << 16 | g << 8 | b as float
+ *   bits; otherwise x = y = z = the quiet NaN 0x7fc00000 and the word 0.  status (may be NULL): the ray's status, one
+ *   byte per pixel.  The cloud is organised (rows x cols) and is an ordinary input of rgbdfe_display_geometry, the voxel
+ *   filter, ICP and rgbdfe_upload_node_cloud.
+ *   Work bound: a key that is not in the table costs a probe run to the next free slot -- 1/2 (1 + 1 / (1 - load)^2)
+ *   probes expected: 2.5 at load 0.5, 8.5 at 0.75, most of the table when it is nearly full, once per step of every ray.
+ *   Every call of this block with work to do therefore returns RGBDFE_ERR_CAPACITY, nothing run ("reserve" in the
+ *   message), when 4 * leaves > 3 * capacity_cells; rgbdfe_octomap_reserve first (the wrappers reserve to a load of at
+ *   most 0.5 and repeat the call).
+ * rgbdfe_octomap_search: n points (3 floats each) from host memory; found[i] and leaves[i] as above.
+ * rgbdfe_octomap_cast_rays: n origins and n directions (3 floats each) from host memory, one ignore_unknown / max_range
+ *   / occupied_log_odds for all; hits[i] as above.
+ * rgbdfe_octomap_view_cloud: the view to host memory (out: rows * cols * 4 floats; status: rows * cols bytes or NULL).
+ *   rgbdfe_octomap_view_cloud_device: the same into device memory of the map's device (`stream` NULL: the context's
+ *   stream; the call returns when the rows are in place); nothing is read back.
+ * Arguments: n < 0, rows < 0, cols < 0, or a NULL array with work to do: RGBDFE_ERR_INVALID_ARG.  n or rows * cols >=
+ *   2^31: RGBDFE_ERR_CAPACITY.  n == 0 or rows * cols == 0 succeeds and launches nothing (before the work bound is
+ *   looked at).  One kernel launch per call: rgbdfe_octomap_stats has it as out[4] (0 after an empty call).
+ * None of these calls changes a leaf; a query between two inserts does not alter what the later insert produces. */
+#define RGBDFE_OCTOMAP_RAY_HIT 1
+#define RGBDFE_OCTOMAP_RAY_UNKNOWN 2
+#define RGBDFE_OCTOMAP_RAY_OUT_OF_RANGE 3
+#define RGBDFE_OCTOMAP_RAY_OUT_OF_BOUNDS 4
+#define RGBDFE_OCTOMAP_RAY_BAD_ORIGIN 5
+#define RGBDFE_OCTOMAP_RAY_BAD_DIRECTION 6
+#define RGBDFE_OCTOMAP_RAY_STEP_LIMIT 7
+typedef struct rgbdfe_octomap_ray_hit {
+  int32_t status;    /* RGBDFE_OCTOMAP_RAY_* */
+  uint32_t steps;
+  uint16_t key[3];
+  uint16_t zero0;
+  float centre[3];
+  float log_odds;
+  uint8_t rgb[3];
+  uint8_t zero1;
+} rgbdfe_octomap_ray_hit;
+int rgbdfe_sizeof_octomap_ray_hit(void);
+int rgbdfe_octomap_occupied_log_odds(rgbdfe_octomap* map, float* out);
+int rgbdfe_octomap_search(rgbdfe_octomap* map, const float* points, int64_t n, int32_t* found,
+                          rgbdfe_octomap_leaf* leaves);
+int rgbdfe_octomap_cast_rays(rgbdfe_octomap* map, const float* origins, const float* directions, int64_t n,
+                             int32_t ignore_unknown, double max_range, float occupied_log_odds,
+                             rgbdfe_octomap_ray_hit* hits);
+int rgbdfe_octomap_view_cloud(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy,
+                              int32_t rows, int32_t cols, int32_t ignore_unknown, double max_range,
+                              float occupied_log_odds, float* out, uint8_t* status);
+int rgbdfe_octomap_view_cloud_device(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx,
+                                     double cy, int32_t rows, int32_t cols, int32_t ignore_unknown, double max_range,
+                                     float occupied_log_odds, void* d_out, void* d_status, void* stream);
 
 /* ---- candidate selection for loop closure ----------------------------------
  * rgbdfe_potential_edge_targets is GraphManager::getPotentialEdgeTargetsWithDijkstra (graph_manager.cpp:204-324): the

@@ -680,7 +680,62 @@ class OctoMap {
     return map_ && rgbdfe_octomap_set_leaves(map_.get(), leaves.data(), (int64_t)leaves.size()) == RGBDFE_OK;
   }
 
+  // ---- the read side.  A table loaded above 3/4 refuses queries (RGBDFE_ERR_CAPACITY): the leaves are then re-housed
+  // at a load of at most 0.5 and the call repeated, as insertClouds doubles a full table.
+  // logodds(occupancy_threshold), what a query takes for "occupied" when it is given NAN
+  bool occupiedLogOdds(float* out) const { return map_ && rgbdfe_octomap_occupied_log_odds(map_.get(), out) == RGBDFE_OK; }
+  // OcTreeBaseImpl::search for points (x, y, z each): found[i] = 0 no leaf, 1 leaves[i] is the cell's leaf, 2 no valid key
+  bool search(const std::vector<float>& points, std::vector<int32_t>* found, std::vector<rgbdfe_octomap_leaf>* leaves) {
+    if (!map_ || points.size() % 3 != 0) return false;
+    const int64_t n = (int64_t)(points.size() / 3);
+    found->assign((size_t)n, 0);
+    leaves->assign((size_t)n, rgbdfe_octomap_leaf{});
+    return query([&] { return rgbdfe_octomap_search(map_.get(), points.data(), n, found->data(), leaves->data()); });
+  }
+  // OccupancyOcTreeBase::castRay for rays (origin and direction x, y, z each; max_range <= 0: no limit)
+  bool castRays(const std::vector<float>& origins, const std::vector<float>& directions, bool ignore_unknown, double max_range,
+                std::vector<rgbdfe_octomap_ray_hit>* hits, float occupied_log_odds = NAN) {
+    if (!map_ || origins.size() % 3 != 0 || directions.size() != origins.size()) return false;
+    const int64_t n = (int64_t)(origins.size() / 3);
+    hits->assign((size_t)n, rgbdfe_octomap_ray_hit{});
+    return query([&] {
+      return rgbdfe_octomap_cast_rays(map_.get(), origins.data(), directions.data(), n, ignore_unknown ? 1 : 0, max_range,
+                                      occupied_log_odds, hits->data());
+    });
+  }
+  // the map seen from cam2world (column-major Matrix4f): rows x cols rows of a node cloud (x, y, z in the camera frame, rgb
+  // bits; NaN where the pixel's ray hits nothing); status (may be NULL): the rays' RGBDFE_OCTOMAP_RAY_* per pixel
+  bool viewCloud(const std::array<float, 16>& cam2world, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols,
+                 bool ignore_unknown, double max_range, std::vector<float>* cloud, std::vector<uint8_t>* status = nullptr,
+                 float occupied_log_odds = NAN) {
+    if (!map_ || rows < 0 || cols < 0) return false;
+    const size_t n = (size_t)rows * (size_t)cols;
+    cloud->assign(4 * n, 0.0f);
+    if (status) status->assign(n, 0);
+    return query([&] {
+      return rgbdfe_octomap_view_cloud(map_.get(), cam2world.data(), fx, fy, cx, cy, rows, cols, ignore_unknown ? 1 : 0, max_range,
+                                       occupied_log_odds, cloud->data(), status ? status->data() : nullptr);
+    });
+  }
+  // the same into device memory of the map's device (d_status may be NULL); nothing is read back
+  bool viewCloudDevice(const std::array<float, 16>& cam2world, double fx, double fy, double cx, double cy, int32_t rows,
+                       int32_t cols, bool ignore_unknown, double max_range, void* d_cloud, void* d_status = nullptr,
+                       void* stream = nullptr, float occupied_log_odds = NAN) {
+    if (!map_) return false;
+    return query([&] {
+      return rgbdfe_octomap_view_cloud_device(map_.get(), cam2world.data(), fx, fy, cx, cy, rows, cols, ignore_unknown ? 1 : 0,
+                                              max_range, occupied_log_odds, d_cloud, d_status, stream);
+    });
+  }
+
  private:
+  template <class Call>
+  bool query(Call call) {
+    int rc = call();
+    const int64_t n = size();
+    if (rc == RGBDFE_ERR_CAPACITY && n >= 0 && 4 * n > 3 * capacity_ && reserve(2 * n)) rc = call();
+    return rc == RGBDFE_OK;
+  }
   std::unique_ptr<rgbdfe_octomap, void (*)(rgbdfe_octomap*)> map_;
   int64_t capacity_;
 };

@@ -140,6 +140,12 @@ ICP_NO_CORRESPONDENCES, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE 
 OCTOMAP_LEAF_DTYPE = np.dtype([("key", "<u2", (3,)), ("zero0", "<u2"), ("log_odds", "<f4"), ("rgb", "u1", (3,)),
                                ("zero1", "u1")])
 
+# rgbdfe_octomap_ray_hit: the result of one ray (status: OCTOMAP_RAY_*)
+OCTOMAP_RAY_HIT_DTYPE = np.dtype([("status", "<i4"), ("steps", "<u4"), ("key", "<u2", (3,)), ("zero0", "<u2"),
+                                  ("centre", "<f4", (3,)), ("log_odds", "<f4"), ("rgb", "u1", (3,)), ("zero1", "u1")])
+assert OCTOMAP_RAY_HIT_DTYPE.itemsize == 36
+(OCTOMAP_RAY_HIT, OCTOMAP_RAY_UNKNOWN, OCTOMAP_RAY_OUT_OF_RANGE, OCTOMAP_RAY_OUT_OF_BOUNDS, OCTOMAP_RAY_BAD_ORIGIN,
+ OCTOMAP_RAY_BAD_DIRECTION, OCTOMAP_RAY_STEP_LIMIT) = range(1, 8)
 # rgbdfe_octomap_node: the 8 bytes of a node in an .ot file
 OCTOMAP_NODE_DTYPE = np.dtype([("log_odds", "<f4"), ("rgb", "u1", (3,)), ("children", "u1")])
 
@@ -411,6 +417,19 @@ def load():
     L.rgbdfe_octomap_set_leaves.argtypes = [omap, vp, C.c_int64]
     L.rgbdfe_octomap_read.restype = C.c_int
     L.rgbdfe_octomap_read.argtypes = [omap, C.c_char_p]
+    L.rgbdfe_sizeof_octomap_ray_hit.restype = C.c_int
+    L.rgbdfe_sizeof_octomap_ray_hit.argtypes = []
+    L.rgbdfe_octomap_occupied_log_odds.restype = C.c_int
+    L.rgbdfe_octomap_occupied_log_odds.argtypes = [omap, C.POINTER(C.c_float)]
+    L.rgbdfe_octomap_search.restype = C.c_int
+    L.rgbdfe_octomap_search.argtypes = [omap, vp, C.c_int64, vp, vp]
+    L.rgbdfe_octomap_cast_rays.restype = C.c_int
+    L.rgbdfe_octomap_cast_rays.argtypes = [omap, vp, vp, C.c_int64, i32, C.c_double, C.c_float, vp]
+    view = [omap, vp] + [C.c_double] * 4 + [i32, i32, i32, C.c_double, C.c_float]
+    L.rgbdfe_octomap_view_cloud.restype = C.c_int
+    L.rgbdfe_octomap_view_cloud.argtypes = view + [vp, vp]
+    L.rgbdfe_octomap_view_cloud_device.restype = C.c_int
+    L.rgbdfe_octomap_view_cloud_device.argtypes = view + [vp, vp, vp]
     L.rgbdfe_observation_criterion_met.restype = C.c_int
     L.rgbdfe_observation_criterion_met.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
                                                    C.POINTER(C.c_double)]
@@ -594,6 +613,8 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_octomap_leaves", "rgbdfe_octomap_stats",
     "rgbdfe_octomap_tree", "rgbdfe_octomap_tree_device", "rgbdfe_octomap_nodes_at_depth", "rgbdfe_octomap_write",
     "rgbdfe_octomap_set_leaves", "rgbdfe_octomap_read",
+    "rgbdfe_sizeof_octomap_ray_hit", "rgbdfe_octomap_occupied_log_odds", "rgbdfe_octomap_search", "rgbdfe_octomap_cast_rays",
+    "rgbdfe_octomap_view_cloud", "rgbdfe_octomap_view_cloud_device",
     "rgbdfe_observation_criterion_met", "rgbdfe_set_latency_mode", "rgbdfe_set_profiling", "rgbdfe_get_kernel_time",
     "rgbdfe_reset_kernel_time", "rgbdfe_graph_stats", "rgbdfe_set_graph_capture", "rgbdfe_match_pair_list_allgather_inliers", "rgbdfe_pack_inliers", "rgbdfe_sizeof_inlier_header", "rgbdfe_sizeof_match_result", "rgbdfe_abi_version",
     "rgbdfe_pose_graph_create", "rgbdfe_pose_graph_destroy", "rgbdfe_pose_graph_add_node",

@@ -20,6 +20,7 @@ struct rgbdfe_octomap {
   // the tree calls' workspace (octomap_tree.hip): one allocation, grown when a call needs more, freed with the map
   GrowBuffer tree_ws;
   int64_t tree_launches = 0;    // kernel launches of the last tree / depth / write call (tools/bench_octomap_tree.py)
+  int64_t query_launches = 0;   // kernel launches of the last search / cast / view call (tools/bench_octomap_query.py)
 };
 
 namespace impl {
@@ -303,8 +304,8 @@ int rgbdfe_octomap_stats(rgbdfe_octomap* map, int64_t* out, int32_t n_out) {
   rgbdfe_ctx* ctx = map->ctx;
   if (!out || n_out < 0) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const int64_t v[4] = {(int64_t)map->tb.cap, map->n_leaves, map->launches, map->tree_launches};
-  for (int32_t i = 0; i < n_out; ++i) out[i] = i < 4 ? v[i] : 0;
+  const int64_t v[5] = {(int64_t)map->tb.cap, map->n_leaves, map->launches, map->tree_launches, map->query_launches};
+  for (int32_t i = 0; i < n_out; ++i) out[i] = i < 5 ? v[i] : 0;
   return RGBDFE_OK;
 }
 
@@ -581,6 +582,148 @@ int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path) {
   std::string err;
   if (!ot_parse(bytes.data(), bytes.size(), res, &leaves, &err)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "octomap: " + err);
   return set_leaves_locked(map, leaves.data(), (int64_t)leaves.size());
+}
+
+// ---- the read side: point lookups, ray casts, the map seen from a pose (kernels: octomap_query.hip) ----------------------
+
+namespace {
+
+// logodds(occupancy_threshold), checked here, where it is used
+int map_occupied(rgbdfe_octomap* map, float* out) {
+  const double t = map->prm.occupancy_threshold;
+  if (!(t > 0.0 && t < 1.0)) return fail(map->ctx, RGBDFE_ERR_INVALID_ARG, "octomap: occupancy_threshold must lie inside (0, 1)");
+  *out = (float)log(t / (1.0 - t));
+  return RGBDFE_OK;
+}
+
+// the work bound of the block, then the walk's parameters; ctx->mu is held
+int query_setup(rgbdfe_octomap* map, int32_t ignore_unknown, double max_range, float occupied_log_odds, OctoQuery* q) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (4 * map->n_leaves > 3 * (int64_t)map->tb.cap)
+    return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: the table is loaded above 3/4, a query would crawl (reserve more cells first)");
+  q->res = map->prm.resolution;
+  q->inv_res = 1.0 / map->prm.resolution;
+  q->max_range2 = max_range > 0.0 ? max_range * max_range : -1.0;
+  q->ignore_unknown = ignore_unknown != 0 ? 1u : 0u;
+  q->occupied = occupied_log_odds;
+  return std::isnan(occupied_log_odds) ? map_occupied(map, &q->occupied) : RGBDFE_OK;
+}
+
+int view_common(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols,
+                int32_t ignore_unknown, double max_range, float occupied_log_odds, float* h_out, uint8_t* h_status, void* d_out,
+                void* d_status, bool to_device, void* stream) {
+  rgbdfe_ctx* ctx = map->ctx;
+  const int64_t n = (int64_t)rows * (int64_t)cols;
+  if (rows < 0 || cols < 0 || !transform || !range_ok(max_range) || (n > 0 && !(to_device ? d_out : (void*)h_out)))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad octomap view arguments");
+  if (n > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: 2^31 pixels or more in one view");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  map->query_launches = 0;
+  if (n == 0) return RGBDFE_OK;
+  OctoQuery q{};
+  int rc = query_setup(map, ignore_unknown, max_range, occupied_log_odds, &q);
+  if (rc != RGBDFE_OK) return rc;
+  OctoView v{};
+  rigid_of_matrix4f(transform, v.R, v.t);
+  v.fx = (float)fx; v.fy = (float)fy; v.cx = (float)cx; v.cy = (float)cy;
+  v.rows = (uint32_t)rows; v.cols = (uint32_t)cols;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = (to_device && stream) ? (hipStream_t)stream : ctx->stream;
+  const bool want_status = to_device ? d_status != nullptr : h_status != nullptr;
+  OutputSink cloud(to_device ? d_out : nullptr), plane(to_device ? d_status : nullptr);
+  rc = cloud.ready(ctx, (size_t)n * sizeof(float4), "octomap: staging allocation failed");
+  if (rc == RGBDFE_OK && want_status && !to_device) rc = plane.ready(ctx, (size_t)n, "octomap: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  launch_octo_view(map->tb, v, q, (float4*)cloud.d, want_status ? (uint8_t*)plane.d : nullptr, st);
+  HIP_TRY(ctx, hipGetLastError());
+  map->query_launches = 1;
+  HIP_TRY(ctx, cloud.finish(h_out, st));
+  if (want_status && !to_device) HIP_TRY(ctx, plane.finish(h_status, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return RGBDFE_OK;
+}
+
+}  // namespace
+
+int rgbdfe_octomap_occupied_log_odds(rgbdfe_octomap* map, float* out) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (!out) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return map_occupied(map, out);
+}
+
+int rgbdfe_octomap_search(rgbdfe_octomap* map, const float* points, int64_t n, int32_t* found, rgbdfe_octomap_leaf* leaves) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (n < 0 || (n > 0 && (!points || !found || !leaves))) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad octomap search arguments");
+  if (n > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: 2^31 points or more in one search");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  map->query_launches = 0;
+  if (n == 0) return RGBDFE_OK;
+  OctoQuery q{};
+  int rc = query_setup(map, 0, -1.0, 0.0f, &q);
+  if (rc != RGBDFE_OK) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = ctx->stream;
+  DeviceLayout lay;
+  const Block b_pts = lay.room(12 * (size_t)n), b_found = lay.room(4 * (size_t)n), b_leaves = lay.room(16 * (size_t)n);
+  DeviceBuffer stage;
+  rc = stage.alloc(ctx, lay.total(), "octomap: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(at<float>(stage.p, b_pts), points, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+  launch_octo_search(map->tb, at<float>(stage.p, b_pts), (uint32_t)n, q.inv_res, at<int32_t>(stage.p, b_found),
+                     at<uint4>(stage.p, b_leaves), st);
+  HIP_TRY(ctx, hipGetLastError());
+  map->query_launches = 1;
+  HIP_TRY(ctx, hipMemcpyAsync(found, at<int32_t>(stage.p, b_found), 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(leaves, at<uint4>(stage.p, b_leaves), 16 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_cast_rays(rgbdfe_octomap* map, const float* origins, const float* directions, int64_t n, int32_t ignore_unknown,
+                             double max_range, float occupied_log_odds, rgbdfe_octomap_ray_hit* hits) {
+  rgbdfe_ctx* ctx = map->ctx;
+  if (n < 0 || (n > 0 && (!origins || !directions || !hits)) || !range_ok(max_range))
+    return fail(ctx, RGBDFE_ERR_INVALID_ARG, "bad octomap ray cast arguments");
+  if (n > (int64_t)INT32_MAX) return fail(ctx, RGBDFE_ERR_CAPACITY, "octomap: 2^31 rays or more in one call");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  map->query_launches = 0;
+  if (n == 0) return RGBDFE_OK;
+  OctoQuery q{};
+  int rc = query_setup(map, ignore_unknown, max_range, occupied_log_odds, &q);
+  if (rc != RGBDFE_OK) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->cfg.device_id));
+  hipStream_t st = ctx->stream;
+  DeviceLayout lay;
+  const Block b_o = lay.room(12 * (size_t)n), b_d = lay.room(12 * (size_t)n),
+              b_hits = lay.room(sizeof(rgbdfe_octomap_ray_hit) * (size_t)n);
+  DeviceBuffer stage;
+  rc = stage.alloc(ctx, lay.total(), "octomap: staging allocation failed");
+  if (rc != RGBDFE_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(at<float>(stage.p, b_o), origins, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(at<float>(stage.p, b_d), directions, 12 * (size_t)n, hipMemcpyHostToDevice, st));
+  launch_octo_cast(map->tb, at<float>(stage.p, b_o), at<float>(stage.p, b_d), (uint32_t)n, q,
+                   at<rgbdfe_octomap_ray_hit>(stage.p, b_hits), st);
+  HIP_TRY(ctx, hipGetLastError());
+  map->query_launches = 1;
+  HIP_TRY(ctx, hipMemcpyAsync(hits, at<rgbdfe_octomap_ray_hit>(stage.p, b_hits), sizeof(rgbdfe_octomap_ray_hit) * (size_t)n,
+                              hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return RGBDFE_OK;
+}
+
+int rgbdfe_octomap_view_cloud(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy, int32_t rows,
+                              int32_t cols, int32_t ignore_unknown, double max_range, float occupied_log_odds, float* out,
+                              uint8_t* status) {
+  return view_common(map, transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range, occupied_log_odds, out, status, nullptr,
+                     nullptr, false, nullptr);
+}
+
+int rgbdfe_octomap_view_cloud_device(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy,
+                                     int32_t rows, int32_t cols, int32_t ignore_unknown, double max_range, float occupied_log_odds,
+                                     void* d_out, void* d_status, void* stream) {
+  return view_common(map, transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range, occupied_log_odds, nullptr, nullptr, d_out,
+                     d_status, true, stream);
 }
 
 }  // namespace impl

@@ -23,16 +23,13 @@
 // Which slot a key lands in depends on arrival; nothing that leaves the device does (the leaves go out sorted by key).
 // No float atomics, no workgroup waits for another, the launches of a cloud do not depend on its size.
 #include "rgbdfe_internal.h"
+#include "octomap_table.h"
 
 #include <cfloat>
 
 namespace rgbdfe {
 
 namespace {
-
-constexpr uint32_t kNoSlot = 0xffffffffu;
-
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // the world-frame point of a row; false: the row contributes nothing
 __device__ __forceinline__ bool octo_point(const float4& p, const OctoCloud& c, float& x, float& y, float& z) {
@@ -41,26 +38,6 @@ __device__ __forceinline__ bool octo_point(const float4& p, const OctoCloud& c, 
   y = ((c.R[3] * p.x + c.R[4] * p.y) + c.R[5] * p.z) + c.t[1];
   z = ((c.R[6] * p.x + c.R[7] * p.y) + c.R[8] * p.z) + c.t[2];
   return finite_bits(x) && finite_bits(y) && finite_bits(z);
-}
-
-__device__ __forceinline__ bool octo_key1(double inv_res, float v, uint32_t& k) {
-  const double f = floor(inv_res * (double)v) + 32768.0;
-  if (!(f >= 0.0 && f < 65536.0)) return false;  // NaN too
-  k = (uint32_t)f;
-  return true;
-}
-__device__ __forceinline__ bool octo_key(double inv_res, float x, float y, float z, uint32_t& k0, uint32_t& k1, uint32_t& k2) {
-  const bool a = octo_key1(inv_res, x, k0), b = octo_key1(inv_res, y, k1), c = octo_key1(inv_res, z, k2);
-  return a && b && c;
-}
-__device__ __forceinline__ unsigned long long pack_key(uint32_t k0, uint32_t k1, uint32_t k2) {
-  return (unsigned long long)k0 | ((unsigned long long)k1 << 16) | ((unsigned long long)k2 << 32);
-}
-
-__device__ __forceinline__ uint32_t home_slot(unsigned long long key, uint32_t cap) {
-  unsigned long long h = key;  // the 64-bit finaliser of MurmurHash3
-  h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-  return (uint32_t)(((h >> 32) * (unsigned long long)cap) >> 32);  // < cap
 }
 
 // the slot of `key`, claimed if it has none; kNoSlot when `cap` probes found neither the key nor a free slot
@@ -73,18 +50,6 @@ __device__ __forceinline__ uint32_t find_or_claim(const OctoTable& tb, OctoCtl* 
     unsigned long long k = __hip_atomic_load(&tb.key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (k == kOctoEmptyKey) k = atomicCAS(&tb.key[i], kOctoEmptyKey, key);  // the word before the exchange
     if (k == key || k == kOctoEmptyKey) return i;
-    i = i + 1u == tb.cap ? 0u : i + 1u;
-  }
-  return kNoSlot;
-}
-
-// the slot of `key` if it is there (no kernel claims keys while this runs)
-__device__ __forceinline__ uint32_t find_slot(const OctoTable& tb, unsigned long long key) {
-  uint32_t i = home_slot(key, tb.cap);
-  for (uint32_t probe = 0; probe < tb.cap; ++probe) {
-    const unsigned long long k = tb.key[i];
-    if (k == key) return i;
-    if (k == kOctoEmptyKey) return kNoSlot;
     i = i + 1u == tb.cap ? 0u : i + 1u;
   }
   return kNoSlot;

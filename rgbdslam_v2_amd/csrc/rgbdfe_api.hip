@@ -942,6 +942,35 @@ int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* le
 }
 
 int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path) { RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_read(map, path)); }
+
+int rgbdfe_sizeof_octomap_ray_hit(void) { return (int)sizeof(rgbdfe_octomap_ray_hit); }
+
+int rgbdfe_octomap_occupied_log_odds(rgbdfe_octomap* map, float* out) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_occupied_log_odds(map, out));
+}
+
+int rgbdfe_octomap_search(rgbdfe_octomap* map, const float* points, int64_t n, int32_t* found, rgbdfe_octomap_leaf* leaves) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_search(map, points, n, found, leaves));
+}
+
+int rgbdfe_octomap_cast_rays(rgbdfe_octomap* map, const float* origins, const float* directions, int64_t n, int32_t ignore_unknown,
+                             double max_range, float occupied_log_odds, rgbdfe_octomap_ray_hit* hits) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_cast_rays(map, origins, directions, n, ignore_unknown, max_range, occupied_log_odds, hits));
+}
+
+int rgbdfe_octomap_view_cloud(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy, int32_t rows,
+                              int32_t cols, int32_t ignore_unknown, double max_range, float occupied_log_odds, float* out,
+                              uint8_t* status) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_view_cloud(map, transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range,
+                                                     occupied_log_odds, out, status));
+}
+
+int rgbdfe_octomap_view_cloud_device(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy,
+                                     int32_t rows, int32_t cols, int32_t ignore_unknown, double max_range, float occupied_log_odds,
+                                     void* d_out, void* d_status, void* stream) {
+  RGBDFE_ON_MAP(map, impl::rgbdfe_octomap_view_cloud_device(map, transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range,
+                                                            occupied_log_odds, d_out, d_status, stream));
+}
 #undef RGBDFE_ON_MAP
 
 // pose-graph optimisation runs on one device (the first of a group)

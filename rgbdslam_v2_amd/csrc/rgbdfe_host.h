@@ -708,6 +708,11 @@ int rgbdfe_octomap_nodes_at_depth(rgbdfe_octomap* map, int32_t depth, float min_
 int rgbdfe_octomap_write(rgbdfe_octomap* map, const char* path);
 int rgbdfe_octomap_set_leaves(rgbdfe_octomap* map, const rgbdfe_octomap_leaf* leaves, int64_t n);
 int rgbdfe_octomap_read(rgbdfe_octomap* map, const char* path);
+int rgbdfe_octomap_occupied_log_odds(rgbdfe_octomap* map, float* out);
+int rgbdfe_octomap_search(rgbdfe_octomap* map, const float* points, int64_t n, int32_t* found, rgbdfe_octomap_leaf* leaves);
+int rgbdfe_octomap_cast_rays(rgbdfe_octomap* map, const float* origins, const float* directions, int64_t n, int32_t ignore_unknown, double max_range, float occupied_log_odds, rgbdfe_octomap_ray_hit* hits);
+int rgbdfe_octomap_view_cloud(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols, int32_t ignore_unknown, double max_range, float occupied_log_odds, float* out, uint8_t* status);
+int rgbdfe_octomap_view_cloud_device(rgbdfe_octomap* map, const float* transform, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols, int32_t ignore_unknown, double max_range, float occupied_log_odds, void* d_out, void* d_status, void* stream);
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids, const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out);
 int rgbdfe_observation_criterion_met(uint32_t inliers, uint32_t outliers, uint32_t all, double observability_threshold, double* quality);
 int rgbdfe_set_latency_mode(rgbdfe_ctx* ctx, int32_t max_pairs, int32_t chunk_iterations);

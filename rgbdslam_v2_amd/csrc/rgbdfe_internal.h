@@ -344,6 +344,27 @@ struct OctoLeafIn {
   uint32_t colour;
 };
 void launch_octo_set_leaves(const OctoLeafIn* src, uint32_t n, const OctoTable& to, OctoCtl* ctl, uint32_t* dup, hipStream_t stream);
+// octomap_query.hip: the read side (include/rgbdfe.h, "occupancy map: the read side").  The kernels read the table and write
+// their own output rows, nothing else; one launch each.
+struct OctoQuery {
+  double inv_res, res;      // 1.0 / resolution, resolution
+  double max_range2;        // max_range * max_range; < 0: no range limit
+  float occupied;           // a leaf is occupied iff its log-odds >= this
+  uint32_t ignore_unknown;
+};
+struct OctoView {
+  float R[9], t[3];         // as MapNode: row-major rotation camera -> world, translation = the ray origin
+  float fx, fy, cx, cy;
+  uint32_t rows, cols;
+};
+// points: n rows of 3 floats; found[i] = 0 / 1 / 2, leaves[i] = the rgbdfe_octomap_leaf record of point i
+void launch_octo_search(const OctoTable& tb, const float* points, uint32_t n, double inv_res, int32_t* found, uint4* leaves,
+                        hipStream_t stream);
+// rays: n origins (3 floats each), then n directions; hits: n rgbdfe_octomap_ray_hit records
+void launch_octo_cast(const OctoTable& tb, const float* origins, const float* directions, uint32_t n, const OctoQuery& q,
+                      rgbdfe_octomap_ray_hit* hits, hipStream_t stream);
+// cloud: rows * cols rows of the node-cloud format; status: a byte per pixel, may be NULL
+void launch_octo_view(const OctoTable& tb, const OctoView& v, const OctoQuery& q, float4* cloud, uint8_t* status, hipStream_t stream);
 // octomap_tree.hip: the octree of a map's leaves (include/rgbdfe.h, "the tree of a leaf set"; the stages: the head of that
 // file).  Workspace of a map of n leaves in a table of cap slots: see tree_workspace (api_octomap.hip).
 constexpr uint32_t kTreeTile = 1024;  // elements of a workgroup in a count / write pass

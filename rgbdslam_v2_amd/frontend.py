@@ -1669,3 +1669,91 @@ class OctoMap:
         """The map's contents replaced by these leaves (_lib.OCTOMAP_LEAF_DTYPE records, any order)."""
         lv = np.ascontiguousarray(leaves, _lib.OCTOMAP_LEAF_DTYPE).reshape(-1)
         self._fe._check(self._L.rgbdfe_octomap_set_leaves(self._map, lv.ctypes.data if len(lv) else None, len(lv)))
+
+    # ---- the read side (include/rgbdfe.h, "occupancy map: the read side") ------------------------------------------------
+    @property
+    def last_query_launches(self) -> int:
+        """Kernel launches of the last search / cast_rays / view_cloud / view_cloud_device call."""
+        out = np.zeros(5, np.int64)
+        self._fe._check(self._L.rgbdfe_octomap_stats(self._map, out.ctypes.data, 5))
+        return int(out[4])
+
+    @property
+    def occupied_log_odds(self) -> float:
+        """logodds(occupancy_threshold): the threshold a query uses when it is given none."""
+        v = C.c_float(0.0)
+        self._fe._check(self._L.rgbdfe_octomap_occupied_log_odds(self._map, C.byref(v)))
+        return v.value
+
+    def _query(self, call, grow):
+        """call() -> status.  A table loaded above 3/4 refuses queries (RGBDFE_ERR_CAPACITY): with grow, the leaves are
+        re-housed at a load of at most 0.5 and the call repeated, as insert_nodes doubles a full table."""
+        st = call()
+        if st == -5 and grow and 4 * len(self) > 3 * self.capacity:
+            self.reserve(2 * len(self))
+            st = call()
+        self._fe._check(st)
+
+    @staticmethod
+    def _threshold(occupied_log_odds):
+        return float("nan") if occupied_log_odds is None else float(occupied_log_odds)
+
+    def search(self, points, grow=True):
+        """OcTreeBaseImpl::search for n world-frame points ([n, 3] float32): (found, leaves) with found[i] = 0 (no leaf),
+        1 (leaves[i] is the leaf of the point's cell) or 2 (a non-finite coordinate or a key out of range), leaves as
+        _lib.OCTOMAP_LEAF_DTYPE records."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(pts)
+        found, leaves = np.zeros(n, np.int32), np.zeros(n, _lib.OCTOMAP_LEAF_DTYPE)
+        self._query(lambda: self._L.rgbdfe_octomap_search(self._map, pts.ctypes.data if n else None, n,
+                                                          found.ctypes.data if n else None, leaves.ctypes.data if n else None), grow)
+        return found, leaves
+
+    def cast_rays(self, origins, directions, ignore_unknown=False, max_range=-1.0, occupied_log_odds=None, grow=True):
+        """OccupancyOcTreeBase::castRay for n rays ([n, 3] float32 origins and directions, world frame; a direction need not
+        be normalised): _lib.OCTOMAP_RAY_HIT_DTYPE records (status: _lib.OCTOMAP_RAY_*; steps; the end cell's key and
+        centre; log_odds and rgb of the leaf for a hit).  max_range <= 0: no limit; occupied_log_odds None: the map's
+        occupancy_threshold."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("as many directions as origins")
+        n = len(o)
+        hits = np.zeros(n, _lib.OCTOMAP_RAY_HIT_DTYPE)
+        self._query(lambda: self._L.rgbdfe_octomap_cast_rays(
+            self._map, o.ctypes.data if n else None, d.ctypes.data if n else None, n, int(bool(ignore_unknown)), float(max_range),
+            self._threshold(occupied_log_odds), hits.ctypes.data if n else None), grow)
+        return hits
+
+    def _view_args(self, transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range, occupied_log_odds):
+        T = np.ascontiguousarray(np.asarray(transform, np.float32).reshape(4, 4).T)  # column-major
+        return T, (T.ctypes.data, float(fx), float(fy), float(cx), float(cy), int(rows), int(cols), int(bool(ignore_unknown)),
+                   float(max_range), self._threshold(occupied_log_odds))
+
+    def view_cloud(self, transform, fx, fy, cx, cy, rows, cols, ignore_unknown=False, max_range=-1.0, occupied_log_odds=None,
+                   with_status=False, grow=True):
+        """The map seen from a pose: an organised cloud [rows, cols, 4] float32 in the node-cloud row format (x, y, z in the
+        camera frame, rgb bits; NaN rows and word 0 where the pixel's ray hits nothing).  transform: camera -> world, a
+        row-major 4 x 4 matrix as insert_cloud takes it.  with_status: also the rays' statuses, [rows, cols] uint8."""
+        T, args = self._view_args(transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range, occupied_log_odds)
+        n = int(rows) * int(cols)
+        out = np.zeros((max(int(rows), 0), max(int(cols), 0), 4), np.float32)
+        status = np.zeros(out.shape[:2], np.uint8) if with_status else None
+        self._query(lambda: self._L.rgbdfe_octomap_view_cloud(
+            self._map, *args, out.ctypes.data if n > 0 else None, status.ctypes.data if with_status and n > 0 else None), grow)
+        return (out, status) if with_status else out
+
+    def view_cloud_device(self, out, transform, fx, fy, cx, cy, ignore_unknown=False, max_range=-1.0, occupied_log_odds=None,
+                          status=None, stream=None, grow=True):
+        """The same into `out`, a contiguous float32 torch tensor [rows, cols, 4] on the map's device (status: a contiguous
+        uint8 tensor [rows, cols] there, or None); nothing crosses to the host."""
+        if not (out.is_cuda and out.is_contiguous() and out.dim() == 3 and out.shape[2] == 4 and out.element_size() == 4):
+            raise ValueError("out must be a contiguous [rows, cols, 4] float32 tensor on the device")
+        rows, cols = int(out.shape[0]), int(out.shape[1])
+        if status is not None and not (status.is_cuda and status.is_contiguous() and tuple(status.shape) == (rows, cols)
+                                       and status.element_size() == 1):
+            raise ValueError("status must be a contiguous [rows, cols] uint8 tensor on the device")
+        T, args = self._view_args(transform, fx, fy, cx, cy, rows, cols, ignore_unknown, max_range, occupied_log_odds)
+        n = rows * cols
+        self._query(lambda: self._L.rgbdfe_octomap_view_cloud_device(
+            self._map, *args, out.data_ptr() if n else None, status.data_ptr() if status is not None and n else None, stream), grow)
