@@ -304,14 +304,17 @@ class Node {  // the slice of src/node.h the pair path touches
     return rgbdfe_upload_node_cloud(fe_.get(), id_, depth, rows, cols, rgb, rgb_channels, encoding_bgr ? 1 : 0, fx, fy,
                                     cx, cy, depth_scaling, minimum_depth, cloud_creation_skip_step, nullptr) == RGBDFE_OK;
   }
-  // ... and a copy of it for the host: rows x cols x (x, y, z, rgb bits), also for a cloud the sensor batch path has kept
+  // ... and a copy of it for the host: rows x cols x (x, y, z, rgb bits), also for a cloud the sensor batch path has kept.
+  // A cloud of no points (a reduced cloud without a valid point: 1 row, 0 columns) is a cloud too: true and empty.
   bool pointCloud(std::vector<float>* cloud, int* rows = nullptr, int* cols = nullptr) const {
     int32_t r = 0, c = 0;
-    if (rgbdfe_download_node_cloud(fe_.get(), id_, nullptr, 0, &r, &c) != RGBDFE_ERR_CAPACITY) return false;
+    // the size first (RGBDFE_ERR_CAPACITY reports it; a cloud of no points is RGBDFE_OK), then the points
+    const int rc = rgbdfe_download_node_cloud(fe_.get(), id_, nullptr, 0, &r, &c);
+    if (rc != RGBDFE_OK && rc != RGBDFE_ERR_CAPACITY) return false;
     cloud->resize((size_t)r * (size_t)c * 4);
     if (rows) *rows = r;
     if (cols) *cols = c;
-    return rgbdfe_download_node_cloud(fe_.get(), id_, cloud->data(), (int64_t)r * c, &r, &c) == RGBDFE_OK;
+    return rc == RGBDFE_OK || rgbdfe_download_node_cloud(fe_.get(), id_, cloud->data(), (int64_t)r * c, &r, &c) == RGBDFE_OK;
   }
   // Node::reducePointCloud (src/node.cpp:1448-1460): pc_col becomes its voxel-filtered cloud, unstructured (pointCloud()
   // then reports 1 row).  Like the reference, vfs <= 0 changes nothing (the reference warns: "Point Clouds can't be reduced
@@ -385,7 +388,9 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
   // verdicts (optional): RGBDFE_PRUNE_* per measured edge in insertion order
   int pruneEdgesWithErrorAbove(float thresh, std::vector<uint8_t>* verdicts = nullptr) {
     int32_t n = 0;
-    rgbdfe_pose_graph_edge_errors(fe_.get(), topology_.get(), nullptr, nullptr, nullptr, 0, &n);  // the edge count
+    // the edge count: RGBDFE_ERR_CAPACITY reports it, a graph without measured edges is RGBDFE_OK
+    const int rc = rgbdfe_pose_graph_edge_errors(fe_.get(), topology_.get(), nullptr, nullptr, nullptr, 0, &n);
+    if (rc != RGBDFE_OK && rc != RGBDFE_ERR_CAPACITY) return -1;
     std::vector<uint8_t> local((size_t)n);
     int32_t pruned = 0;
     if (rgbdfe_pose_graph_prune_edges(fe_.get(), topology_.get(), thresh, local.data(), n, &pruned) != RGBDFE_OK) return -1;
