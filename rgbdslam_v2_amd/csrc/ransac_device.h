@@ -383,8 +383,10 @@ __device__ __forceinline__ void transpose_records(const float* __restrict__ M, f
     S4[v] = M[(blk * 4 + (r & 3)) * kRec + (r >> 2)];
   }
 }
-__device__ __forceinline__ uint32_t prescreen_may_pass_s4(const float* hypR, const float* hypt, const float* __restrict__ S4,
-                                                       int n_all, float pmax, const RansacConst& rc) {
+// (first_block, block_step): the blocks this lane walks, first_block, first_block + block_step, ... -- (0, 1) is every block.
+__device__ __forceinline__ uint32_t prescreen_count_s4(const float* hypR, const float* hypt, const float* __restrict__ S4,
+                                                    int n_all, float pmax, const RansacConst& rc, int first_block,
+                                                    int block_step) {
   const float u4 = 4.0f * 5.9604645e-8f;
   float es = 0.0f;
 #pragma unroll
@@ -403,9 +405,10 @@ __device__ __forceinline__ uint32_t prescreen_may_pass_s4(const float* hypR, con
 #pragma unroll
   for (int i = 0; i < 3; ++i) t2[i] = v2f{hypt[i], hypt[i]};
   const v4f* __restrict__ blocks = reinterpret_cast<const v4f*>(S4);
+  const int n_blocks = (n_all + 3) >> 2;
 #pragma unroll 1
-  for (int m0 = 0; m0 < n_all; m0 += 4) {
-    const v4f* __restrict__ b = blocks + (m0 >> 2) * 6;
+  for (int blk = first_block; blk < n_blocks; blk += block_step) {
+    const v4f* __restrict__ b = blocks + blk * 6;
     const v4f px = b[0], py = b[1], pz = b[2], qx = b[3], qy = b[4], qz = b[5];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -418,6 +421,35 @@ __device__ __forceinline__ uint32_t prescreen_may_pass_s4(const float* hypR, con
       may_pass += !(dsq.y > hi_f) ? 1u : 0u;
     }
   }
+  return may_pass;
+}
+__device__ __forceinline__ uint32_t prescreen_may_pass_s4(const float* hypR, const float* hypt, const float* __restrict__ S4,
+                                                       int n_all, float pmax, const RansacConst& rc) {
+  return prescreen_count_s4(hypR, hypt, S4, n_all, pmax, rc, 0, 1);
+}
+
+// The same count for a wave that holds at most 64 / G hypotheses in its first lanes (G = 1 << log2_groups = 2, 4 or 8): the
+// wave's lanes are regrouped as lane = g * (64 / G) + j, lane j's hypothesis goes to its G lanes through ds_bpermute (in
+// place: lane j < 64 / G keeps its own twelve floats, the others' are dead by now), group g counts blocks g, g + G, g + 2G,
+// ... of S4 and a butterfly over the groups leaves the sum in every lane of j -- the integer prescreen_may_pass_s4 gives
+// lane j, from the same blocks and the same arithmetic per match, in a G-th of the trips.  All 64 lanes must be active.
+// Interleaved blocks, not one contiguous share per group: the reads are no broadcast here, and a ds_read_b128 serves a
+// 16-lane group in one cycle only if its distinct addresses fall on different 16-byte slots of the 256-byte bank row.  A
+// block is six slots, so blocks b .. b + 7 start at slots 6b mod 16 = 0, 6, 12, 2, 8, 14, 4, 10 (rotated): any G <= 8
+// consecutive blocks are conflict-free for every component, whichever lanes the hardware groups.  Contiguous shares
+// (75 blocks over 8 groups: 10 blocks = 60 slots = 12 mod 16 apart) would put groups 0 and 4, 1 and 5, ... on one slot.
+__device__ __forceinline__ uint32_t prescreen_may_pass_s4_split(float* hypR, float* hypt, const float* __restrict__ S4,
+                                                             int n_all, float pmax, const RansacConst& rc, int lane,
+                                                             int log2_groups) {
+  const int per_group = kWave >> log2_groups;
+  const int src = (lane & (per_group - 1)) << 2;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) hypR[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(hypR[i])));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) hypt[i] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(hypt[i])));
+  uint32_t may_pass = prescreen_count_s4(hypR, hypt, S4, n_all, pmax, rc, lane >> (6 - log2_groups), 1 << log2_groups);
+  for (int d = per_group; d < kWave; d <<= 1)
+    may_pass += (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ d) << 2, (int)may_pass);
   return may_pass;
 }
 

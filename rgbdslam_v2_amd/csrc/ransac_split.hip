@@ -13,7 +13,8 @@
 //   ransac_hyp_kernel     LANE = ITERATION, one 256-thread workgroup per pair, all iterations of the pair at once: the
 //                         4-point sample, the weighted fit, the 3x3 Jacobi SVD and the pre-screen (an upper bound of the
 //                         matches that can pass errorFunction2's shortcut test; fewer than the inlier threshold => the
-//                         iteration certainly ends with refined_matches empty, node.cpp:1148-1154).  Leaves, per pair, a
+//                         iteration certainly ends with refined_matches empty, node.cpp:1148-1154); a last wave that is
+//                         at most half full spreads each hypothesis' pre-screen over its idle lanes.  Leaves, per pair, a
 //                         bit mask of the viable iterations and their transforms (in the rR / rt fields of the iteration's
 //                         record), the pair's initial walk state, and its place in the ORDER BUCKETS (pairs by their number of
 //                         viable iterations: the refinement launch takes the fullest first).  No slot machinery, no scoring state.
@@ -513,7 +514,15 @@ __global__ __launch_bounds__(kHypThreads) void ransac_hyp_kernel(const PairWork*
     tfc_get_transformation(acc, hypR, hypt);
     // a NaN transform leaves the refinement loop at once (:1144); so does, after its first scoring, a hypothesis that
     // cannot reach `thr` candidates (:1154) -- with the same outcome: refined_matches stays empty (:1133-1134)
-    const uint32_t may_pass = prescreen_may_pass_s4(hypR, hypt, S4, n_all, pmax, rc);
+    // The pair's last wave with iterations, when at most half full (200 iterations: 8 lanes of the fourth wave), spreads
+    // every hypothesis' pre-screen over 2, 4 or 8 lanes (prescreen_may_pass_s4_split); its lanes beyond the iterations are
+    // not in range, so nothing below reads the twelve floats the split leaves in them.
+    const int n_wave_iters = I - k0 - (__builtin_amdgcn_readfirstlane(tid >> 6) << 6);
+    uint32_t may_pass;
+    if (n_wave_iters >= 1 && n_wave_iters <= kWave / 2)
+      may_pass = prescreen_may_pass_s4_split(hypR, hypt, S4, n_all, pmax, rc, lane, n_wave_iters <= 8 ? 3 : n_wave_iters <= 16 ? 2 : 1);
+    else
+      may_pass = prescreen_may_pass_s4(hypR, hypt, S4, n_all, pmax, rc);
     const bool viable = in_range && !has_nan12(hypR, hypt) && may_pass >= thr;
     const uint64_t vm = __ballot(viable);
     if (lane == 0) vm_pair[k >> 6] = vm;  // (k0 and the wave's first lane are multiples of 64)
