@@ -1452,6 +1452,185 @@ int rgbdfe_sensor_detect_describe_batch_nodes(rgbdfe_ctx* ctx, int32_t n_frames,
                                               float* xyz1, int32_t* n_out, const int32_t* node_ids,
                                               const rgbdfe_sensor_cloud* cloud);
 
+/* ---- the SLAM step (GraphManager::addNode, graph_manager.cpp:360-898; isBigTrafo / isSmallTrafo misc.cpp:272-315) --------
+ * One call per frame over the stages above: the frame is uploaded or detected into a node of the context first (the
+ * caller names it: `slot` below is that node id), rgbdfe_slam_add_node then selects candidates, compares, decides, updates
+ * the pose graph and optimises, and reports what it did.  The contract is the reference's code with its quirks
+ * (restated; DESIGN.md 4.27 names every choice and deviation).
+ *
+ * An rgbdfe_slam borrows a context (may be NULL: the decision machine alone, see rgbdfe_slam_begin) and a pose graph the
+ *   caller made; the strategy is whatever the caller set on that graph.  It keeps graph_ as a table graph id -> slot,
+ *   keyframe_ids_, next_seq_id, curr_best_result_, valid_tf_estimate_ and the stamp of every node, and the counters of
+ *   sequential and loop-closure edges.  Graph ids are the reference's: id = graph_.size() when the frame passes the feature
+ *   gate, vertex_id = id.  Every output speaks in graph ids.  A dropped frame consumes no id and its slot stays the caller's.
+ * The step, for a node of n_rows rows stamped (stamp_sec, stamp_nsec):
+ *   1. n_rows < min_matches: RGBDFE_SLAM_TOO_FEW_FEATURES, nothing changes (also with keep_all_nodes, addNode :687).
+ *   2. Empty graph: firstNode (:360-402): id 0, estimate init_base_pose, fixed, keyframe 0: RGBDFE_SLAM_FIRST.
+ *   3. nodeComparisons (:421-658).  earliest_loop_closure_node = the new id, under every strategy, RGBDFE_POSE_RELATIVE_TO_NONE
+ *      included (:444; the keyframe rule below reads it, the optimiser only under LARGEST_LOOP).  prev_best is read from a
+ *      fresh result and is always -1 (:452-453): the "reuse best" append of :524-526 never happens.
+ *      Initial comparison, only when min_translation_meter > 0 or min_rotation_degree > 0: against graph_[size - 1].  An
+ *        edge with !isBigTrafo || !isSmallTrafo: RGBDFE_SLAM_MOTION_OUT_OF_BOUNDS, the frame is dropped, curr_best_result_
+ *        keeps the result and broadcast_pose = X(previous) * Z.  Otherwise addEdgeToG2O(edge, largeEdge = 1, set_estimate =
+ *        1) and predecessor_matched = 1.
+ *      Candidates: rgbdfe_potential_edge_targets(predecessor_candidates - 1, neighbor_candidates, min_sampled_candidates,
+ *        geodesic_depth, ...): after a matched predecessor with predecessor_id = curr_best.id1 and include_predecessor = 0,
+ *        otherwise with the sequentially previous id and include_predecessor = 1.  Draws: the generator of
+ *        rgbdfe_slam_set_rand, else the counter-based one seeded with seed + (add_node / begin calls before this one).
+ *      Comparisons in list order as one batch (the concurrent_edge_construction branch, :531-583).  Per result with an edge:
+ *        dt = stamp(new) - stamp(older) as ros::Duration (integer seconds and nanoseconds, normalised, sec + 1e-9 nsec);
+ *        accepted iff isSmallTrafo(T, dt) and addEdgeToG2O(edge, largeEdge = isBigTrafo(T), set_estimate = n_inl > best.n_inl);
+ *        then predecessor_matched |= (id1 == id2 - 1), updateInlierFeatures, valid_tf_estimate[id1] = 1, best = this result if
+ *        n_inl > best.n_inl, edge_to_keyframe |= (id1 is a keyframe).
+ *      addEdgeToG2O (:811-898): the new node has no vertex yet and !largeEdge: refused.  Otherwise the vertex is created
+ *        (rgbdfe_pose_graph_add_node) with X2 = X1 * Z, or X2 = X1 * Z is written when set_estimate; the edge is
+ *        rgbdfe_pose_graph_add_edge_se3 with information I * info_scale (1e-2 I for an ICP edge, node.cpp:1407 -- the only value
+ *        the reference defines for one); |id1 - id2| > predecessor_candidates counts as a loop closure, else as sequential.
+ *      isBigTrafo / isSmallTrafo on the double cast of the float transform, host libm, no contraction: angle = acos((trace -
+ *        1) / 2) * 180 / pi without a clamp (a NaN fails both comparisons), dist = sqrt((tx tx + ty ty) + tz tz); big: dist >
+ *        min_translation_meter || angle > min_rotation_degree; small: seconds <= 0, or dist / seconds < max_translation_meter
+ *        && angle / seconds < max_rotation_degree.
+ *      Constant-position edge (:624-655) iff (!found && have_odometry_frame) || (!found && keep_anyway) ||
+ *        (!predecessor_matched && |dt_prev| < 0.1), keep_anyway = keep_all_nodes || (n_rows > min_matches && keep_good_nodes),
+ *        |dt_prev| as float: edge (previous id -> new id, identity, I / |dt_prev|) with largeEdge = set_estimate = 1,
+ *        valid_tf_estimate[new] = 0, curr_best_result_ = an empty result carrying this edge.  Deviation: |dt_prev| == 0 would
+ *        hand the optimiser an infinite matrix; the edge is then not added (constant_position = RGBDFE_SLAM_CONSTANT_SKIPPED).
+ *      found = an edge was added, the constant-position edge included.
+ *   4. found (:704-751): id % create_cloud_every_nth_node != 0: the node's cloud is released.  !edge_to_keyframe &&
+ *      earliest_loop_closure_node > keyframe_ids_.back(): addKeyframe(id - 1) (earliest is lowered only under LARGEST_LOOP).
+ *      optimizer_skip_step > 0 && vertices % optimizer_skip_step == 0: rgbdfe_pose_graph_optimize_graph(optimizer_iterations),
+ *      synchronously.  RGBDFE_SLAM_ADDED.
+ *      not found, one node in the graph and n_rows > rows of node 0 (:762-769): the graph is reset and the new node becomes
+ *      firstNode: RGBDFE_SLAM_REPLACED_FIRST (node 0's slot is released); otherwise RGBDFE_SLAM_NO_MATCH, the frame is dropped.
+ *   5. addKeyframe (:784-809): with clear_non_keyframes and >= 2 keyframes every node strictly between the two most recent
+ *      keyframes loses its features and its cloud (its slot is released, slot_of becomes -1, matchable 0), before the new
+ *      id is appended.  A later comparison with such a node gives no edge.
+ * Not built: localization_only_, landmarks, odometry edges from tf, GUI signals and rviz markers,
+ *   octomap_online_creation (chain rgbdfe_octomap_insert_nodes), concurrent optimisation, the non-concurrent comparison order,
+ *   max_connections.
+ * matchNodePair's chain behind the pair op (node.cpp:1340-1377), inside rgbdfe_slam_add_node, each stage one batch per list:
+ *   use_icp != 0: the ICP fallback (rgbdfe_icp_align_nodes with its default parameters, the older node's cloud onto the new
+ *   node's, identity guess) serves the results WITHOUT a RANSAC transformation whose node is adjacent (new id - its id <= 1);
+ *   a converged alignment is an edge with final_trafo = icp_trafo (the literal assignment), information 1e-2 I, no inliers
+ *   (RGBDFE_SLAM_RESULT_ICP).  observability_threshold > 0: the pairwise observation likelihood (two
+ *   rgbdfe_observation_likelihood jobs per edge with emm__skip_step, rgbdfe_observation_criterion_met) on the RANSAC edges
+ *   only; an edge it withdraws (RGBDFE_SLAM_RESULT_WITHDRAWN) is not offered to ICP.  The nodes named need resident clouds
+ *   (RGBDFE_ERR_UNKNOWN_NODE otherwise).
+ *
+ * rgbdfe_slam_begin / rgbdfe_slam_feed: the decision machine without the device, for callers that run the comparisons
+ *   themselves.  begin either finishes the step (*n_ids = 0, *step filled) or hands out graph ids to compare the new node
+ *   with (*n_ids > 0); feed takes their results -- results[k] belongs to ids[k]: an edge iff results[k].id1 >= 0, its ids are
+ *   taken from the list, not from the record (whose ids name the context's nodes) -- and again finishes or hands out the
+ *   next list.  flags (may be NULL) per result: RGBDFE_SLAM_RESULT_ICP: an ICP edge; RGBDFE_SLAM_RESULT_WITHDRAWN: the
+ *   measurement model withdrew the edge.  A node whose slot was released (slot_of -1) has no features: feed a record
+ *   with id1 = -1 for it.  With a context, the finished step releases slots and clouds and optimises as add_node does;
+ *   without one the step only says what is due (optimize_due, cloud_released, cleared_first / _last, released_slot).
+ * rgbdfe_slam_add_node = begin, rgbdfe_match_pair_list_device per list, feed, and ONE launch of the inlier-statistics
+ *   kernel over the batch's records where they lie in device memory.  Single-device contexts.  rgbdfe_slam_create refuses
+ *   (RGBDFE_ERR_CAPACITY) parameters whose longest candidate list -- predecessor + neighbor + sampled candidates -- exceeds
+ *   max_pairs_per_batch or RGBDFE_SLAM_MAX_CANDIDATES, so no step can fail for its size half way.  A device error in the
+ *   middle of a step (a failed launch or copy) abandons the step: the call returns the error, and what the step had added to
+ *   the graph by then stays -- rgbdfe_slam_reset before the object is used again.
+ * feature_matching_stats_ (node.h, updateInlierFeatures graph_manager.cpp:409-419): every node slot of a context has
+ *   max_keypoints saturating 8-bit counters, zero when a node is uploaded or detected into the slot.
+ *   rgbdfe_update_inlier_features: for every pair k with accept[k] != 0 and every set bit m of its record's inlier_mask,
+ *   stats[query_ids[k]][all_q[m]] and stats[train_ids[k]][all_t[m]] are incremented, stopping at 255 -- the sequential loop's
+ *   result whatever the order (32-bit compare-and-swap on the containing word; integers only).  d_records: n
+ *   rgbdfe_match_result in device memory (what rgbdfe_match_pair_list_device left); the lists make no second trip to the
+ *   host.  No launch when no accept byte is set.  *launched (may be NULL) = kernel launches.
+ *   rgbdfe_node_feature_stats: the counters of a node's rows (capacity < rows: RGBDFE_ERR_CAPACITY); returns the row count.
+ * rgbdfe_pose_graph_add_keyframe: appends to keyframe_ids_ (the reference promotes id - 1 after the fact).
+ * rgbdfe_pose_graph_clear: resetGraph: nodes, edges, keyframes gone; the strategy stays. */
+#define RGBDFE_SLAM_MAX_CANDIDATES 64
+#define RGBDFE_SLAM_TOO_FEW_FEATURES 1
+#define RGBDFE_SLAM_FIRST 2
+#define RGBDFE_SLAM_MOTION_OUT_OF_BOUNDS 3
+#define RGBDFE_SLAM_ADDED 4
+#define RGBDFE_SLAM_NO_MATCH 5
+#define RGBDFE_SLAM_REPLACED_FIRST 6
+#define RGBDFE_SLAM_VERDICT_NO_EDGE 0
+#define RGBDFE_SLAM_VERDICT_ACCEPTED 1
+#define RGBDFE_SLAM_VERDICT_NOT_SMALL 2
+#define RGBDFE_SLAM_VERDICT_TOO_SHORT 3      /* addEdgeToG2O refused: no vertex yet and not a big transformation */
+#define RGBDFE_SLAM_VERDICT_WITHDRAWN 4      /* by the measurement model */
+#define RGBDFE_SLAM_VERDICT_OUT_OF_BOUNDS 5  /* the initial comparison's edge */
+#define RGBDFE_SLAM_VERDICT_ICP 16           /* or-ed in: the edge came from the ICP fallback */
+#define RGBDFE_SLAM_RESULT_ICP 1
+#define RGBDFE_SLAM_RESULT_WITHDRAWN 2
+#define RGBDFE_SLAM_CONSTANT_NONE 0
+#define RGBDFE_SLAM_CONSTANT_ADDED 1
+#define RGBDFE_SLAM_CONSTANT_SKIPPED 2
+typedef struct rgbdfe_slam_params {
+  int32_t min_matches;              /* 20    (parameter_server.cpp:85) */
+  int32_t predecessor_candidates;   /* 4 */
+  int32_t neighbor_candidates;      /* 4 */
+  int32_t min_sampled_candidates;   /* 4 */
+  int32_t geodesic_depth;           /* 3 */
+  int32_t keep_all_nodes;           /* 0 */
+  int32_t keep_good_nodes;          /* 0 */
+  int32_t clear_non_keyframes;      /* 0 */
+  int32_t create_cloud_every_nth_node;  /* 1 */
+  int32_t optimizer_skip_step;      /* 1 */
+  int32_t use_icp;                  /* 0 */
+  int32_t emm__skip_step;           /* 8 */
+  int32_t have_odometry_frame;      /* 0: "odom_frame_name" is empty */
+  uint32_t seed;                    /* 0 */
+  double min_translation_meter;     /* 0.0 */
+  double min_rotation_degree;       /* 0.0 */
+  double max_translation_meter;     /* 1e10 */
+  double max_rotation_degree;       /* 360 */
+  double optimizer_iterations;      /* 0.01 */
+  double observability_threshold;   /* -0.6 */
+  double init_base_pose[16];        /* identity; column-major */
+} rgbdfe_slam_params;
+typedef struct rgbdfe_slam_step {
+  int32_t status;                   /* RGBDFE_SLAM_* */
+  int32_t id;                       /* the graph id assigned, or -1 */
+  int32_t found;                    /* nodeComparisons' return value */
+  int32_t initial_id;               /* the node of the initial comparison, or -1 */
+  int32_t initial_verdict;
+  int32_t n_candidates;
+  int32_t candidates[RGBDFE_SLAM_MAX_CANDIDATES];
+  uint8_t verdicts[RGBDFE_SLAM_MAX_CANDIDATES];
+  int32_t best_id1, best_id2, best_n_inl;   /* curr_best_result_ after the step (-1, -1, 0: an empty result) */
+  int32_t predecessor_matched;
+  int32_t edge_to_keyframe;
+  int32_t keyframe_added;           /* or -1 */
+  int32_t cleared_first, cleared_last;  /* the ids addKeyframe cleared (inclusive), or -1, -1 */
+  int32_t released_slot;            /* REPLACED_FIRST: the slot of the node that was replaced, else -1 */
+  int32_t constant_position;        /* RGBDFE_SLAM_CONSTANT_* */
+  int32_t cloud_released;           /* id % create_cloud_every_nth_node != 0 */
+  int32_t has_broadcast_pose;
+  int32_t optimize_due, optimized, lm_iterations;
+  int32_t sequential_edges, loop_closure_edges;   /* the counters after the step */
+  int32_t stats_launches;           /* launches of the inlier-statistics kernel (0 or 1) */
+  double motion_estimate[16];       /* curr_motion_estimate: the new vertex's estimate when it was last written */
+  double broadcast_pose[16];        /* MOTION_OUT_OF_BOUNDS: previous * incremental */
+  double chi2;                      /* after the optimisation */
+  double seconds[4];                /* candidates, comparisons, decisions, optimisation */
+} rgbdfe_slam_step;
+typedef struct rgbdfe_slam rgbdfe_slam;
+void rgbdfe_slam_default_params(rgbdfe_slam_params* p);
+int rgbdfe_slam_create(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, const rgbdfe_slam_params* p, rgbdfe_slam** out);
+void rgbdfe_slam_destroy(rgbdfe_slam* s);
+int rgbdfe_slam_reset(rgbdfe_slam* s);
+int rgbdfe_slam_set_rand(rgbdfe_slam* s, rgbdfe_rand_fn rand_fn, void* rand_state);
+int rgbdfe_slam_add_node(rgbdfe_slam* s, int32_t slot, int64_t stamp_sec, int32_t stamp_nsec, rgbdfe_slam_step* out);
+int rgbdfe_slam_begin(rgbdfe_slam* s, int32_t slot, int32_t n_rows, int64_t stamp_sec, int32_t stamp_nsec, int32_t* ids,
+                      int32_t capacity, int32_t* n_ids, rgbdfe_slam_step* step);
+int rgbdfe_slam_feed(rgbdfe_slam* s, const rgbdfe_compact_result* results, const uint8_t* flags, int32_t n, int32_t* ids,
+                     int32_t capacity, int32_t* n_ids, rgbdfe_slam_step* step);
+int rgbdfe_slam_node_count(const rgbdfe_slam* s);                 /* graph_.size() */
+int rgbdfe_slam_slot_of(const rgbdfe_slam* s, int32_t id);        /* the slot, -1: released, < -1: an error status */
+int rgbdfe_slam_valid_tf(const rgbdfe_slam* s, int32_t id);       /* 0 / 1, or an error status */
+int rgbdfe_slam_keyframes(const rgbdfe_slam* s, int32_t* ids, int32_t capacity, int32_t* n_out);
+int rgbdfe_sizeof_slam_step(void);
+int rgbdfe_update_inlier_features(rgbdfe_ctx* ctx, const void* d_records, const int32_t* query_ids, const int32_t* train_ids,
+                                  const uint8_t* accept, int32_t n, int32_t* launched);
+int rgbdfe_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, uint8_t* out, int32_t capacity);
+int rgbdfe_pose_graph_add_keyframe(rgbdfe_pose_graph* g, int32_t node_id);
+int rgbdfe_pose_graph_clear(rgbdfe_pose_graph* g);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, every launch of the dominant kernels is bracketed by HIP events on the
  * stream it runs on; totals are read back with rgbdfe_get_kernel_time. */

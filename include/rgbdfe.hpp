@@ -511,9 +511,51 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
     return out;
   }
 
+  // bool GraphManager::addNode(Node* new_node) (graph_manager.cpp:681-782) as one call over the stages above: the node is
+  // resident under new_node->id_ (its slot), the stamp is its header's.  Candidate selection, the pair batch, the
+  // decisions, the pose graph, updateInlierFeatures and the optimiser run inside; `step` (optional) says what happened, in
+  // graph ids (step->id: the id the node got, -1 when the frame was dropped; slotOf(id) leads back to the slot).  The
+  // parameters are fixed by the first call (slamParams() before it changes them).  Returns what the reference returns:
+  // the node was added.  false is a dropped frame OR a failed call: lastAddNodeStatus() tells them apart (RGBDFE_OK after a
+  // step that ran, whatever it decided; the rgbdfe_status of the failing call otherwise, rgbdfe_last_error has its words).
+  // Do not mix with nodeAdded / addEdgeToG2O on the same object: the step keeps the graph itself.
+  rgbdfe_slam_params& slamParams() {
+    if (!slam_params_set_) { rgbdfe_slam_default_params(&slam_params_); slam_params_set_ = true; }
+    return slam_params_;
+  }
+  bool addNode(const Node* new_node, int64_t stamp_sec, int32_t stamp_nsec, rgbdfe_slam_step* step = nullptr) {
+    if (!slam_) {
+      rgbdfe_slam* s = nullptr;
+      add_node_status_ = rgbdfe_slam_create(fe_.get(), topology_.get(), &slamParams(), &s);
+      if (add_node_status_ != RGBDFE_OK) return false;
+      slam_.reset(s);
+    }
+    rgbdfe_slam_step local;
+    rgbdfe_slam_step* st = step ? step : &local;
+    add_node_status_ = rgbdfe_slam_add_node(slam_.get(), new_node->id_, stamp_sec, stamp_nsec, st);
+    if (add_node_status_ != RGBDFE_OK) return false;
+    return st->status == RGBDFE_SLAM_FIRST || st->status == RGBDFE_SLAM_ADDED || st->status == RGBDFE_SLAM_REPLACED_FIRST;
+  }
+  int lastAddNodeStatus() const { return add_node_status_; }
+  int slotOf(int graph_id) const { return slam_ ? rgbdfe_slam_slot_of(slam_.get(), graph_id) : RGBDFE_ERR_UNKNOWN_NODE; }
+  bool validTfEstimate(int graph_id) const { return slam_ && rgbdfe_slam_valid_tf(slam_.get(), graph_id) == 1; }
+  std::vector<int32_t> keyframeIds() const {
+    std::vector<int32_t> ids;
+    if (!slam_) return ids;
+    int32_t n = 0;
+    ids.resize((size_t)rgbdfe_slam_node_count(slam_.get()) + 1);
+    if (rgbdfe_slam_keyframes(slam_.get(), ids.data(), (int32_t)ids.size(), &n) != RGBDFE_OK) n = 0;
+    ids.resize((size_t)n);
+    return ids;
+  }
+
  private:
   const FrontEnd& fe_;
   std::unique_ptr<rgbdfe_pose_graph, void (*)(rgbdfe_pose_graph*)> topology_;
+  std::unique_ptr<rgbdfe_slam, void (*)(rgbdfe_slam*)> slam_{nullptr, &rgbdfe_slam_destroy};   // (goes before topology_)
+  rgbdfe_slam_params slam_params_;
+  bool slam_params_set_ = false;
+  int add_node_status_ = RGBDFE_OK;
 };
 
 // The loop of GraphManager::saveAllCloudsToFile (src/graph_mgr_io.cpp:529-552): transformAndAppendPointCloud

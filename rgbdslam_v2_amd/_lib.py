@@ -121,6 +121,41 @@ class IcpParams(C.Structure):   # rgbdfe_icp_params
                 ("euclidean_fitness_epsilon", C.c_double), ("max_iterations", C.c_int32), ("desired_size", C.c_int32)]
 
 
+SLAM_MAX_CANDIDATES = 64   # RGBDFE_SLAM_MAX_CANDIDATES
+SLAM_STATUS = {1: "too_few_features", 2: "first", 3: "motion_out_of_bounds", 4: "added", 5: "no_match",
+               6: "replaced_first"}                                                  # RGBDFE_SLAM_*
+SLAM_VERDICTS = ("no_edge", "accepted", "not_small", "too_short", "withdrawn", "out_of_bounds")   # RGBDFE_SLAM_VERDICT_*
+SLAM_VERDICT_ICP = 16
+SLAM_RESULT_ICP, SLAM_RESULT_WITHDRAWN = 1, 2
+SLAM_CONSTANT_NONE, SLAM_CONSTANT_ADDED, SLAM_CONSTANT_SKIPPED = 0, 1, 2
+
+
+class SlamParams(C.Structure):   # rgbdfe_slam_params
+    _fields_ = [("min_matches", C.c_int32), ("predecessor_candidates", C.c_int32), ("neighbor_candidates", C.c_int32),
+                ("min_sampled_candidates", C.c_int32), ("geodesic_depth", C.c_int32), ("keep_all_nodes", C.c_int32),
+                ("keep_good_nodes", C.c_int32), ("clear_non_keyframes", C.c_int32),
+                ("create_cloud_every_nth_node", C.c_int32), ("optimizer_skip_step", C.c_int32), ("use_icp", C.c_int32),
+                ("emm__skip_step", C.c_int32), ("have_odometry_frame", C.c_int32), ("seed", C.c_uint32),
+                ("min_translation_meter", C.c_double), ("min_rotation_degree", C.c_double),
+                ("max_translation_meter", C.c_double), ("max_rotation_degree", C.c_double),
+                ("optimizer_iterations", C.c_double), ("observability_threshold", C.c_double),
+                ("init_base_pose", C.c_double * 16)]
+
+
+class SlamStep(C.Structure):   # rgbdfe_slam_step
+    _fields_ = [("status", C.c_int32), ("id", C.c_int32), ("found", C.c_int32), ("initial_id", C.c_int32),
+                ("initial_verdict", C.c_int32), ("n_candidates", C.c_int32),
+                ("candidates", C.c_int32 * SLAM_MAX_CANDIDATES), ("verdicts", C.c_uint8 * SLAM_MAX_CANDIDATES),
+                ("best_id1", C.c_int32), ("best_id2", C.c_int32), ("best_n_inl", C.c_int32),
+                ("predecessor_matched", C.c_int32), ("edge_to_keyframe", C.c_int32), ("keyframe_added", C.c_int32),
+                ("cleared_first", C.c_int32), ("cleared_last", C.c_int32), ("released_slot", C.c_int32),
+                ("constant_position", C.c_int32), ("cloud_released", C.c_int32), ("has_broadcast_pose", C.c_int32),
+                ("optimize_due", C.c_int32), ("optimized", C.c_int32), ("lm_iterations", C.c_int32),
+                ("sequential_edges", C.c_int32), ("loop_closure_edges", C.c_int32), ("stats_launches", C.c_int32),
+                ("motion_estimate", C.c_double * 16), ("broadcast_pose", C.c_double * 16), ("chi2", C.c_double),
+                ("seconds", C.c_double * 4)]
+
+
 class RgbdfeDisplayParams(C.Structure):   # rgbdfe_display_params
     _fields_ = [("display_type", C.c_int32), ("visualization_skip_step", C.c_int32),
                 ("squared_meshing_threshold", C.c_double), ("maximum_depth", C.c_double)]
@@ -588,6 +623,39 @@ def load():
     L.rgbdfe_icp_align_clouds.argtypes = [vp, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(IcpParams), vp, vp, vp, vp, C.c_int64]
     L.rgbdfe_filter_cloud.restype = C.c_int
     L.rgbdfe_filter_cloud.argtypes = [vp, vp, C.c_int64, i32, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    L.rgbdfe_slam_default_params.restype = None
+    L.rgbdfe_slam_default_params.argtypes = [C.POINTER(SlamParams)]
+    L.rgbdfe_slam_create.restype = C.c_int
+    L.rgbdfe_slam_create.argtypes = [vp, vp, C.POINTER(SlamParams), C.POINTER(vp)]
+    L.rgbdfe_slam_destroy.restype = None
+    L.rgbdfe_slam_destroy.argtypes = [vp]
+    L.rgbdfe_slam_reset.restype = C.c_int
+    L.rgbdfe_slam_reset.argtypes = [vp]
+    L.rgbdfe_slam_set_rand.restype = C.c_int
+    L.rgbdfe_slam_set_rand.argtypes = [vp, RAND_FN, vp]
+    L.rgbdfe_slam_add_node.restype = C.c_int
+    L.rgbdfe_slam_add_node.argtypes = [vp, i32, C.c_int64, i32, C.POINTER(SlamStep)]
+    L.rgbdfe_slam_begin.restype = C.c_int
+    L.rgbdfe_slam_begin.argtypes = [vp, i32, i32, C.c_int64, i32, vp, i32, C.POINTER(i32), C.POINTER(SlamStep)]
+    L.rgbdfe_slam_feed.restype = C.c_int
+    L.rgbdfe_slam_feed.argtypes = [vp, vp, vp, i32, vp, i32, C.POINTER(i32), C.POINTER(SlamStep)]
+    for name in ("rgbdfe_slam_node_count", "rgbdfe_slam_slot_of", "rgbdfe_slam_valid_tf"):
+        getattr(L, name).restype = C.c_int
+    L.rgbdfe_slam_node_count.argtypes = [vp]
+    L.rgbdfe_slam_slot_of.argtypes = [vp, i32]
+    L.rgbdfe_slam_valid_tf.argtypes = [vp, i32]
+    L.rgbdfe_slam_keyframes.restype = C.c_int
+    L.rgbdfe_slam_keyframes.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.rgbdfe_sizeof_slam_step.restype = C.c_int
+    L.rgbdfe_sizeof_slam_step.argtypes = []
+    L.rgbdfe_update_inlier_features.restype = C.c_int
+    L.rgbdfe_update_inlier_features.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(i32)]
+    L.rgbdfe_node_feature_stats.restype = C.c_int
+    L.rgbdfe_node_feature_stats.argtypes = [vp, i32, vp, i32]
+    L.rgbdfe_pose_graph_add_keyframe.restype = C.c_int
+    L.rgbdfe_pose_graph_add_keyframe.argtypes = [vp, i32]
+    L.rgbdfe_pose_graph_clear.restype = C.c_int
+    L.rgbdfe_pose_graph_clear.argtypes = [vp]
     _lib = L
     return L
 
@@ -639,4 +707,8 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_sizeof_sensor_frame", "rgbdfe_ingest_frame", "rgbdfe_sensor_detect_describe",
     "rgbdfe_sensor_detect_describe_batch_nodes",
     "rgbdfe_icp_default_params", "rgbdfe_icp_align_nodes", "rgbdfe_icp_align_clouds", "rgbdfe_filter_cloud",
+    "rgbdfe_slam_default_params", "rgbdfe_slam_create", "rgbdfe_slam_destroy", "rgbdfe_slam_reset", "rgbdfe_slam_set_rand",
+    "rgbdfe_slam_add_node", "rgbdfe_slam_begin", "rgbdfe_slam_feed", "rgbdfe_slam_node_count", "rgbdfe_slam_slot_of",
+    "rgbdfe_slam_valid_tf", "rgbdfe_slam_keyframes", "rgbdfe_sizeof_slam_step", "rgbdfe_update_inlier_features",
+    "rgbdfe_node_feature_stats", "rgbdfe_pose_graph_add_keyframe", "rgbdfe_pose_graph_clear",
 ]

@@ -145,6 +145,7 @@ void rgbdfe_destroy(rgbdfe_ctx* ctx) {
   if (ctx->nodes_ready_ev) (void)hipEventDestroy(ctx->nodes_ready_ev);
   if (ctx->d_desc4) (void)hipFree(ctx->d_desc4);
   if (ctx->d_kp2d) (void)hipFree(ctx->d_kp2d);
+  if (ctx->d_feat_stats) (void)hipFree(ctx->d_feat_stats);
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->icp.p) (void)hipFree(ctx->icp.p);
   for (hipEvent_t e : ctx->orb_upload_done) if (e) (void)hipEventDestroy(e);
@@ -201,15 +202,25 @@ static uint32_t register_fresh_node(rgbdfe_ctx* ctx, int32_t node_id, uint32_t k
   return slot;
 }
 
+// A node is about to be written into `slot`: its feature_matching_stats_ start at zero.  On the context's stream, where the
+// statistics kernel and rgbdfe_node_feature_stats run.  Nothing to do before the counters exist (api_slam.hip).
+static int zero_feature_stats(rgbdfe_ctx* ctx, uint32_t slot) {
+  if (!ctx->d_feat_stats) return RGBDFE_OK;
+  const size_t stride = ctx->feat_stats_stride();
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_feat_stats + (size_t)slot * stride, 0, stride, ctx->stream));
+  return RGBDFE_OK;
+}
+
 int acquire_node_slot(rgbdfe_ctx* ctx, int32_t node_id, uint32_t kind, uint32_t* slot, bool lanes_idle) {
   auto it = ctx->nodes.find(node_id);
   if (it != ctx->nodes.end()) {  // overwrite in place: wait for batches that may still read it
     *slot = it->second.slot;
+    if (const int rc = zero_feature_stats(ctx, *slot)) return rc;
     return lanes_idle ? RGBDFE_OK : wait_for_pair_lanes(ctx);
   }
   if (ctx->free_slots.empty()) return no_free_slot(ctx);
   *slot = register_fresh_node(ctx, node_id, kind);
-  return RGBDFE_OK;
+  return zero_feature_stats(ctx, *slot);
 }
 
 bool node_id_twice(int32_t n, const int32_t* node_ids, bool negative_is_none) {
@@ -238,6 +249,7 @@ int reserve_node_slots(rgbdfe_ctx* ctx, int32_t n, const int32_t* node_ids, uint
     if (none(i)) continue;
     auto it = ctx->nodes.find(node_ids[i]);
     (*slot_of)[(size_t)i] = it != ctx->nodes.end() ? it->second.slot : register_fresh_node(ctx, node_ids[i], kind);
+    if (const int rc = zero_feature_stats(ctx, (uint32_t)(*slot_of)[(size_t)i])) return rc;
   }
   return RGBDFE_OK;
 }

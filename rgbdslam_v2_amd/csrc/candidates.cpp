@@ -124,6 +124,31 @@ int rgbdfe_pose_graph_set_matchable(rgbdfe_pose_graph* g, int32_t node_id, int32
   return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
 }
 
+// GraphManager::addKeyframe's keyframe_ids_.push_back (graph_manager.cpp:804): the reference promotes id - 1 after the fact
+int rgbdfe_pose_graph_add_keyframe(rgbdfe_pose_graph* g, int32_t node_id) try {
+  if (!g) return RGBDFE_ERR_INVALID_ARG;
+  if (g->nodes.find(node_id) == g->nodes.end()) return RGBDFE_ERR_UNKNOWN_NODE;
+  g->keyframes.push_back(node_id);
+  return RGBDFE_OK;
+} catch (const std::bad_alloc&) {
+  return RGBDFE_ERR_OUT_OF_MEMORY;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+// resetGraph: nodes, edges and keyframes go; the strategy stays, and so do the optimiser's device buffers (they are sized
+// again by the next plan)
+int rgbdfe_pose_graph_clear(rgbdfe_pose_graph* g) {
+  if (!g) return RGBDFE_ERR_INVALID_ARG;
+  g->nodes.clear();
+  g->camera_vertices.clear();
+  g->adjacency.clear();
+  g->keyframes.clear();
+  g->edges.clear();
+  g->earliest_loop_closure_node = 0;
+  return RGBDFE_OK;
+}
+
 int rgbdfe_potential_edge_targets(const rgbdfe_pose_graph* g, int32_t sequential_targets, int32_t geodesic_targets,
                                   int32_t sampled_targets, int32_t geodesic_depth, int32_t predecessor_id,
                                   int32_t include_predecessor, rgbdfe_rand_fn rand_fn, void* rand_state, uint32_t seed,

@@ -1169,6 +1169,18 @@ int rgbdfe_graph_stats(rgbdfe_ctx* ctx, int64_t* out, int32_t n_out) {
 
 int rgbdfe_sizeof_match_result(void) { return impl::rgbdfe_sizeof_match_result(); }
 int rgbdfe_sizeof_compact_result(void) { return impl::rgbdfe_sizeof_compact_result(); }
+int rgbdfe_update_inlier_features(rgbdfe_ctx* ctx, const void* d_records, const int32_t* query_ids, const int32_t* train_ids,
+                                  const uint8_t* accept, int32_t n, int32_t* launched) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  if (RGBDFE_IS_GROUP(ctx)) return fail(ctx, RGBDFE_ERR_INVALID_ARG, "rgbdfe_update_inlier_features takes device pointers: single-device contexts only");
+  return guarded(ctx, [&]() -> int { return impl::rgbdfe_update_inlier_features(ctx, d_records, query_ids, train_ids, accept, n, launched); });
+}
+
+int rgbdfe_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, uint8_t* out, int32_t capacity) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_node_feature_stats(c, node_id, out, capacity));
+}
+
 int rgbdfe_abi_version(void) { return impl::rgbdfe_abi_version(); }
 
 }  // extern "C"

@@ -203,6 +203,9 @@ struct rgbdfe_ctx {
   uint32_t* d_desc4 = nullptr; // max_nodes x max_kp x 32 dwords: every descriptor bit as an fp4 (+-1) operand nibble, in
                                // MFMA fragment order per tile of 32 rows (hamming_mfma.hip)
   float* d_kp2d = nullptr;     // max_nodes x max_kp x 2: KeyPoint.pt (allocated with the first rgbdfe_upload_node_keypoints)
+  uint8_t* d_feat_stats = nullptr;  // max_nodes x feat_stats_stride(): feature_matching_stats_ (api_slam.hip), allocated zeroed
+                                    // with the first call that reads or writes it; until then every counter is 0 by definition
+  size_t feat_stats_stride() const { return ((size_t)cfg.max_keypoints + 3u) & ~(size_t)3u; }
   hipStream_t orb_upload_stream = nullptr;  // rgbdfe_detect_describe_batch: uploads of frame k+1 beside frame k
   hipStream_t orb_compute_stream = nullptr; // ... and frame k's description beside frame k+1's detection
   hipEvent_t orb_upload_done[OrbWorkspace::kSets] = {};
@@ -731,6 +734,9 @@ int rgbdfe_pack_inliers(rgbdfe_ctx* ctx, const void* d_records, int32_t n, int32
 int rgbdfe_sizeof_inlier_header(void);
 int rgbdfe_graph_stats(rgbdfe_ctx* ctx, int64_t* out, int32_t n_out);
 int rgbdfe_abi_version(void);
+int rgbdfe_update_inlier_features(rgbdfe_ctx* ctx, const void* d_records, const int32_t* query_ids, const int32_t* train_ids,
+                                  const uint8_t* accept, int32_t n, int32_t* launched);
+int rgbdfe_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, uint8_t* out, int32_t capacity);
 }  // namespace impl
 
 // ---- several devices behind one handle (api_group.hip)

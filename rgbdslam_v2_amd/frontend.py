@@ -232,7 +232,7 @@ class FrontEnd:
 
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value:
-            for ref in getattr(self, "_octomaps", []):  # a map goes before the context it lives on
+            for ref in getattr(self, "_octomaps", []) + getattr(self, "_slams", []):  # a map or a SLAM object goes before the context it lives on
                 m = ref()
                 if m is not None:
                     m.close()
@@ -279,6 +279,23 @@ class FrontEnd:
 
     def node_count(self, node_id: int) -> int:
         return self._L.rgbdfe_node_count(self._ctx, node_id)
+
+    def node_feature_stats(self, node_id: int) -> np.ndarray:
+        """Node::feature_matching_stats_ of a resident node: a saturating 8-bit counter per row (updateInlierFeatures)."""
+        out = np.zeros(max(self.node_count(node_id), 0), np.uint8)
+        n = self._L.rgbdfe_node_feature_stats(self._ctx, int(node_id), out.ctypes.data, len(out))
+        if n < 0:
+            self._check(n)
+        return out[:n]
+
+    def update_inlier_features(self, d_records_ptr: int, query_ids, train_ids, accept) -> int:
+        """updateInlierFeatures over n records in device memory for the pairs with accept != 0; returns the kernel launches."""
+        q, t = np.ascontiguousarray(query_ids, np.int32), np.ascontiguousarray(train_ids, np.int32)
+        a = np.ascontiguousarray(accept, np.uint8)
+        launched = C.c_int32(0)
+        self._check(self._L.rgbdfe_update_inlier_features(self._ctx, d_records_ptr, q.ctypes.data, t.ctypes.data, a.ctypes.data,
+                                                          len(q), C.byref(launched)))
+        return launched.value
 
     # -- the pair op ---------------------------------------------------------------
     def match_pair_list(self, query_ids: Sequence[int], train_ids: Sequence[int]) -> np.ndarray:
@@ -1497,6 +1514,130 @@ class GraphManager:
     def nodeComparisons(self, new_node: Node, nodes_to_comp: Sequence[Node]) -> List[MatchingResult]:
         recs = self.frontend.match_node_pairs(new_node.id_, [n.id_ for n in nodes_to_comp])
         return [record_to_matching_result(r) for r in recs]
+
+    def slam(self, **params) -> "Slam":
+        """The SLAM-step object over this manager's front end and pose graph (made by the first addNode with the defaults)."""
+        if getattr(self, "_slam", None) is None:
+            self._slam = Slam(self.frontend, self._graph(), **params)
+        elif params:
+            raise ValueError("the SLAM step's parameters are fixed when it is made")
+        return self._slam
+
+    def addNode(self, node: Node, stamp=(0, 0)) -> "SlamStepRecord":
+        """GraphManager::addNode (src/graph_manager.cpp:681-782) for a node that is resident under node.id_ (its slot);
+        stamp = (sec, nsec).  The step record says what happened; record.id is the graph id (node.id_ stays the slot)."""
+        return self.slam().add_node(node.id_, stamp)
+
+    def firstNode(self, node: Node, stamp=(0, 0)) -> "SlamStepRecord":
+        """GraphManager::firstNode (:360-402): addNode on an empty graph."""
+        if self.slam().node_count() != 0:
+            raise ValueError("firstNode: the graph is not empty")
+        return self.addNode(node, stamp)
+
+
+class SlamStepRecord:
+    """An rgbdfe_slam_step with names for its codes."""
+
+    def __init__(self, raw: "_lib.SlamStep"):
+        self.raw = raw
+        for name, _ in raw._fields_:
+            v = getattr(raw, name)
+            setattr(self, name, v if isinstance(v, (int, float)) else list(v))
+        n = raw.n_candidates
+        self.candidates, self.verdicts = self.candidates[:n], self.verdicts[:n]
+        self.status_name = _lib.SLAM_STATUS.get(raw.status, "?")
+        self.verdict_names = [_lib.SLAM_VERDICTS[v & 15] + ("+icp" if v & _lib.SLAM_VERDICT_ICP else "") for v in self.verdicts]
+        self.motion_estimate = np.array(raw.motion_estimate).reshape(4, 4).T
+        self.broadcast_pose = np.array(raw.broadcast_pose).reshape(4, 4).T
+
+    def __bool__(self):   # addNode's return value: "iff the node could be added"
+        return self.raw.status in (2, 4, 6)
+
+
+class Slam:
+    """rgbdfe_slam: GraphManager::addNode as one call (add_node), or as the decision machine alone (begin / feed) for callers
+    that run the comparisons themselves.  frontend may be None (no device: begin / feed only)."""
+
+    def __init__(self, frontend: Optional[FrontEnd], pose_graph, **params):
+        self._L = _lib.load()
+        self.frontend, self.pose_graph = frontend, pose_graph
+        self.params = _lib.SlamParams()
+        self._L.rgbdfe_slam_default_params(C.byref(self.params))
+        for k, v in params.items():
+            if k == "init_base_pose":
+                v = (C.c_double * 16)(*np.asarray(v, np.float64).reshape(4, 4).T.reshape(16))
+            elif not hasattr(self.params, k):
+                raise ValueError("unknown SLAM parameter " + k)
+            setattr(self.params, k, v)
+        self._s = C.c_void_p()
+        st = self._L.rgbdfe_slam_create(frontend._ctx if frontend is not None else None, pose_graph._g, C.byref(self.params),
+                                        C.byref(self._s))
+        if st != 0:
+            raise RgbdfeError(self._L.rgbdfe_status_string(st).decode())
+        self._ids = np.zeros(_lib.SLAM_MAX_CANDIDATES, np.int32)
+        if frontend is not None:
+            if not hasattr(frontend, "_slams"):
+                frontend._slams = []
+            frontend._slams.append(weakref.ref(self))
+
+    def close(self):
+        if getattr(self, "_s", None) and self._s.value:
+            self._L.rgbdfe_slam_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        if st != 0:
+            msg = self._L.rgbdfe_last_error(self.frontend._ctx).decode() if self.frontend is not None else ""
+            raise RgbdfeError(f"{self._L.rgbdfe_status_string(st).decode()}: {msg}")
+
+    def reset(self):
+        self._check(self._L.rgbdfe_slam_reset(self._s))
+
+    def add_node(self, slot: int, stamp=(0, 0)) -> SlamStepRecord:
+        st = _lib.SlamStep()
+        self._check(self._L.rgbdfe_slam_add_node(self._s, int(slot), int(stamp[0]), int(stamp[1]), C.byref(st)))
+        return SlamStepRecord(st)
+
+    def begin(self, slot: int, n_rows: int, stamp=(0, 0)):
+        """-> (graph ids to compare the new node with, None) or ([], the finished step record)."""
+        st, n = _lib.SlamStep(), C.c_int32(0)
+        self._check(self._L.rgbdfe_slam_begin(self._s, int(slot), int(n_rows), int(stamp[0]), int(stamp[1]), self._ids.ctypes.data,
+                                              len(self._ids), C.byref(n), C.byref(st)))
+        return ([int(i) for i in self._ids[:n.value]], None) if n.value else ([], SlamStepRecord(st))
+
+    def feed(self, results, flags=None):
+        """results: RESULT_DTYPE or COMPACT_DTYPE records, one per id handed out; -> as begin."""
+        results = np.asarray(results)
+        rec = results if results.dtype == _lib.COMPACT_DTYPE else _lib.compact_of(results)
+        rec = np.ascontiguousarray(rec)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        st, n = _lib.SlamStep(), C.c_int32(0)
+        self._check(self._L.rgbdfe_slam_feed(self._s, rec.ctypes.data, None if fl is None else fl.ctypes.data, len(rec),
+                                             self._ids.ctypes.data, len(self._ids), C.byref(n), C.byref(st)))
+        return ([int(i) for i in self._ids[:n.value]], None) if n.value else ([], SlamStepRecord(st))
+
+    def node_count(self) -> int:
+        return self._L.rgbdfe_slam_node_count(self._s)
+
+    def slot_of(self, graph_id: int) -> int:
+        return self._L.rgbdfe_slam_slot_of(self._s, int(graph_id))
+
+    def slots(self) -> List[int]:
+        return [self.slot_of(i) for i in range(self.node_count())]
+
+    def valid_tf(self) -> List[int]:
+        return [self._L.rgbdfe_slam_valid_tf(self._s, i) for i in range(self.node_count())]
+
+    def keyframes(self) -> List[int]:
+        ids, n = np.zeros(self.node_count() + 1, np.int32), C.c_int32(0)
+        self._check(self._L.rgbdfe_slam_keyframes(self._s, ids.ctypes.data, len(ids), C.byref(n)))
+        return [int(i) for i in ids[:n.value]]
 
 
 class OctoMap:
