@@ -1148,6 +1148,112 @@ int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32
                                    int64_t* n_vertices, int64_t* node_offsets, void* d_strips, int64_t strip_capacity,
                                    int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, void* stream);
 
+/* ---- rendering: the display-geometry stream rasterised into images on the device -----------------------------
+ * rgbdfe_render_nodes is what GL does with the vertex rows in GLViewer::paintGL / drawClouds / drawOneCloud
+ *   (glviewer.cpp:291-425) under the state of initializeGL (:195-211): a software rasteriser, since an Instinct card
+ *   has no graphics pipeline.  GL leaves rasterisation details to the implementation; this block fixes one admissible
+ *   choice (restated, not pinned; DESIGN.md 4.28 names each choice).  tests/render_oracle.py restates it in Python.
+ *   Input.  node_ids / transforms / display_params exactly as rgbdfe_display_geometry takes them.  The primitives are
+ *   that call's vertex stream; node k is drawn in the form that call reports in node_types[k]; a vertex is the stream's
+ *   row, bit for bit.  A primitive's id is the index in the whole stream of its first vertex: a point's id is its own
+ *   vertex; list triangle j of a node whose stream starts at o has id o + 3 j and vertices (o + 3 j, + 1, + 2) (one or
+ *   two rows left over at the end of a node draw nothing); triangle i of a strip record (s, count), 0 <= i < count - 2,
+ *   has id s + i and vertices (s + i, s + i + 1, s + i + 2) for even i, (s + i + 1, s + i, s + i + 2) for odd i.
+ *   Strips of fewer than three vertices draw nothing.  A stream of more than 2^32 - 2 vertices: RGBDFE_ERR_CAPACITY.
+ *   Camera.  view (GL's modelview without the per-cloud matrix) and projection, 4 x 4 doubles, column-major as the
+ *   Matrix4f of `transforms` (element (row, column) at [4 * column + row]).  Per vertex, in double, one rounding per
+ *   operation, a sum of products as ((a0 b0 + a1 b1) + a2 b2) + a3 b3:
+ *     world = the row's x, y, z (already ((R0 x + R1 y) + R2 z) + t in float), w = 1 (so a3 b3 is view's fourth column);
+ *     eye = view . world;  clip = projection . eye;  ndc = clip.xyz / clip.w (three divisions);
+ *     x_w = ((ndc.x + 1) * W) / 2,  y_w = ((ndc.y + 1) * H) / 2,  z_w = (ndc.z / 2) + 1/2.
+ *   y_w points up: image row = H - 1 - window row.  No transcendental function runs on the device.
+ *   Depth test.  GL_LESS with the primitives drawn in stream order: a pixel shows the fragment with the smallest
+ *   float32 depth, among equal depths the one of the smallest primitive id.  The images do not depend on the order in
+ *   which the device meets the primitives, nor on max_vertices_in_flight.
+ *   Points (glPointSize(gl_point_size), not smoothed).  n = floor(gl_point_size + 1/2) clamped to [1, 64].  A point whose
+ *   clip coordinates fail -w <= x, y, z <= w, or whose w is not positive and finite, is not drawn.  Otherwise it covers
+ *   the n x n pixels from floor(x_w) - (n - 1) / 2 (odd n) or floor(x_w + 1/2) - n / 2 (even n) on, the same in y, cut
+ *   at the viewport.  Every covered pixel takes (float)z_w and the vertex's colour word (bytes 0, 1, 2 of the row's
+ *   fourth float = b, g, r; alpha 255).
+ *   Triangles (GL_FILL, GL_SMOOTH, GL_CULL_FACE with counter-clockwise front faces, no blending, :355).
+ *     Deviation from GL, stated: nothing is clipped against near / far or a guard band.  A triangle with a vertex whose w
+ *     is not positive and finite, that fails -w <= z <= w, or whose |x_w| or |y_w| is not <= 16384 is not drawn at all
+ *     (so every edge function stays below 2^53 and converts to double exactly).
+ *     Snapping: X = floor(x_w * 256 + 1/2), Y likewise (1/256 pixel; ties go up), as 64-bit integers.
+ *     area = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0).  Zero draws nothing.  Negative (seen from behind): not drawn when
+ *     cull is 1; when cull is 0 vertices 1 and 2 change places and the triangle is drawn.
+ *     Coverage: the sample of pixel (px, py) is (256 px + 128, 256 py + 128).  e_i for i = 0, 1, 2 is the edge function of
+ *     the edge from vertex a = (i + 1) % 3 to b = (i + 2) % 3: e_i = (Xb - Xa)(sy - Ya) - (Yb - Ya)(sx - Xa).  The sample is
+ *     covered iff every e_i > 0, or e_i = 0 on an edge that owns its samples: Yb - Ya < 0, or Yb - Ya = 0 and Xb - Xa < 0
+ *     (the left and the top edges of the triangle in the image: a top-left rule).  A sample on an edge two triangles
+ *     share belongs to exactly one of them.
+ *     Depth = (float)(((e0 z0 + e1 z1) + e2 z2) / ((e0 + e1) + e2)) with the vertices' double z_w and the e_i converted to
+ *     double: GL's screen-space interpolation.
+ *     Colour per channel: q_i = e_i / w_i (w = clip.w), c = ((q0 c0 + q1 c1) + q2 c2) / ((q0 + q1) + q2), then
+ *     floor(c + 1/2) clamped to [0, 255] (perspective-correct, GL_SMOOTH); alpha 255.
+ *   Output.  H x W images, row 0 at the top.  rgba: 4 bytes per pixel, r, g, b, a; clear_rgba where nothing was drawn.
+ *   depth: float32, 1.0 where nothing was drawn (what glReadPixels(GL_DEPTH_COMPONENT) gives).  ids (may be NULL): int64
+ *   primitive id, -1 where nothing was drawn.  node_index (may be NULL): int32 position in node_ids of the primitive's
+ *   node, -1 where nothing was drawn.
+ *   max_vertices_in_flight: 0 = the library's default (2^23); above 0 the node list is processed in groups of consecutive
+ *   nodes whose vertices together stay within it (at most 2^30); a single node with more: RGBDFE_ERR_CAPACITY.  The
+ *   scratch is 20 bytes per vertex in flight and 8 per pixel.
+ *   Errors.  NULL ctx / params / rgba / depth, width or height outside [1, 4096], a view / projection entry or
+ *   gl_point_size that is not finite, gl_point_size <= 0, cull not 0 or 1, max_vertices_in_flight < 0, and whatever
+ *   rgbdfe_display_geometry refuses: RGBDFE_ERR_INVALID_ARG, nothing is written.  An id without a cloud:
+ *   RGBDFE_ERR_UNKNOWN_NODE before any device work, nothing is written.  n_nodes == 0: RGBDFE_OK, cleared images.
+ * rgbdfe_render_nodes_device: the same with device pointers of the context's device for the four images; the kernels
+ *   run on `stream` (NULL: the context's own); the call returns when they have finished.
+ * rgbdfe_render_default_params: 640 x 480, the view of rgbdfe_render_viewer_view's defaults, the projection of
+ *   rgbdfe_render_perspective's defaults at aspect 640 / 480, gl_point_size 1 (parameter_server.cpp:143), cull 1,
+ *   clear_rgba 3, 3, 3, 3 (the viewer's 0.01 grey, :128), max_vertices_in_flight 0.
+ * Host helpers, plain double arithmetic, sums of products left to right (csrc/render_camera.h):
+ *   rgbdfe_render_perspective(fovy, aspect, z_near, z_far, out): gluPerspective; fovy in DEGREES.  The reference passes
+ *   fov_ = 100 / 180 * pi -- radians -- as that argument (:118, :444), so its field of view is 1.745 degrees; the
+ *   reference's values are fovy = 100.0 / 180.0 * 3.14159265358979323846, z_near 0.1, z_far 1e4 and
+ *   aspect = (float)W / (float)H.
+ *   rgbdfe_render_viewer_view(x_tra, y_tra, z_tra, x_rot, y_rot, z_rot, rotation_stepping, viewpoint, out): the
+ *   modelview of drawClouds (:356-377): glTranslatef, glRotatef about x, y, z by (int)((rot / 16) / rotation_stepping) *
+ *   rotation_stepping degrees, glMultMatrix(viewpoint).  The translations and angles are rounded to float as GL takes
+ *   them.  viewpoint (NULL: identity) is the INVERSE of a camera pose, as setViewPoint makes it (:1122-1125).
+ *   initialPosition's values (:137-144): 0, 0, -50, 180 * 16, 0, 0, stepping 1.
+ *   rgbdfe_render_sensor_camera(fx, fy, cx, cy, W, H, z_near, z_far, pose, view_out, projection_out): the camera
+ *   under which a point (x, y, z) of the sensor frame at the rigid `pose` (NULL: identity; z forward, y down) lands at
+ *   x_w = fx x / z + cx + 1/2 and at image row fy y / z + cy + 1/2 from the top (y_w = H - that): a cloud rendered
+ *   through its own intrinsics puts point (u, v) on pixel (u, v).
+ *   rgbdfe_render_unproject(x, y, depth, view, projection, W, H, out3): gluUnProject over the viewport (0, 0, W, H), as
+ *   setClickedPosition uses it (:1127-1153; x, y in window coordinates, y up).  Returns RGBDFE_OK, or
+ *   RGBDFE_ERR_INVALID_ARG when projection . view is singular.
+ * rgbdfe_render_fragment_stats(ctx, enable, out2): diagnostics (tools/bench_render.py).  out2 (may be NULL) receives what
+ *   the latest render call counted: the fragments offered to the depth test, and those that lowered a pixel's word when
+ *   they arrived (this one depends on the order of arrival; at least the pixels drawn).  Both are 0 unless counting was
+ *   on.  Then enable = 1 / 0 turns the counting kernels on / off for the calls that follow (-1: as it is).  The images
+ *   are the same bytes either way; the counting kernels take a returning atomic per won fragment and two adds per lane. */
+typedef struct rgbdfe_render_params {
+  int32_t width, height;
+  double view[16];
+  double projection[16];
+  double gl_point_size;
+  int32_t cull;
+  uint8_t clear_rgba[4];
+  int64_t max_vertices_in_flight;
+} rgbdfe_render_params;
+void rgbdfe_render_default_params(rgbdfe_render_params* p);
+int rgbdfe_render_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                        const rgbdfe_display_params* display_params, const rgbdfe_render_params* render_params,
+                        uint8_t* rgba, float* depth, int64_t* ids, int32_t* node_index);
+int rgbdfe_render_nodes_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                               const rgbdfe_display_params* display_params, const rgbdfe_render_params* render_params,
+                               void* d_rgba, void* d_depth, void* d_ids, void* d_node_index, void* stream);
+void rgbdfe_render_perspective(double fovy, double aspect, double z_near, double z_far, double* out16);
+void rgbdfe_render_viewer_view(double x_tra, double y_tra, double z_tra, double x_rot, double y_rot, double z_rot,
+                               double rotation_stepping, const double* viewpoint, double* out16);
+void rgbdfe_render_sensor_camera(double fx, double fy, double cx, double cy, int32_t width, int32_t height, double z_near,
+                                 double z_far, const double* pose, double* view_out16, double* projection_out16);
+int rgbdfe_render_unproject(double x, double y, double depth, const double* view, const double* projection, int32_t width,
+                            int32_t height, double* out3);
+int rgbdfe_render_fragment_stats(rgbdfe_ctx* ctx, int32_t enable, int64_t* out2);
+
 /* GPU prefilter in front of the pair path (second half): what loop_closing.cpp's
  * GraphManager::getNeighbours (:190-277, behind DO_LOOP_CLOSING, never wired into nodeComparisons) sketched -- every
  * descriptor of the new node votes `k_neighbours - rank` (:241) for the nodes holding its k nearest descriptors, a

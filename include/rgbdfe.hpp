@@ -633,6 +633,66 @@ inline bool displayGeometry(const FrontEnd& fe, const std::vector<int32_t>& node
   return true;
 }
 
+// GLViewer::paintGL without a GL context (src/glviewer.cpp:291-425): the listed nodes' display geometry rasterised on the device
+// (rgbdfe_render_nodes; the contract is include/rgbdfe.h, "rendering").  world2cam as displayGeometry takes it; render_params
+// from renderParams() below, or rgbdfe_render_default_params for the viewer's initial position.  Images are height x width,
+// row 0 at the top: rgba 4 bytes per pixel (a screencast frame), depth as glReadPixels(GL_DEPTH_COMPONENT) gives it, ids the
+// primitive's first vertex in the stream (-1: nothing drawn), node_index the position in node_ids (-1).
+struct RenderedImages {
+  int32_t width = 0, height = 0;
+  std::vector<uint8_t> rgba;
+  std::vector<float> depth;
+  std::vector<int64_t> ids;
+  std::vector<int32_t> node_index;
+};
+// The viewer's camera at a window size: setViewPoint(pose) + drawClouds' modelview + resizeGL's projection.  viewpoint_pose: 16
+// doubles, column-major (a cloud matrix, follow_mode_'s last one), or NULL for no viewpoint; the helper inverts it as
+// setViewPoint does (a rigid pose).
+inline rgbdfe_render_params renderParams(int32_t width, int32_t height, const double* viewpoint_pose = nullptr) {
+  rgbdfe_render_params p;
+  rgbdfe_render_default_params(&p);
+  p.width = width;
+  p.height = height;
+  if (viewpoint_pose) {
+    double inv[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) inv[4 * c + r] = viewpoint_pose[4 * r + c];
+      inv[12 + r] = -(viewpoint_pose[4 * r] * viewpoint_pose[12] + viewpoint_pose[4 * r + 1] * viewpoint_pose[13] +
+                      viewpoint_pose[4 * r + 2] * viewpoint_pose[14]);
+    }
+    rgbdfe_render_viewer_view(0.0, 0.0, -50.0, 180.0 * 16.0, 0.0, 0.0, 1.0, inv, p.view);  // initialPosition (:137-144)
+  }
+  rgbdfe_render_perspective(100.0 / 180.0 * 3.14159265358979323846, (double)((float)width / (float)height), 0.1, 1e4,
+                            p.projection);  // fov_ as degrees, the reference's quirk (:118, :444)
+  return p;
+}
+inline bool render(const FrontEnd& fe, const std::vector<int32_t>& node_ids, const std::vector<float>& world2cam,
+                   const rgbdfe_display_params& display_params, const rgbdfe_render_params& render_params, RenderedImages* out,
+                   bool with_ids = true) {
+  if (!world2cam.empty() && world2cam.size() != node_ids.size() * 16) return false;
+  if (render_params.width < 1 || render_params.height < 1 || render_params.width > 4096 || render_params.height > 4096) return false;
+  const size_t n = (size_t)render_params.width * (size_t)render_params.height;
+  out->width = render_params.width;
+  out->height = render_params.height;
+  out->rgba.resize(4 * n);
+  out->depth.resize(n);
+  out->ids.resize(with_ids ? n : 0);
+  out->node_index.resize(with_ids ? n : 0);
+  return rgbdfe_render_nodes(fe.get(), (int32_t)node_ids.size(), node_ids.data(), world2cam.empty() ? nullptr : world2cam.data(),
+                             &display_params, &render_params, out->rgba.data(), out->depth.data(),
+                             with_ids ? out->ids.data() : nullptr, with_ids ? out->node_index.data() : nullptr) == RGBDFE_OK;
+}
+// GLViewer::setClickedPosition (:1127-1153) on a rendered depth image: the world point under window pixel (x, y) with y
+// counted from the top as Qt does, or false where nothing was drawn (depth 1).  The depth is the pixel's own; the reference
+// reads window row height - y, the row above it, and hands the same winY to gluUnProject, as this does.
+inline bool clickedPosition(const RenderedImages& img, const rgbdfe_render_params& render_params, int x, int y, double pos[3]) {
+  if (x < 0 || y < 0 || x >= img.width || y >= img.height) return false;
+  const float win_z = img.depth[(size_t)y * (size_t)img.width + (size_t)x];
+  if (win_z == 1.0f) return false;  // :1141
+  return rgbdfe_render_unproject((double)(float)x, (double)((float)img.height - (float)y), (double)win_z, render_params.view,
+                                 render_params.projection, img.width, img.height, pos) == RGBDFE_OK;
+}
+
 // pcl::VoxelGrid with a cubic leaf of voxelfilter_size over a device buffer of n_in rows (x, y, z, rgb bits) into another of
 // `capacity` rows on the context's device (rgbdfe_voxel_filter_device): the consumer of rgbdfe_assemble_map_device's output.
 // Returns the rows written, or -1 (needed: the rows that would have been; flags: RGBDFE_VOXEL_LEAF_TOO_SMALL).

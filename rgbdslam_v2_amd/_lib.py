@@ -164,6 +164,12 @@ class RgbdfeDisplayParams(C.Structure):   # rgbdfe_display_params
 DISPLAY_POINTS, DISPLAY_TRIANGLES, DISPLAY_TRIANGLE_STRIP = 0, 1, 2
 
 
+class RgbdfeRenderParams(C.Structure):   # rgbdfe_render_params
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("view", C.c_double * 16), ("projection", C.c_double * 16),
+                ("gl_point_size", C.c_double), ("cull", C.c_int32), ("clear_rgba", C.c_uint8 * 4),
+                ("max_vertices_in_flight", C.c_int64)]
+
+
 # rgbdfe_icp_report
 ICP_REPORT_DTYPE = np.dtype([("converged", "<i4"), ("state", "<i4"), ("iterations", "<i4"), ("correspondences", "<i4"),
                              ("mse", "<f8"), ("n_source", "<i4"), ("n_target", "<i4"), ("launches", "<i8"),
@@ -410,6 +416,23 @@ def load():
                                           vp, vp, C.c_int64, C.POINTER(C.c_int64), vp, vp]
     L.rgbdfe_display_geometry_device.restype = C.c_int
     L.rgbdfe_display_geometry_device.argtypes = L.rgbdfe_display_geometry.argtypes + [vp]
+    dbl = C.c_double
+    L.rgbdfe_render_default_params.restype = None
+    L.rgbdfe_render_default_params.argtypes = [C.POINTER(RgbdfeRenderParams)]
+    L.rgbdfe_render_nodes.restype = C.c_int
+    L.rgbdfe_render_nodes.argtypes = [ctx, i32, vp, vp, C.POINTER(RgbdfeDisplayParams), C.POINTER(RgbdfeRenderParams), vp, vp, vp, vp]
+    L.rgbdfe_render_nodes_device.restype = C.c_int
+    L.rgbdfe_render_nodes_device.argtypes = L.rgbdfe_render_nodes.argtypes + [vp]
+    L.rgbdfe_render_perspective.restype = None
+    L.rgbdfe_render_perspective.argtypes = [dbl, dbl, dbl, dbl, vp]
+    L.rgbdfe_render_viewer_view.restype = None
+    L.rgbdfe_render_viewer_view.argtypes = [dbl] * 7 + [vp, vp]
+    L.rgbdfe_render_sensor_camera.restype = None
+    L.rgbdfe_render_sensor_camera.argtypes = [dbl, dbl, dbl, dbl, i32, i32, dbl, dbl, vp, vp, vp]
+    L.rgbdfe_render_unproject.restype = C.c_int
+    L.rgbdfe_render_unproject.argtypes = [dbl, dbl, dbl, vp, vp, i32, i32, vp]
+    L.rgbdfe_render_fragment_stats.restype = C.c_int
+    L.rgbdfe_render_fragment_stats.argtypes = [ctx, i32, vp]
     L.rgbdfe_download_node_cloud.restype = C.c_int
     L.rgbdfe_download_node_cloud.argtypes = [ctx, i32, vp, C.c_int64, C.POINTER(i32), C.POINTER(i32)]
     L.rgbdfe_voxel_filter.restype = C.c_int
@@ -676,6 +699,8 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_assemble_map", "rgbdfe_assemble_map_device", "rgbdfe_download_node_cloud",
     "rgbdfe_voxel_filter", "rgbdfe_voxel_filter_device", "rgbdfe_reduce_node_cloud",
     "rgbdfe_display_default_params", "rgbdfe_display_geometry", "rgbdfe_display_geometry_device",
+    "rgbdfe_render_default_params", "rgbdfe_render_nodes", "rgbdfe_render_nodes_device", "rgbdfe_render_perspective",
+    "rgbdfe_render_viewer_view", "rgbdfe_render_sensor_camera", "rgbdfe_render_unproject", "rgbdfe_render_fragment_stats",
     "rgbdfe_octomap_default_params", "rgbdfe_octomap_create", "rgbdfe_octomap_destroy", "rgbdfe_octomap_reset",
     "rgbdfe_octomap_reserve", "rgbdfe_octomap_insert_nodes", "rgbdfe_octomap_insert_cloud", "rgbdfe_octomap_size",
     "rgbdfe_octomap_leaves", "rgbdfe_octomap_stats",

@@ -7,14 +7,13 @@
 
 namespace impl {
 
-namespace {
-
 // GLViewer::addPointCloud (glviewer.cpp:693-711) for every listed node.  Exactly one of the host / device pairs receives
-// the output.
-int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+// the output.  ctx->mu is held.  sizes_only: the sizes, offsets and forms, then RGBDFE_OK without a vertex written.
+int display_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
                    const rgbdfe_display_params* params, float* h_vertices, void* d_vertices, int64_t vertex_capacity,
                    int64_t* n_vertices, int64_t* node_offsets, int64_t* h_strips, void* d_strips, int64_t strip_capacity,
-                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, bool to_device, void* stream) {
+                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, bool to_device, void* stream,
+                   bool sizes_only) {
   if (!ctx || n_nodes < 0 || !params || !n_vertices || !n_strips || vertex_capacity < 0 || strip_capacity < 0 ||
       (n_nodes > 0 && !node_ids) || (vertex_capacity > 0 && !(to_device ? d_vertices != nullptr : h_vertices != nullptr)) ||
       (strip_capacity > 0 && !(to_device ? d_strips != nullptr : h_strips != nullptr)))
@@ -24,7 +23,6 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "display geometry: unknown display_type");
   if (params->visualization_skip_step < 1)
     return fail(ctx, RGBDFE_ERR_INVALID_ARG, "display geometry: visualization_skip_step must be at least 1");
-  std::lock_guard<std::mutex> g(ctx->mu);
   // the node table and the tile -> node map: one blob, one copy
   const size_t n = (size_t)n_nodes;
   std::vector<DispNode> table(n + 1);
@@ -116,6 +114,7 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
     if (node_offsets) node_offsets[k] = first[2 * k];
     if (node_strip_offsets) node_strip_offsets[k] = first[2 * k + 1];
   }
+  if (sizes_only) return RGBDFE_OK;
   if (vertex_capacity < total_v || strip_capacity < total_s)
     return fail(ctx, RGBDFE_ERR_CAPACITY, "display geometry: a buffer is too small (*n_vertices rows and *n_strips records are needed)");
   if (total_v == 0) return RGBDFE_OK;  // no vertex, so no strip either
@@ -132,6 +131,19 @@ int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, co
   // the table in the context's scratch is this call's: it returns when the stream has passed it
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return RGBDFE_OK;
+}
+
+namespace {
+
+int display_common(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                   const rgbdfe_display_params* params, float* h_vertices, void* d_vertices, int64_t vertex_capacity,
+                   int64_t* n_vertices, int64_t* node_offsets, int64_t* h_strips, void* d_strips, int64_t strip_capacity,
+                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, bool to_device, void* stream) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return display_locked(ctx, n_nodes, node_ids, transforms, params, h_vertices, d_vertices, vertex_capacity, n_vertices,
+                        node_offsets, h_strips, d_strips, strip_capacity, n_strips, node_strip_offsets, node_types, to_device,
+                        stream, false);
 }
 
 }  // namespace

@@ -1066,6 +1066,49 @@ int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32
                                                                 strip_capacity, n_strips, node_strip_offsets, node_types, stream));
 }
 
+void rgbdfe_render_default_params(rgbdfe_render_params* p) { impl::rgbdfe_render_default_params(p); }
+
+// served from the first device of a group, like display geometry
+int rgbdfe_render_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                        const rgbdfe_display_params* display_params, const rgbdfe_render_params* render_params, uint8_t* rgba,
+                        float* depth, int64_t* ids, int32_t* node_index) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_render_nodes(c, n_nodes, node_ids, transforms, display_params, render_params, rgba, depth,
+                                                     ids, node_index));
+}
+
+int rgbdfe_render_nodes_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                               const rgbdfe_display_params* display_params, const rgbdfe_render_params* render_params,
+                               void* d_rgba, void* d_depth, void* d_ids, void* d_node_index, void* stream) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_render_nodes_device(c, n_nodes, node_ids, transforms, display_params, render_params, d_rgba,
+                                                            d_depth, d_ids, d_node_index, stream));
+}
+
+void rgbdfe_render_perspective(double fovy, double aspect, double z_near, double z_far, double* out16) {
+  impl::rgbdfe_render_perspective(fovy, aspect, z_near, z_far, out16);
+}
+
+void rgbdfe_render_viewer_view(double x_tra, double y_tra, double z_tra, double x_rot, double y_rot, double z_rot,
+                               double rotation_stepping, const double* viewpoint, double* out16) {
+  impl::rgbdfe_render_viewer_view(x_tra, y_tra, z_tra, x_rot, y_rot, z_rot, rotation_stepping, viewpoint, out16);
+}
+
+void rgbdfe_render_sensor_camera(double fx, double fy, double cx, double cy, int32_t width, int32_t height, double z_near,
+                                 double z_far, const double* pose, double* view_out16, double* projection_out16) {
+  impl::rgbdfe_render_sensor_camera(fx, fy, cx, cy, width, height, z_near, z_far, pose, view_out16, projection_out16);
+}
+
+int rgbdfe_render_unproject(double x, double y, double depth, const double* view, const double* projection, int32_t width,
+                            int32_t height, double* out3) {
+  return impl::rgbdfe_render_unproject(x, y, depth, view, projection, width, height, out3);
+}
+
+int rgbdfe_render_fragment_stats(rgbdfe_ctx* ctx, int32_t enable, int64_t* out2) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_render_fragment_stats(c, enable, out2));
+}
+
 int rgbdfe_observation_likelihood(rgbdfe_ctx* ctx, int32_t n, const int32_t* new_ids, const int32_t* old_ids,
                                   const float* transforms, int32_t emm_skip_step, rgbdfe_emm_counts* out) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;

@@ -322,6 +322,9 @@ struct rgbdfe_ctx {
   // scratch for single-pair helpers / project_to_3d
   void* d_scratch = nullptr;
   size_t scratch_bytes = 0;
+  GrowBuffer render;         // api_render.hip: a call's visibility words, staged images, vertex group and queue
+  bool render_count_fragments = false;   // rgbdfe_render_fragment_stats: the counting kernels (diagnostics)
+  int64_t render_fragments[2] = {0, 0};  // the latest render call's fragments offered / that lowered a word on arrival
   GrowBuffer icp;            // api_icp.hip: the samples, working copies and records of a call (d_scratch holds its tile counts and offsets)
   OrbWorkspace orb;
   OrbWorkspace orb_super;  // rgbdfe_detect_describe_batch: up to 7 frames per launch chain (its own image sets)
@@ -567,6 +570,12 @@ namespace impl {
 // helpers shared between the implementation files
 int upload_nodes_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const uint8_t* const* desc,
                         const float* const* xyz1, const int32_t* counts);
+// rgbdfe_display_geometry(_device) with ctx->mu held (api_display.hip); api_render.hip draws what it writes
+int display_locked(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms,
+                   const rgbdfe_display_params* params, float* h_vertices, void* d_vertices, int64_t vertex_capacity,
+                   int64_t* n_vertices, int64_t* node_offsets, int64_t* h_strips, void* d_strips, int64_t strip_capacity,
+                   int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, bool to_device, void* stream,
+                   bool sizes_only);
 void ensure_detector(rgbdfe_ctx* ctx);
 int ensure_sift(rgbdfe_ctx* ctx);                 // the float / bf16 node slabs (api_pairs.hip)
 void sift_nodes_release(rgbdfe_ctx* ctx);        // rgbdfe_ctx::sn (api_detect.hip)
@@ -680,6 +689,15 @@ int rgbdfe_reduce_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, double voxelfilte
 void rgbdfe_display_default_params(rgbdfe_display_params* p);
 int rgbdfe_display_geometry(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, const rgbdfe_display_params* params, float* vertices, int64_t vertex_capacity, int64_t* n_vertices, int64_t* node_offsets, int64_t* strips, int64_t strip_capacity, int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types);
 int rgbdfe_display_geometry_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, const rgbdfe_display_params* params, void* d_vertices, int64_t vertex_capacity, int64_t* n_vertices, int64_t* node_offsets, void* d_strips, int64_t strip_capacity, int64_t* n_strips, int64_t* node_strip_offsets, int32_t* node_types, void* stream);
+// api_render.hip
+void rgbdfe_render_default_params(rgbdfe_render_params* p);
+int rgbdfe_render_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, const rgbdfe_display_params* display_params, const rgbdfe_render_params* render_params, uint8_t* rgba, float* depth, int64_t* ids, int32_t* node_index);
+int rgbdfe_render_nodes_device(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, const rgbdfe_display_params* display_params, const rgbdfe_render_params* render_params, void* d_rgba, void* d_depth, void* d_ids, void* d_node_index, void* stream);
+void rgbdfe_render_perspective(double fovy, double aspect, double z_near, double z_far, double* out16);
+void rgbdfe_render_viewer_view(double x_tra, double y_tra, double z_tra, double x_rot, double y_rot, double z_rot, double rotation_stepping, const double* viewpoint, double* out16);
+void rgbdfe_render_sensor_camera(double fx, double fy, double cx, double cy, int32_t width, int32_t height, double z_near, double z_far, const double* pose, double* view_out16, double* projection_out16);
+int rgbdfe_render_unproject(double x, double y, double depth, const double* view, const double* projection, int32_t width, int32_t height, double* out3);
+int rgbdfe_render_fragment_stats(rgbdfe_ctx* ctx, int32_t enable, int64_t* out2);
 // api_pose_graph.hip
 int rgbdfe_pose_graph_chi2(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* chi2);
 int rgbdfe_pose_graph_linearize(rgbdfe_ctx* ctx, rgbdfe_pose_graph* g, double* errors, double* weights, int32_t edge_capacity, int32_t* n_edges, int32_t* free_ids, double* h_diag, double* b, int32_t vertex_capacity, int32_t* n_free, int32_t* off_rows, int32_t* off_cols, double* h_off, int32_t block_capacity, int32_t* n_blocks, double* chi2);

@@ -78,6 +78,50 @@ def record_to_matching_result(rec) -> MatchingResult:
     return mr
 
 
+def _matrix_out(buf):
+    return np.array(buf, np.float64).reshape(4, 4).T.copy()
+
+
+def _matrix_in(M):
+    return (C.c_double * 16)(*[float(v) for v in np.asarray(M, np.float64).reshape(4, 4).T.reshape(-1)])
+
+
+REFERENCE_FOVY = 100.0 / 180.0 * 3.14159265358979323846   # fov_ (glviewer.cpp:118): radians, handed to gluPerspective as degrees
+
+
+def render_perspective(fovy=REFERENCE_FOVY, aspect=float(np.float32(640) / np.float32(480)), z_near=0.1, z_far=1e4):
+    """gluPerspective as a 4 x 4 float64 matrix (row-major numpy sense); the defaults are what the reference passes."""
+    out = (C.c_double * 16)()
+    _lib.load().rgbdfe_render_perspective(fovy, aspect, z_near, z_far, out)
+    return _matrix_out(out)
+
+
+def render_viewer_view(x_tra=0.0, y_tra=0.0, z_tra=-50.0, x_rot=180.0 * 16.0, y_rot=0.0, z_rot=0.0, rotation_stepping=1.0,
+                       viewpoint=None):
+    """The modelview of GLViewer::drawClouds (glviewer.cpp:356-377); viewpoint: the INVERSE of a camera pose, 4 x 4."""
+    out = (C.c_double * 16)()
+    _lib.load().rgbdfe_render_viewer_view(x_tra, y_tra, z_tra, x_rot, y_rot, z_rot, rotation_stepping,
+                                          _matrix_in(viewpoint) if viewpoint is not None else None, out)
+    return _matrix_out(out)
+
+
+def render_sensor_camera(fx, fy, cx, cy, width, height, z_near=0.1, z_far=1e4, pose=None):
+    """(view, projection) of the sensor's own pinhole at the rigid 4 x 4 pose: point (u, v) of a cloud lands on pixel (u, v)."""
+    view, proj = (C.c_double * 16)(), (C.c_double * 16)()
+    _lib.load().rgbdfe_render_sensor_camera(fx, fy, cx, cy, int(width), int(height), z_near, z_far,
+                                            _matrix_in(pose) if pose is not None else None, view, proj)
+    return _matrix_out(view), _matrix_out(proj)
+
+
+def render_unproject(x, y, depth, view, projection, width, height):
+    """gluUnProject as GLViewer::setClickedPosition uses it: window x, y (y up: height - image row) and a depth image value
+    to the world point, or None when projection . view is singular."""
+    out = (C.c_double * 3)()
+    st = _lib.load().rgbdfe_render_unproject(float(x), float(y), float(depth), _matrix_in(view), _matrix_in(projection),
+                                             int(width), int(height), out)
+    return np.array(out, np.float64) if st == 0 else None
+
+
 class FrontEnd:
     """One rgbdfe context = one GPU: resident node features + the batched pair op."""
 
@@ -1243,6 +1287,70 @@ class FrontEnd:
             strips.data_ptr() if strips.shape[0] else None, int(strips.shape[0]), C.byref(ns), soff.ctypes.data,
             types.ctypes.data, stream))
         return dict(n_vertices=nv.value, n_strips=ns.value, node_offsets=off, node_strip_offsets=soff, node_types=types)
+
+    def _render_args(self, node_ids, transforms, width, height, view, projection, gl_point_size, cull, clear_rgba,
+                     max_vertices_in_flight, display):
+        node_ids, T, dp = self._display_args(node_ids, transforms, display.get("display_type", DISPLAY_POINTS),
+                                             display.get("visualization_skip_step", 1),
+                                             display.get("squared_meshing_threshold", 0.0009),
+                                             display.get("maximum_depth", float("inf")))
+        rp = _lib.RgbdfeRenderParams()
+        self._L.rgbdfe_render_default_params(C.byref(rp))
+        rp.width, rp.height = int(width), int(height)
+        if projection is None:  # the viewer's own, at this size (resizeGL, glviewer.cpp:443-444)
+            projection = render_perspective(aspect=float(np.float32(width) / np.float32(height)))
+        for name, M in (("view", view), ("projection", projection)):
+            if M is not None:
+                getattr(rp, name)[:] = [float(v) for v in np.asarray(M, np.float64).reshape(4, 4).T.reshape(-1)]
+        rp.gl_point_size, rp.cull = float(gl_point_size), int(cull)
+        rp.clear_rgba[:] = [int(v) for v in clear_rgba]
+        rp.max_vertices_in_flight = int(max_vertices_in_flight)
+        return node_ids, T, dp, rp
+
+    def render_nodes(self, node_ids, transforms=None, width=640, height=480, view=None, projection=None, gl_point_size=1.0,
+                     cull=True, clear_rgba=(3, 3, 3, 3), max_vertices_in_flight=0, return_ids=True, **display):
+        """What GLViewer::paintGL draws of the listed nodes' clouds (include/rgbdfe.h, "rendering"): their display-geometry
+        stream (display_type, visualization_skip_step, squared_meshing_threshold, maximum_depth as display_geometry takes
+        them) rasterised on the device.  view / projection: 4 x 4 matrices in the row-major numpy sense (render_viewer_view,
+        render_perspective, render_sensor_camera make them); None: the viewer's initial position and its projection at
+        this size.  Returns a dict of [height, width] images, row 0 at the top: rgba uint8 [.., 4], depth float32 (1.0 where
+        nothing was drawn), and with return_ids also ids int64 (the primitive's first vertex in the stream, -1) and
+        node_index int32 (position in node_ids, -1)."""
+        node_ids, T, dp, rp = self._render_args(node_ids, transforms, width, height, view, projection, gl_point_size, cull,
+                                                clear_rgba, max_vertices_in_flight, display)
+        H, W = int(height), int(width)
+        out = dict(rgba=np.empty((H, W, 4), np.uint8), depth=np.empty((H, W), np.float32))
+        if return_ids:
+            out.update(ids=np.empty((H, W), np.int64), node_index=np.empty((H, W), np.int32))
+        self._check(self._L.rgbdfe_render_nodes(
+            self._ctx, len(node_ids), node_ids.ctypes.data, T.ctypes.data if T is not None else None, C.byref(dp), C.byref(rp),
+            out["rgba"].ctypes.data, out["depth"].ctypes.data, out["ids"].ctypes.data if return_ids else None,
+            out["node_index"].ctypes.data if return_ids else None))
+        return out
+
+    def render_nodes_device(self, node_ids, rgba, depth, ids=None, node_index=None, transforms=None, view=None,
+                            projection=None, gl_point_size=1.0, cull=True, clear_rgba=(3, 3, 3, 3), max_vertices_in_flight=0,
+                            stream=None, **display):
+        """render_nodes into contiguous torch tensors on this context's device: rgba uint8 [H, W, 4], depth float32 [H, W],
+        and optionally ids int64 [H, W], node_index int32 [H, W]; no pixel crosses to the host."""
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        for t, shape, size, name in ((rgba, (H, W, 4), 1, "rgba"), (depth, (H, W), 4, "depth"), (ids, (H, W), 8, "ids"),
+                                     (node_index, (H, W), 4, "node_index")):
+            if t is not None and not (t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape and t.element_size() == size):
+                raise ValueError("%s must be a contiguous %s tensor of %d-byte elements on the device" % (name, shape, size))
+        node_ids, T, dp, rp = self._render_args(node_ids, transforms, W, H, view, projection, gl_point_size, cull, clear_rgba,
+                                                max_vertices_in_flight, display)
+        self._check(self._L.rgbdfe_render_nodes_device(
+            self._ctx, len(node_ids), node_ids.ctypes.data, T.ctypes.data if T is not None else None, C.byref(dp), C.byref(rp),
+            rgba.data_ptr(), depth.data_ptr(), ids.data_ptr() if ids is not None else None,
+            node_index.data_ptr() if node_index is not None else None, stream))
+
+    def render_fragment_stats(self, enable=None):
+        """Diagnostics: (fragments offered, fragments that lowered a pixel's word on arrival) of the latest render call while
+        counting was on; enable = True / False turns the counting kernels on / off for the calls that follow."""
+        out = np.zeros(2, np.int64)
+        self._check(self._L.rgbdfe_render_fragment_stats(self._ctx, -1 if enable is None else int(bool(enable)), out.ctypes.data))
+        return int(out[0]), int(out[1])
 
     def voxel_filter(self, points, voxelfilter_size, return_flags=False):
         """pcl::VoxelGrid with a cubic leaf of voxelfilter_size (Node::reducePointCloud, node.cpp:1448-1460) over points,

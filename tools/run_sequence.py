@@ -6,7 +6,8 @@ sensor_detect_describe_batch_nodes, features detected on the device) enters a no
 GraphManager.addNode -- candidate selection, the pair batch, the decisions, the pose graph, the optimiser.  Then
 saveTrajectory's estimate file is written and tools/evaluate_ate.py compares it with the synthetic poses (feature
 sequences only: the image sequence has no camera poses); --map also assembles the clouds of the nodes with a valid
-estimate (image sequences: they carry clouds) and inserts them into an OctoMap.
+estimate (image sequences: they carry clouds) and inserts them into an OctoMap; --render FILE renders those clouds on the
+device, seen through the sensor from the last pose, into a PNG or PPM (tools/render_map.py).
 
 Prints one JSON line (--out FILE also writes it there): frames, frames dropped by status, vertices, edges, keyframes, ATE,
 ms per frame in total and per stage (upload, candidates, comparisons, decisions, optimisation) as means and medians of the
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--strategy", default="first")
     ap.add_argument("--fps", type=float, default=30.0)
     ap.add_argument("--map", action="store_true")
+    ap.add_argument("--render", metavar="FILE", help="with --images: the map seen from the last pose, as .png or .ppm")
     ap.add_argument("--seed", type=int, default=20260923)
     ap.add_argument("--out")
     a = ap.parse_args()
@@ -70,7 +72,7 @@ def main():
         fe.detector_configure(max_keypoints=600)
         t0 = time.perf_counter()
         fe.sensor_detect_describe_batch_nodes(list(seq["gray"]), list(seq["depth"]), seq["fx"], seq["fy"], seq["cx"], seq["cy"],
-                                              node_ids=np.arange(a.frames), cloud_skip=8 if a.map else None)
+                                              node_ids=np.arange(a.frames), cloud_skip=8 if (a.map or a.render) else None)
         upload_s = [(time.perf_counter() - t0) / a.frames] * a.frames
     else:
         seq = synth.make_sequence(n_frames=a.frames, n_kp=a.n_kp, seed=a.seed)
@@ -123,6 +125,18 @@ def main():
         with fe.octomap(1 << 20) as om:
             om.insert_nodes([frame_of[i] for i in valid], T)
             res["map"].update(octomap_leaves=len(om), octomap_ms=1e3 * (time.perf_counter() - t0))
+    if a.render and a.images:
+        import render_map
+        valid = [i for i in ids if slam.valid_tf()[i] and frame_of[i] >= 0]
+        T = gm.pose_graph.transforms(valid)
+        view, proj = render_map.camera_for("sensor", np.asarray(T[-1], np.float64), seq["fx"], seq["fy"], seq["cx"], seq["cy"],
+                                           a.width, a.height)
+        t0 = time.perf_counter()
+        img = fe.render_nodes([frame_of[i] for i in valid], T, width=a.width, height=a.height, view=view, projection=proj,
+                              gl_point_size=8.0)  # the clouds were made at cloud_skip 8
+        res["render"] = dict(file=a.render, nodes=len(valid), render_ms=1e3 * (time.perf_counter() - t0),
+                             pixels_drawn=int(np.sum(img["ids"] >= 0)))
+        render_map.write_image(a.render, img["rgba"])
     slam.close()
     fe.close()
     try:
