@@ -221,6 +221,45 @@ int rgbdfe_upload_node_keypoints(rgbdfe_ctx* ctx, int32_t node_id, const float* 
 int rgbdfe_release_node(rgbdfe_ctx* ctx, int32_t node_id);
 int rgbdfe_node_count(rgbdfe_ctx* ctx, int32_t node_id); /* rows of a resident node or <0 */
 
+/* ---- node read-back: the way out of the slabs (nodes that a batch detector wrote straight into their slots with NULL host
+ *      outputs exist nowhere else) ------------------------------------------------------------------------------------
+ * rgbdfe_download_nodes: the listed resident nodes in the order given (an id may appear twice).  Row counts are prefix-
+ *   summed into row_offsets[n_nodes + 1]; every array is packed without gaps in that order, node i's rows at
+ *   row_offsets[i] .. row_offsets[i + 1]:
+ *     desc   32 bytes per row for ORB nodes (kind 0); 128 floats per row for SIFT (1) and float / FLANN (2) nodes, rows of a
+ *            narrower float node zero-padded as they are resident -- the raw form the node was uploaded or detected with,
+ *            not the fp4 / bf16 operands derived from it.  One call takes nodes of ONE kind: a mixed list is
+ *            RGBDFE_ERR_INVALID_ARG.
+ *     xyz1   4 floats per row.
+ *     kp_xy  2 floats per row (rgbdfe_upload_node_keypoints); zeros for a node that holds no keypoints.
+ *     stats  1 byte per row: feature_matching_stats_ (rgbdfe_node_feature_stats).  Zeros while no call has ever counted on
+ *            this context; the read-back does not allocate the counters.
+ *     kinds  [n_nodes]: the kind, with RGBDFE_NODE_HAS_KEYPOINTS or-ed in for a node that holds keypoints.
+ *   Any output pointer may be NULL.  capacity_rows (of every array given) below the total is RGBDFE_ERR_CAPACITY with the
+ *   total in row_offsets[n_nodes] and nothing else written.  With every array NULL and a capacity that suffices the call
+ *   only fills row_offsets and kinds, without device work: the sizing call in front of the real one.  An id that is not
+ *   resident is RGBDFE_ERR_UNKNOWN_NODE before any device work.  The call waits for the batches in flight on the context,
+ *   as overwriting a node does.  Cost: one small table upload, ONE kernel launch, one device-to-host copy per array given
+ *   and one wait, whatever n_nodes -- rgbdfe_upload_nodes' mirror image.  Single-device contexts (a multi-device handle
+ *   answers from its first device, where every node is resident too).
+ * rgbdfe_download_node: one node; returns its row count (>= 0) or a status; *kind and *has_keypoints may be NULL.
+ * rgbdfe_download_nodes_stats: out[0..n_out) = { kernel launches of the latest read-back, its device-to-host copies, bytes
+ *   of the read-back staging buffer, 1 if the context's feature counters have been allocated else 0 }.
+ * rgbdfe_set_node_feature_stats: writes a resident node's counters back (n must equal its rows): what a restore needs
+ *   behind the upload, which zeroes them. */
+#define RGBDFE_NODE_HAS_KEYPOINTS 0x100
+#define RGBDFE_DOWNLOAD_STATS 4
+int rgbdfe_download_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, int64_t capacity_rows, void* desc,
+                          float* xyz1, float* kp_xy, uint8_t* stats, int64_t* row_offsets, int32_t* kinds);
+int rgbdfe_download_node(rgbdfe_ctx* ctx, int32_t node_id, int32_t capacity_rows, void* desc, float* xyz1, float* kp_xy,
+                         uint8_t* stats, int32_t* kind, int32_t* has_keypoints);
+int rgbdfe_download_nodes_stats(rgbdfe_ctx* ctx, int64_t* out, int32_t n_out);
+/* diagnostics (tools/bench_session.py): rgbdfe_download_nodes' result through the obvious way -- per node one device-to-host
+ * copy per array straight out of the slabs, one wait at the end; rgbdfe_download_nodes_stats then counts no launch and the copies */
+int rgbdfe_debug_download_nodes_copy_loop(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, int64_t capacity_rows, void* desc,
+                                          float* xyz1, float* kp_xy, uint8_t* stats, int64_t* row_offsets, int32_t* kinds);
+int rgbdfe_set_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, const uint8_t* stats, int32_t n);
+
 /* ---- the pair op -------------------------------------------------------- */
 /* Batched Node::matchNodePair (node.h:85, node.cpp:1305-1429): for one new node and
  * n candidates.  1:1 replacement of
@@ -1300,6 +1339,10 @@ int rgbdfe_detector_configure(rgbdfe_ctx* ctx, int32_t max_keypoints, int32_t gr
                               int32_t adjuster_max_iterations);
 /* the current per-cell FAST thresholds (grid_resolution^2 doubles) */
 int rgbdfe_detector_thresholds(rgbdfe_ctx* ctx, double* thresholds, int32_t* n_cells);
+/* The inverse: n_cells must equal grid_resolution^2 of the configured grid, every threshold must be finite.  The thresholds
+ * are all a grid detector (either type) carries from one frame to the next, so a context that is configured like another
+ * and given its thresholds detects the following frames as that one would. */
+int rgbdfe_detector_set_thresholds(rgbdfe_ctx* ctx, const double* thresholds, int32_t n_cells);
 /* Parameter "feature_detector_type" (parameter_server.cpp, createDetector in features.cpp:63-113) with the default ORB
  * extractor.  RGBDFE_DETECTOR_ORB (the default): the grid of adaptive cv::ORB detectors.  RGBDFE_DETECTOR_FAST: the same grid
  * and threshold adaptation around cv::FastFeatureDetector (DetectorAdjuster("FAST", 20), feature_adjuster.cpp:88-91):
@@ -1736,6 +1779,88 @@ int rgbdfe_update_inlier_features(rgbdfe_ctx* ctx, const void* d_records, const 
 int rgbdfe_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, uint8_t* out, int32_t capacity);
 int rgbdfe_pose_graph_add_keyframe(rgbdfe_pose_graph* g, int32_t node_id);
 int rgbdfe_pose_graph_clear(rgbdfe_pose_graph* g);
+
+/* ---- session files: save and resume nodes, pose graph and SLAM state --------------------------------------------------
+ * A run that is saved, torn down, loaded into fresh objects and continued produces, byte for byte, what the uninterrupted
+ * run produces.  Everything below is little-endian; doubles and floats travel as their bytes (NaN payloads, -0.0 and
+ * denormals survive); "zeros to 8" pads with zero bytes up to the next multiple of 8 counted from the start of the string,
+ * payload or file.  CRC-32 is zlib's (zlib.crc32).  Nothing depends on time, pointers, slot numbers or hash-map order:
+ * the same state gives the same bytes.
+ *
+ * The two byte strings (no device, no context: both work on objects created with ctx == NULL).  Envelope: 8 bytes magic,
+ * u32 version 1, u32 CRC-32 of the bytes [16, length), u64 length of the whole string (a multiple of 8), then the body.
+ *   Two-call pattern: *bytes is the length; capacity below it is RGBDFE_ERR_CAPACITY with nothing written.  A failed call
+ *   leaves its cause with rgbdfe_last_error(NULL) (per calling thread), and with the context's where the object has one.
+ * rgbdfe_pose_graph_serialize / _deserialize, magic "RGBDFEPG".  Body:
+ *     i32 strategy, i32 earliest_loop_closure_node, u32 n_nodes, u32 n_edges, u32 n_keyframes, u32 n_links,
+ *     u32 n_extra_vertices, u32 0
+ *     nodes in ascending id, 112 bytes each: i32 node id, i32 vertex id, u8 matchable, u8 fixed, 6 x u8 0, 12 x f64 estimate
+ *       (rotation row-major, then translation: rgbdfe_pose_graph_get_estimate's matrix is column-major)
+ *     edges in insertion order, 400 bytes each: i32 id1, i32 id2, u8 active, 7 x u8 0, 12 x f64 measurement (as an estimate),
+ *       36 x f64 information row-major
+ *     keyframes: n x i32;  links: n x (i32 u, i32 v), u < v, ascending: edges without a measurement
+ *       (rgbdfe_pose_graph_add_edge), as vertex ids;  extra vertices: n x i32 ascending: camera vertices that are no node's
+ *       vertex id;  zeros to 8.
+ *   camera_vertices and the adjacency are rebuilt from those.  The target of a deserialise must be empty (a new graph, or
+ *   rgbdfe_pose_graph_clear), else RGBDFE_ERR_INVALID_ARG; it takes the stored strategy, and the optimiser's device buffers
+ *   are dropped, so that no plan of an earlier graph survives.  A string that is truncated, extended or changed in any byte
+ *   is refused (RGBDFE_ERR_INVALID_ARG) and the graph stays empty.
+ * rgbdfe_slam_serialize / _deserialize, magic "RGBDFESM".  Body:
+ *     the parameters in the order of rgbdfe_slam_params: 13 x i32 (min_matches .. have_odometry_frame), u32 seed, 6 x f64
+ *     (min_translation_meter .. observability_threshold), 16 x f64 init_base_pose
+ *     u32 n_nodes, u32 n_keyframes, i32 next_seq_id, u32 calls (steps begun: the library's own generator draws from seed +
+ *     calls), i32 sequential_edges, i32 loop_closure_edges, i32 best_id1, i32 best_id2, i32 best_n_inl (curr_best_result_), u32 0
+ *     per graph id: n x i32 slot (-1: released), n x i32 rows, n x i64 stamp seconds, n x i32 stamp nanoseconds, n x u8
+ *     valid_tf, zeros to 4, keyframes n x i32, zeros to 8.
+ *   Serialising while a step is in flight (between rgbdfe_slam_begin and the rgbdfe_slam_feed that finishes it) is refused
+ *   with RGBDFE_ERR_INVALID_ARG.  The target of a deserialise must be fresh or reset (rgbdfe_slam_reset) and must have been
+ *   created with the stored parameters: otherwise RGBDFE_ERR_INVALID_ARG, the message naming the first field that differs.
+ *   Its graph is not touched: deserialise that one too.  A generator given with rgbdfe_slam_set_rand and its state stay the
+ *   caller's: neither is stored, and a resumed run draws what the uninterrupted one draws only if the caller restores them.
+ * rgbdfe_pose_graph_node_ids: the graph's node ids in ascending order (capacity below *n_out: RGBDFE_ERR_CAPACITY).
+ *
+ * rgbdfe_session_save(ctx, slam, graph, flags, path) / rgbdfe_session_load(ctx, slam, graph, path); slam / graph may be NULL.
+ * The file: a 32-byte header -- the 8 bytes "RGBDFESS", u32 version 1, u32 flags, u64 file length, u64 0 -- then chunks of
+ * (4-byte tag, u32 CRC-32 of the payload, u64 payload length, payload, zeros to 8) in the fixed order
+ *   "CONF"  i32 max_keypoints of the context, i32 rgbdfe_abi_version(), u32 node kinds present (bit k: kind k), u32 0
+ *   "DETE"  i32 detector type (RGBDFE_DETECTOR_*), i32 detector max_keypoints, i32 grid_resolution, i32 adjuster_max_iterations,
+ *           i32 feature_min_depth (0 / 1), i32 n_cells, n_cells x f64 thresholds
+ *   "NODE"  u32 n_nodes, u32 0, then n x i32 each: ids (ascending), kinds, rows, has_keypoints (0 / 1); then for every kind
+ *           present, in the order 0 (ORB), 1 (SIFT), 2 (float), that kind's nodes in ascending id packed as
+ *           rgbdfe_download_nodes packs them: desc (32 bytes per row for kind 0, else 128 x f32), zeros to 8, xyz1 (4 x f32
+ *           per row), zeros to 8, kp_xy (2 x f32 per row; zeros for a node without keypoints), zeros to 8, stats (1 byte per
+ *           row), zeros to 8
+ *   "CLOU"  only with RGBDFE_SESSION_CLOUDS in flags: u32 n_clouds, u32 0, then per cloud in ascending node id: i32 id,
+ *           i32 rows, i32 cols, i32 cloud_skip, f32 fx, fy, cx, cy, rows x cols x 4 x f32 points (rgbdfe_download_node_cloud's)
+ *   "GRPH"  the graph's byte string, when a graph was passed;  "SLAM"  the machine's, when a slam was passed
+ *   "END "  empty.
+ * Saving: written to path + ".tmp", then renamed; if anything fails nothing stays under either name.  Refused
+ *   (RGBDFE_ERR_INVALID_ARG, "busy") while a host job (rgbdfe_submit_pair_list_host) or a step is pending.  Single-device
+ *   contexts.  The OctoMap keeps its own .ot files and is not part of a session.
+ * Loading: the whole file is validated before anything changes -- magic, version, length, every CRC, every count against its
+ *   chunk's length, then capacity (rows above the context's max_keypoints, or more nodes than free slots:
+ *   RGBDFE_ERR_CAPACITY), then the id rule (an id of the file that is already resident, with or without a cloud, a graph
+ *   or slam target that is not empty, a slam whose parameters differ: RGBDFE_ERR_INVALID_ARG; a GRPH / SLAM chunk without an
+ *   object to take it is validated and skipped -- a viewer loads the nodes and the graph alone); every other defect is RGBDFE_ERR_INVALID_ARG with the cause in rgbdfe_last_error.  Then the nodes
+ *   go in through the upload paths (every derived form -- fp4 operands, bf16, flags -- is rebuilt by the code that builds it
+ *   for an upload), keypoints, counters, clouds, the detector's type, configuration and thresholds, feature_min_depth, the
+ *   graph and the machine.  RANSAC and matcher parameters (rgbdfe_set_params) are the caller's to set again.
+ * rgbdfe_restore_node_cloud: a resident cloud from the points rgbdfe_download_node_cloud returns and the fields
+ *   rgbdfe_node_cloud_info reports: indistinguishable from the cloud that rgbdfe_upload_node_cloud or the sensor path built
+ *   (the depth plane behind the points is their z; the measurement model's samples are rebuilt on first use). */
+#define RGBDFE_SESSION_CLOUDS 1
+int rgbdfe_pose_graph_serialize(const rgbdfe_pose_graph* g, uint8_t* out, int64_t capacity, int64_t* bytes);
+int rgbdfe_pose_graph_deserialize(rgbdfe_pose_graph* g, const uint8_t* in, int64_t bytes);
+int rgbdfe_pose_graph_node_ids(const rgbdfe_pose_graph* g, int32_t* ids, int32_t capacity, int32_t* n_out);
+int rgbdfe_slam_serialize(rgbdfe_slam* s, uint8_t* out, int64_t capacity, int64_t* bytes);
+int rgbdfe_slam_deserialize(rgbdfe_slam* s, const uint8_t* in, int64_t bytes);
+int rgbdfe_session_save(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, uint32_t flags, const char* path);
+int rgbdfe_session_load(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, const char* path);
+int rgbdfe_restore_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* points, int32_t rows, int32_t cols, double fx,
+                              double fy, double cx, double cy, int32_t cloud_skip);
+/* out8 = { rows, cols, cloud_skip, fx, fy, cx, cy, 0 } of a node's resident cloud (the intrinsics as the floats they are
+ * kept as) */
+int rgbdfe_node_cloud_info(rgbdfe_ctx* ctx, int32_t node_id, double* out8);
 
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, every launch of the dominant kernels is bracketed by HIP events on the

@@ -121,6 +121,58 @@ class FrontEnd {
     return kp;
   }
 
+  // Resident nodes back on the host (rgbdfe_download_nodes): the listed nodes, all of one kind, in the order given and
+  // packed without gaps -- node i's rows are row_offsets[i] .. row_offsets[i + 1] of every array.  desc holds 32 bytes per
+  // row for ORB nodes and 128 floats per row for SIFT / float nodes; kp_xy is zero for a node without keypoints.
+  struct NodeRows {
+    std::vector<int64_t> row_offsets;
+    std::vector<int32_t> kinds;           // 0 ORB, 1 SIFT, 2 float
+    std::vector<uint8_t> has_keypoints;
+    std::vector<uint8_t> desc;            // bytes
+    std::vector<float> xyz1, kp_xy;
+    std::vector<uint8_t> stats;           // feature_matching_stats_
+  };
+  // Throws on failure (an id that is not resident, nodes of different kinds).
+  NodeRows downloadNodes(const std::vector<int32_t>& node_ids) const {
+    NodeRows r;
+    const int32_t n = (int32_t)node_ids.size();
+    r.row_offsets.assign((size_t)n + 1, 0);
+    r.kinds.assign((size_t)n, 0);
+    int st = rgbdfe_download_nodes(ctx_.get(), n, node_ids.data(), INT64_MAX, nullptr, nullptr, nullptr, nullptr,
+                                   r.row_offsets.data(), r.kinds.data());   // the sizing call: no array, no device work
+    const size_t rows = (size_t)r.row_offsets[(size_t)n];
+    if (st == RGBDFE_OK && rows > 0) {
+      r.desc.resize(rows * ((n > 0 && (r.kinds[0] & 0xff) != 0) ? 512 : 32));
+      r.xyz1.resize(rows * 4);
+      r.kp_xy.resize(rows * 2);
+      r.stats.resize(rows);
+      st = rgbdfe_download_nodes(ctx_.get(), n, node_ids.data(), (int64_t)rows, r.desc.data(), r.xyz1.data(), r.kp_xy.data(),
+                                 r.stats.data(), r.row_offsets.data(), r.kinds.data());
+    }
+    if (st != RGBDFE_OK) throw std::runtime_error(std::string("rgbdfe_download_nodes: ") + rgbdfe_last_error(ctx_.get()));
+    r.has_keypoints.resize((size_t)n);
+    for (int32_t i = 0; i < n; ++i) {
+      r.has_keypoints[(size_t)i] = (r.kinds[(size_t)i] & RGBDFE_NODE_HAS_KEYPOINTS) ? 1 : 0;
+      r.kinds[(size_t)i] &= 0xff;
+    }
+    return r;
+  }
+  // a node's feature_matching_stats_ written back behind its upload (a restore); false: not resident, or a wrong count
+  bool setNodeFeatureStats(int32_t node_id, const std::vector<uint8_t>& stats) const {
+    return rgbdfe_set_node_feature_stats(ctx_.get(), node_id, stats.data(), (int32_t)stats.size()) == RGBDFE_OK;
+  }
+  // The grid detector's per-cell thresholds: all it carries from frame to frame.
+  std::vector<double> detectorThresholds() const {
+    std::vector<double> t(64);
+    int32_t n = 0;
+    if (rgbdfe_detector_thresholds(ctx_.get(), t.data(), &n) != RGBDFE_OK) n = 0;
+    t.resize((size_t)n);
+    return t;
+  }
+  bool setDetectorThresholds(const std::vector<double>& t) const {
+    return rgbdfe_detector_set_thresholds(ctx_.get(), t.data(), (int32_t)t.size()) == RGBDFE_OK;
+  }
+
  private:
   std::shared_ptr<rgbdfe_ctx> ctx_;
 };
@@ -537,6 +589,26 @@ class GraphManager {  // candidate selection (graph_manager.cpp:204-324) + the f
     return st->status == RGBDFE_SLAM_FIRST || st->status == RGBDFE_SLAM_ADDED || st->status == RGBDFE_SLAM_REPLACED_FIRST;
   }
   int lastAddNodeStatus() const { return add_node_status_; }
+  // Session files (rgbdfe_session_save / _load): the front end's resident nodes -- features, keypoints, counters, with
+  // `clouds` their clouds --, the detector's state, this object's graph and, once addNode has run, its decision machine.
+  // loadSession wants a fresh GraphManager on a FrontEnd that holds none of the file's nodes, with slamParams() as they were
+  // when the file was written; the run then continues, byte for byte, as the saved one would have.  The loaded nodes are
+  // resident under their ids without a Node object: release them with rgbdfe_release_node.  false: lastAddNodeStatus() has
+  // the status, rgbdfe_last_error the cause.
+  bool saveSession(const std::string& path, bool clouds = false) {
+    add_node_status_ = rgbdfe_session_save(fe_.get(), slam_.get(), topology_.get(), clouds ? RGBDFE_SESSION_CLOUDS : 0u, path.c_str());
+    return add_node_status_ == RGBDFE_OK;
+  }
+  bool loadSession(const std::string& path) {
+    if (!slam_) {
+      rgbdfe_slam* s = nullptr;
+      add_node_status_ = rgbdfe_slam_create(fe_.get(), topology_.get(), &slamParams(), &s);
+      if (add_node_status_ != RGBDFE_OK) return false;
+      slam_.reset(s);
+    }
+    add_node_status_ = rgbdfe_session_load(fe_.get(), slam_.get(), topology_.get(), path.c_str());
+    return add_node_status_ == RGBDFE_OK;
+  }
   int slotOf(int graph_id) const { return slam_ ? rgbdfe_slam_slot_of(slam_.get(), graph_id) : RGBDFE_ERR_UNKNOWN_NODE; }
   bool validTfEstimate(int graph_id) const { return slam_ && rgbdfe_slam_valid_tf(slam_.get(), graph_id) == 1; }
   std::vector<int32_t> keyframeIds() const {

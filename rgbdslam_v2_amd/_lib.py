@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("RGBDFE_LIB", os.path.join(_HERE, "librgbdfe.so"))  # 
 
 RGBDFE_MAX_MATCHES = 320
 RGBDFE_MASK_WORDS = 5
+RGBDFE_NODE_HAS_KEYPOINTS = 0x100   # or-ed into rgbdfe_download_nodes' kinds
+RGBDFE_SESSION_CLOUDS = 1   # rgbdfe_session_save's flags
 
 DEFAULT_HAMMING_MODE = 3   # RGBDFE_HAMMING_MODE_DEFAULT of include/rgbdfe.h (tests/test_abi.py keeps the two equal)
 KERNEL_HAMMING = 0
@@ -679,6 +681,37 @@ def load():
     L.rgbdfe_pose_graph_add_keyframe.argtypes = [vp, i32]
     L.rgbdfe_pose_graph_clear.restype = C.c_int
     L.rgbdfe_pose_graph_clear.argtypes = [vp]
+    L.rgbdfe_download_nodes.restype = C.c_int
+    L.rgbdfe_download_nodes.argtypes = [vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.rgbdfe_debug_download_nodes_copy_loop.restype = C.c_int
+    L.rgbdfe_debug_download_nodes_copy_loop.argtypes = [vp, i32, vp, C.c_int64, vp, vp, vp, vp, vp, vp]
+    L.rgbdfe_download_node.restype = C.c_int
+    L.rgbdfe_download_node.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.rgbdfe_download_nodes_stats.restype = C.c_int
+    L.rgbdfe_download_nodes_stats.argtypes = [vp, vp, i32]
+    L.rgbdfe_set_node_feature_stats.restype = C.c_int
+    L.rgbdfe_set_node_feature_stats.argtypes = [vp, i32, vp, i32]
+    L.rgbdfe_detector_set_thresholds.restype = C.c_int
+    L.rgbdfe_detector_set_thresholds.argtypes = [vp, vp, i32]
+    i64 = C.c_int64
+    L.rgbdfe_pose_graph_serialize.restype = C.c_int
+    L.rgbdfe_pose_graph_serialize.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.rgbdfe_pose_graph_deserialize.restype = C.c_int
+    L.rgbdfe_pose_graph_deserialize.argtypes = [vp, vp, i64]
+    L.rgbdfe_pose_graph_node_ids.restype = C.c_int
+    L.rgbdfe_pose_graph_node_ids.argtypes = [vp, vp, i32, C.POINTER(i32)]
+    L.rgbdfe_slam_serialize.restype = C.c_int
+    L.rgbdfe_slam_serialize.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.rgbdfe_slam_deserialize.restype = C.c_int
+    L.rgbdfe_slam_deserialize.argtypes = [vp, vp, i64]
+    L.rgbdfe_session_save.restype = C.c_int
+    L.rgbdfe_session_save.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p]
+    L.rgbdfe_session_load.restype = C.c_int
+    L.rgbdfe_session_load.argtypes = [vp, vp, vp, C.c_char_p]
+    L.rgbdfe_restore_node_cloud.restype = C.c_int
+    L.rgbdfe_restore_node_cloud.argtypes = [vp, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32]
+    L.rgbdfe_node_cloud_info.restype = C.c_int
+    L.rgbdfe_node_cloud_info.argtypes = [vp, i32, vp]
     _lib = L
     return L
 
@@ -736,4 +769,8 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_slam_add_node", "rgbdfe_slam_begin", "rgbdfe_slam_feed", "rgbdfe_slam_node_count", "rgbdfe_slam_slot_of",
     "rgbdfe_slam_valid_tf", "rgbdfe_slam_keyframes", "rgbdfe_sizeof_slam_step", "rgbdfe_update_inlier_features",
     "rgbdfe_node_feature_stats", "rgbdfe_pose_graph_add_keyframe", "rgbdfe_pose_graph_clear",
+    "rgbdfe_download_nodes", "rgbdfe_debug_download_nodes_copy_loop", "rgbdfe_download_node", "rgbdfe_download_nodes_stats", "rgbdfe_set_node_feature_stats",
+    "rgbdfe_detector_set_thresholds",
+    "rgbdfe_pose_graph_serialize", "rgbdfe_pose_graph_deserialize", "rgbdfe_pose_graph_node_ids", "rgbdfe_slam_serialize",
+    "rgbdfe_slam_deserialize", "rgbdfe_session_save", "rgbdfe_session_load", "rgbdfe_restore_node_cloud", "rgbdfe_node_cloud_info",
 ]

@@ -200,6 +200,42 @@ class PoseGraph:
         self._check(self._L.rgbdfe_pose_graph_transforms(self._g, len(ids), ids.ctypes.data, out.ctypes.data))
         return out.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
 
+    # ---- the graph as a byte string (include/rgbdfe.h, "session files") ----
+    def _check_string(self, rc):
+        if rc != 0:
+            raise _lib.RgbdfeError("%s: %s" % (self._L.rgbdfe_status_string(rc).decode(), self._L.rgbdfe_last_error(None).decode()))
+
+    def serialize(self) -> bytes:
+        """Everything in the graph -- nodes with their estimates and flags, edges with their pruning gates, keyframes,
+        strategy, earliest_loop_closure_node -- as one byte string; the same graph gives the same bytes."""
+        n = C.c_int64(0)
+        rc = self._L.rgbdfe_pose_graph_serialize(self._g, None, 0, C.byref(n))
+        if rc not in (0, -5):  # RGBDFE_ERR_CAPACITY: the length is set
+            self._check_string(rc)
+        buf = np.zeros(max(n.value, 1), np.uint8)
+        self._check_string(self._L.rgbdfe_pose_graph_serialize(self._g, buf.ctypes.data, n.value, C.byref(n)))
+        return buf[: n.value].tobytes()
+
+    def deserialize(self, data: bytes):
+        """Into an empty graph (a new one, or after clear): refused otherwise, and for any string that is not exactly what
+        serialize returned."""
+        buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+        self._check_string(self._L.rgbdfe_pose_graph_deserialize(self._g, buf.ctypes.data, len(data)))
+        self._sync_ids()
+
+    def node_ids(self):
+        n = C.c_int32(0)
+        rc = self._L.rgbdfe_pose_graph_node_ids(self._g, None, 0, C.byref(n))
+        if rc not in (0, -5):
+            self._check(rc)
+        ids = np.zeros(max(n.value, 1), np.int32)
+        self._check(self._L.rgbdfe_pose_graph_node_ids(self._g, ids.ctypes.data, n.value, C.byref(n)))
+        return ids[: n.value].copy()
+
+    def _sync_ids(self):
+        """After the C side filled the graph (deserialize, FrontEnd.load_session)."""
+        self._ids = set(int(i) for i in self.node_ids())
+
     def set_matchable(self, node_id, matchable):
         self._check(self._L.rgbdfe_pose_graph_set_matchable(self._g, int(node_id), int(bool(matchable))))
 

@@ -149,6 +149,7 @@ void rgbdfe_destroy(rgbdfe_ctx* ctx) {
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->icp.p) (void)hipFree(ctx->icp.p);
   if (ctx->render.p) (void)hipFree(ctx->render.p);
+  if (ctx->node_pack.p) (void)hipFree(ctx->node_pack.p);
   for (hipEvent_t e : ctx->orb_upload_done) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->orb_describe_done) if (e) (void)hipEventDestroy(e);
   if (ctx->orb_upload_stream) (void)hipStreamDestroy(ctx->orb_upload_stream);

@@ -5,13 +5,14 @@
 #include <new>
 
 #include "rgbdfe_host.h"
+#include "session_format.h"
 #include "slam_machine.h"
 #include "slam_step.h"
 
 namespace impl {
 
 // the counters of every slot, allocated zeroed on first use (rgbdfe_host.h: d_feat_stats); ctx->mu is held
-static int ensure_feature_stats(rgbdfe_ctx* ctx) {
+int ensure_feature_stats(rgbdfe_ctx* ctx) {
   if (ctx->d_feat_stats) return RGBDFE_OK;
   const size_t bytes = (size_t)ctx->cfg.max_nodes * ctx->feat_stats_stride();
   if (hipMalloc((void**)&ctx->d_feat_stats, bytes) != hipSuccess) {
@@ -187,6 +188,10 @@ int matchnodepair_tail(rgbdfe_slam* s, int32_t new_slot, const int32_t* ids, con
   }
   return RGBDFE_OK;
 }
+
+}  // namespace
+namespace rgbdfe_host { int slam_fail(rgbdfe_slam* s, int code, const std::string& msg); }
+namespace {
 
 template <class F>
 int slam_guarded(F&& f) noexcept {
@@ -427,4 +432,48 @@ int rgbdfe_slam_keyframes(const rgbdfe_slam* s, int32_t* ids, int32_t capacity, 
 
 int rgbdfe_sizeof_slam_step(void) { return (int)sizeof(rgbdfe_slam_step); }
 
+int rgbdfe_slam_serialize(rgbdfe_slam* s, uint8_t* out, int64_t capacity, int64_t* bytes) {
+  return slam_guarded([&]() -> int {
+    if (!s || !bytes || capacity < 0 || (capacity > 0 && !out)) return slam_fail(s, RGBDFE_ERR_INVALID_ARG, "slam state: bad arguments");
+    std::vector<uint8_t> b;
+    {
+      std::lock_guard<std::mutex> l(s->mu);
+      if (s->m.phase != rgbdfe_slam_machine::Machine::kIdle)
+        return slam_fail(s, RGBDFE_ERR_INVALID_ARG, "slam state: busy: a step is in flight (between rgbdfe_slam_begin and the last rgbdfe_slam_feed)");
+      rgbdfe_session::slam_serialize(s->m, b);
+    }
+    *bytes = (int64_t)b.size();
+    if ((int64_t)b.size() > capacity) return slam_fail(s, RGBDFE_ERR_CAPACITY, "slam state: capacity below the string's length (*bytes holds it)");
+    std::copy(b.begin(), b.end(), out);
+    return RGBDFE_OK;
+  });
+}
+
+int rgbdfe_slam_deserialize(rgbdfe_slam* s, const uint8_t* in, int64_t bytes) {
+  return slam_guarded([&]() -> int { return rgbdfe_host::slam_deserialize(s, in, bytes, true); });
+}
+
 }  // extern "C"
+
+namespace rgbdfe_host {
+int slam_fail(rgbdfe_slam* s, int code, const std::string& msg) {
+  rgbdfe_session::contextless_error() = msg;
+  return (s && s->ctx) ? fail(s->ctx, code, msg) : code;
+}
+// everything rgbdfe_slam_deserialize checks; the object changes only with `commit` and only when nothing was wrong
+int slam_deserialize(rgbdfe_slam* s, const uint8_t* in, int64_t bytes, bool commit) {
+  if (!s || !in || bytes < 0) return slam_fail(s, RGBDFE_ERR_INVALID_ARG, "slam state: bad arguments");
+  rgbdfe_session::SlamImage img;
+  const std::string err = rgbdfe_session::slam_parse(in, (size_t)bytes, img);
+  if (!err.empty()) return slam_fail(s, RGBDFE_ERR_INVALID_ARG, err);
+  std::lock_guard<std::mutex> l(s->mu);
+  if (!rgbdfe_session::slam_is_fresh(s->m))
+    return slam_fail(s, RGBDFE_ERR_INVALID_ARG, "slam state: the target of a deserialise must be fresh or reset (rgbdfe_slam_reset)");
+  if (const char* field = rgbdfe_session::slam_params_differ(s->m.prm, img.prm))
+    return slam_fail(s, RGBDFE_ERR_INVALID_ARG, std::string("slam state: the object's parameters differ from the stored ones: ") + field);
+  if (commit) rgbdfe_session::slam_commit(s->m, img);
+  return RGBDFE_OK;
+}
+rgbdfe_ctx* slam_context(rgbdfe_slam* s) { return s->ctx; }
+rgbdfe_pose_graph* slam_graph(rgbdfe_slam* s) { return s->m.g; }
+}  // namespace rgbdfe_host

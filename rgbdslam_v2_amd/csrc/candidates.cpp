@@ -23,8 +23,11 @@
 #include <utility>
 #include <vector>
 
+#include <string>
+
 #include "rgbdfe.h"
 #include "pose_graph_host.h"
+#include "session_format.h"
 
 namespace {
 
@@ -72,6 +75,11 @@ struct CounterRand {  // stand-in for rand() when the caller brings no generator
 };
 
 }  // namespace
+
+std::string& rgbdfe_session::contextless_error() {
+  static thread_local std::string msg;
+  return msg;
+}
 
 extern "C" {
 
@@ -146,6 +154,54 @@ int rgbdfe_pose_graph_clear(rgbdfe_pose_graph* g) {
   g->keyframes.clear();
   g->edges.clear();
   g->earliest_loop_closure_node = 0;
+  return RGBDFE_OK;
+}
+
+// ---- the graph as a byte string (session_format.h) ---------------------------------------------------------------------
+namespace {
+int graph_fail(int code, const std::string& msg) {
+  rgbdfe_session::contextless_error() = msg;
+  return code;
+}
+}  // namespace
+
+int rgbdfe_pose_graph_serialize(const rgbdfe_pose_graph* g, uint8_t* out, int64_t capacity, int64_t* bytes) try {
+  if (!g || !bytes || capacity < 0 || (capacity > 0 && !out)) return graph_fail(RGBDFE_ERR_INVALID_ARG, "pose graph: bad arguments");
+  std::vector<uint8_t> b;
+  std::string err;
+  const int rc = rgbdfe_session::graph_serialize(*g, b, err);
+  if (rc != RGBDFE_OK) return graph_fail(rc, err);
+  *bytes = (int64_t)b.size();
+  if ((int64_t)b.size() > capacity) return graph_fail(RGBDFE_ERR_CAPACITY, "pose graph: capacity below the string's length (*bytes holds it)");
+  std::copy(b.begin(), b.end(), out);
+  return RGBDFE_OK;
+} catch (const std::bad_alloc&) {
+  return RGBDFE_ERR_OUT_OF_MEMORY;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_deserialize(rgbdfe_pose_graph* g, const uint8_t* in, int64_t bytes) try {
+  if (!g || !in || bytes < 0) return graph_fail(RGBDFE_ERR_INVALID_ARG, "pose graph: bad arguments");
+  if (!rgbdfe_session::graph_is_empty(*g))
+    return graph_fail(RGBDFE_ERR_INVALID_ARG, "pose graph: the target of a deserialise must be empty (rgbdfe_pose_graph_clear)");
+  rgbdfe_session::GraphImage img;
+  const std::string err = rgbdfe_session::graph_parse(in, (size_t)bytes, img);
+  if (!err.empty()) return graph_fail(RGBDFE_ERR_INVALID_ARG, err);
+  rgbdfe_session::graph_commit(*g, img);
+  return RGBDFE_OK;
+} catch (const std::bad_alloc&) {
+  return RGBDFE_ERR_OUT_OF_MEMORY;
+} catch (...) {
+  return RGBDFE_ERR_INTERNAL;  // no exception crosses the C ABI
+}
+
+int rgbdfe_pose_graph_node_ids(const rgbdfe_pose_graph* g, int32_t* ids, int32_t capacity, int32_t* n_out) {
+  if (!g || !n_out || capacity < 0 || (capacity > 0 && !ids)) return RGBDFE_ERR_INVALID_ARG;
+  *n_out = (int32_t)g->nodes.size();
+  if (*n_out > capacity) return RGBDFE_ERR_CAPACITY;
+  int32_t k = 0;
+  for (const auto& kv : g->nodes) ids[k++] = kv.first;
   return RGBDFE_OK;
 }
 

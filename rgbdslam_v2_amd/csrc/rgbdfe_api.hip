@@ -2,6 +2,7 @@
 // single-device implementation (namespace impl) or to the multi-device group.  There is no CPU fallback: without a HIP device
 // every entry point reports RGBDFE_ERR_NO_DEVICE.
 #include "rgbdfe_host.h"
+#include "session_format.h"
 
 extern "C" {
 
@@ -80,6 +81,8 @@ const char* rgbdfe_last_error(rgbdfe_ctx* ctx) {
     if (ctx) {
       std::lock_guard<std::mutex> g(ctx->err_mu);
       buf = ctx->last_error;
+    } else {
+      buf = rgbdfe_session::contextless_error();   // pose-graph / slam byte strings: calls without a context
     }
     return buf.c_str();
   } catch (...) {
@@ -1222,6 +1225,70 @@ int rgbdfe_update_inlier_features(rgbdfe_ctx* ctx, const void* d_records, const 
 int rgbdfe_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, uint8_t* out, int32_t capacity) {
   if (!ctx) return RGBDFE_ERR_INVALID_ARG;
   return RGBDFE_FIRST(ctx, impl::rgbdfe_node_feature_stats(c, node_id, out, capacity));
+}
+
+// a multi-device handle answers from its first device: every node is resident on all of them
+int rgbdfe_download_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, int64_t capacity_rows, void* desc,
+                          float* xyz1, float* kp_xy, uint8_t* stats, int64_t* row_offsets, int32_t* kinds) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_download_nodes(c, n_nodes, node_ids, capacity_rows, desc, xyz1, kp_xy, stats, row_offsets, kinds));
+}
+
+int rgbdfe_debug_download_nodes_copy_loop(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, int64_t capacity_rows, void* desc,
+                                          float* xyz1, float* kp_xy, uint8_t* stats, int64_t* row_offsets, int32_t* kinds) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_debug_download_nodes_copy_loop(c, n_nodes, node_ids, capacity_rows, desc, xyz1, kp_xy, stats, row_offsets, kinds));
+}
+
+int rgbdfe_download_node(rgbdfe_ctx* ctx, int32_t node_id, int32_t capacity_rows, void* desc, float* xyz1, float* kp_xy,
+                         uint8_t* stats, int32_t* kind, int32_t* has_keypoints) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return guarded(ctx, [&]() -> int {   // (the return value is a row count: not through RGBDFE_FIRST, which reads it as a status)
+    return impl::rgbdfe_download_node(RGBDFE_IS_GROUP(ctx) ? ctx->group->children[0] : ctx, node_id, capacity_rows, desc, xyz1,
+                                      kp_xy, stats, kind, has_keypoints);
+  });
+}
+
+int rgbdfe_download_nodes_stats(rgbdfe_ctx* ctx, int64_t* out, int32_t n_out) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_download_nodes_stats(c, out, n_out));
+}
+
+int rgbdfe_set_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, const uint8_t* stats, int32_t n) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_ALL(ctx, impl::rgbdfe_set_node_feature_stats(c, node_id, stats, n));
+}
+
+int rgbdfe_detector_set_thresholds(rgbdfe_ctx* ctx, const double* thresholds, int32_t n_cells) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_detector_set_thresholds(c, thresholds, n_cells));
+}
+
+int rgbdfe_node_cloud_info(rgbdfe_ctx* ctx, int32_t node_id, double* out8) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_node_cloud_info(c, node_id, out8));
+}
+
+int rgbdfe_restore_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* points, int32_t rows, int32_t cols, double fx, double fy,
+                              double cx, double cy, int32_t cloud_skip) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_ALL(ctx, impl::rgbdfe_restore_node_cloud(c, node_id, points, rows, cols, fx, fy, cx, cy, cloud_skip));
+}
+
+int rgbdfe_session_save(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, uint32_t flags, const char* path) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return guarded(ctx, [&]() -> int {
+    if (RGBDFE_IS_GROUP(ctx)) return group_only_single(ctx, "rgbdfe_session_save");
+    return impl::rgbdfe_session_save(ctx, slam, graph, flags, path);
+  });
+}
+
+int rgbdfe_session_load(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, const char* path) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return guarded(ctx, [&]() -> int {
+    if (RGBDFE_IS_GROUP(ctx)) return group_only_single(ctx, "rgbdfe_session_load");
+    return impl::rgbdfe_session_load(ctx, slam, graph, path);
+  });
 }
 
 int rgbdfe_abi_version(void) { return impl::rgbdfe_abi_version(); }

@@ -149,6 +149,8 @@ inline hipError_t create_side_stream(hipStream_t* s, int which) {
 }
 
 struct rgbdfe_ctx;
+struct rgbdfe_slam;
+struct rgbdfe_pose_graph;
 namespace rgbdfe_host {
 int fail(rgbdfe_ctx* ctx, int code, const std::string& msg);
 
@@ -325,6 +327,8 @@ struct rgbdfe_ctx {
   GrowBuffer render;         // api_render.hip: a call's visibility words, staged images, vertex group and queue
   bool render_count_fragments = false;   // rgbdfe_render_fragment_stats: the counting kernels (diagnostics)
   int64_t render_fragments[2] = {0, 0};  // the latest render call's fragments offered / that lowered a word on arrival
+  GrowBuffer node_pack;      // api_session.hip: a read-back's node table and packed rows (rgbdfe_download_nodes)
+  int64_t node_pack_launches = 0, node_pack_copies = 0;   // the latest read-back's kernel launches / device-to-host copies
   GrowBuffer icp;            // api_icp.hip: the samples, working copies and records of a call (d_scratch holds its tile counts and offsets)
   OrbWorkspace orb;
   OrbWorkspace orb_super;  // rgbdfe_detect_describe_batch: up to 7 frames per launch chain (its own image sets)
@@ -755,7 +759,31 @@ int rgbdfe_abi_version(void);
 int rgbdfe_update_inlier_features(rgbdfe_ctx* ctx, const void* d_records, const int32_t* query_ids, const int32_t* train_ids,
                                   const uint8_t* accept, int32_t n, int32_t* launched);
 int rgbdfe_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, uint8_t* out, int32_t capacity);
+int ensure_feature_stats(rgbdfe_ctx* ctx);       // the counters of every slot, allocated zeroed on first use (api_slam.hip)
+// api_session.hip
+int rgbdfe_download_nodes(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, int64_t capacity_rows, void* desc, float* xyz1,
+                          float* kp_xy, uint8_t* stats, int64_t* row_offsets, int32_t* kinds);
+int rgbdfe_debug_download_nodes_copy_loop(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, int64_t capacity_rows, void* desc,
+                                          float* xyz1, float* kp_xy, uint8_t* stats, int64_t* row_offsets, int32_t* kinds);
+int rgbdfe_download_node(rgbdfe_ctx* ctx, int32_t node_id, int32_t capacity_rows, void* desc, float* xyz1, float* kp_xy,
+                         uint8_t* stats, int32_t* kind, int32_t* has_keypoints);
+int rgbdfe_download_nodes_stats(rgbdfe_ctx* ctx, int64_t* out, int32_t n_out);
+int rgbdfe_set_node_feature_stats(rgbdfe_ctx* ctx, int32_t node_id, const uint8_t* stats, int32_t n);
+int rgbdfe_detector_set_thresholds(rgbdfe_ctx* ctx, const double* thresholds, int32_t n_cells);
+int rgbdfe_node_cloud_info(rgbdfe_ctx* ctx, int32_t node_id, double* out8);
+int rgbdfe_restore_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* points, int32_t rows, int32_t cols, double fx, double fy,
+                              double cx, double cy, int32_t cloud_skip);
+int rgbdfe_session_save(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, uint32_t flags, const char* path);
+int rgbdfe_session_load(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, const char* path);
 }  // namespace impl
+
+// ---- the rgbdfe_slam object as api_session.hip needs it (api_slam.hip)
+namespace rgbdfe_host {
+// rgbdfe_slam_deserialize's checks (the string, a fresh target, equal parameters); the object changes only with `commit`
+int slam_deserialize(rgbdfe_slam* s, const uint8_t* in, int64_t bytes, bool commit);
+rgbdfe_ctx* slam_context(rgbdfe_slam* s);
+rgbdfe_pose_graph* slam_graph(rgbdfe_slam* s);
+}  // namespace rgbdfe_host
 
 // ---- several devices behind one handle (api_group.hip)
 #include <dlfcn.h>

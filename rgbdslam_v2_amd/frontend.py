@@ -332,6 +332,79 @@ class FrontEnd:
             self._check(n)
         return out[:n]
 
+    def set_node_feature_stats(self, node_id: int, stats):
+        """Writes a resident node's counters back (one byte per row): what a restore needs behind the upload."""
+        s = np.ascontiguousarray(stats, np.uint8).reshape(-1)
+        self._check(self._L.rgbdfe_set_node_feature_stats(self._ctx, int(node_id), s.ctypes.data, len(s)))
+
+    def download_nodes(self, node_ids, fields=("desc", "xyz1", "kp_xy", "stats")) -> dict:
+        """rgbdfe_download_nodes: the listed resident nodes (of one kind) in the order given, packed without gaps.  Returns
+        {"row_offsets": [n + 1] int64, "kinds": [n] (0 ORB, 1 SIFT, 2 float), "has_keypoints": [n] bool} plus the arrays named
+        in `fields`: desc [rows, 32] uint8 (ORB) or [rows, 128] float32, xyz1 [rows, 4], kp_xy [rows, 2] (zeros for a node
+        without keypoints), stats [rows] uint8.  Node i's rows are row_offsets[i] : row_offsets[i + 1] of each."""
+        ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        unknown = set(fields) - {"desc", "xyz1", "kp_xy", "stats"}
+        if unknown:
+            raise ValueError("unknown fields: %s" % sorted(unknown))
+        n = len(ids)
+        off = np.zeros(n + 1, np.int64)
+        kinds = np.zeros(n, np.int32)
+        # sizing call: no array given, so any capacity serves and no device work happens; offsets and kinds come back
+        self._check(self._L.rgbdfe_download_nodes(self._ctx, n, ids.ctypes.data, 2 ** 62, None, None, None, None, off.ctypes.data,
+                                                  kinds.ctypes.data))
+        rows = int(off[n])
+        orb = n == 0 or (int(kinds[0]) & 0xff) == 0
+        shapes = {"desc": ((rows, 32), np.uint8) if orb else ((rows, 128), np.float32), "xyz1": ((rows, 4), np.float32),
+                  "kp_xy": ((rows, 2), np.float32), "stats": ((rows,), np.uint8)}
+        out = {f: np.zeros(*shapes[f]) for f in fields}
+        if rows and out:
+            ptr = {f: (out[f].ctypes.data if f in out else None) for f in shapes}
+            self._check(self._L.rgbdfe_download_nodes(self._ctx, n, ids.ctypes.data, rows, ptr["desc"], ptr["xyz1"], ptr["kp_xy"],
+                                                      ptr["stats"], off.ctypes.data, kinds.ctypes.data))
+        out["row_offsets"] = off
+        out["kinds"] = kinds & 0xff
+        out["has_keypoints"] = (kinds & _lib.RGBDFE_NODE_HAS_KEYPOINTS) != 0
+        return out
+
+    # -- session files (include/rgbdfe.h, "session files") -----------------------------------------
+    def save_session(self, path, slam=None, graph=None, clouds=False):
+        """rgbdfe_session_save: the resident nodes (features, keypoints, counters), the detector's state, with clouds=True the
+        resident clouds, and the graph's and the Slam's byte strings when given.  The same state gives the same bytes."""
+        self._check(self._L.rgbdfe_session_save(self._ctx, None if slam is None else slam._s, None if graph is None else graph._g,
+                                                _lib.RGBDFE_SESSION_CLOUDS if clouds else 0, str(path).encode()))
+
+    def load_session(self, path, slam=None, graph=None):
+        """rgbdfe_session_load into this context and (when the file holds them) a fresh Slam and an empty PoseGraph: validated
+        as a whole before anything changes.  RANSAC / matcher parameters are the caller's to set again (set_params)."""
+        self._check(self._L.rgbdfe_session_load(self._ctx, None if slam is None else slam._s, None if graph is None else graph._g,
+                                                str(path).encode()))
+        if graph is not None:
+            graph._sync_ids()
+        with open(path, "rb") as f:   # the detector's max_keypoints sizes detect_describe's outputs on this side
+            f.seek(80)                # header 32, CONF chunk 16 + 16, DETE chunk header 16: its payload, i32 type, i32 max_keypoints
+            self._max_keypoints = int(np.frombuffer(f.read(8), np.int32)[1])
+
+    def node_cloud_info(self, node_id) -> dict:
+        """rows, cols, cloud_skip and the intrinsics (as the floats they are kept as) of a node's resident cloud."""
+        v = np.zeros(8, np.float64)
+        self._check(self._L.rgbdfe_node_cloud_info(self._ctx, int(node_id), v.ctypes.data))
+        return dict(rows=int(v[0]), cols=int(v[1]), cloud_skip=int(v[2]), fx=float(v[3]), fy=float(v[4]), cx=float(v[5]), cy=float(v[6]))
+
+    def restore_node_cloud(self, node_id, points, fx, fy, cx, cy, cloud_skip=1):
+        """A resident cloud from node_cloud's points [rows, cols, 4] and node_cloud_info's fields."""
+        pts = np.ascontiguousarray(points, np.float32)
+        if pts.ndim != 3 or pts.shape[2] != 4:
+            raise ValueError("points must be [rows, cols, 4] float32")
+        self._check(self._L.rgbdfe_restore_node_cloud(self._ctx, int(node_id), pts.ctypes.data, pts.shape[0], pts.shape[1],
+                                                      float(fx), float(fy), float(cx), float(cy), int(cloud_skip)))
+
+    def download_nodes_stats(self) -> dict:
+        """The latest download_nodes call: kernel launches, device-to-host copies, bytes of the staging buffer, and whether the
+        context's feature counters have been allocated."""
+        v = np.zeros(4, np.int64)
+        self._check(self._L.rgbdfe_download_nodes_stats(self._ctx, v.ctypes.data, len(v)))
+        return {"launches": int(v[0]), "copies": int(v[1]), "staging_bytes": int(v[2]), "feature_stats_allocated": bool(v[3])}
+
     def update_inlier_features(self, d_records_ptr: int, query_ids, train_ids, accept) -> int:
         """updateInlierFeatures over n records in device memory for the pairs with accept != 0; returns the kernel launches."""
         q, t = np.ascontiguousarray(query_ids, np.int32), np.ascontiguousarray(train_ids, np.int32)
@@ -449,6 +522,11 @@ class FrontEnd:
         n = C.c_int32(0)
         self._check(self._L.rgbdfe_detector_thresholds(self._ctx, t.ctypes.data, C.byref(n)))
         return t[: n.value].copy()
+
+    def detector_set_thresholds(self, thresholds):
+        """The inverse of detector_thresholds (grid_resolution^2 values): all a grid detector carries between frames."""
+        t = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+        self._check(self._L.rgbdfe_detector_set_thresholds(self._ctx, t.ctypes.data, len(t)))
 
     def host_register(self, array):
         """Page-locks a numpy array's memory (rgbdfe_host_register): detect_describe then copies it to the device directly
@@ -1643,6 +1721,56 @@ class GraphManager:
         return self.addNode(node, stamp)
 
 
+def read_session_chunks(path) -> dict:
+    """The chunks of a session file by tag ("CONF", "DETE", "NODE", "CLOU", "GRPH", "SLAM"), every CRC checked: for tools that
+    need a field before they can build the objects to load into (include/rgbdfe.h, "session files")."""
+    import struct
+    import zlib
+    with open(path, "rb") as f:
+        b = f.read()
+    if b[:8] != b"RGBDFESS" or len(b) < 32 or struct.unpack_from("<IIQ", b, 8)[0::2] != (1, len(b)):
+        raise RgbdfeError("not a session file: " + str(path))
+    at, out = 32, {}
+    while at + 16 <= len(b):
+        tag = b[at:at + 4].decode("ascii", "replace")
+        crc, n = struct.unpack_from("<IQ", b, at + 4)
+        payload = b[at + 16:at + 16 + n]
+        if len(payload) != n or zlib.crc32(payload) != crc:
+            raise RgbdfeError("session file: bad chunk " + tag)
+        if tag == "END ":
+            return out
+        out[tag] = payload
+        at += 16 + n + (-n % 8)
+    raise RgbdfeError("session file: no END chunk")
+
+
+def parse_slam_state(data: bytes) -> dict:
+    """Slam.serialize()'s string (a session file's SLAM chunk) as a dict: params (the 13 int32 in the order of
+    rgbdfe_slam_params, seed, the 6 doubles, init_base_pose), calls (steps begun), per graph id slots / rows / stamps /
+    valid_tf, keyframes, the edge counters."""
+    import struct
+    if data[:8] != b"RGBDFESM":
+        raise RgbdfeError("not a slam state")
+    names_i = [n for n, _ in _lib.SlamParams._fields_][:13]
+    names_d = [n for n, _ in _lib.SlamParams._fields_][14:20]
+    at = 24
+    params = dict(zip(names_i, struct.unpack_from("<13i", data, at)))
+    params["seed"] = struct.unpack_from("<I", data, at + 52)[0]
+    params.update(zip(names_d, struct.unpack_from("<6d", data, at + 56)))
+    params["init_base_pose"] = np.array(struct.unpack_from("<16d", data, at + 104)).reshape(4, 4).T
+    at += 232
+    n, n_kf, next_seq_id, calls, seq_edges, loop_edges, b1, b2, bn, _ = struct.unpack_from("<IIiIiiiiiI", data, at)
+    at += 40
+    slots = list(struct.unpack_from("<%di" % n, data, at)); at += 4 * n
+    rows = list(struct.unpack_from("<%di" % n, data, at)); at += 4 * n
+    sec = struct.unpack_from("<%dq" % n, data, at); at += 8 * n
+    nsec = struct.unpack_from("<%di" % n, data, at); at += 4 * n
+    valid = list(struct.unpack_from("<%dB" % n, data, at)); at += n + (-n % 4)
+    keyframes = list(struct.unpack_from("<%di" % n_kf, data, at))
+    return dict(params=params, calls=calls, slots=slots, rows=rows, stamps=list(zip(sec, nsec)), valid_tf=valid, keyframes=keyframes,
+                sequential_edges=seq_edges, loop_closure_edges=loop_edges, best=(b1, b2, bn), next_seq_id=next_seq_id)
+
+
 class SlamStepRecord:
     """An rgbdfe_slam_step with names for its codes."""
 
@@ -1706,6 +1834,27 @@ class Slam:
 
     def reset(self):
         self._check(self._L.rgbdfe_slam_reset(self._s))
+
+    def _check_string(self, st):
+        if st != 0:
+            raise RgbdfeError(f"{self._L.rgbdfe_status_string(st).decode()}: {self._L.rgbdfe_last_error(None).decode()}")
+
+    def serialize(self) -> bytes:
+        """The machine between two steps -- slot table, stamps, valid_tf, keyframes, counters, curr_best_result_, the draw
+        counter and the parameters -- as one byte string; refused while a step is in flight (between begin and feed)."""
+        n = C.c_int64(0)
+        st = self._L.rgbdfe_slam_serialize(self._s, None, 0, C.byref(n))
+        if st not in (0, -5):  # RGBDFE_ERR_CAPACITY: the length is set
+            self._check_string(st)
+        buf = np.zeros(max(n.value, 1), np.uint8)
+        self._check_string(self._L.rgbdfe_slam_serialize(self._s, buf.ctypes.data, n.value, C.byref(n)))
+        return buf[: n.value].tobytes()
+
+    def deserialize(self, data: bytes):
+        """Into a fresh or reset Slam created with the stored parameters (the error names the first field that differs).  The
+        pose graph is not part of the string: PoseGraph.deserialize."""
+        buf = np.frombuffer(bytes(data), np.uint8) if len(data) else np.zeros(1, np.uint8)
+        self._check_string(self._L.rgbdfe_slam_deserialize(self._s, buf.ctypes.data, len(data)))
 
     def add_node(self, slot: int, stamp=(0, 0)) -> SlamStepRecord:
         st = _lib.SlamStep()

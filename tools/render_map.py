@@ -90,10 +90,56 @@ def camera_for(kind, pose, fx, fy, cx, cy, width, height, z_near=0.1, z_far=1e4)
     return view, F.render_perspective(aspect=float(np.float32(width) / np.float32(height)))
 
 
+def draw_session(a):
+    """The clouds of a session file at the estimates of its pose graph: loaded, not computed again."""
+    import struct
+    from rgbdslam_v2_amd.candidates import PoseGraph
+    from rgbdslam_v2_amd.frontend import FrontEnd, parse_slam_state, read_session_chunks
+    chunks = read_session_chunks(a.session)
+    if "CLOU" not in chunks or "GRPH" not in chunks or "SLAM" not in chunks:
+        raise SystemExit("the session holds no clouds, no graph or no slam state (save_session(..., slam, graph, clouds=True))")
+    max_keypoints = struct.unpack_from("<i", chunks["CONF"], 0)[0]
+    n_nodes = struct.unpack_from("<I", chunks["NODE"], 0)[0]
+    state = parse_slam_state(chunks["SLAM"])
+    fe = FrontEnd(device_id=0, max_nodes=n_nodes + 1, max_keypoints=max_keypoints, max_pairs_per_batch=8)
+    graph = PoseGraph()
+    fe.load_session(a.session, None, graph)   # the machine's chunk stays in the file: its slot table was read above
+    clouds = {}
+    for i, slot in enumerate(state["slots"]):
+        if slot >= 0 and state["valid_tf"][i]:
+            try:
+                clouds[i] = fe.node_cloud_info(slot)
+            except Exception:
+                pass   # a node whose cloud the run released
+    if not clouds:
+        raise SystemExit("no node of the session has both a valid estimate and a cloud")
+    ids = sorted(clouds)
+    T = graph.transforms(ids)
+    c = clouds[ids[a.pose_index]]
+    w, h = c["cols"] * c["cloud_skip"], c["rows"] * c["cloud_skip"]
+    W, H = a.width or w, a.height or h
+    sx, sy = W / w, H / h
+    view, proj = camera_for(a.camera, np.asarray(T[a.pose_index], np.float64), c["fx"] * sx, c["fy"] * sy, (c["cx"] + 0.5) * sx - 0.5,
+                            (c["cy"] + 0.5) * sy - 0.5, W, H)
+    t0 = time.perf_counter()
+    out = fe.render_nodes([state["slots"][i] for i in ids], T, width=W, height=H, view=view, projection=proj, display_type=FORMS[a.form],
+                          gl_point_size=a.point_size if a.point_size is not None else float(c["cloud_skip"]),
+                          max_vertices_in_flight=a.max_vertices_in_flight)
+    ms = 1e3 * (time.perf_counter() - t0)
+    write_image(a.out, out["rgba"])
+    if a.depth_out:
+        np.save(a.depth_out, out["depth"])
+    fe.close()
+    print(json.dumps(dict(tool="render_map", session=a.session, out=a.out, nodes=len(ids), form=a.form, camera=a.camera, width=W, height=H,
+                          render_ms=ms, pixels_drawn=int(np.sum(out["ids"] >= 0)))))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--frames", required=True, help=".npz: depth [n, h, w], rgb [n, h, w, 3] (optional), fx, fy, cx, cy")
-    ap.add_argument("--trajectory", required=True)
+    ap.add_argument("--frames", help=".npz: depth [n, h, w], rgb [n, h, w, 3] (optional), fx, fy, cx, cy")
+    ap.add_argument("--trajectory")
+    ap.add_argument("--session", metavar="FILE", help="draw a saved run (FrontEnd.save_session with clouds) instead of --frames and "
+                    "--trajectory: its clouds at its graph's estimates, nothing is run again")
     ap.add_argument("--out", required=True, help=".png or .ppm")
     ap.add_argument("--form", choices=sorted(FORMS), default="POINTS")
     ap.add_argument("--camera", choices=("sensor", "viewer"), default="sensor")
@@ -107,6 +153,10 @@ def main():
     a = ap.parse_args()
 
     from rgbdslam_v2_amd.frontend import FrontEnd
+    if a.session:
+        return draw_session(a)
+    if not a.frames or not a.trajectory:
+        ap.error("--frames and --trajectory, or --session")
     data = np.load(a.frames)
     depth = np.asarray(data["depth"], np.float32)
     rgb = np.asarray(data["rgb"], np.uint8) if "rgb" in data.files else None

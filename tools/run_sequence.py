@@ -9,6 +9,11 @@ sequences only: the image sequence has no camera poses); --map also assembles th
 estimate (image sequences: they carry clouds) and inserts them into an OctoMap; --render FILE renders those clouds on the
 device, seen through the sensor from the last pose, into a PNG or PPM (tools/render_map.py).
 
+--save-session FILE writes the run's state -- resident nodes, the detector's thresholds, with --map / --render the clouds, the
+pose graph and the decision machine -- when the run ends, or after K frames with --stop-after K; --resume FILE loads such a
+file into fresh objects and continues with the frame behind the last one the file has seen.  The resumed run's steps, graph
+and trajectory are, byte for byte, those of the run that was never stopped (the same --frames, --seed and parameters).
+
 Prints one JSON line (--out FILE also writes it there): frames, frames dropped by status, vertices, edges, keyframes, ATE,
 ms per frame in total and per stage (upload, candidates, comparisons, decisions, optimisation) as means and medians of the
 step records' times.  The line is stamped with the device's name and with `git rev-parse --short HEAD` of the tree (BENCH_COMMIT
@@ -32,7 +37,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import evaluate_ate  # noqa: E402
 from rgbdslam_v2_amd import synth  # noqa: E402
 from rgbdslam_v2_amd.candidates import PoseGraph  # noqa: E402
-from rgbdslam_v2_amd.frontend import FrontEnd, GraphManager, Node  # noqa: E402
+from rgbdslam_v2_amd.frontend import FrontEnd, GraphManager, Node, parse_slam_state, read_session_chunks  # noqa: E402
 
 STAGES = ("candidates", "comparisons", "decisions", "optimisation")
 
@@ -57,6 +62,9 @@ def main():
     ap.add_argument("--render", metavar="FILE", help="with --images: the map seen from the last pose, as .png or .ppm")
     ap.add_argument("--seed", type=int, default=20260923)
     ap.add_argument("--out")
+    ap.add_argument("--save-session", metavar="FILE", help="save nodes, detector state, graph and machine when the run ends")
+    ap.add_argument("--stop-after", type=int, metavar="K", help="with --save-session: end the run after K frames")
+    ap.add_argument("--resume", metavar="FILE", help="load a saved session and continue behind its last frame")
     a = ap.parse_args()
 
     fe = FrontEnd(device_id=0, max_nodes=a.frames + 1, max_keypoints=max(a.n_kp, 600), max_pairs_per_batch=64)
@@ -67,18 +75,25 @@ def main():
     stamps = [((k * ns) // 1000000000, (k * ns) % 1000000000) for k in range(a.frames)]
     poses = None
     upload_s = []
+    start, stop = 0, a.frames if a.stop_after is None else max(0, min(a.frames, a.stop_after))
+    if a.resume:   # before anything enters the context: the file's node ids must not be resident
+        start = parse_slam_state(read_session_chunks(a.resume)["SLAM"])["calls"]   # one step per frame so far
+        fe.load_session(a.resume, slam, gm.pose_graph)
     if a.images:
         seq = synth.make_image_sequence(n_frames=a.frames, width=a.width, height=a.height, seed=a.seed)
-        fe.detector_configure(max_keypoints=600)
+        if not a.resume:   # (a resumed detector has its configuration and thresholds from the file)
+            fe.detector_configure(max_keypoints=600)
         t0 = time.perf_counter()
-        fe.sensor_detect_describe_batch_nodes(list(seq["gray"]), list(seq["depth"]), seq["fx"], seq["fy"], seq["cx"], seq["cy"],
-                                              node_ids=np.arange(a.frames), cloud_skip=8 if (a.map or a.render) else None)
-        upload_s = [(time.perf_counter() - t0) / a.frames] * a.frames
+        if stop > start:
+            fe.sensor_detect_describe_batch_nodes(list(seq["gray"][start:stop]), list(seq["depth"][start:stop]), seq["fx"], seq["fy"],
+                                                  seq["cx"], seq["cy"], node_ids=np.arange(start, stop),
+                                                  cloud_skip=8 if (a.map or a.render) else None)
+        upload_s = [(time.perf_counter() - t0) / max(stop - start, 1)] * (stop - start)
     else:
         seq = synth.make_sequence(n_frames=a.frames, n_kp=a.n_kp, seed=a.seed)
         poses = seq["poses"]
     records, wall = [], []
-    for k in range(a.frames):
+    for k in range(start, stop):
         if not a.images:
             t0 = time.perf_counter()
             fe.upload_node(k, seq["desc"][k], seq["xyz1"][k])
@@ -86,19 +101,22 @@ def main():
         t0 = time.perf_counter()
         records.append(gm.addNode(resident_node(fe, k), stamps[k]))
         wall.append(time.perf_counter() - t0)
+    if a.save_session:
+        fe.save_session(a.save_session, slam, gm.pose_graph, clouds=bool(a.images and (a.map or a.render)))
 
     ids = list(range(slam.node_count()))
     slots = slam.slots()
     frame_of = {i: slots[i] for i in ids}   # a frame's slot is its index; a cleared node keeps no slot, its stamp is its record's
-    stamp_of = {r.id: stamps[k] for k, r in enumerate(records) if r.id >= 0 and r.status_name != "replaced_first"}
-    res = dict(tool="run_sequence", frames=a.frames, images=bool(a.images), n_kp=a.n_kp, optimizer_skip_step=a.optimizer_skip_step,
+    state = parse_slam_state(slam.serialize())
+    stamp_of = dict(enumerate(state["stamps"]))   # by graph id, the frames of before a --resume included
+    res = dict(tool="run_sequence", frames=a.frames, first_frame=start, frames_run=stop - start, resumed=a.resume, saved=a.save_session, images=bool(a.images), n_kp=a.n_kp, optimizer_skip_step=a.optimizer_skip_step,
                strategy=a.strategy, vertices=len(ids), keyframes=len(slam.keyframes()),
-               sequential_edges=records[-1].sequential_edges, loop_closure_edges=records[-1].loop_closure_edges,
+               sequential_edges=state["sequential_edges"], loop_closure_edges=state["loop_closure_edges"],
                status={}, optimisations=sum(r.optimized for r in records), stats_launches=sum(r.stats_launches for r in records))
     for r in records:
         res["status"][r.status_name] = res["status"].get(r.status_name, 0) + 1
-    res["dropped"] = a.frames - len(ids)
-    ms = lambda v: dict(mean=1e3 * statistics.fmean(v), median=1e3 * statistics.median(v), max=1e3 * max(v))
+    res["dropped"] = stop - len(ids)
+    ms = lambda v: dict(mean=1e3 * statistics.fmean(v), median=1e3 * statistics.median(v), max=1e3 * max(v)) if len(v) else None
     res["ms_per_frame"] = dict(add_node=ms(wall), upload=ms(upload_s),
                                **{name: ms([r.seconds[i] for r in records]) for i, name in enumerate(STAGES)})
     res["ms_per_frame"]["total"] = ms([w + u for w, u in zip(wall, upload_s)])
@@ -110,11 +128,12 @@ def main():
         if poses is not None:
             gt = os.path.join(d, "groundtruth.txt")
             with open(gt, "w") as f:
-                for k in range(a.frames):
+                for k in range(stop):
                     p = np.linalg.inv(poses[0]) @ poses[k]
                     f.write("%.6f %.6f %.6f %.6f 0 0 0 1\n" % (stamps[k][0] + 1e-9 * stamps[k][1], p[0, 3], p[1, 3], p[2, 3]))
             res["ate"] = evaluate_ate.ate(evaluate_ate.read_trajectory(gt), evaluate_ate.read_trajectory(est))
-            res["path_length_m"] = float(sum(np.linalg.norm(poses[k + 1][:3, 3] - poses[k][:3, 3]) for k in range(a.frames - 1)))
+            res["path_length_m"] = float(sum(np.linalg.norm(poses[k + 1][:3, 3] - poses[k][:3, 3]) for k in range(stop - 1)))
+            res["estimate_sha1"] = __import__("hashlib").sha1(open(est, "rb").read()).hexdigest()   # equal for a resumed and an uninterrupted run
     if a.map and a.images:
         valid = [i for i in ids if slam.valid_tf()[i] and frame_of[i] >= 0]
         t0 = time.perf_counter()
