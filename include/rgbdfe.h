@@ -1862,6 +1862,101 @@ int rgbdfe_restore_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* poi
  * kept as) */
 int rgbdfe_node_cloud_info(rgbdfe_ctx* ctx, int32_t node_id, double* out8);
 
+/* ---- map files: PCD and PLY of the assembled map and of node clouds ------------------------------------------------------
+ * GraphManager::saveAllCloudsToFile (graph_mgr_io.cpp:502-582) and saveIndividualCloudsToFile (:330-433): what a batch run
+ * ends with.  The two file formats are restated from PCL 1.7's writers, NOT pinned on PCL's compiled code (PCL is on no
+ * machine this library is built on): the statements below are the contract.  Everything is little-endian.
+ *
+ * PCD -- pcl::io::savePCDFile(name, cloud, true) of a PointXYZRGB cloud.  The header is exactly these lines, each ended by
+ *   '\n', followed by the data with no padding:
+ *       # .PCD v0.7 - Point Cloud Data file format
+ *       VERSION 0.7
+ *       FIELDS x y z rgb
+ *       SIZE 4 4 4 4
+ *       TYPE F F F F
+ *       COUNT 1 1 1 1
+ *       WIDTH <w>
+ *       HEIGHT <h>
+ *       VIEWPOINT <ox> <oy> <oz> <qw> <qx> <qy> <qz>
+ *       POINTS <w*h>
+ *       DATA binary
+ *   The data is w*h rows of 16 bytes: this library's cloud row (x, y, z, rgb word) bit for bit, NaN payloads included.  Each
+ *   viewpoint number is the float as a C++ stream prints it by default: printf("%g") of the value.  The aggregate map has
+ *   WIDTH n, HEIGHT 1, VIEWPOINT 0 0 0 1 0 0 0.
+ * PLY -- pcl::io::savePLYFileBinary.  The header is "ply", "format binary_little_endian 1.0", "comment PCL generated",
+ *   "element vertex <n>", "property float x" / y / z, "property uchar red" / green / blue, "element camera 1", then one
+ *   "property float" line each for view_px view_py view_pz x_axisx x_axisy x_axisz y_axisx y_axisy y_axisz z_axisx z_axisy
+ *   z_axisz focal scalex scaley centerx centery, "property int viewportx", "property int viewporty", "property float k1",
+ *   "property float k2", "end_header", each line ended by '\n'.  Then n vertex records of 15 bytes: x, y, z as float bits, then
+ *   r, g, b = bits 23-16, 15-8 and 7-0 of the rgb word.  Every row of the cloud is a vertex, raster mode's NaN rows included.
+ *   The camera record (84 bytes) follows: origin 0 0 0, the identity rotation row by row, five zero floats, viewportx = width
+ *   and viewporty = height as int32, two zero floats.
+ * Name rule (the reference's): a path ending in ".ply" in any letter case gives PLY; any other path gives PCD, and ".pcd" is
+ *   appended unless the path already ends in it in any case (rgbdfe_cloud_file_path applies the rule without writing).
+ * Deviations from the reference: an aggregate of zero points creates no file and returns RGBDFE_OK with a count of 0 (PCL
+ *   throws); 2^31 points or more is RGBDFE_ERR_CAPACITY; a path that cannot be opened is RGBDFE_ERR_INVALID_ARG; a failed write
+ *   is RGBDFE_ERR_INTERNAL and the file is removed (as rgbdfe_octomap_write); rgbdfe_save_node_clouds leaves the resident
+ *   cloud as it is (the reference transforms it in place, so a second save there moves it twice).
+ *
+ * rgbdfe_save_map is saveAllCloudsToFile: node_ids / transforms / maximum_depth / preserve_raster mean exactly what they
+ *   mean for rgbdfe_assemble_map, and the file's data section is, byte for byte, the rows that call returns (their 15-byte
+ *   repacking for PLY).  The map is never whole anywhere: a count and a scan over the list give the total and every node's
+ *   first row (the header is written from them), then the list is cut into groups of consecutive nodes whose clouds sum to
+ *   at most chunk_points points (0: 2^20; values below 64 count as 64; a larger cloud is a group of its own), each group is
+ *   assembled into one of two device buffers, its file bytes land in one of two page-locked slots (PLY: packed by
+ *   cloud_pack_ply_kernel straight into the slot; PCD: an asynchronous copy), and a writer thread writes slot g while group
+ *   g + 1 runs.  The file's bytes do not depend on chunk_points.  path_written (may be NULL) receives the path after the
+ *   name rule, NUL-terminated (path_capacity too small: RGBDFE_ERR_CAPACITY before anything happens).  stats (may be NULL):
+ *   device_scratch_bytes = pinned_bytes = 2 x 16 x the largest group's points <= 2 x 16 x max(chunk_points, largest listed
+ *   cloud); table_bytes = the node and tile tables beside them in the context's scratch.
+ * rgbdfe_save_node_clouds is saveIndividualCloudsToFile without its ground-truth branch: every listed node with a non-empty
+ *   cloud gets <basename>_%04d.pcd and <basename>_%04d.txt, numbered by graph_ids[k] (NULL: node_ids[k]).  poses: n
+ *   column-major 4x4 doubles (the vertex estimates; tf is the caller's).  transform_individual_clouds == 0: the resident
+ *   cloud untouched, organised (WIDTH cols, HEIGHT rows); its viewpoint is the pose: the translation cast to float, the
+ *   rotation through the matrix -> quaternion conversion of rgbdfe_pose_graph_write_trajectory, cast to float.  != 0:
+ *   pcl::transformPointCloud with the pose cast to float (== raster-mode assembly of the node alone with the clip off), and
+ *   the reference's quirk: Quaternionf(0,0,0,1) is (w, x, y, z), so the viewpoint is "0 0 0 0 0 0 1" and the exported
+ *   rotation is diag(-1, -1, 1).  The .txt holds three rows "r0 r1 r2 t " of Eigen's Quaternionf::toRotationMatrix() of the
+ *   float quaternion (restated) and the float origin, then "0 0 0 1" and a newline, every number as printf("%g").
+ *   An unknown node is RGBDFE_ERR_UNKNOWN_NODE before anything is written; *n_written counts the nodes written.
+ * Host-only calls (no device, no context; the cause of a failure: rgbdfe_last_error(NULL)):
+ *   rgbdfe_save_cloud_file writes width x height rows held in host memory (viewpoint: 7 floats or NULL for the aggregate's;
+ *     PLY ignores it and stores width / height as the viewport).
+ *   rgbdfe_cloud_file_info reads a file's header; rgbdfe_load_cloud_file also returns its rows as 4-float rows (a PLY
+ *     vertex's rgb word has a zero top byte); capacity below the file's points is RGBDFE_ERR_CAPACITY with *info filled.
+ *     Both read exactly the two layouts above with a data section of exactly the promised length: other field lists, ascii
+ *     or compressed data, big-endian, counts that are not decimal numbers below 2^31, a shorter or longer file are
+ *     RGBDFE_ERR_INVALID_ARG.  Nothing is read past the file. */
+#define RGBDFE_CLOUD_FILE_PCD 0
+#define RGBDFE_CLOUD_FILE_PLY 1
+typedef struct rgbdfe_map_file_stats {
+  int64_t points;                /* rows of the file */
+  int64_t bytes_written;         /* the whole file */
+  int32_t format;                /* RGBDFE_CLOUD_FILE_* */
+  int32_t groups;
+  int64_t device_scratch_bytes;  /* the two group buffers */
+  int64_t pinned_bytes;          /* the two page-locked slots */
+  int64_t table_bytes;           /* node table, tile tables, counts */
+} rgbdfe_map_file_stats;
+typedef struct rgbdfe_cloud_file_header {
+  int32_t format;                /* RGBDFE_CLOUD_FILE_* */
+  int32_t width, height;         /* PLY: the camera record's viewport */
+  int32_t reserved;
+  int64_t points, header_bytes, data_bytes;
+  float viewpoint[7];            /* ox oy oz qw qx qy qz (PLY: 0 0 0 1 0 0 0) */
+  float reserved2;
+} rgbdfe_cloud_file_header;
+int rgbdfe_save_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth,
+                    int32_t preserve_raster, const char* path, int64_t chunk_points, char* path_written, int64_t path_capacity,
+                    rgbdfe_map_file_stats* stats);
+int rgbdfe_save_node_clouds(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const int32_t* graph_ids,
+                            const double* poses, int32_t transform_individual_clouds, const char* basename, int32_t* n_written);
+int rgbdfe_save_cloud_file(const float* points, int32_t width, int32_t height, const float* viewpoint, int32_t format,
+                           const char* path);
+int rgbdfe_cloud_file_info(const char* path, rgbdfe_cloud_file_header* info);
+int rgbdfe_load_cloud_file(const char* path, float* out, int64_t capacity, rgbdfe_cloud_file_header* info);
+int rgbdfe_cloud_file_path(const char* path, char* path_out, int64_t capacity, int32_t* format);
+
 /* ---- measurement --------------------------------------------------------- */
 /* When enabled, every launch of the dominant kernels is bracketed by HIP events on the
  * stream it runs on; totals are read back with rgbdfe_get_kernel_time. */

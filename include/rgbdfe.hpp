@@ -667,6 +667,54 @@ inline bool assembleAllClouds(const FrontEnd& fe, const std::vector<int32_t>& no
   return true;
 }
 
+// GraphManager::saveAllCloudsToFile (src/graph_mgr_io.cpp:502-582) as a whole: the loop above AND the file, streamed group
+// by group so that the map is never whole in memory (rgbdfe_save_map).  filename follows the reference's name rule (*.ply in
+// any case: binary PLY; otherwise binary PCD, ".pcd" appended unless it is there); path_written (optional) receives the
+// name after the rule, stats (optional) the call's report.  No point: no file, true, stats->points == 0.
+inline bool rgbdfe_save_map(const FrontEnd& fe, const std::vector<int32_t>& node_ids, const std::vector<float>& world2cam,
+                            double maximum_depth, bool preserve_raster_on_save, const std::string& filename,
+                            std::string* path_written = nullptr, rgbdfe_map_file_stats* stats = nullptr, int64_t chunk_points = 0) {
+  if (world2cam.size() != node_ids.size() * 16) return false;
+  std::vector<char> written(filename.size() + 8, 0);
+  if (::rgbdfe_save_map(fe.get(), (int32_t)node_ids.size(), node_ids.data(), world2cam.data(), maximum_depth,
+                        preserve_raster_on_save ? 1 : 0, filename.c_str(), chunk_points, written.data(), (int64_t)written.size(),
+                        stats) != RGBDFE_OK)
+    return false;
+  if (path_written) *path_written = written.data();
+  return true;
+}
+
+// GraphManager::saveIndividualCloudsToFile (src/graph_mgr_io.cpp:330-433) without its ground-truth branch:
+// <file_basename>_%04d.pcd and .txt per listed node with a non-empty cloud, numbered by graph_ids (empty: node_ids).  poses =
+// n x 16 doubles, the column-major v->estimate().matrix() per node (world2points where tf is involved: the caller's);
+// transform_individual_clouds is the parameter of that name.  The resident clouds stay as they are.
+inline bool rgbdfe_save_node_clouds(const FrontEnd& fe, const std::vector<int32_t>& node_ids, const std::vector<int32_t>& graph_ids,
+                                    const std::vector<double>& poses, bool transform_individual_clouds,
+                                    const std::string& file_basename, int32_t* n_written = nullptr) {
+  if (poses.size() != node_ids.size() * 16 || (!graph_ids.empty() && graph_ids.size() != node_ids.size())) return false;
+  return ::rgbdfe_save_node_clouds(fe.get(), (int32_t)node_ids.size(), node_ids.data(), graph_ids.empty() ? nullptr : graph_ids.data(),
+                                   poses.data(), transform_individual_clouds ? 1 : 0, file_basename.c_str(), n_written) == RGBDFE_OK;
+}
+
+// The host-only calls: a cloud in host memory (rows of x, y, z, rgb bits) to a file of `format` (RGBDFE_CLOUD_FILE_*), a
+// file's header, and a file's rows.  No device, no context: rgbdfe_last_error(NULL) has the cause of a failure.
+inline bool rgbdfe_save_cloud_file(const std::vector<float>& points, int32_t width, int32_t height, int32_t format,
+                                   const std::string& path, const float* viewpoint7 = nullptr) {
+  if (width < 0 || height < 0 || points.size() != (size_t)width * (size_t)height * 4) return false;
+  return ::rgbdfe_save_cloud_file(points.data(), width, height, viewpoint7, format, path.c_str()) == RGBDFE_OK;
+}
+inline bool rgbdfe_cloud_file_info(const std::string& path, rgbdfe_cloud_file_header* info) {
+  return ::rgbdfe_cloud_file_info(path.c_str(), info) == RGBDFE_OK;
+}
+inline bool rgbdfe_load_cloud_file(const std::string& path, std::vector<float>* points, rgbdfe_cloud_file_header* info = nullptr) {
+  rgbdfe_cloud_file_header h;
+  if (::rgbdfe_cloud_file_info(path.c_str(), &h) != RGBDFE_OK) return false;
+  points->resize((size_t)h.points * 4);
+  if (::rgbdfe_load_cloud_file(path.c_str(), points->data(), h.points, &h) != RGBDFE_OK) return false;
+  if (info) *info = h;
+  return true;
+}
+
 // GLViewer::addPointCloud (src/glviewer.cpp:693-735) for every listed node, on the device: what pointCloud2GLPoints,
 // pointCloud2GLTriangleList or pointCloud2GLStrip would have sent to the node's display list (rgbdfe_display_geometry).
 // display_type is the parameter "cloud_display_type" ("POINTS", "TRIANGLES", anything else but "ELLIPSOIDS" / "NONE":

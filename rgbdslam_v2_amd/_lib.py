@@ -270,6 +270,20 @@ class RgbdfeError(RuntimeError):
     pass
 
 
+CLOUD_FILE_PCD, CLOUD_FILE_PLY = 0, 1   # RGBDFE_CLOUD_FILE_*
+
+
+class MapFileStats(C.Structure):   # rgbdfe_map_file_stats
+    _fields_ = [("points", C.c_int64), ("bytes_written", C.c_int64), ("format", C.c_int32), ("groups", C.c_int32),
+                ("device_scratch_bytes", C.c_int64), ("pinned_bytes", C.c_int64), ("table_bytes", C.c_int64)]
+
+
+class CloudFileHeader(C.Structure):   # rgbdfe_cloud_file_header
+    _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_int32),
+                ("points", C.c_int64), ("header_bytes", C.c_int64), ("data_bytes", C.c_int64),
+                ("viewpoint", C.c_float * 7), ("reserved2", C.c_float)]
+
+
 def load():
     """Load librgbdfe.so; raises if it has not been built."""
     global _lib
@@ -712,6 +726,18 @@ def load():
     L.rgbdfe_restore_node_cloud.argtypes = [vp, i32, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32]
     L.rgbdfe_node_cloud_info.restype = C.c_int
     L.rgbdfe_node_cloud_info.argtypes = [vp, i32, vp]
+    L.rgbdfe_save_map.restype = C.c_int
+    L.rgbdfe_save_map.argtypes = [ctx, i32, vp, vp, C.c_double, i32, C.c_char_p, i64, vp, i64, vp]
+    L.rgbdfe_save_node_clouds.restype = C.c_int
+    L.rgbdfe_save_node_clouds.argtypes = [ctx, i32, vp, vp, vp, i32, C.c_char_p, C.POINTER(i32)]
+    L.rgbdfe_save_cloud_file.restype = C.c_int
+    L.rgbdfe_save_cloud_file.argtypes = [vp, i32, i32, vp, i32, C.c_char_p]
+    L.rgbdfe_cloud_file_info.restype = C.c_int
+    L.rgbdfe_cloud_file_info.argtypes = [C.c_char_p, vp]
+    L.rgbdfe_load_cloud_file.restype = C.c_int
+    L.rgbdfe_load_cloud_file.argtypes = [C.c_char_p, vp, i64, vp]
+    L.rgbdfe_cloud_file_path.restype = C.c_int
+    L.rgbdfe_cloud_file_path.argtypes = [C.c_char_p, vp, i64, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -773,4 +799,6 @@ EXPORTED_SYMBOLS = [
     "rgbdfe_detector_set_thresholds",
     "rgbdfe_pose_graph_serialize", "rgbdfe_pose_graph_deserialize", "rgbdfe_pose_graph_node_ids", "rgbdfe_slam_serialize",
     "rgbdfe_slam_deserialize", "rgbdfe_session_save", "rgbdfe_session_load", "rgbdfe_restore_node_cloud", "rgbdfe_node_cloud_info",
+    "rgbdfe_save_map", "rgbdfe_save_node_clouds", "rgbdfe_save_cloud_file", "rgbdfe_cloud_file_info", "rgbdfe_load_cloud_file",
+    "rgbdfe_cloud_file_path",
 ]

@@ -492,6 +492,10 @@ void quat_from_rot(const double* R, double* q) {
 }
 }  // namespace
 
+}  // extern "C"
+void rgbdfe_host::quat_from_rot_xyzw(const double* R, double* q) { quat_from_rot(R, q); }   // the node cloud files' viewpoint
+extern "C" {
+
 int rgbdfe_pose_graph_write_trajectory(const rgbdfe_pose_graph* g, const char* path, int32_t n, const int32_t* node_ids,
                                        const double* timestamps, const double* base2points, const double* init_base_pose,
                                        const char* frame_id, const char* child_frame_id) try {

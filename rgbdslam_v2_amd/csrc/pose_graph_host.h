@@ -31,3 +31,8 @@ struct rgbdfe_pose_graph {
   void* device = nullptr;                            // the optimiser's buffers (api_pose_graph.hip)
   void (*device_free)(void*) = nullptr;
 };
+
+namespace rgbdfe_host {
+// the trajectory writer's matrix -> quaternion conversion (candidates.cpp): R row-major, q = (x, y, z, w)
+void quat_from_rot_xyzw(const double* R, double* q);
+}  // namespace rgbdfe_host

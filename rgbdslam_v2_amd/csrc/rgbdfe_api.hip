@@ -1291,6 +1291,23 @@ int rgbdfe_session_load(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* g
   });
 }
 
+// (the host-only calls of the map files -- rgbdfe_save_cloud_file, rgbdfe_cloud_file_info, rgbdfe_load_cloud_file,
+// rgbdfe_cloud_file_path -- take no context: api_map_files.hip defines them behind a barrier of their own)
+int rgbdfe_save_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth,
+                    int32_t preserve_raster, const char* path, int64_t chunk_points, char* path_written, int64_t path_capacity,
+                    rgbdfe_map_file_stats* stats) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_save_map(c, n_nodes, node_ids, transforms, maximum_depth, preserve_raster, path, chunk_points,
+                                                 path_written, path_capacity, stats));
+}
+
+int rgbdfe_save_node_clouds(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const int32_t* graph_ids, const double* poses,
+                            int32_t transform_individual_clouds, const char* basename, int32_t* n_written) {
+  if (!ctx) return RGBDFE_ERR_INVALID_ARG;
+  return RGBDFE_FIRST(ctx, impl::rgbdfe_save_node_clouds(c, n_nodes, node_ids, graph_ids, poses, transform_individual_clouds, basename,
+                                                         n_written));
+}
+
 int rgbdfe_abi_version(void) { return impl::rgbdfe_abi_version(); }
 
 }  // extern "C"

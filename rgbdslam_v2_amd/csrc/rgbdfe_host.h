@@ -775,6 +775,12 @@ int rgbdfe_restore_node_cloud(rgbdfe_ctx* ctx, int32_t node_id, const float* poi
                               double cx, double cy, int32_t cloud_skip);
 int rgbdfe_session_save(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, uint32_t flags, const char* path);
 int rgbdfe_session_load(rgbdfe_ctx* ctx, rgbdfe_slam* slam, rgbdfe_pose_graph* graph, const char* path);
+// api_map_files.hip
+int rgbdfe_save_map(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const float* transforms, double maximum_depth,
+                    int32_t preserve_raster, const char* path, int64_t chunk_points, char* path_written, int64_t path_capacity,
+                    rgbdfe_map_file_stats* stats);
+int rgbdfe_save_node_clouds(rgbdfe_ctx* ctx, int32_t n_nodes, const int32_t* node_ids, const int32_t* graph_ids, const double* poses,
+                            int32_t transform_individual_clouds, const char* basename, int32_t* n_written);
 }  // namespace impl
 
 // ---- the rgbdfe_slam object as api_session.hip needs it (api_slam.hip)

@@ -1305,6 +1305,40 @@ class FrontEnd:
             out.data_ptr() if out.shape[0] else None, int(out.shape[0]), C.byref(n_out), offsets.ctypes.data, stream))
         return (n_out.value, offsets) if return_offsets else n_out.value
 
+    def save_map(self, path, node_ids, transforms, maximum_depth=float("inf"), preserve_raster=False, chunk_points=0):
+        """GraphManager::saveAllCloudsToFile: assemble_map's rows as a binary PCD file, or as a binary PLY file when `path`
+        ends in .ply (any case; otherwise .pcd is appended unless it is there).  The map is streamed group by group through
+        two device buffers and two page-locked slots of at most max(chunk_points, the largest cloud) rows (0: 2^20), so it
+        is never whole in memory; the file does not depend on chunk_points.  Returns a dict: path (as written), points,
+        bytes_written, format ("pcd" / "ply"), groups, device_scratch_bytes, pinned_bytes, table_bytes.  No point: no file."""
+        node_ids, T = self._map_args(node_ids, transforms)
+        stats = _lib.MapFileStats()
+        written = C.create_string_buffer(len(os.fsencode(path)) + 8)
+        self._check(self._L.rgbdfe_save_map(self._ctx, len(node_ids), node_ids.ctypes.data, T.ctypes.data, float(maximum_depth),
+                                            int(bool(preserve_raster)), os.fsencode(path), int(chunk_points), written,
+                                            len(written), C.byref(stats)))
+        out = {name: getattr(stats, name) for name, _ in stats._fields_}
+        out["format"] = ("pcd", "ply")[stats.format]
+        out["path"] = os.fsdecode(written.value)
+        return out
+
+    def save_node_clouds(self, basename, node_ids, poses, graph_ids=None, transform_individual_clouds=False):
+        """GraphManager::saveIndividualCloudsToFile: <basename>_%04d.pcd and .txt for every listed node with a non-empty
+        cloud, numbered by graph_ids (default: node_ids).  poses: n x 4 x 4 (row-major numpy matrices, float64: the vertex
+        estimates).  The resident clouds stay as they are.  Returns the number of nodes written."""
+        node_ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
+        P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))  # column-major
+        if len(P) != len(node_ids):
+            raise ValueError("one 4 x 4 pose per listed node")
+        gids = None if graph_ids is None else np.ascontiguousarray(graph_ids, np.int32).reshape(-1)
+        if gids is not None and len(gids) != len(node_ids):
+            raise ValueError("one graph id per listed node")
+        n = C.c_int32(0)
+        self._check(self._L.rgbdfe_save_node_clouds(self._ctx, len(node_ids), node_ids.ctypes.data,
+                                                    None if gids is None else gids.ctypes.data, P.ctypes.data,
+                                                    int(bool(transform_individual_clouds)), os.fsencode(basename), C.byref(n)))
+        return n.value
+
     def _display_args(self, node_ids, transforms, display_type, visualization_skip_step, squared_meshing_threshold,
                       maximum_depth):
         node_ids = np.ascontiguousarray(node_ids, np.int32).reshape(-1)
@@ -1719,6 +1753,51 @@ class GraphManager:
         if self.slam().node_count() != 0:
             raise ValueError("firstNode: the graph is not empty")
         return self.addNode(node, stamp)
+
+
+def _check_contextless(L, st):
+    if st != 0:
+        raise RgbdfeError(f"{L.rgbdfe_status_string(st).decode()}: {L.rgbdfe_last_error(None).decode()}")
+
+
+def cloud_file_path(path):
+    """The reference's name rule: (path as it is written, "pcd" / "ply")."""
+    L = _lib.load()
+    out = C.create_string_buffer(len(os.fsencode(path)) + 8)
+    fmt = C.c_int32(0)
+    _check_contextless(L, L.rgbdfe_cloud_file_path(os.fsencode(path), out, len(out), C.byref(fmt)))
+    return os.fsdecode(out.value), ("pcd", "ply")[fmt.value]
+
+
+def save_cloud_file(path, points, viewpoint=None, format=None):
+    """A cloud held in host memory as a binary PCD / PLY file (include/rgbdfe.h, "map files"); no device.  points: [n, 4] (written
+    as WIDTH n, HEIGHT 1) or [rows, cols, 4] float32 (x, y, z, rgb bits); viewpoint: ox oy oz qw qx qy qz (PCD only).  `path` is
+    written as given; format: "pcd" / "ply", by default by the name rule's reading of the path."""
+    L = _lib.load()
+    pts = np.ascontiguousarray(points, np.float32)
+    if pts.ndim not in (2, 3) or pts.shape[-1] != 4:
+        raise ValueError("points must be [n, 4] or [rows, cols, 4]")
+    height, width = (1, pts.shape[0]) if pts.ndim == 2 else pts.shape[:2]
+    fmt = cloud_file_path(path)[1] if format is None else format
+    vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32).reshape(7)
+    _check_contextless(L, L.rgbdfe_save_cloud_file(pts.ctypes.data, int(width), int(height), None if vp is None else vp.ctypes.data,
+                                                   ("pcd", "ply").index(fmt), os.fsencode(path)))
+
+
+def read_cloud_file(path, header_only=False):
+    """A file of one of the two layouts this library writes: (points [height, width, 4] float32, info) with info = format,
+    width, height, points, header_bytes, data_bytes, viewpoint.  A PLY vertex's rgb word has a zero top byte.  Anything else is
+    refused.  header_only: info alone."""
+    L = _lib.load()
+    h = _lib.CloudFileHeader()
+    _check_contextless(L, L.rgbdfe_cloud_file_info(os.fsencode(path), C.byref(h)))
+    info = dict(format=("pcd", "ply")[h.format], width=h.width, height=h.height, points=h.points, header_bytes=h.header_bytes,
+                data_bytes=h.data_bytes, viewpoint=np.array(h.viewpoint[:], np.float32))
+    if header_only:
+        return info
+    out = np.empty((h.height, h.width, 4), np.float32)
+    _check_contextless(L, L.rgbdfe_load_cloud_file(os.fsencode(path), out.ctypes.data, int(h.points), C.byref(h)))
+    return out, info
 
 
 def read_session_chunks(path) -> dict:

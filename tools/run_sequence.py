@@ -7,7 +7,10 @@ GraphManager.addNode -- candidate selection, the pair batch, the decisions, the 
 saveTrajectory's estimate file is written and tools/evaluate_ate.py compares it with the synthetic poses (feature
 sequences only: the image sequence has no camera poses); --map also assembles the clouds of the nodes with a valid
 estimate (image sequences: they carry clouds) and inserts them into an OctoMap; --render FILE renders those clouds on the
-device, seen through the sensor from the last pose, into a PNG or PPM (tools/render_map.py).
+device, seen through the sensor from the last pose, into a PNG or PPM (tools/render_map.py).  --save-map FILE writes that
+map as a file (saveAllCloudsToFile: binary PLY when FILE ends in .ply, else binary PCD), streamed from the device without
+ever holding it whole; --save-clouds BASENAME writes BASENAME_%04d.pcd / .txt per node (saveIndividualCloudsToFile).  Both act
+on the nodes with a valid estimate, in graph order.
 
 --save-session FILE writes the run's state -- resident nodes, the detector's thresholds, with --map / --render the clouds, the
 pose graph and the decision machine -- when the run ends, or after K frames with --stop-after K; --resume FILE loads such a
@@ -60,6 +63,8 @@ def main():
     ap.add_argument("--fps", type=float, default=30.0)
     ap.add_argument("--map", action="store_true")
     ap.add_argument("--render", metavar="FILE", help="with --images: the map seen from the last pose, as .png or .ppm")
+    ap.add_argument("--save-map", metavar="FILE", help="with --images: the assembled map as a .pcd / .ply file")
+    ap.add_argument("--save-clouds", metavar="BASENAME", help="with --images: BASENAME_%%04d.pcd and .txt per node")
     ap.add_argument("--seed", type=int, default=20260923)
     ap.add_argument("--out")
     ap.add_argument("--save-session", metavar="FILE", help="save nodes, detector state, graph and machine when the run ends")
@@ -87,7 +92,7 @@ def main():
         if stop > start:
             fe.sensor_detect_describe_batch_nodes(list(seq["gray"][start:stop]), list(seq["depth"][start:stop]), seq["fx"], seq["fy"],
                                                   seq["cx"], seq["cy"], node_ids=np.arange(start, stop),
-                                                  cloud_skip=8 if (a.map or a.render) else None)
+                                                  cloud_skip=8 if (a.map or a.render or a.save_map or a.save_clouds) else None)
         upload_s = [(time.perf_counter() - t0) / max(stop - start, 1)] * (stop - start)
     else:
         seq = synth.make_sequence(n_frames=a.frames, n_kp=a.n_kp, seed=a.seed)
@@ -144,6 +149,18 @@ def main():
         with fe.octomap(1 << 20) as om:
             om.insert_nodes([frame_of[i] for i in valid], T)
             res["map"].update(octomap_leaves=len(om), octomap_ms=1e3 * (time.perf_counter() - t0))
+    if (a.save_map or a.save_clouds) and a.images:
+        valid = [i for i in ids if slam.valid_tf()[i] and frame_of[i] >= 0]
+        res["map_files"] = dict(nodes=len(valid))
+        if a.save_map:
+            t0 = time.perf_counter()
+            st = fe.save_map(a.save_map, [frame_of[i] for i in valid], gm.pose_graph.transforms(valid))
+            res["map_files"].update(map=st, save_map_ms=1e3 * (time.perf_counter() - t0))
+        if a.save_clouds:
+            t0 = time.perf_counter()
+            n = fe.save_node_clouds(a.save_clouds, [frame_of[i] for i in valid], [gm.pose_graph.get_estimate(i) for i in valid],
+                                    graph_ids=valid)
+            res["map_files"].update(clouds_basename=a.save_clouds, clouds_written=n, save_clouds_ms=1e3 * (time.perf_counter() - t0))
     if a.render and a.images:
         import render_map
         valid = [i for i in ids if slam.valid_tf()[i] and frame_of[i] >= 0]
